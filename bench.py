@@ -14,9 +14,10 @@ tests/golden/yunet_n_synth_trained.pth with structured synthetic faces (SimOTA d
 --weights init = random initialisation on noise images.  --dtype bf16 = the second line (configs[2]);
 --gpus N without a launcher re-executes under torch.distributed.run.
 
-The timed window is at least 0.5 s: K steps are timed as asked; if they took less, the window is repeated with
-ceil(0.5 s / ms_per_step) steps and THAT window is reported (`steps` = the steps actually timed, `steps_requested` = K,
-`first_window` = the K-step timing) -- a 0.1 s window sits on the clock ramp and the pool's boxes differ by 10 %.
+The timed window is exactly K = --steps steps after W = --warmup untimed ones; `ms_per_step` is its wall time over K
+(a window much shorter than 0.5 s sits on the clock ramp: choose K from a first run's `ms_per_step`).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64 losses, float32 gradients and
+post-update state): the inputs depend only on the arguments, so two builds can be compared output for output.
 
 Extra objects on that line (N=1 only):
   roofline     -- the dominant kernel FAMILY of the step (all template instances of one __global__ function, e.g. the
@@ -32,7 +33,6 @@ self-check passes; both are printed under `dist` (`value` stays the RCCL figure 
 import argparse
 import ctypes as C
 import json
-import math
 import os
 import platform
 import sys
@@ -48,7 +48,7 @@ HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MI
 MFMA_F32_PEAK_TFLOPS = 157.3   # v_mfma_f32_16x16x4_f32: 256 CU x 4 SIMD x 64 FLOP/clk x 2.4 GHz
 MFMA_BF16_PEAK_TFLOPS = 2500.0  # dense bf16 (MI355X_MICROARCH.md; the headline 5 PF figure includes 2:1 sparsity)
 KIND, H, W, BATCH = 'n', 320, 320, 256
-MIN_WINDOW_S = 0.5        # shortest timed window reported (SURVEY 8d asks for >= 50 timed steps)
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def parse():
@@ -60,7 +60,9 @@ def parse():
     p.add_argument('--size', type=int, default=H)
     p.add_argument('--kind', default=KIND, choices=['n', 's'])
     p.add_argument('--exact-steps', action='store_true',
-                   help='report the K-step window even if it is shorter than 0.5 s (A/B scripts that alternate builds)')
+                   help='accepted for older scripts: the timed window is always exactly --steps steps')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write the last timed step\'s losses, gradients and updated state as DIR/<name>.npy')
     p.add_argument('--no-cpu-baseline', action='store_true')
     p.add_argument('--cpu-baseline-only', action='store_true', help=argparse.SUPPRESS)
     p.add_argument('--gpu-eager-only', action='store_true', help=argparse.SUPPRESS)
@@ -103,6 +105,26 @@ def self_launch(a):
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={a.gpus}',
            '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:]
     raise SystemExit(subprocess.call(cmd, env=env))
+
+
+def dump_outputs(path, model, opt, out):
+    """What one training step hands its caller, as DIR/<name>.npy: the five logged losses (float64), every parameter's
+    gradient (grad.<name>, float32) and the state after the SGD update (state.<key>: parameters and BatchNorm buffers,
+    float32, the integer batch counter as float64; momentum_buffer: the optimizer's flat float32 buffer)."""
+    import numpy as np
+    arrays = {k: np.array(float(v), dtype=np.float64) for k, v in out['log_vars'].items()}
+    for name, p in model.named_parameters():
+        arrays[f'grad.{name}'] = p.grad.detach().float().cpu().numpy()
+    for k, v in model.state_dict().items():
+        v = v.detach().cpu()
+        arrays[f'state.{k}'] = (v.float() if v.is_floating_point() else v.double()).numpy()
+    arrays['momentum_buffer'] = opt.state_dict()['momentum_buffer'].float().cpu().numpy()
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f'--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit')
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, f'{k}.npy'), v)
 
 
 # ----------------------------------------------------------------- algorithmic byte model
@@ -758,17 +780,10 @@ def main():
             every = [float(v.item()) for v in got]
         return max(every), every, c0, c1, o, rep            # the job is as fast as its slowest rank
 
-    steps_requested = a.steps
     dt, per_rank, clk0, clk1, out, comm = window(a.steps)
-    first_window = None
-    if dt < MIN_WINDOW_S and not a.exact_steps:
-        # K steps took less than 0.5 s: time ceil(0.5 s / ms_per_step) steps instead and report THAT window (every rank
-        # derives the same count from the max-over-ranks time); the K-step timing stays in `first_window`
-        first_window = {'steps': a.steps, 'ms_per_step': round(1000.0 * dt / a.steps, 3),
-                        'value': round(world * a.batch * a.steps / dt, 1)}
-        a.steps = max(a.steps, int(math.ceil(MIN_WINDOW_S / (dt / a.steps))))
-        dt, per_rank, clk0, clk1, out, comm = window(a.steps)
     last_loss = float(out['log_vars']['loss'])
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, model, opt, out)      # before any later section runs another step
 
     res = None
     if rank == 0:
@@ -777,8 +792,7 @@ def main():
                        else f'training images/sec, YuNet_{a.kind} {a.size}x{a.size} bs={a.batch}/GPU') +
             (', bf16 fwd / fp32 grads' if a.dtype == 'bf16' else ''),
             'value': round(world * a.batch * a.steps / dt, 1), 'unit': 'images/sec',
-            'n_gpus': world, 'steps': a.steps, 'steps_requested': steps_requested, 'first_window': first_window,
-            'warmup': a.warmup,
+            'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup,
             'ms_per_step': round(1000.0 * dt / a.steps, 3), 'higher_is_better': True,
             'scaling': 'weak', 'vs_baseline': None, 'dtype': a.dtype,
             'data': 'synthetic' if not trained else 'synthetic (face patterns painted over noise at the GT boxes)',

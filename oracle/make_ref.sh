@@ -30,7 +30,15 @@ for leaf in ref_stub._LEAVES:
     n += 1
 for cfg in ('yunet_n.py', 'yunet_s.py'):
     shutil.copyfile(os.path.join(src, 'configs', cfg), os.path.join(dst, 'configs', cfg))
-print(f'oracle/_ref: {n} reference modules + 2 configs from {src}')
+# the further files the live comparisons under tests/ load: where oracle/_ref exists, ref_stub.available() is true and
+# those tests run against this copy, so it must hold all of them
+for rel in ('mmdet/core/bbox/transforms.py', 'mmdet/core/evaluation/bbox_overlaps.py',
+            'mmdet/datasets/pipelines/transforms.py', 'mmdet/datasets/samplers/group_sampler.py',
+            'tools/yunet2cpp.py', 'weights/yunet_n.pth', 'weights/yunet_s.pth'):
+    os.makedirs(os.path.dirname(os.path.join(dst, rel)), exist_ok=True)
+    shutil.copyfile(os.path.join(src, rel), os.path.join(dst, rel))
+    n += 1
+print(f'oracle/_ref: {n} reference files + 2 configs from {src}')
 PY
 rm -rf "$DST"
 mv "$TMP" "$DST"

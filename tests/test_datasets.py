@@ -12,6 +12,8 @@ import pytest
 
 REF = '/root/reference'
 LABELS = os.path.join(REF, 'data', 'widerface', 'labelv2', 'val', 'labelv2.txt')
+# the reference class's reading of the random label files below, stored by oracle/make_golden_live.py
+STORED = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'labelv2_reference.npz')
 
 
 def reference_class():
@@ -164,13 +166,10 @@ def test_dataset_min_side_filter_exif_and_decode_ahead(tmp_path):
         assert all(np.array_equal(x['img'], y['img']) for x, y in zip(sa, sb))
 
 
-@pytest.mark.skipif(not os.path.exists(LABELS), reason='reference tree not present')
-@pytest.mark.parametrize('seed', range(12))
-def test_random_label_files_match_reference(tmp_path, seed):
-    """Random labelv2 training files -- every row kind (15 landmark values with visible / occluded / missing (-1)
-    points, optional score, single ignore flag), tiny boxes against a random min_size, empty images, repeated image
-    headers -- parsed by this reader and by the UNMODIFIED reference class: same images, same arrays."""
-    import yunet_amd.datasets as DS
+def random_label_file(f, seed):
+    """A random labelv2 training file at path `f` -- every row kind (15 landmark values with visible / occluded /
+    missing (-1) points, optional score, single ignore flag), tiny boxes, empty images, repeated image headers; returns
+    the min_size to read it with."""
     rng = np.random.default_rng(100 + seed)
     lines, names = [], []
     for i in range(int(rng.integers(3, 25))):
@@ -194,15 +193,41 @@ def test_random_label_files_match_reference(tmp_path, seed):
             else:
                 row = box + ' ' + str(int(rng.integers(0, 2)))
             lines.append(row)
-    f = tmp_path / 'l.txt'
     f.write_text('\n'.join(lines) + '\n')
     min_size = None if rng.random() < 0.3 else int(rng.integers(2, 20))
-    mine = DS.load_labelv2(str(f), min_size=min_size)
+    return min_size
+
+
+def reference_label_results(f, seed, live=None):
+    """(filename, width, height) of every image and its get_ann_info arrays as the UNMODIFIED reference class reads
+    random_label_file(f, seed): live where its tree exists (or when live=True), otherwise read from
+    tests/golden/labelv2_reference.npz (oracle/make_golden_live.py)."""
+    min_size = random_label_file(f, seed)
+    if not (os.path.exists(LABELS) if live is None else live):
+        with np.load(STORED) as z:
+            got = {k.split('/', 1)[1]: z[k] for k in z.files if k.startswith(f'{seed}/')}
+        infos = [(str(n), int(w), int(h)) for n, (w, h) in zip(got.pop('filename'), got.pop('size'))]
+        anns = [{} for _ in infos]
+        for k, v in got.items():
+            i, key = k.split('/')
+            anns[int(i)][key] = v
+        return min_size, infos, anns
     ref = _ref_instance(str(f), min_size, False)
-    assert [(it['filename'], it['width'], it['height']) for it in mine] == \
-        [(it['filename'], it['width'], it['height']) for it in ref.data_infos]
+    return (min_size, [(it['filename'], it['width'], it['height']) for it in ref.data_infos],
+            [ref.get_ann_info(i) for i in range(len(ref.data_infos))])
+
+
+@pytest.mark.parametrize('seed', range(12))
+def test_random_label_files_match_reference(tmp_path, seed):
+    """Random labelv2 training files parsed by this reader and by the UNMODIFIED reference class: same images, same
+    arrays."""
+    import yunet_amd.datasets as DS
+    f = tmp_path / 'l.txt'
+    min_size, ref_infos, ref_anns = reference_label_results(f, seed)
+    mine = DS.load_labelv2(str(f), min_size=min_size)
+    assert [(it['filename'], it['width'], it['height']) for it in mine] == ref_infos
     for i in range(len(mine)):
-        x, y = DS.ann_info(mine[i]), ref.get_ann_info(i)
+        x, y = DS.ann_info(mine[i]), ref_anns[i]
         assert set(x) == set(y)
         for k in x:
             assert x[k].dtype == y[k].dtype and x[k].shape == y[k].shape and np.array_equal(x[k], y[k]), (i, k)

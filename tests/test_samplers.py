@@ -1,6 +1,7 @@
 """Epoch sample order: yunet_amd.samplers against orders produced by the UNMODIFIED reference samplers
-(tests/golden/group_sampler.npz, written by oracle/make_golden_sampler.py; re-checked live where /root/reference
-exists), the properties a distributed sampler must have, and RetinaFaceSource's use of it."""
+(tests/golden/group_sampler.npz, written by oracle/make_golden_sampler.py; more cases live where /root/reference
+exists, against their stored results elsewhere), the properties a distributed sampler must have, and
+RetinaFaceSource's use of it."""
 import os
 import sys
 
@@ -12,6 +13,8 @@ from yunet_amd import samplers as S
 HERE = os.path.dirname(os.path.abspath(__file__))
 G = np.load(os.path.join(HERE, 'golden', 'group_sampler.npz'))
 NCASES = len([k for k in G.files if k.endswith('_flag')])
+# the reference samplers' orders for live_cases(), stored by oracle/make_golden_live.py for machines without its tree
+LIVE_STORED = os.path.join(HERE, 'golden', 'group_sampler_live_reference.npz')
 
 
 class FlagOnly:
@@ -45,28 +48,48 @@ def test_orders_equal_the_reference_samplers(ci):
     assert len(g) == len(got) and np.array_equal(got, G[f'c{ci}_group'])
 
 
-def test_live_reference_when_present():
-    sys.path.insert(0, os.path.join(HERE, '..', 'oracle'))
-    import ref_stub
-    if not ref_stub.available():
-        pytest.skip('reference tree not present')
-    import make_golden_sampler as M
-    ref = M.reference_module()
+def live_cases():
+    """Six random (flag, samples_per_gpu, world, seed, epoch) settings beyond the committed fixture's."""
     rng = np.random.default_rng(5)
     for _ in range(6):
         n, spg, world = int(rng.integers(5, 300)), int(rng.choice([1, 3, 8, 16])), int(rng.choice([1, 2, 4, 8]))
         flag = (rng.random(n) < rng.random()).astype(np.uint8)
         seed, ep = int(rng.integers(0, 100)), int(rng.integers(0, 50))
+        yield flag, spg, world, seed, ep
+
+
+def reference_live_orders(live=None):
+    """Per live case, every rank's DistributedGroupSampler order and the GroupSampler order of the UNMODIFIED reference
+    samplers: live where the reference tree is present (or when live=True), otherwise read from LIVE_STORED."""
+    sys.path.insert(0, os.path.join(HERE, '..', 'oracle'))
+    import ref_stub
+    if not (ref_stub.available() if live is None else live):
+        with np.load(LIVE_STORED) as z:
+            return [([z[f'{c}/rank{r}'] for r in range(world)], z[f'{c}/group'])
+                    for c, (_, _, world, _, _) in enumerate(live_cases())]
+    import make_golden_sampler as M
+    ref = M.reference_module()
+    out = []
+    for flag, spg, world, seed, ep in live_cases():
+        ranks = []
         for r in range(world):
             a = ref.DistributedGroupSampler(FlagOnly(flag), spg, world, r, seed=seed)
-            b = S.DistributedGroupSampler(FlagOnly(flag), spg, world, r, seed=seed)
             a.set_epoch(ep)
+            ranks.append(np.array(list(iter(a)), np.int64))
+            assert len(a) == len(ranks[-1])
+        np.random.seed(seed)
+        out.append((ranks, np.array(list(iter(ref.GroupSampler(FlagOnly(flag), spg))), np.int64)))
+    return out
+
+
+def test_live_reference_when_present():
+    for (flag, spg, world, seed, ep), (ranks, group) in zip(live_cases(), reference_live_orders()):
+        for r in range(world):
+            b = S.DistributedGroupSampler(FlagOnly(flag), spg, world, r, seed=seed)
             b.set_epoch(ep)
-            assert list(iter(a)) == list(iter(b)) and len(a) == len(b)
+            assert list(iter(b)) == ranks[r].tolist() and len(b) == len(ranks[r])
         np.random.seed(seed)
-        x = list(iter(ref.GroupSampler(FlagOnly(flag), spg)))
-        np.random.seed(seed)
-        assert x == list(iter(S.GroupSampler(FlagOnly(flag), spg)))
+        assert group.tolist() == list(iter(S.GroupSampler(FlagOnly(flag), spg)))
 
 
 def test_retinaface_source_follows_the_distributed_group_sampler(tmp_path):

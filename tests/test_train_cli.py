@@ -66,21 +66,22 @@ def test_argument_surface_and_config_rules(tmp_path):
         T.parse_args([CFG, '--cfg-options', 'novalue'])
 
 
-def test_auto_scale_lr():
+def test_auto_scale_lr(tmp_path):
     from yunet_amd.runner import auto_scale_lr
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter('always')
         cfg = T.prepare_config(T.parse_args([CFG, '--auto-scale-lr']))            # the shipped config has no such section
         assert len(w) == 1 and auto_scale_lr(cfg, False, lambda *a: None) == 0.01
-    (open('/tmp/asl_cfg.py', 'w')).write(open(CFG).read() + '\nauto_scale_lr = dict(enable=False, base_batch_size=64)\n')
-    cfg = T.prepare_config(T.parse_args(['/tmp/asl_cfg.py']))
+    asl_cfg = str(tmp_path / 'asl_cfg.py')
+    (open(asl_cfg, 'w')).write(open(CFG).read() + '\nauto_scale_lr = dict(enable=False, base_batch_size=64)\n')
+    cfg = T.prepare_config(T.parse_args([asl_cfg]))
     assert auto_scale_lr(cfg, False, lambda *a: None) == 0.01                     # present but not enabled
-    cfg = T.prepare_config(T.parse_args(['/tmp/asl_cfg.py', '--auto-scale-lr', '--cfg-options', 'data.samples_per_gpu=16']))
+    cfg = T.prepare_config(T.parse_args([asl_cfg, '--auto-scale-lr', '--cfg-options', 'data.samples_per_gpu=16']))
     assert cfg.auto_scale_lr.enable is True
     msgs = []
     assert auto_scale_lr(cfg, False, msgs.append) == pytest.approx(0.01 * 16 / 64) and cfg.optimizer.lr == pytest.approx(0.0025)
     assert any('automatically scaled' in m for m in msgs)
-    cfg = T.prepare_config(T.parse_args(['/tmp/asl_cfg.py', '--auto-scale-lr', '--cfg-options', 'data.samples_per_gpu=64']))
+    cfg = T.prepare_config(T.parse_args([asl_cfg, '--auto-scale-lr', '--cfg-options', 'data.samples_per_gpu=64']))
     assert auto_scale_lr(cfg, False, lambda *a: None) == 0.01                     # batch == base: unchanged
 
 
