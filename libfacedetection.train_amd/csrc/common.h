@@ -56,6 +56,17 @@ __device__ __forceinline__ act_raw4 act_pack(const float4 v) {
     return act_raw4{__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
 #endif
 }
+// the value an activation store keeps: its RNE bf16 rounding in the bf16 build, the value itself in the fp32 build.  The
+// fused-pooling forwards pick each 2 x 2 winner among these, so that with bf16 storage two fp32 values that round to the
+// same stored value tie and the first window position takes them -- the rule of pool_fwd / pool_bwd on the stored tensor
+// (and of F.max_pool2d); comparing the fp32 values instead recorded the later element of such a tie.
+__device__ __forceinline__ float act_round(float v) {
+#ifdef YUNET_ACT_BF16
+    return __uint_as_float(pack_bf16x2(v, 0.0f) << 16);
+#else
+    return v;
+#endif
+}
 // Cache policy of the big streaming stores: bit 1 = "nt" (non-temporal) on gfx950.  Round 6, same-box alternations of bench.py
 // (profiles/r06_bench_ab_nt*.log): the dx stores of the BACKWARD units on the unpacked maps (>= 40 x 40: 105 MB - 1 GB per
 // tensor, nothing of it survives in a cache until its consumer runs) are better kept out of the 4 MB L2 of their XCD, where

@@ -559,7 +559,8 @@ __global__ __launch_bounds__(256) void dp_fwd_kernel(const YunetDP d, const Pack
                     } else {
                         // rows r-1 | r of this column, then the column to the right (lane + C4O); ties go to
                         // the smaller window position
-                        const float a[4] = {oprev.x, oprev.y, oprev.z, oprev.w}, b[4] = {o.x, o.y, o.z, o.w};
+                        const float a[4] = {act_round(oprev.x), act_round(oprev.y), act_round(oprev.z), act_round(oprev.w)},
+                                    b[4] = {act_round(o.x), act_round(o.y), act_round(o.z), act_round(o.w)};
                         float v[4];
                         unsigned jv = 0;
 #pragma unroll

@@ -197,7 +197,8 @@ void dp_fwd16s_kernel(const YunetDP d, const int R) {
                         // window (rows q - 1, q; pixels k, k + 1 with k even): pooled pixel (NSEG sg + k) / 2 of the strip
 #pragma unroll
                         for (int k = 0; k < NSEG; k += 2) {
-                            const float tl = zprev[k], tr = zprev[k + 1], bl = zdone[k], br = zdone[k + 1];
+                            const float tl = act_round(zprev[k]), tr = act_round(zprev[k + 1]),
+                                        bl = act_round(zdone[k]), br = act_round(zdone[k + 1]);
                             const bool lowl = bl * sgn > tl * sgn, lowr = br * sgn > tr * sgn;
                             const float vl = lowl ? bl : tl, vr = lowr ? br : tr;
                             const unsigned jl = lowl ? 2u : 0u, jr = lowr ? 3u : 1u;

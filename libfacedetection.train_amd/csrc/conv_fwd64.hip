@@ -225,10 +225,14 @@ __device__ __forceinline__ void dp_fwd64s_body(const YunetDP& d, const int R, co
                     const unsigned prow = (unsigned)((yy >> 1) * (W >> 1) * C);
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
-                        const float tl[4] = {prev[2 * q].x, prev[2 * q].y, prev[2 * q].z, prev[2 * q].w};
-                        const float bl[4] = {dn[2 * q].x, dn[2 * q].y, dn[2 * q].z, dn[2 * q].w};
-                        const float tr[4] = {prev[2 * q + 1].x, prev[2 * q + 1].y, prev[2 * q + 1].z, prev[2 * q + 1].w};
-                        const float br[4] = {dn[2 * q + 1].x, dn[2 * q + 1].y, dn[2 * q + 1].z, dn[2 * q + 1].w};
+                        const float tl[4] = {act_round(prev[2 * q].x), act_round(prev[2 * q].y), act_round(prev[2 * q].z),
+                                             act_round(prev[2 * q].w)};
+                        const float bl[4] = {act_round(dn[2 * q].x), act_round(dn[2 * q].y), act_round(dn[2 * q].z),
+                                             act_round(dn[2 * q].w)};
+                        const float tr[4] = {act_round(prev[2 * q + 1].x), act_round(prev[2 * q + 1].y),
+                                             act_round(prev[2 * q + 1].z), act_round(prev[2 * q + 1].w)};
+                        const float br[4] = {act_round(dn[2 * q + 1].x), act_round(dn[2 * q + 1].y),
+                                             act_round(dn[2 * q + 1].z), act_round(dn[2 * q + 1].w)};
                         float v[4];
                         unsigned jw = 0;
 #pragma unroll

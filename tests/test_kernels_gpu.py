@@ -71,9 +71,14 @@ SHAPES = [(2, 10, 10), (3, 20, 40), (1, 24, 16), (2, 5, 5),
 #   CU (round 3): 1000 tiles > the 512-workgroup grid, the one-float-per-thread remainder of its halo.
 #   (3, 40, 72), (5, 50, 70): big-tile class with ragged strips / bands of the wave-streaming 16 -> 16 backward
 #   (conv_bwd16.hip: 28-column strips -> 28 + 28 + 16 and 28 + 28 + 14 columns; band heights that do not divide H)
+#   (40, 80, 80) for (16, 32) / (32, 32) / (32, 64): the 80 x 80 units of YuNet_s -- dp_bwd<16|32,32,8,16,..,FULL>, the split-bf16
+#   dp_bwd<32,64,8,16,false,1,..,FULL> (option bwd32_split) walking 2000 tiles, and the matching forward tiles
 BIG_SHAPES = {(16, 16): [(2, 64, 96), (1, 160, 160), (9, 96, 128), (3, 40, 72), (5, 50, 70)],
               (64, 64): [(40, 80, 80), (70, 20, 20), (40, 40, 40)],
               (16, 64): [(40, 80, 80)],
+              (16, 32): [(40, 80, 80)],
+              (32, 32): [(40, 80, 80)],
+              (32, 64): [(40, 80, 80)],
               (64, 16): [(40, 80, 80), (70, 20, 20)]}
 
 
@@ -130,8 +135,10 @@ def exact_fp32_backward():
 def test_dp_bwd_exact_fp32mma(mode, exact_fp32_backward):
     """test_dp_bwd[64-64-*] with bwd_fp32mma = 1: dp_bwd_kernel<64,64,8,16,PACKED,GEMM=0> on the plain 80 x 80 /
     40 x 40 maps and the packed 20 x 20 canvas (BIG_SHAPES walks > 256 tiles per workgroup grid).  Same fp64 yardstick;
-    the bar is the forward kernels' 2e-5 (the split-bf16 default gets 5e-5)."""
+    the bar is the forward kernels' 2e-5 (the split-bf16 default gets 5e-5).  The 32 -> 64 unit of YuNet_s at its
+    80 x 80 walk shape too: with the option it leaves the split-bf16 GEMM = 1 instance for dp_bwd_kernel<32,64,..,GEMM=0>."""
     _dp_bwd_case(64, 64, mode, tol=2e-5)
+    _dp_bwd_case(32, 64, mode, tol=2e-5, shapes=[(40, 80, 80)])
 
 
 def test_fused_pooling_exact_fp32mma(exact_fp32_backward):
@@ -147,12 +154,16 @@ def test_dp_bwd(cin, cout, mode):
     _dp_bwd_case(cin, cout, mode, tol=5e-5)
 
 
-def _dp_bwd_case(cin, cout, mode, tol):
+def _dp_bwd_case(cin, cout, mode, tol, shapes=None):
     k = K()
     g = torch.Generator().manual_seed(7 + cin * 100 + cout)
     in_bn_on = mode.startswith('bn')
     out_bn_on = mode.endswith('_bn')
-    for (n, h, w) in shapes_for(cin, cout):
+    for (n, h, w) in shapes or shapes_for(cin, cout):
+        tiles = n * ((w + 15) // 16) * ((h + 7) // 8)
+        if (n, h, w) in BIG_SHAPES.get((cin, cout), []) and (cin, cout) in ((16, 32), (32, 32), (32, 64)):
+            assert tiles > k.dp_grid(n, h, w, cin, cout), ('walk shape does not walk', n, h, w)
+            assert tiles > 4 * torch.cuda.get_device_properties(0).multi_processor_count    # forward grid too
         x = (torch.randn(n, cin, h, w, generator=g) * 2 + 0.5).double()
         w_pw, b_pw, w_dw, b_dw = [t.double().requires_grad_(True) for t in mk_unit(cin, cout, g)]
         gi, bi = (torch.rand(cin, generator=g) + 0.5).double(), (torch.randn(cin, generator=g) * .2).double()
@@ -301,15 +312,23 @@ def test_pool_fwd_bwd(c):
 
 
 @pytest.mark.parametrize('ci,c,n,h,w', [(16, 16, 2, 64, 96), (16, 16, 1, 160, 160), (64, 64, 3, 40, 48),
-                                        (64, 64, 20, 80, 80), (32, 64, 3, 40, 48), (64, 64, 12, 40, 40)])
+                                        (64, 64, 20, 80, 80), (32, 64, 3, 40, 48), (64, 64, 12, 40, 40),
+                                        (32, 64, 40, 80, 80), (16, 16, 44, 160, 160)])
 def test_fused_pooling(ci, c, n, h, w):
     """unit P -> BN -> ReLU -> max_pool2d(2) -> unit Q without a pooling kernel and without a full-size
     gradient of P's output: P's forward also writes the raw window winners + their positions (some gammas are
     negative or zero: minimum / first element), Q reads them through the BN+ReLU input transform of P's
     BatchNorm, Q's backward writes the masked pooled gradient and the BN-backward sums, P's backward
     (pool_idx) expands it while staging.  Against fp64 autograd through the same graph.
-    (20, 80, 80) walks the prefetch path of both kernels."""
+    (20, 80, 80) walks the prefetch path of both kernels; (32, 64, 40, 80, 80) is YuNet_s's unit in front of its 80 x 80
+    pool (tile forward and the split-bf16 pooled backward walking the grid); (16, 16, 44, 160, 160) gives the
+    wave-streaming 16 -> 16 kernels more 28-column strips than the backward grid has workgroups."""
     k = K()
+    if (ci, c, n) == (32, 64, 40):
+        tiles = n * (w // 16) * (h // 8)
+        assert tiles > k.dp_grid(n, h, w, ci, c) and tiles > 4 * torch.cuda.get_device_properties(0).multi_processor_count
+    if (ci, c, n) == (16, 16, 44):
+        assert n * ((w + 27) // 28) > k.dp_grid(n, h, w, ci, c)
     g = torch.Generator().manual_seed(c + h + ci)
     x = (torch.randn(n, ci, h, w, generator=g) * 1.5 + 0.3).double().requires_grad_(True)
     P = [t.double().requires_grad_(True) for t in mk_unit(ci, c, g)]
