@@ -437,6 +437,32 @@ int yunet_aug_decide(const int32_t* src_hw, const float* boxes, const float* kps
  * (src + src_off[n], BGR as loaded) to planar fp32 [N,3,S,S]; `params` from yunet_aug_decide. */
 int yunet_aug_pixels(const uint8_t* src, const long long* src_off, const int32_t* src_hw,
                      const int32_t* params, const YunetAugCfg* cfg, int N, float* out_img, void* stream);
+/* yunet_aug_pixels on a compact window buffer: image n is the source rectangle rect[n] = (row0, col0, rows, cols)
+ * stored at win + win_off[n] with row pitch cols * 3 (yunet_aug_window_plan, yunet_upload_windows); src_hw are the
+ * FULL source sizes.  Same float operations as yunet_aug_pixels: bit-identical output for the plan of `params`. */
+int yunet_aug_pixels_window(const uint8_t* win, const long long* win_off, const int32_t* rect, const int32_t* src_hw,
+                            const int32_t* params, const YunetAugCfg* cfg, int N, float* out_img, void* stream);
+
+/* Decoded-source store (pipelines.SourceStore).  One launch builds a batch's SourceBatch tables from the store's
+ * per-image tables (M images: byte offset, (h, w), first GT row, GT count; boxes [*,4], kps [*,5,3]) and a device
+ * index vector idx [N] (repeats allowed, 1 <= N <= 8192): src_off [N], src_hw [N,2], gt_off [N+1] (exclusive scan of
+ * the picked counts), boxes [G,4] / kps [G,5,3] packed in order; rows at or beyond g_cap are not written.  An index
+ * outside [0, M) picks an empty image. */
+int yunet_aug_gather(const int32_t* idx, int N, int M, const long long* store_off, const int32_t* store_hw,
+                     const int32_t* store_goff, const int32_t* store_gcnt, const float* store_boxes,
+                     const float* store_kps, int g_cap, long long* src_off, int32_t* src_hw, int32_t* gt_off,
+                     float* boxes, float* kps, void* stream);
+/* From yunet_aug_decide's params [N,8] and src_hw [N,2]: rect [N,4] int32 = (row0, col0, rows, cols), the source
+ * pixels yunet_aug_pixels can read -- rows [max(top,0), min(top+cw,h)), cols [max(left,0), min(left+cw,w)), all zero
+ * when cw == 0 or the window misses the image -- and win_off [N+1] int64, the exclusive scan of rows * cols * 3
+ * (win_off[N] = bytes of the compact window buffer).  One workgroup. */
+int yunet_aug_window_plan(const int32_t* params, const int32_t* src_hw, int N, int32_t* rect, long long* win_off,
+                          void* stream);
+/* Host code: one hipMemcpy2DAsync per non-empty rectangle, from image n of a pinned host store (host_src + src_off[n],
+ * uint8 HWC, src_hw[n]) to win + win_off[n] on `stream`.  src_off, src_hw, rect, win_off are HOST arrays (the plan
+ * copied back); the plan is checked against the image sizes and win_bytes before the first copy (YUNET_EINVAL). */
+int yunet_upload_windows(const uint8_t* host_src, const long long* src_off, const int32_t* src_hw, const int32_t* rect,
+                         const long long* win_off, int N, uint8_t* win, long long win_bytes, void* stream);
 
 /* Measurement switches of the dispatchers (ABI 6).  The library reads the environment ONCE, the first time an
  * option is needed (YUNET_NO_PACK, YUNET_BWD_FP32MMA, YUNET_BWD64_NW, YUNET_EW_GRID, YUNET_DP_FWD_BLOCKS_PER_CU);

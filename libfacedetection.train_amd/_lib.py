@@ -117,6 +117,12 @@ _SIGNATURES = {
     'yunet_aug_decide': (C.c_int, [C.c_void_p] * 4 + [C.POINTER(YunetAugCfg), C.c_uint32, C.c_int] +
                          [C.c_void_p] * 5),
     'yunet_aug_pixels': (C.c_int, [C.c_void_p] * 4 + [C.POINTER(YunetAugCfg), C.c_int, C.c_void_p, C.c_void_p]),
+    'yunet_aug_pixels_window': (C.c_int, [C.c_void_p] * 5 + [C.POINTER(YunetAugCfg), C.c_int, C.c_void_p,
+                                                             C.c_void_p]),
+    'yunet_aug_gather': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int] +
+                         [C.c_void_p] * 6),
+    'yunet_aug_window_plan': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'yunet_upload_windows': (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
     'yunet_reduce_partials': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                         C.c_void_p]),
     'yunet_assign': (C.c_int, [C.c_void_p] * 5 + [C.POINTER(YunetLevels)] + [C.c_int] * 3 +

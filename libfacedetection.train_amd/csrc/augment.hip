@@ -150,13 +150,21 @@ __device__ __forceinline__ void lin_coef(int d, int dst, int src, int& s0, int& 
     w1 = f;
 }
 
+// WIN = false: image n is src + src_off[n], row pitch w (the resident / whole-upload layout).
+// WIN = true : image n is the rectangle rect[n] = (row0, col0, rows, cols) of the source, stored compactly at
+//   src + src_off[n] with row pitch cols (yunet_aug_window_plan; the host-store upload).  The float operations are
+//   those of WIN = false, so the output is bit-identical; the extra rectangle test only ever fails when the plan
+//   does not belong to these params, and then it reads pad instead of leaving the window buffer.
+template <bool WIN>
 __global__ __launch_bounds__(256) void aug_pixels_kernel(
     const uint8_t* __restrict__ src, const long long* __restrict__ src_off, const int32_t* __restrict__ src_hw,
-    const int32_t* __restrict__ params, int S, float pad, float* __restrict__ out) {
+    const int32_t* __restrict__ rect, const int32_t* __restrict__ params, int S, float pad, float* __restrict__ out) {
     const int n = blockIdx.y;
     const int32_t* p = params + 8 * n;
     const int left = p[AUG_P_LEFT], top = p[AUG_P_TOP], cw = p[AUG_P_CW], flip = p[AUG_P_FLIP];
     const int h = src_hw[2 * n], w = src_hw[2 * n + 1];
+    const int ry = WIN ? rect[4 * n + 0] : 0, rx = WIN ? rect[4 * n + 1] : 0;
+    const int rh = WIN ? rect[4 * n + 2] : h, rw = WIN ? rect[4 * n + 3] : w;
     const uint8_t* im = src + src_off[n];
     float* o = out + (size_t)n * 3 * S * S;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < S * S; i += gridDim.x * 256) {
@@ -169,10 +177,14 @@ __global__ __launch_bounds__(256) void aug_pixels_kernel(
             lin_coef(dxs, S, cw, sx0, sx1, a0, a1);
             lin_coef(dy, S, cw, sy0, sy1, b0, b1);
             const int X0 = left + sx0, X1 = left + sx1, Y0 = top + sy0, Y1 = top + sy1;
-            const bool x0in = X0 >= 0 && X0 < w, x1in = X1 >= 0 && X1 < w;
-            const bool y0in = Y0 >= 0 && Y0 < h, y1in = Y1 >= 0 && Y1 < h;
-            const uint8_t* r0 = im + ((size_t)Y0 * w) * 3;
-            const uint8_t* r1 = im + ((size_t)Y1 * w) * 3;
+            bool x0in = X0 >= 0 && X0 < w, x1in = X1 >= 0 && X1 < w;
+            bool y0in = Y0 >= 0 && Y0 < h, y1in = Y1 >= 0 && Y1 < h;
+            if (WIN) {
+                x0in = x0in && X0 >= rx && X0 < rx + rw; x1in = x1in && X1 >= rx && X1 < rx + rw;
+                y0in = y0in && Y0 >= ry && Y0 < ry + rh; y1in = y1in && Y1 >= ry && Y1 < ry + rh;
+            }
+            const uint8_t* r0 = im + ((size_t)(Y0 - ry) * rw) * 3 - (size_t)rx * 3;
+            const uint8_t* r1 = im + ((size_t)(Y1 - ry) * rw) * 3 - (size_t)rx * 3;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float v00 = (y0in && x0in) ? (float)r0[3 * X0 + c] : pad;
@@ -211,7 +223,19 @@ extern "C" int yunet_aug_pixels(const uint8_t* src, const long long* src_off, co
     const int S = cfg->out_size;
     int bx = (S * S + 255) / 256;
     if (bx > 64) bx = 64;                       // grid-stride over the pixels of one image
-    hipLaunchKernelGGL(aug_pixels_kernel, dim3(bx, N), dim3(256), 0, (hipStream_t)stream, src, src_off,
-                       src_hw, params, S, cfg->pad_value, out_img);
+    hipLaunchKernelGGL(aug_pixels_kernel<false>, dim3(bx, N), dim3(256), 0, (hipStream_t)stream, src, src_off,
+                       src_hw, nullptr, params, S, cfg->pad_value, out_img);
+    return hip_status();
+}
+
+extern "C" int yunet_aug_pixels_window(const uint8_t* win, const long long* win_off, const int32_t* rect,
+                                       const int32_t* src_hw, const int32_t* params, const YunetAugCfg* cfg, int N,
+                                       float* out_img, void* stream) {
+    if (!cfg || N < 1 || cfg->out_size < 1) return YUNET_EINVAL;
+    const int S = cfg->out_size;
+    int bx = (S * S + 255) / 256;
+    if (bx > 64) bx = 64;
+    hipLaunchKernelGGL(aug_pixels_kernel<true>, dim3(bx, N), dim3(256), 0, (hipStream_t)stream, win, win_off,
+                       src_hw, rect, params, S, cfg->pad_value, out_img);
     return hip_status();
 }

@@ -164,10 +164,21 @@ class RetinaFaceSource:
     reference's DistributedGroupSampler(dataset, samples_per_gpu, world, r, seed) in epoch it // iters_per_epoch
     (samplers.py; the order `tools/dist_train.sh` feeds, also used at world size 1, where the reference's
     GroupSampler draws from numpy's global generator and is not reproducible).  Samples are decoded with PIL on
-    the host and augmented on the GPU by the config's own pipeline (pipelines.DevicePipeline)."""
+    the host and augmented on the GPU by the config's own pipeline (pipelines.DevicePipeline).
 
-    def __init__(self, dataset, pipeline, samples_per_gpu=16, rank=0, world=1, seed=0, max_gt=64, workers=4):
+    cache=None    : every use of a sample decodes it again (PIL) and uploads the whole decoded image.
+    cache='device': each sample is decoded the first time the sampler yields it and kept in a device SourceStore
+                    (source_store.py; decoded WIDER-Face train is ~30 GB of HBM); a batch is a gather of store indices.
+    cache='host'  : the same in a PINNED host SourceStore (that many bytes of pinned RAM per rank); per batch only the
+                    crop-window rectangles travel (WindowFeed).
+    All three give bit-identical batches; the image sizes of the labelv2 headers must be the decoded ones."""
+
+    def __init__(self, dataset, pipeline, samples_per_gpu=16, rank=0, world=1, seed=0, max_gt=64, workers=4,
+                 cache=None):
         from .pipelines import DevicePipeline
+        if cache not in (None, 'device', 'host'):
+            raise ValueError(f"RetinaFaceSource cache must be None, 'device' or 'host', got {cache!r}")
+        self.cache, self.store, self._feed, self._decoding = cache, None, None, {}
         self.ds, self.bs, self.rank, self.world, self.seed = dataset, samples_per_gpu, rank, world, seed
         self.pipe = DevicePipeline(pipeline, seed=seed + 7919 * rank, gmax=64 if max_gt <= 64 else 128)
         from .samplers import DistributedGroupSampler
@@ -203,9 +214,57 @@ class RetinaFaceSource:
             del self._ahead[k]
         return [f.result() for f in futs]
 
+    def _fill(self, it):
+        """Decode the images of iteration it that the store lacks (and queue those of it + 1), store them; -> indices."""
+        idx = self._indices(it)
+        ahead = self._indices(it + 1) if self.workers else []
+        if self.workers and self._pool is None:
+            from concurrent.futures import ThreadPoolExecutor
+            self._pool = ThreadPoolExecutor(self.workers)
+        for i in list(dict.fromkeys(idx)) + [i for i in ahead if i not in idx]:
+            if not self.store.has(i) and i not in self._decoding and self.workers:
+                self._decoding[i] = self._pool.submit(self.ds.load_image, i)
+        for i in dict.fromkeys(idx):
+            if not self.store.has(i):
+                fut = self._decoding.pop(i, None)
+                img = fut.result() if fut is not None else self.ds.load_image(i)
+                ann = self.ds.get_ann_info(i)
+                self.store.put(i, img, ann['bboxes'], ann['keypointss'])
+        return idx
+
+    def _cached_batch(self, it, device):
+        from .source_store import SourceStore, WindowFeed
+        if self.store is None:
+            sizes = [(info['height'], info['width']) for info in self.ds.data_infos]
+            self.store = SourceStore(sizes, placement=self.cache, device=device)
+        idx = self._fill(it)
+        if self.cache == 'device':
+            return self.pipe(self.store.batch(idx), it)
+        f = self._feed
+        if f is None:       # two window buffers, each the bs largest images (a window never exceeds its image)
+            big = int(np.sort(self.store.image_bytes)[::-1][:self.bs].sum())
+            f = self._feed = WindowFeed(self.pipe, self.store, big)
+        if not f.uploaded(it):
+            if not f.planned(it):
+                f.plan(it, idx)
+            f.upload(it)
+        out, _ = f.run(it)
+        # once every image of the next iterations is stored (from the second epoch on): the upload of it + 1 travels
+        # under this step, and the plan of it + 2 is made now so that batch(it + 1) finds it done
+        nxt, nxt2 = self._indices(it + 1), self._indices(it + 2)
+        if all(self.store.has(i) for i in nxt) and not f.uploaded(it + 1):
+            if not f.planned(it + 1):
+                f.plan(it + 1, nxt)
+            f.upload(it + 1)
+        if all(self.store.has(i) for i in nxt2) and not f.planned(it + 2):
+            f.plan(it + 2, nxt2)
+        return out
+
     def batch(self, it, device=None):
         if device is None:
             raise RuntimeError('RetinaFaceSource augments on the GPU: a device is required')
+        if self.cache is not None:
+            return self._cached_batch(it, device)
         from .pipelines import SourceBatch
         samples = self._decoded(it)
         src = SourceBatch.from_lists([s['img'] for s in samples], [s['gt_bboxes'] for s in samples],

@@ -189,6 +189,17 @@ class DevicePipeline:
         if dev.type != 'cuda':
             raise RuntimeError('DevicePipeline needs device-resident sources: HIP kernels only, no CPU fallback')
         img = torch.empty(n, 3, S, S, device=dev, dtype=torch.float32)
+        gb, gk, cnt, params = self._decide(src, iteration, dev)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+        L.check(lib.yunet_aug_pixels(p(src.src), p(src.src_off), p(src.src_hw), p(params), C.byref(self.cfg), n,
+                                     p(img), stream), 'yunet_aug_pixels')
+        return self._collate(img, gb, gk, cnt, params, dev)
+
+    def _decide(self, src, iteration, dev):
+        """yunet_aug_decide on the current stream -> (padded boxes, padded keypoints, counts, params)."""
+        lib = L.load()
+        n = src.n
         gb = torch.empty(n, self.gmax, 4, device=dev, dtype=torch.float32)
         gk = torch.empty(n, self.gmax, 5, 3, device=dev, dtype=torch.float32)
         cnt = torch.empty(n, device=dev, dtype=torch.int32)
@@ -198,8 +209,10 @@ class DevicePipeline:
         L.check(lib.yunet_aug_decide(p(src.src_hw), p(src.boxes), p(src.kps), p(src.gt_off), C.byref(self.cfg),
                                      int(iteration) & 0xFFFFFFFF, n, p(params), p(gb), p(gk), p(cnt), stream),
                 'yunet_aug_decide')
-        L.check(lib.yunet_aug_pixels(p(src.src), p(src.src_off), p(src.src_hw), p(params), C.byref(self.cfg), n,
-                                     p(img), stream), 'yunet_aug_pixels')
+        return gb, gk, cnt, params
+
+    def _collate(self, img, gb, gk, cnt, params, dev):
+        n, S = img.shape[0], self.out_size
         self.params = params
         boxes, kps = DeviceGT(list(gb)), DeviceGT(list(gk))
         boxes.padded, boxes.counts = gb, cnt
@@ -207,6 +220,37 @@ class DevicePipeline:
         labels = GTList([torch.zeros(self.gmax, dtype=torch.int64, device=dev)] * n)
         metas = [dict(img_shape=(S, S, 3), pad_shape=(S, S, 3), batch_input_shape=(S, S)) for _ in range(n)]
         return dict(img=img, img_metas=metas, gt_bboxes=boxes, gt_labels=labels, gt_keypointss=kps)
+
+    def window_plan(self, src, iteration, dev):
+        """The source rectangles this pipeline's pixel pass will read at `iteration` (aug_decide is keyed by
+        (seed, iteration, image), so this can run ahead of the iteration): -> (params [N,8], rect [N,4] int32
+        (row0, col0, rows, cols), win_off [N+1] int64 byte offsets of a compact window buffer, win_off[N] = total).
+        Runs on the current stream; `src` needs only src_hw / boxes / kps / gt_off on the device."""
+        lib = L.load()
+        _, _, _, params = self._decide(src, iteration, dev)
+        rect = torch.empty(src.n, 4, device=dev, dtype=torch.int32)
+        off = torch.empty(src.n + 1, device=dev, dtype=torch.int64)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+        L.check(lib.yunet_aug_window_plan(p(params), p(src.src_hw), src.n, p(rect), p(off), stream),
+                'yunet_aug_window_plan')
+        return params, rect, off
+
+    def windowed(self, src, iteration, win, rect, win_off):
+        """The pipeline on a compact window buffer `win` (uint8, device) holding, at win_off[n], the rectangle
+        rect[n] of image n (window_plan of the same iteration): bit-identical to __call__ on the full sources."""
+        lib = L.load()
+        dev = win.device
+        if dev.type != 'cuda':
+            raise RuntimeError('DevicePipeline needs a device-resident window buffer: HIP kernels only')
+        n, S = src.n, self.out_size
+        img = torch.empty(n, 3, S, S, device=dev, dtype=torch.float32)
+        gb, gk, cnt, params = self._decide(src, iteration, dev)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+        L.check(lib.yunet_aug_pixels_window(p(win), p(win_off), p(rect), p(src.src_hw), p(params), C.byref(self.cfg),
+                                            n, p(img), stream), 'yunet_aug_pixels_window')
+        return self._collate(img, gb, gk, cnt, params, dev)
 
     def check(self):
         """Synchronising status check of the last batch: raises like the reference would misbehave

@@ -131,8 +131,11 @@ class SyntheticSourceImages:
     fits 288 GB many times over), an iteration costs the two pipeline launches.
     host_fed=True : the sources live in PINNED HOST memory and every iteration's batch is uploaded on a copy stream into
     one of two device buffers while the previous step runs (what a host data loader has to pay: the decoded uint8
-    source of an image is 1 - 2.4 MB, more than its 320 x 320 fp32 crop).  `timing=True` records events around the
-    upload and the pipeline (`report()`)."""
+    source of an image is 1 - 2.4 MB, more than its 320 x 320 fp32 crop).
+    host_fed='window': the same pinned sources as a host SourceStore; per batch only the rectangle of each image that
+    the crop can read travels (source_store.WindowFeed: plans made two iterations ahead, 2D copies on a copy stream,
+    the pixel pass on the window buffer) -- outputs bit-identical to the other modes.
+    `timing=True` records events around the upload and the pipeline (`report()`)."""
 
     def __init__(self, pipeline, samples_per_gpu=16, iters_per_epoch=403, rank=0, pool=64,
                  src_hw=((768, 1024), (1024, 683), (500, 375), (683, 1024)), max_gt=synthetic.MAX_GT,
@@ -141,13 +144,14 @@ class SyntheticSourceImages:
         self.pipe = DevicePipeline(pipeline, seed=seed + 7919 * rank, gmax=64 if max_gt <= 64 else 128)
         self.bs, self.iters_per_epoch, self.rank = samples_per_gpu, iters_per_epoch, rank
         self.pool, self.src_hw, self.max_gt, self.seed = pool, src_hw, max_gt, seed
-        self.host_fed, self.timing = bool(host_fed), bool(timing)
+        if host_fed not in (False, True, 'window'):
+            raise ValueError(f"host_fed must be False, True or 'window', got {host_fed!r}")
+        self.host_fed, self.timing = (host_fed if host_fed == 'window' else bool(host_fed)), bool(timing)
         self._src = None
         self._ev = []
 
-    def _build(self, device):
+    def _pool_sources(self):
         import numpy as np
-        from .pipelines import SourceBatch
         rng = np.random.default_rng(self.seed + 1000 * self.rank)
         gen = torch.Generator().manual_seed(self.seed + 1000 * self.rank)
         imgs, boxes, kps = [], [], []
@@ -157,7 +161,11 @@ class SyntheticSourceImages:
             b, _, k = synthetic.make_gt(1, h, w, gen, self.max_gt)
             boxes.append(b[0])
             kps.append(k[0])
-        idx = [i % self.pool for i in range(self.bs)]
+        return imgs, boxes, kps, [i % self.pool for i in range(self.bs)]
+
+    def _build(self, device):
+        from .pipelines import SourceBatch
+        imgs, boxes, kps, idx = self._pool_sources()
         return SourceBatch.from_lists([imgs[i] for i in idx], [boxes[i] for i in idx],
                                       [kps[i] for i in idx], 'cpu' if self.host_fed else device)
 
@@ -173,6 +181,40 @@ class SyntheticSourceImages:
         self._uploaded = [None, None]          # event: buffer b holds iteration's sources
         self._consumed = [None, None]          # event: the pipeline that read buffer b has run
         self._pending = {}
+
+    def _build_window(self, device):
+        """The pool as a pinned host SourceStore (batch = store indices, with repeats when bs > pool) + a WindowFeed whose
+        two window buffers hold a whole batch (a window never exceeds its image)."""
+        from .source_store import SourceStore, WindowFeed
+        imgs, boxes, kps, idx = self._pool_sources()
+        store = SourceStore([im.shape[:2] for im in imgs], placement='host', device=device)
+        for i, im in enumerate(imgs):
+            store.put(i, im, boxes[i], kps[i])
+        self._idx = idx
+        self._batch_bytes = int(store.image_bytes[idx].sum())
+        self._feed = WindowFeed(self.pipe, store, self._batch_bytes, timing=self.timing)
+
+    def _window_batch(self, it, device):
+        if self._src is None:
+            self._src = True
+            self._build_window(device)
+        f = self._feed
+        for k in (it, it + 1):              # start-up / a caller that jumps: plans before the first upload waits
+            if not f.planned(k) and not f.uploaded(k):
+                f.plan(k, self._idx)
+        if not f.uploaded(it):
+            f.upload(it)
+        cur = torch.cuda.current_stream()
+        p0 = self._mark(cur)
+        out, h2d = f.run(it)
+        if self.timing:
+            done = self._mark(cur)
+            self._ev.append((h2d, (p0, done)))
+        if not f.uploaded(it + 1):
+            f.upload(it + 1)                # the next batch's windows travel while this step runs
+        if not f.planned(it + 2):
+            f.plan(it + 2, self._idx)       # its plan is done long before batch(it + 1) waits for it
+        return out
 
     def _upload(self, it):
         b = it % 2
@@ -190,6 +232,8 @@ class SyntheticSourceImages:
     def batch(self, it, device=None):
         if device is None:
             raise RuntimeError('SyntheticSourceImages augments on the GPU: a device is required')
+        if self.host_fed == 'window':
+            return self._window_batch(it, device)
         cur = torch.cuda.current_stream()
         if not self.host_fed:
             if self._src is None:
@@ -233,11 +277,16 @@ class SyntheticSourceImages:
         torch.cuda.synchronize()
         ev = self._ev[skip:]
         out = {'batches_timed': len(ev)}
-        h = [a.elapsed_time(b) for (hd, _) in ev if hd is not None for a, b in [hd]]
+        h = [hd[0].elapsed_time(hd[1]) for (hd, _) in ev if hd is not None]
         p = [a.elapsed_time(b) for (_, (a, b)) in ev if a is not None]
         if h:
             out['h2d_ms'] = sum(h) / len(h)
-            out['h2d_bytes'] = int(self._host_src.numel())
+            if self.host_fed == 'window':         # mean bytes actually copied per batch, next to the whole sources
+                nb = [hd[2] for (hd, _) in ev]
+                out['h2d_bytes'] = sum(nb) / len(nb)
+                out['src_bytes'] = self._batch_bytes
+            else:
+                out['h2d_bytes'] = int(self._host_src.numel())
             out['h2d_GBs'] = out['h2d_bytes'] / (out['h2d_ms'] * 1e-3) / 1e9
         if p:
             out['pipeline_ms'] = sum(p) / len(p)

@@ -106,9 +106,12 @@ def build_source(cfg, rank, world, seed):
         return R.SyntheticSourceImages(samples_per_gpu=cfg.data.samples_per_gpu, rank=rank, seed=seed, **kw)
     if dcfg.get('type') == 'RetinaFaceDataset':          # labelv2 annotations + image files (PIL decode)
         from yunet_amd.datasets import RetinaFaceSource
+        cache = dcfg.get('cache')                        # data.train.cache=device|host: decode once (SourceStore)
+        if cache not in (None, 'device', 'host'):
+            raise ValueError(f"data.train.cache must be device or host (or unset), got {cache!r}")
         dataset = yunet_amd.build_dataset(dcfg)
         return RetinaFaceSource(dataset, dcfg['pipeline'], samples_per_gpu=cfg.data.samples_per_gpu, rank=rank,
-                                world=world, seed=seed)
+                                world=world, seed=seed, cache=cache)
     raise SystemExit('data sources: RetinaFaceDataset (labelv2 + image files, augmented on the GPU), '
                      'SyntheticWiderFace (ready batches) or SyntheticSourceImages (decoded synthetic '
                      'sources + the reference train pipeline on the GPU)')

@@ -8,6 +8,8 @@ configs/yunet_n.py (YuNet_n 320 x 320, 256 images per GPU) from three data sourc
                                     Resize -> RandomFlip -> Normalize -> collate) on the GPU every iteration
   host_fed  SyntheticSourceImages   the same sources in PINNED HOST memory, each batch uploaded on a copy stream into one of
             (host_fed=True)         two device buffers while the previous step runs
+  host_window SyntheticSourceImages   the same pinned sources as a host SourceStore: per batch only each image's crop-window
+            (host_fed='window')     rectangle travels (2D copies on a copy stream, planned two iterations ahead)
 
     python tools/train_e2e.py [--iters 200] [--out profiles/r06_train_e2e.json]
 
@@ -37,13 +39,18 @@ def main():
     ap.add_argument('--iters', type=int, default=200)
     ap.add_argument('--config', default=os.path.join(ROOT, 'configs', 'yunet_n.py'))
     ap.add_argument('--out', default=None)
+    ap.add_argument('--modes', default=None, help='comma-separated subset of ready,resident,host_fed,host_window')
     a = ap.parse_args()
     import torch
     T = load_train_tool()
     fixture = os.path.join(ROOT, 'tests', 'golden', 'yunet_n_synth_trained.pth')
     modes = [('ready', ['data.train.type=SyntheticWiderFace', 'data.train.resident=2']),
              ('resident', ['data.train.type=SyntheticSourceImages', 'data.train.timing=True']),
-             ('host_fed', ['data.train.type=SyntheticSourceImages', 'data.train.timing=True', 'data.train.host_fed=True'])]
+             ('host_fed', ['data.train.type=SyntheticSourceImages', 'data.train.timing=True', 'data.train.host_fed=True']),
+             ('host_window', ['data.train.type=SyntheticSourceImages', 'data.train.timing=True',
+                              'data.train.host_fed=window'])]
+    if a.modes:
+        modes = [m for m in modes if m[0] in a.modes.split(',')]
     res = {'what': __doc__.split('\n')[0], 'config': os.path.basename(a.config), 'iters': a.iters, 'modes': {}}
     for name, opts in modes:
         with tempfile.TemporaryDirectory() as wd:
