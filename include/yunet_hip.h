@@ -463,6 +463,19 @@ int yunet_aug_window_plan(const int32_t* params, const int32_t* src_hw, int N, i
  * copied back); the plan is checked against the image sizes and win_bytes before the first copy (YUNET_EINVAL). */
 int yunet_upload_windows(const uint8_t* host_src, const long long* src_off, const int32_t* src_hw, const int32_t* rect,
                          const long long* win_off, int N, uint8_t* win, long long win_bytes, void* stream);
+/* The window buffer of yunet_upload_windows, read by the GPU itself from the pinned host store (host_src, store_bytes:
+ * all of it pinned host memory with a device mapping, else YUNET_EINVAL and nothing is launched; 1 <= N <= 8192).
+ * src_off, src_hw (the SourceBatch tables), rect and win_off (yunet_aug_window_plan) are DEVICE arrays: no host
+ * round trip.  Validated on the device: an image whose rectangle leaves src_hw[n], whose source span leaves
+ * [0, store_bytes) or whose destination leaves [0, win_bytes), [win_off[n], win_off[n+1]] or starts before an earlier
+ * win_off is neither read nor written, and its YUNET_FETCH_BAD_* bits are OR-ed into *status (device int32, left
+ * as it is otherwise).  Non-persistent grid of 48 KiB chunks (image, row band). */
+#define YUNET_FETCH_BAD_RECT 1  /* rectangle outside its image (or negative) */
+#define YUNET_FETCH_BAD_SRC 2   /* source span outside the store */
+#define YUNET_FETCH_BAD_DST 4   /* destination outside win_bytes / its win_off slot, or before an earlier one */
+int yunet_fetch_windows(const uint8_t* host_src, long long store_bytes, const long long* src_off, const int32_t* src_hw,
+                        const int32_t* rect, const long long* win_off, int N, uint8_t* win, long long win_bytes,
+                        int32_t* status, void* stream);
 
 /* Measurement switches of the dispatchers (ABI 6).  The library reads the environment ONCE, the first time an
  * option is needed (YUNET_NO_PACK, YUNET_BWD_FP32MMA, YUNET_BWD64_NW, YUNET_EW_GRID, YUNET_DP_FWD_BLOCKS_PER_CU);

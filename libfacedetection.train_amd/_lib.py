@@ -14,6 +14,7 @@ c_f32p = C.c_void_p
 MAX_LEVELS = 5
 
 EINVAL, EOPCODE = -1, -2            # YUNET_EINVAL / YUNET_EOPCODE (include/yunet_hip.h)
+FETCH_BAD_RECT, FETCH_BAD_SRC, FETCH_BAD_DST = 1, 2, 4      # YUNET_FETCH_BAD_* (yunet_fetch_windows status bits)
 T_IDENTITY, T_BNRELU = 0, 1
 F32, BF16 = 0, 1
 BOX_EIOU, BOX_DIOU, BOX_IOU_LINEAR, BOX_IOU_SQUARE, BOX_IOU_LOG, BOX_GIOU, BOX_CIOU = 0, 1, 2, 3, 4, 5, 6
@@ -123,6 +124,8 @@ _SIGNATURES = {
                          [C.c_void_p] * 6),
     'yunet_aug_window_plan': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'yunet_upload_windows': (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    'yunet_fetch_windows': (C.c_int, [C.c_void_p, C.c_longlong] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_longlong,
+                                                                         C.c_void_p, C.c_void_p]),
     'yunet_reduce_partials': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                         C.c_void_p]),
     'yunet_assign': (C.c_int, [C.c_void_p] * 5 + [C.POINTER(YunetLevels)] + [C.c_int] * 3 +

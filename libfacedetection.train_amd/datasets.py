@@ -170,14 +170,21 @@ class RetinaFaceSource:
     cache='device': each sample is decoded the first time the sampler yields it and kept in a device SourceStore
                     (source_store.py; decoded WIDER-Face train is ~30 GB of HBM); a batch is a gather of store indices.
     cache='host'  : the same in a PINNED host SourceStore (that many bytes of pinned RAM per rank); per batch only the
-                    crop-window rectangles travel (WindowFeed).
+                    crop-window rectangles travel (WindowFeed).  host_fetch (cache='host' only): None or 'dma' = one
+                    hipMemcpy2DAsync per rectangle after a host wait on the plan; 'kernel' = the GPU reads the
+                    rectangles from the pinned store itself (yunet_fetch_windows), no host wait.
     All three give bit-identical batches; the image sizes of the labelv2 headers must be the decoded ones."""
 
     def __init__(self, dataset, pipeline, samples_per_gpu=16, rank=0, world=1, seed=0, max_gt=64, workers=4,
-                 cache=None):
+                 cache=None, host_fetch=None):
         from .pipelines import DevicePipeline
         if cache not in (None, 'device', 'host'):
             raise ValueError(f"RetinaFaceSource cache must be None, 'device' or 'host', got {cache!r}")
+        if host_fetch not in (None, 'dma', 'kernel'):
+            raise ValueError(f"RetinaFaceSource host_fetch must be 'dma' or 'kernel' (or unset), got {host_fetch!r}")
+        if host_fetch is not None and cache != 'host':
+            raise ValueError(f"RetinaFaceSource host_fetch applies to cache='host' only, not cache={cache!r}")
+        self.host_fetch = host_fetch
         self.cache, self.store, self._feed, self._decoding = cache, None, None, {}
         self.ds, self.bs, self.rank, self.world, self.seed = dataset, samples_per_gpu, rank, world, seed
         self.pipe = DevicePipeline(pipeline, seed=seed + 7919 * rank, gmax=64 if max_gt <= 64 else 128)
@@ -243,7 +250,7 @@ class RetinaFaceSource:
         f = self._feed
         if f is None:       # two window buffers, each the bs largest images (a window never exceeds its image)
             big = int(np.sort(self.store.image_bytes)[::-1][:self.bs].sum())
-            f = self._feed = WindowFeed(self.pipe, self.store, big)
+            f = self._feed = WindowFeed(self.pipe, self.store, big, fetch=self.host_fetch or 'dma')
         if not f.uploaded(it):
             if not f.planned(it):
                 f.plan(it, idx)

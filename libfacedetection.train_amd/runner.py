@@ -134,12 +134,14 @@ class SyntheticSourceImages:
     source of an image is 1 - 2.4 MB, more than its 320 x 320 fp32 crop).
     host_fed='window': the same pinned sources as a host SourceStore; per batch only the rectangle of each image that
     the crop can read travels (source_store.WindowFeed: plans made two iterations ahead, 2D copies on a copy stream,
-    the pixel pass on the window buffer) -- outputs bit-identical to the other modes.
+    the pixel pass on the window buffer) -- outputs bit-identical to the other modes.  host_fetch (host_fed='window'
+    only): None or 'dma' = one hipMemcpy2DAsync per rectangle after a host wait on the plan; 'kernel' = the GPU reads
+    the rectangles from the pinned store itself (yunet_fetch_windows), no host wait.
     `timing=True` records events around the upload and the pipeline (`report()`)."""
 
     def __init__(self, pipeline, samples_per_gpu=16, iters_per_epoch=403, rank=0, pool=64,
                  src_hw=((768, 1024), (1024, 683), (500, 375), (683, 1024)), max_gt=synthetic.MAX_GT,
-                 seed=0, host_fed=False, timing=False, **_):
+                 seed=0, host_fed=False, timing=False, host_fetch=None, **_):
         from .pipelines import DevicePipeline
         self.pipe = DevicePipeline(pipeline, seed=seed + 7919 * rank, gmax=64 if max_gt <= 64 else 128)
         self.bs, self.iters_per_epoch, self.rank = samples_per_gpu, iters_per_epoch, rank
@@ -147,6 +149,11 @@ class SyntheticSourceImages:
         if host_fed not in (False, True, 'window'):
             raise ValueError(f"host_fed must be False, True or 'window', got {host_fed!r}")
         self.host_fed, self.timing = (host_fed if host_fed == 'window' else bool(host_fed)), bool(timing)
+        if host_fetch not in (None, 'dma', 'kernel'):
+            raise ValueError(f"host_fetch must be 'dma' or 'kernel' (or unset), got {host_fetch!r}")
+        if host_fetch is not None and self.host_fed != 'window':
+            raise ValueError(f"host_fetch applies to host_fed='window' only, not host_fed={host_fed!r}")
+        self.host_fetch = host_fetch
         self._src = None
         self._ev = []
 
@@ -192,7 +199,7 @@ class SyntheticSourceImages:
             store.put(i, im, boxes[i], kps[i])
         self._idx = idx
         self._batch_bytes = int(store.image_bytes[idx].sum())
-        self._feed = WindowFeed(self.pipe, store, self._batch_bytes, timing=self.timing)
+        self._feed = WindowFeed(self.pipe, store, self._batch_bytes, timing=self.timing, fetch=self.host_fetch or 'dma')
 
     def _window_batch(self, it, device):
         if self._src is None:
@@ -282,7 +289,7 @@ class SyntheticSourceImages:
         if h:
             out['h2d_ms'] = sum(h) / len(h)
             if self.host_fed == 'window':         # mean bytes actually copied per batch, next to the whole sources
-                nb = [hd[2] for (hd, _) in ev]
+                nb = [float(hd[2]) for (hd, _) in ev]       # fetch='kernel': a device scalar (synchronised above)
                 out['h2d_bytes'] = sum(nb) / len(nb)
                 out['src_bytes'] = self._batch_bytes
             else:

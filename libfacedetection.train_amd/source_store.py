@@ -8,8 +8,8 @@
 Two placements:
   device  the decoded images live in HBM; a batch is a gather of store indices (csrc/source.hip aug_gather_kernel).
   host    the decoded images live in PINNED host memory (their bytes, per rank); per batch only the rectangle of each
-          image that the pixel pass can read travels (WindowFeed: yunet_aug_window_plan -> yunet_upload_windows ->
-          yunet_aug_pixels_window).
+          image that the pixel pass can read travels (WindowFeed: yunet_aug_window_plan -> yunet_upload_windows or,
+          with fetch='kernel', yunet_fetch_windows -> yunet_aug_pixels_window).
 Annotations and the per-image tables always live on the device.
 """
 import ctypes as C
@@ -175,23 +175,30 @@ class SourceStore:
 
 
 class WindowFeed:
-    """Host-placement feed: per iteration it, on a plan stream, gather -> aug_decide(it) -> window plan -> D2H of the
-    plan into a pinned ring; then (host, once that plan has landed) yunet_upload_windows on a copy stream into one of
-    two device window buffers; then, on the current stream, the pipeline on that window buffer.  aug_decide is keyed
-    by (seed, iteration, image), so a plan can be made iterations ahead and the real aug_decide of the iteration gives
-    the same params.  The host waits only on plan events (a gather + two small kernels on their own stream, in steady
-    state done long before); buffer reuse waits on GPU events."""
+    """Host-placement feed: per iteration it, on a plan stream, gather -> aug_decide(it) -> window plan; then the windows
+    travel on a copy stream into one of two device window buffers; then, on the current stream, the pipeline on that
+    window buffer.  aug_decide is keyed by (seed, iteration, image), so a plan can be made iterations ahead and the real
+    aug_decide of the iteration gives the same params.  Buffer reuse waits on GPU events.  How the windows travel:
+
+      fetch='dma'    the plan is copied back into a pinned ring and, once it has landed (the host waits on the plan
+                     event), yunet_upload_windows queues one hipMemcpy2DAsync per rectangle.
+      fetch='kernel' the copy stream waits on the plan event on the GPU and yunet_fetch_windows reads the rectangles
+                     from the pinned store itself, with the plan taken from device memory: no host wait, no plan copy.
+                     Invalid plan rows are skipped on the device and flagged in a device status word: check()."""
 
     RING = 3
 
-    def __init__(self, pipe, store, win_bytes, timing=False):
+    def __init__(self, pipe, store, win_bytes, timing=False, fetch='dma'):
         if store.placement != 'host':
             raise ValueError('WindowFeed feeds from a host-placement SourceStore')
+        if fetch not in ('dma', 'kernel'):
+            raise ValueError(f"WindowFeed fetch must be 'dma' or 'kernel', got {fetch!r}")
         dev = store.device
-        self.pipe, self.store, self.timing = pipe, store, bool(timing)
+        self.pipe, self.store, self.timing, self.fetch = pipe, store, bool(timing), fetch
         self._plan_stream = torch.cuda.Stream(device=dev)
         self._copy = torch.cuda.Stream(device=dev)
         self._bufs = [torch.empty(int(win_bytes), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self._status = torch.zeros(1, dtype=torch.int32, device=dev) if fetch == 'kernel' else None
         self._consumed = [None, None]          # event: the pipeline that read buffer b has run
         self._ring = None
         self._nplans = 0
@@ -207,6 +214,14 @@ class WindowFeed:
     def plan(self, it, idx):
         """Enqueue the plan of iteration it (store images idx) on the plan stream."""
         st = self._plan_stream
+        if self.fetch == 'kernel':
+            with torch.cuda.stream(st):
+                sb = self.store.batch(idx)
+                _, rect, off = self.pipe.window_plan(sb, it, self.store.device)
+                ev = torch.cuda.Event()
+                ev.record(st)
+            self._planned[it] = dict(sb=sb, rect=rect, off=off, ev=ev)
+            return
         n = len(idx)
         if self._ring is None or self._ring[0][0].shape[0] != n:
             self._ring = [(torch.empty(n, 4, dtype=torch.int32, pin_memory=True),
@@ -224,6 +239,8 @@ class WindowFeed:
 
     def upload(self, it):
         """Issue the copies of iteration it's windows (its plan must have been enqueued)."""
+        if self.fetch == 'kernel':
+            return self._fetch(it)
         P = self._planned[it]
         P['ev'].synchronize()
         b = it % 2
@@ -245,8 +262,45 @@ class WindowFeed:
             e1.record(self._copy)
         self._uploaded[it] = (b, e0, e1, total)
 
+    def _fetch(self, it):
+        """fetch='kernel': yunet_fetch_windows on the copy stream, after the plan (GPU wait) and after the pipeline that
+        last read the buffer.  Both callers size the buffers for the batch's largest images, and the kernel skips (and
+        flags) any rectangle that would not fit.  The byte count stays on the device (win_off[N])."""
+        P = self._planned[it]
+        b, sb, cp = it % 2, P['sb'], self._copy
+        p = lambda x: C.c_void_p(x.data_ptr())   # noqa: E731
+        with torch.cuda.stream(cp):
+            cp.wait_event(P['ev'])
+            if self._consumed[b] is not None:
+                cp.wait_event(self._consumed[b])
+            for t in (sb.src_off, sb.src_hw, P['rect'], P['off']):
+                t.record_stream(cp)
+            e0 = torch.cuda.Event(enable_timing=self.timing)
+            e0.record(cp)
+            L.check(L.load().yunet_fetch_windows(p(self.store.data), self.store.nbytes, p(sb.src_off), p(sb.src_hw),
+                                                 p(P['rect']), p(P['off']), sb.n, p(self._bufs[b]),
+                                                 self._bufs[b].numel(), p(self._status), C.c_void_p(cp.cuda_stream)),
+                    'yunet_fetch_windows')
+            e1 = torch.cuda.Event(enable_timing=self.timing)
+            e1.record(cp)
+        self._uploaded[it] = (b, e0, e1, P['off'][-1])
+
+    def check(self):
+        """fetch='kernel': raise if any fetch so far met an invalid plan row (YUNET_FETCH_BAD_* bits).  Synchronises the
+        copy stream: for the end of an epoch or a test, not for every iteration."""
+        if self._status is None:
+            return
+        self._copy.synchronize()
+        bits = int(self._status.item())
+        if bits:
+            names = [nm for nm, v in (('rectangle outside its image', L.FETCH_BAD_RECT),
+                                      ('source span outside the store', L.FETCH_BAD_SRC),
+                                      ('destination outside the window buffer', L.FETCH_BAD_DST)) if bits & v]
+            raise RuntimeError(f'yunet_fetch_windows skipped invalid plan rows (status {bits}: {", ".join(names)})')
+
     def run(self, it):
-        """The pipeline of iteration it on the current stream -> (batch dict, (e0, e1, bytes) of its upload)."""
+        """The pipeline of iteration it on the current stream -> (batch dict, (e0, e1, bytes) of its upload; with
+        fetch='kernel' bytes is a device scalar)."""
         cur = torch.cuda.current_stream(self.store.device)
         P = self._planned.pop(it)
         b, e0, e1, total = self._uploaded.pop(it)

@@ -109,9 +109,10 @@ def build_source(cfg, rank, world, seed):
         cache = dcfg.get('cache')                        # data.train.cache=device|host: decode once (SourceStore)
         if cache not in (None, 'device', 'host'):
             raise ValueError(f"data.train.cache must be device or host (or unset), got {cache!r}")
+        host_fetch = dcfg.get('host_fetch')              # data.train.host_fetch=dma|kernel (cache=host only)
         dataset = yunet_amd.build_dataset(dcfg)
         return RetinaFaceSource(dataset, dcfg['pipeline'], samples_per_gpu=cfg.data.samples_per_gpu, rank=rank,
-                                world=world, seed=seed, cache=cache)
+                                world=world, seed=seed, cache=cache, host_fetch=host_fetch)
     raise SystemExit('data sources: RetinaFaceDataset (labelv2 + image files, augmented on the GPU), '
                      'SyntheticWiderFace (ready batches) or SyntheticSourceImages (decoded synthetic '
                      'sources + the reference train pipeline on the GPU)')

@@ -10,6 +10,8 @@ configs/yunet_n.py (YuNet_n 320 x 320, 256 images per GPU) from three data sourc
             (host_fed=True)         two device buffers while the previous step runs
   host_window SyntheticSourceImages   the same pinned sources as a host SourceStore: per batch only each image's crop-window
             (host_fed='window')     rectangle travels (2D copies on a copy stream, planned two iterations ahead)
+  host_window_kernel                the same windows read by the GPU itself from the pinned store (yunet_fetch_windows on
+            (+ host_fetch=kernel)   the copy stream, plan from device memory, no host wait)
 
     python tools/train_e2e.py [--iters 200] [--out profiles/r06_train_e2e.json]
 
@@ -39,7 +41,8 @@ def main():
     ap.add_argument('--iters', type=int, default=200)
     ap.add_argument('--config', default=os.path.join(ROOT, 'configs', 'yunet_n.py'))
     ap.add_argument('--out', default=None)
-    ap.add_argument('--modes', default=None, help='comma-separated subset of ready,resident,host_fed,host_window')
+    ap.add_argument('--modes', default=None,
+                    help='comma-separated subset of ready,resident,host_fed,host_window,host_window_kernel')
     a = ap.parse_args()
     import torch
     T = load_train_tool()
@@ -48,7 +51,9 @@ def main():
              ('resident', ['data.train.type=SyntheticSourceImages', 'data.train.timing=True']),
              ('host_fed', ['data.train.type=SyntheticSourceImages', 'data.train.timing=True', 'data.train.host_fed=True']),
              ('host_window', ['data.train.type=SyntheticSourceImages', 'data.train.timing=True',
-                              'data.train.host_fed=window'])]
+                              'data.train.host_fed=window']),
+             ('host_window_kernel', ['data.train.type=SyntheticSourceImages', 'data.train.timing=True',
+                                     'data.train.host_fed=window', 'data.train.host_fetch=kernel'])]
     if a.modes:
         modes = [m for m in modes if m[0] in a.modes.split(',')]
     res = {'what': __doc__.split('\n')[0], 'config': os.path.basename(a.config), 'iters': a.iters, 'modes': {}}
