@@ -443,6 +443,59 @@ int yunet_aug_pixels(const uint8_t* src, const long long* src_off, const int32_t
 int yunet_aug_pixels_window(const uint8_t* win, const long long* win_off, const int32_t* rect, const int32_t* src_hw,
                             const int32_t* params, const YunetAugCfg* cfg, int N, float* out_img, void* stream);
 
+/* PhotoMetricDistortion (transforms.py:1211-1312) inside the pixel pass.  Positions in the pipeline list:
+ *   PRE : between LoadAnnotations and RandomSquareCrop -- each in-image source tap is distorted after its uint8 ->
+ *         float load; the crop's pad_value fill is not distorted (it is written after the transform);
+ *   POST: between RandomFlip and Normalize -- every output pixel (pad pixels included) after the vertical pass.
+ * Draws come from a SUB-STREAM of the counter-based generator: key mix32(stream_key(seed, iteration, image) ^
+ * YUNET_PHOTO_SALT), counter from 0, so crop windows / flips / GT do not depend on whether or where the transform
+ * sits.  The draws follow the reference's call order (conditional draws included):
+ *   randint(2) brightness [uniform(-d, d)]; randint(2) mode; mode 1: randint(2) contrast [uniform];
+ *   randint(2) saturation [uniform]; randint(2) hue [uniform]; mode 0: randint(2) contrast [uniform];
+ *   randint(2) swap [permutation(3)]
+ * randint(2) = u32 >> 31; uniform(a, b) = a + (b - a) * (u32 / 2^32) in double, then rounded to fp32 once (numpy 2 weak
+ * Python-float scalar on a float32 image); permutation(3) = numpy's legacy Fisher-Yates, i = 2 then 1,
+ * j = floor(u32 / 2^32 * (i + 1)).  Pixel arithmetic is fp32 in the reference's order, with cv2.cvtColor's scalar
+ * float BGR<->HSV (h in degrees) restated -- unpinned against the cv2 binary, which is not available. */
+#define YUNET_PHOTO_NONE 0
+#define YUNET_PHOTO_PRE 1
+#define YUNET_PHOTO_POST 2
+#define YUNET_PHOTO_SALT 0x50484D44u   /* "PHMD" */
+/* pparams [N, YUNET_PHOTO_WORDS] fp32 per image: flags are 0 / 1, the permutation entries 0..2 */
+#define YUNET_PHOTO_WORDS 16
+#define YUNET_PHOTO_BRIGHT 0     /* brightness fired */
+#define YUNET_PHOTO_DELTA 1      /* its delta */
+#define YUNET_PHOTO_MODE 2       /* 1: contrast before the HSV round trip, 0: after */
+#define YUNET_PHOTO_CONTRAST 3   /* contrast fired */
+#define YUNET_PHOTO_ALPHA 4
+#define YUNET_PHOTO_SAT 5        /* saturation fired */
+#define YUNET_PHOTO_SAT_F 6
+#define YUNET_PHOTO_HUE 7        /* hue fired */
+#define YUNET_PHOTO_HUE_D 8
+#define YUNET_PHOTO_SWAP 9       /* channel swap fired */
+#define YUNET_PHOTO_PERM 10      /* 10..12: output channel c = input channel perm[c] (identity when not fired) */
+#define YUNET_PHOTO_DRAWS 13     /* u32 draws consumed from the sub-stream; 14, 15 zero */
+typedef struct YunetPhotoCfg {
+    double brightness_delta;     /* 32 */
+    double contrast_lower, contrast_upper;        /* (0.5, 1.5) */
+    double saturation_lower, saturation_upper;    /* (0.5, 1.5) */
+    double hue_delta;            /* 18; at most 360 */
+    int32_t position;            /* YUNET_PHOTO_PRE / YUNET_PHOTO_POST */
+    int32_t reserved_;
+} YunetPhotoCfg;
+/* One thread per image: the draws of (seed, iteration, image) -> pparams.  YUNET_EINVAL for a bad cfg (lower > upper,
+ * a negative or non-finite delta, hue_delta > 360, position not PRE / POST) or N < 1. */
+int yunet_aug_photometric(const YunetPhotoCfg* cfg, uint32_t seed, uint32_t iteration, int N, float* pparams,
+                          void* stream);
+/* yunet_aug_pixels / yunet_aug_pixels_window with the distortion of pparams (yunet_aug_photometric of the same
+ * iteration) at `position` (PRE / POST).  Same crop / resize / flip float operations as the plain entry points. */
+int yunet_aug_pixels_photo(const uint8_t* src, const long long* src_off, const int32_t* src_hw,
+                           const int32_t* params, const float* pparams, int position, const YunetAugCfg* cfg, int N,
+                           float* out_img, void* stream);
+int yunet_aug_pixels_window_photo(const uint8_t* win, const long long* win_off, const int32_t* rect,
+                                  const int32_t* src_hw, const int32_t* params, const float* pparams, int position,
+                                  const YunetAugCfg* cfg, int N, float* out_img, void* stream);
+
 /* Decoded-source store (pipelines.SourceStore).  One launch builds a batch's SourceBatch tables from the store's
  * per-image tables (M images: byte offset, (h, w), first GT row, GT count; boxes [*,4], kps [*,5,3]) and a device
  * index vector idx [N] (repeats allowed, 1 <= N <= 8192): src_off [N], src_hw [N,2], gt_off [N+1] (exclusive scan of

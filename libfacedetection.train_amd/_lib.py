@@ -66,6 +66,19 @@ class YunetAugCfg(C.Structure):
                 ('max_attempts', C.c_int32), ('max_retries', C.c_int32), ('gmax', C.c_int32)]
 
 
+# PhotoMetricDistortion in the pixel pass (YUNET_PHOTO_*): positions, sub-stream salt, per-image table words
+PHOTO_NONE, PHOTO_PRE, PHOTO_POST = 0, 1, 2
+PHOTO_SALT, PHOTO_WORDS = 0x50484D44, 16
+(PHOTO_BRIGHT, PHOTO_DELTA, PHOTO_MODE, PHOTO_CONTRAST, PHOTO_ALPHA, PHOTO_SAT, PHOTO_SAT_F, PHOTO_HUE, PHOTO_HUE_D,
+ PHOTO_SWAP, PHOTO_PERM, PHOTO_DRAWS) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 13
+
+
+class YunetPhotoCfg(C.Structure):
+    _fields_ = [('brightness_delta', C.c_double), ('contrast_lower', C.c_double), ('contrast_upper', C.c_double),
+                ('saturation_lower', C.c_double), ('saturation_upper', C.c_double), ('hue_delta', C.c_double),
+                ('position', C.c_int32), ('reserved_', C.c_int32)]
+
+
 MAX_RANKS, IPC_HANDLE_BYTES, COMM_HEADER_BYTES = 8, 64, 20480
 
 
@@ -120,6 +133,12 @@ _SIGNATURES = {
     'yunet_aug_pixels': (C.c_int, [C.c_void_p] * 4 + [C.POINTER(YunetAugCfg), C.c_int, C.c_void_p, C.c_void_p]),
     'yunet_aug_pixels_window': (C.c_int, [C.c_void_p] * 5 + [C.POINTER(YunetAugCfg), C.c_int, C.c_void_p,
                                                              C.c_void_p]),
+    'yunet_aug_photometric': (C.c_int, [C.POINTER(YunetPhotoCfg), C.c_uint32, C.c_uint32, C.c_int, C.c_void_p,
+                                        C.c_void_p]),
+    'yunet_aug_pixels_photo': (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.POINTER(YunetAugCfg), C.c_int, C.c_void_p,
+                                                            C.c_void_p]),
+    'yunet_aug_pixels_window_photo': (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.POINTER(YunetAugCfg), C.c_int,
+                                                                   C.c_void_p, C.c_void_p]),
     'yunet_aug_gather': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int] +
                          [C.c_void_p] * 6),
     'yunet_aug_window_plan': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

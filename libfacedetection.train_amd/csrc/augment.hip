@@ -13,6 +13,9 @@
 //
 // Built with -ffp-contract=off: every float operation is the single rounded operation numpy
 // performs, so boxes / keypoints are bit-identical to the reference and pixels to the oracle.
+#include <cfloat>
+#include <cmath>
+
 #include "common.h"
 
 namespace {
@@ -150,15 +153,154 @@ __device__ __forceinline__ void lin_coef(int d, int dst, int src, int& s0, int& 
     w1 = f;
 }
 
+// ---- PhotoMetricDistortion (transforms.py:1211-1312; include/yunet_hip.h YUNET_PHOTO_*) ------------------------
+__device__ __forceinline__ uint32_t photo_key(uint32_t seed, uint32_t iteration, uint32_t image) {
+    return mix32(stream_key(seed, iteration, image) ^ YUNET_PHOTO_SALT);
+}
+// numpy.random.uniform(a, b) = a + (b - a) * random_sample() in double; the image op rounds it to fp32 once
+__device__ __forceinline__ float photo_uniform(uint32_t u, double a, double b) {
+    return (float)(a + (b - a) * ((double)u * (1.0 / 4294967296.0)));
+}
+
+__global__ __launch_bounds__(64) void aug_photometric_kernel(const YunetPhotoCfg cfg, uint32_t seed, uint32_t iteration,
+                                                             int N, float* __restrict__ pp) {
+    const int n = blockIdx.x * 64 + threadIdx.x;
+    if (n >= N) return;
+    const uint32_t key = photo_key(seed, iteration, (uint32_t)n);
+    uint32_t ctr = 0;
+    float t[YUNET_PHOTO_WORDS];
+#pragma unroll
+    for (int k = 0; k < YUNET_PHOTO_WORDS; ++k) t[k] = 0.0f;
+    if (rand_u32(key, ctr++) >> 31) {                     // randint(2): brightness
+        t[YUNET_PHOTO_BRIGHT] = 1.0f;
+        t[YUNET_PHOTO_DELTA] = photo_uniform(rand_u32(key, ctr++), -cfg.brightness_delta, cfg.brightness_delta);
+    }
+    const uint32_t mode = rand_u32(key, ctr++) >> 31;
+    t[YUNET_PHOTO_MODE] = (float)mode;
+    if (mode == 1 && (rand_u32(key, ctr++) >> 31)) {      // contrast first
+        t[YUNET_PHOTO_CONTRAST] = 1.0f;
+        t[YUNET_PHOTO_ALPHA] = photo_uniform(rand_u32(key, ctr++), cfg.contrast_lower, cfg.contrast_upper);
+    }
+    if (rand_u32(key, ctr++) >> 31) {                     // saturation
+        t[YUNET_PHOTO_SAT] = 1.0f;
+        t[YUNET_PHOTO_SAT_F] = photo_uniform(rand_u32(key, ctr++), cfg.saturation_lower, cfg.saturation_upper);
+    }
+    if (rand_u32(key, ctr++) >> 31) {                     // hue
+        t[YUNET_PHOTO_HUE] = 1.0f;
+        t[YUNET_PHOTO_HUE_D] = photo_uniform(rand_u32(key, ctr++), -cfg.hue_delta, cfg.hue_delta);
+    }
+    if (mode == 0 && (rand_u32(key, ctr++) >> 31)) {      // contrast last
+        t[YUNET_PHOTO_CONTRAST] = 1.0f;
+        t[YUNET_PHOTO_ALPHA] = photo_uniform(rand_u32(key, ctr++), cfg.contrast_lower, cfg.contrast_upper);
+    }
+    int p0 = 0, p1 = 1, p2 = 2;
+    if (rand_u32(key, ctr++) >> 31) {                     // swap: permutation(3), legacy Fisher-Yates
+        t[YUNET_PHOTO_SWAP] = 1.0f;
+        const int j2 = bounded(rand_u32(key, ctr++), 3);  // i = 2
+        if (j2 == 0) { const int x = p2; p2 = p0; p0 = x; }
+        else if (j2 == 1) { const int x = p2; p2 = p1; p1 = x; }
+        const int j1 = bounded(rand_u32(key, ctr++), 2);  // i = 1
+        if (j1 == 0) { const int x = p1; p1 = p0; p0 = x; }
+    }
+    t[YUNET_PHOTO_PERM + 0] = (float)p0;
+    t[YUNET_PHOTO_PERM + 1] = (float)p1;
+    t[YUNET_PHOTO_PERM + 2] = (float)p2;
+    t[YUNET_PHOTO_DRAWS] = (float)ctr;
+    float* o = pp + (size_t)n * YUNET_PHOTO_WORDS;
+#pragma unroll
+    for (int k = 0; k < YUNET_PHOTO_WORDS; ++k) o[k] = t[k];
+}
+
+// The table of one image, read once per thread (uniform across the workgroup: scalar loads).
+struct Photo {
+    bool bright, contrast, sat, hue, swap;
+    int mode, p0, p1, p2;
+    float delta, alpha, sat_f, hue_d;
+};
+__device__ __forceinline__ Photo load_photo(const float* __restrict__ t) {
+    Photo q;
+    q.bright = t[YUNET_PHOTO_BRIGHT] != 0.0f; q.delta = t[YUNET_PHOTO_DELTA];
+    q.mode = t[YUNET_PHOTO_MODE] != 0.0f ? 1 : 0;
+    q.contrast = t[YUNET_PHOTO_CONTRAST] != 0.0f; q.alpha = t[YUNET_PHOTO_ALPHA];
+    q.sat = t[YUNET_PHOTO_SAT] != 0.0f; q.sat_f = t[YUNET_PHOTO_SAT_F];
+    q.hue = t[YUNET_PHOTO_HUE] != 0.0f; q.hue_d = t[YUNET_PHOTO_HUE_D];
+    q.swap = t[YUNET_PHOTO_SWAP] != 0.0f;
+    q.p0 = (int)t[YUNET_PHOTO_PERM + 0]; q.p1 = (int)t[YUNET_PHOTO_PERM + 1]; q.p2 = (int)t[YUNET_PHOTO_PERM + 2];
+    return q;
+}
+
+// One BGR pixel through PhotoMetricDistortion.__call__, fp32 in the reference's order.  BGR <-> HSV is cv2.cvtColor's
+// scalar float path (RGB2HSV_f / HSV2RGB_f, hrange 360) restated; the sector table of HSV -> BGR is written with
+// selects so that nothing is indexed at run time (no scratch).
+__device__ __forceinline__ void photo_pixel(const Photo& q, float& b, float& g, float& r) {
+    if (q.bright) { b += q.delta; g += q.delta; r += q.delta; }
+    if (q.mode == 1 && q.contrast) { b *= q.alpha; g *= q.alpha; r *= q.alpha; }
+    // BGR -> HSV
+    float v = r, vmin = r;
+    if (v < g) v = g;
+    if (v < b) v = b;
+    if (vmin > g) vmin = g;
+    if (vmin > b) vmin = b;
+    float diff = v - vmin;
+    float s = diff / (fabsf(v) + FLT_EPSILON);
+    diff = (float)(60.0 / (double)(diff + FLT_EPSILON));
+    float h;
+    if (v == r) h = (g - b) * diff;
+    else if (v == g) h = (b - r) * diff + 120.0f;
+    else h = (r - g) * diff + 240.0f;
+    if (h < 0.0f) h += 360.0f;
+    // saturation, hue (strict comparisons, > 360 first)
+    if (q.sat) s *= q.sat_f;
+    if (q.hue) {
+        h += q.hue_d;
+        if (h > 360.0f) h -= 360.0f;
+        if (h < 0.0f) h += 360.0f;
+    }
+    // HSV -> BGR
+    if (s == 0.0f) {
+        b = g = r = v;
+    } else {
+        h *= 6.0f / 360.0f;
+        // cv2 wraps with unbounded loops; h is within [-6, 12] for any table yunet_aug_photometric writes
+        // (hue_delta <= 360), so 64 trips never cut a wrap short there and a corrupt table cannot hang the kernel
+        if (h < 0.0f) {
+            for (int k = 0; k < 64 && h < 0.0f; ++k) h += 6.0f;
+        } else if (h >= 6.0f) {
+            for (int k = 0; k < 64 && h >= 6.0f; ++k) h -= 6.0f;
+        }
+        const float fl = floorf(h);
+        int sector = (int)fl;
+        h -= fl;
+        if ((unsigned)sector >= 6u) { sector = 0; h = 0.0f; }
+        const float t0 = v, t1 = v * (1.0f - s), t2 = v * (1.0f - s * h), t3 = v * (1.0f - s * (1.0f - h));
+        // sector table {1,3,0},{1,0,2},{3,0,1},{0,2,1},{0,1,3},{2,1,0} for (b, g, r)
+        b = sector <= 1 ? t1 : sector == 2 ? t3 : sector == 5 ? t2 : t0;
+        g = sector == 0 ? t3 : sector <= 2 ? t0 : sector == 3 ? t2 : t1;
+        r = (sector == 0 || sector == 5) ? t0 : sector == 1 ? t2 : sector == 4 ? t3 : t1;
+    }
+    if (q.mode == 0 && q.contrast) { b *= q.alpha; g *= q.alpha; r *= q.alpha; }
+    if (q.swap) {
+        const float c[3] = {b, g, r};
+        const float x0 = q.p0 == 0 ? c[0] : q.p0 == 1 ? c[1] : c[2];
+        const float x1 = q.p1 == 0 ? c[0] : q.p1 == 1 ? c[1] : c[2];
+        const float x2 = q.p2 == 0 ? c[0] : q.p2 == 1 ? c[1] : c[2];
+        b = x0; g = x1; r = x2;
+    }
+}
+
 // WIN = false: image n is src + src_off[n], row pitch w (the resident / whole-upload layout).
 // WIN = true : image n is the rectangle rect[n] = (row0, col0, rows, cols) of the source, stored compactly at
 //   src + src_off[n] with row pitch cols (yunet_aug_window_plan; the host-store upload).  The float operations are
 //   those of WIN = false, so the output is bit-identical; the extra rectangle test only ever fails when the plan
 //   does not belong to these params, and then it reads pad instead of leaving the window buffer.
-template <bool WIN>
+// PH = YUNET_PHOTO_NONE: no distortion (yunet_aug_pixels / _window); PRE: each in-image tap pixel is distorted after
+//   its load (pad taps stay pad); POST: the output pixel is distorted after the vertical pass.  `pp` = the table of
+//   yunet_aug_photometric (unused for NONE).
+template <bool WIN, int PH>
 __global__ __launch_bounds__(256) void aug_pixels_kernel(
     const uint8_t* __restrict__ src, const long long* __restrict__ src_off, const int32_t* __restrict__ src_hw,
-    const int32_t* __restrict__ rect, const int32_t* __restrict__ params, int S, float pad, float* __restrict__ out) {
+    const int32_t* __restrict__ rect, const int32_t* __restrict__ params, const float* __restrict__ pp, int S,
+    float pad, float* __restrict__ out) {
     const int n = blockIdx.y;
     const int32_t* p = params + 8 * n;
     const int left = p[AUG_P_LEFT], top = p[AUG_P_TOP], cw = p[AUG_P_CW], flip = p[AUG_P_FLIP];
@@ -167,6 +309,8 @@ __global__ __launch_bounds__(256) void aug_pixels_kernel(
     const int rh = WIN ? rect[4 * n + 2] : h, rw = WIN ? rect[4 * n + 3] : w;
     const uint8_t* im = src + src_off[n];
     float* o = out + (size_t)n * 3 * S * S;
+    Photo q;
+    if (PH != YUNET_PHOTO_NONE) q = load_photo(pp + (size_t)n * YUNET_PHOTO_WORDS);
     for (int i = blockIdx.x * 256 + threadIdx.x; i < S * S; i += gridDim.x * 256) {
         const int dy = i / S, dx = i - dy * S;
         float v[3] = {pad, pad, pad};
@@ -185,17 +329,39 @@ __global__ __launch_bounds__(256) void aug_pixels_kernel(
             }
             const uint8_t* r0 = im + ((size_t)(Y0 - ry) * rw) * 3 - (size_t)rx * 3;
             const uint8_t* r1 = im + ((size_t)(Y1 - ry) * rw) * 3 - (size_t)rx * 3;
+            if (PH == YUNET_PHOTO_PRE) {
+                float t00[3], t01[3], t10[3], t11[3];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float v00 = (y0in && x0in) ? (float)r0[3 * X0 + c] : pad;
-                const float v01 = (y0in && x1in) ? (float)r0[3 * X1 + c] : pad;
-                const float v10 = (y1in && x0in) ? (float)r1[3 * X0 + c] : pad;
-                const float v11 = (y1in && x1in) ? (float)r1[3 * X1 + c] : pad;
-                const float t0 = v00 * a0 + v01 * a1;          // horizontal pass
-                const float t1 = v10 * a0 + v11 * a1;
-                v[c] = t0 * b0 + t1 * b1;                      // vertical pass
+                for (int c = 0; c < 3; ++c) {
+                    t00[c] = (y0in && x0in) ? (float)r0[3 * X0 + c] : pad;
+                    t01[c] = (y0in && x1in) ? (float)r0[3 * X1 + c] : pad;
+                    t10[c] = (y1in && x0in) ? (float)r1[3 * X0 + c] : pad;
+                    t11[c] = (y1in && x1in) ? (float)r1[3 * X1 + c] : pad;
+                }
+                if (y0in && x0in) photo_pixel(q, t00[0], t00[1], t00[2]);
+                if (y0in && x1in) photo_pixel(q, t01[0], t01[1], t01[2]);
+                if (y1in && x0in) photo_pixel(q, t10[0], t10[1], t10[2]);
+                if (y1in && x1in) photo_pixel(q, t11[0], t11[1], t11[2]);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float t0 = t00[c] * a0 + t01[c] * a1;    // horizontal pass
+                    const float t1 = t10[c] * a0 + t11[c] * a1;
+                    v[c] = t0 * b0 + t1 * b1;                      // vertical pass
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float v00 = (y0in && x0in) ? (float)r0[3 * X0 + c] : pad;
+                    const float v01 = (y0in && x1in) ? (float)r0[3 * X1 + c] : pad;
+                    const float v10 = (y1in && x0in) ? (float)r1[3 * X0 + c] : pad;
+                    const float v11 = (y1in && x1in) ? (float)r1[3 * X1 + c] : pad;
+                    const float t0 = v00 * a0 + v01 * a1;          // horizontal pass
+                    const float t1 = v10 * a0 + v11 * a1;
+                    v[c] = t0 * b0 + t1 * b1;                      // vertical pass
+                }
             }
         }
+        if (PH == YUNET_PHOTO_POST) photo_pixel(q, v[0], v[1], v[2]);
         o[i] = v[0];
         o[(size_t)S * S + i] = v[1];
         o[(size_t)2 * S * S + i] = v[2];
@@ -223,8 +389,8 @@ extern "C" int yunet_aug_pixels(const uint8_t* src, const long long* src_off, co
     const int S = cfg->out_size;
     int bx = (S * S + 255) / 256;
     if (bx > 64) bx = 64;                       // grid-stride over the pixels of one image
-    hipLaunchKernelGGL(aug_pixels_kernel<false>, dim3(bx, N), dim3(256), 0, (hipStream_t)stream, src, src_off,
-                       src_hw, nullptr, params, S, cfg->pad_value, out_img);
+    hipLaunchKernelGGL((aug_pixels_kernel<false, YUNET_PHOTO_NONE>), dim3(bx, N), dim3(256), 0, (hipStream_t)stream, src,
+                       src_off, src_hw, nullptr, params, nullptr, S, cfg->pad_value, out_img);
     return hip_status();
 }
 
@@ -235,7 +401,58 @@ extern "C" int yunet_aug_pixels_window(const uint8_t* win, const long long* win_
     const int S = cfg->out_size;
     int bx = (S * S + 255) / 256;
     if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(aug_pixels_kernel<true>, dim3(bx, N), dim3(256), 0, (hipStream_t)stream, win, win_off,
-                       src_hw, rect, params, S, cfg->pad_value, out_img);
+    hipLaunchKernelGGL((aug_pixels_kernel<true, YUNET_PHOTO_NONE>), dim3(bx, N), dim3(256), 0, (hipStream_t)stream, win,
+                       win_off, src_hw, rect, params, nullptr, S, cfg->pad_value, out_img);
     return hip_status();
+}
+
+static bool photo_cfg_ok(const YunetPhotoCfg* c) {
+    const double v[6] = {c->brightness_delta, c->contrast_lower, c->contrast_upper, c->saturation_lower,
+                         c->saturation_upper, c->hue_delta};
+    for (double x : v)
+        if (!std::isfinite(x)) return false;
+    return c->brightness_delta >= 0.0 && c->hue_delta >= 0.0 && c->hue_delta <= 360.0 &&
+           c->contrast_lower <= c->contrast_upper && c->saturation_lower <= c->saturation_upper &&
+           (c->position == YUNET_PHOTO_PRE || c->position == YUNET_PHOTO_POST);
+}
+
+extern "C" int yunet_aug_photometric(const YunetPhotoCfg* cfg, uint32_t seed, uint32_t iteration, int N,
+                                     float* pparams, void* stream) {
+    if (!cfg || !photo_cfg_ok(cfg) || N < 1 || !pparams) return YUNET_EINVAL;
+    hipLaunchKernelGGL(aug_photometric_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, *cfg, seed,
+                       iteration, N, pparams);
+    return hip_status();
+}
+
+template <bool WIN>
+static int launch_pixels_photo(const uint8_t* src, const long long* src_off, const int32_t* src_hw,
+                               const int32_t* rect, const int32_t* params, const float* pparams, int position,
+                               const YunetAugCfg* cfg, int N, float* out_img, void* stream) {
+    if (!cfg || N < 1 || cfg->out_size < 1 || !pparams) return YUNET_EINVAL;
+    const int S = cfg->out_size;
+    int bx = (S * S + 255) / 256;
+    if (bx > 64) bx = 64;
+    if (position == YUNET_PHOTO_PRE)
+        hipLaunchKernelGGL((aug_pixels_kernel<WIN, YUNET_PHOTO_PRE>), dim3(bx, N), dim3(256), 0, (hipStream_t)stream,
+                           src, src_off, src_hw, rect, params, pparams, S, cfg->pad_value, out_img);
+    else if (position == YUNET_PHOTO_POST)
+        hipLaunchKernelGGL((aug_pixels_kernel<WIN, YUNET_PHOTO_POST>), dim3(bx, N), dim3(256), 0, (hipStream_t)stream,
+                           src, src_off, src_hw, rect, params, pparams, S, cfg->pad_value, out_img);
+    else
+        return YUNET_EINVAL;
+    return hip_status();
+}
+
+extern "C" int yunet_aug_pixels_photo(const uint8_t* src, const long long* src_off, const int32_t* src_hw,
+                                      const int32_t* params, const float* pparams, int position,
+                                      const YunetAugCfg* cfg, int N, float* out_img, void* stream) {
+    return launch_pixels_photo<false>(src, src_off, src_hw, nullptr, params, pparams, position, cfg, N, out_img,
+                                      stream);
+}
+
+extern "C" int yunet_aug_pixels_window_photo(const uint8_t* win, const long long* win_off, const int32_t* rect,
+                                             const int32_t* src_hw, const int32_t* params, const float* pparams,
+                                             int position, const YunetAugCfg* cfg, int N, float* out_img,
+                                             void* stream) {
+    return launch_pixels_photo<true>(win, win_off, src_hw, rect, params, pparams, position, cfg, N, out_img, stream);
 }

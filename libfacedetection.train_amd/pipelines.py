@@ -6,12 +6,14 @@
     out = model.train_step(batch, optimizer)
 
 `RandomSquareCrop -> Resize(keep_ratio=False) -> RandomFlip -> Normalize(0, 1) ->
-DefaultFormatBundle -> Collect` run as two HIP kernels (csrc/augment.hip); the classes below carry
+DefaultFormatBundle -> Collect` run as two HIP kernels (csrc/augment.hip), three with an optional
+`PhotoMetricDistortion` before RandomSquareCrop or after RandomFlip; the classes below carry
 the configuration under the reference's registry names (mmdet/datasets/pipelines/transforms.py,
 formatting.py, loading.py) so the reference's config files build unchanged.  Decoding image files
 (LoadImageFromFile) is outside this stage: sources arrive as uint8 HWC arrays.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -91,6 +93,38 @@ class RandomFlip(_Carrier):
 
 
 @PIPELINES.register_module()
+class PhotoMetricDistortion(_Carrier):
+    """transforms.py:1211-1312, the reference's constructor and defaults.  Runs inside the pixel pass at one of two
+    positions of the list (DevicePipeline.PHOTO_POSITIONS); its draws come from a sub-stream of the pipeline's
+    generator (include/yunet_hip.h YUNET_PHOTO_SALT)."""
+
+    def __init__(self, brightness_delta=32, contrast_range=(0.5, 1.5), saturation_range=(0.5, 1.5), hue_delta=18):
+        vals = [brightness_delta, *contrast_range, *saturation_range, hue_delta]
+        if len(vals) != 6 or not all(math.isfinite(float(v)) for v in vals):
+            raise ValueError('PhotoMetricDistortion: finite brightness_delta / hue_delta and (lower, upper) ranges')
+        if brightness_delta < 0 or hue_delta < 0:
+            raise ValueError(f'PhotoMetricDistortion: negative delta (brightness_delta={brightness_delta}, '
+                             f'hue_delta={hue_delta})')
+        if hue_delta > 360:
+            raise ValueError(f'PhotoMetricDistortion: hue_delta={hue_delta} exceeds the 360 degrees of a hue turn')
+        for name, (lo, hi) in (('contrast_range', contrast_range), ('saturation_range', saturation_range)):
+            if lo > hi:
+                raise ValueError(f'PhotoMetricDistortion: {name}={tuple((lo, hi))} has lower > upper')
+        super().__init__(brightness_delta=brightness_delta, contrast_range=tuple(contrast_range),
+                         saturation_range=tuple(saturation_range), hue_delta=hue_delta)
+        self.contrast_lower, self.contrast_upper = contrast_range
+        self.saturation_lower, self.saturation_upper = saturation_range
+
+    def c_cfg(self, position):
+        c = L.YunetPhotoCfg()
+        c.brightness_delta, c.hue_delta = float(self.brightness_delta), float(self.hue_delta)
+        c.contrast_lower, c.contrast_upper = float(self.contrast_lower), float(self.contrast_upper)
+        c.saturation_lower, c.saturation_upper = float(self.saturation_lower), float(self.saturation_upper)
+        c.position = position
+        return c
+
+
+@PIPELINES.register_module()
 class Normalize(_Carrier):
     def __init__(self, mean, std, to_rgb=True):
         if any(float(m) != 0.0 for m in mean) or any(float(s) != 1.0 for s in std) or to_rgb:
@@ -157,12 +191,28 @@ class DevicePipeline:
 
     ORDER = ['LoadImageFromFile', 'LoadAnnotations', 'RandomSquareCrop', 'Resize', 'RandomFlip',
              'Normalize', 'DefaultFormatBundle', 'Collect']
+    # PhotoMetricDistortion may stand, once, at one of two places of ORDER: before index 2 (pre: on the source image,
+    # the crop's pad fill is not distorted) or before index 5 (post: on the resized, flipped image, pad included)
+    PHOTO_POSITIONS = {2: L.PHOTO_PRE, 5: L.PHOTO_POST}
 
     def __init__(self, pipeline, seed=0, gmax=64, pad_value=128.0, max_attempts=250, max_retries=64):
         steps = [build_from_cfg(p, PIPELINES) if isinstance(p, dict) else p for p in pipeline]
         names = [type(s).__name__ for s in steps]
+        self.photo, self.photo_position, self.pparams = None, L.PHOTO_NONE, None
+        if 'PhotoMetricDistortion' in names:
+            at = names.index('PhotoMetricDistortion')
+            rest = names[:at] + names[at + 1:]
+            if names.count('PhotoMetricDistortion') > 1 or rest != self.ORDER or at not in self.PHOTO_POSITIONS:
+                raise NotImplementedError(
+                    'DevicePipeline runs PhotoMetricDistortion once, either between LoadAnnotations and '
+                    'RandomSquareCrop (pre) or between RandomFlip and Normalize (post), in the list '
+                    f'{self.ORDER}; got {names}')
+            self.photo, self.photo_position = steps[at], self.PHOTO_POSITIONS[at]
+            steps = steps[:at] + steps[at + 1:]
+            names = rest
         if names != self.ORDER:
-            raise NotImplementedError(f'DevicePipeline implements exactly {self.ORDER}; got {names}')
+            raise NotImplementedError(f'DevicePipeline implements exactly {self.ORDER} (with an optional '
+                                      f'PhotoMetricDistortion before RandomSquareCrop or after RandomFlip); got {names}')
         self.steps = steps
         by = dict(zip(names, steps))
         if not by['LoadAnnotations'].with_keypoints:
@@ -180,6 +230,7 @@ class DevicePipeline:
         cfg.flip_ratio, cfg.pad_value, cfg.seed = by['RandomFlip'].flip_ratio, pad_value, seed & 0xFFFFFFFF
         cfg.max_attempts, cfg.max_retries, cfg.gmax = max_attempts, max_retries, gmax
         self.cfg = cfg
+        self.photo_cfg = self.photo.c_cfg(self.photo_position) if self.photo is not None else None
         self.gmax = gmax
         self.params = None
 
@@ -192,9 +243,24 @@ class DevicePipeline:
         gb, gk, cnt, params = self._decide(src, iteration, dev)
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-        L.check(lib.yunet_aug_pixels(p(src.src), p(src.src_off), p(src.src_hw), p(params), C.byref(self.cfg), n,
-                                     p(img), stream), 'yunet_aug_pixels')
+        if self.photo is None:
+            L.check(lib.yunet_aug_pixels(p(src.src), p(src.src_off), p(src.src_hw), p(params), C.byref(self.cfg), n,
+                                         p(img), stream), 'yunet_aug_pixels')
+        else:
+            pp = self._photometric(n, iteration, dev)
+            L.check(lib.yunet_aug_pixels_photo(p(src.src), p(src.src_off), p(src.src_hw), p(params), p(pp),
+                                               self.photo_position, C.byref(self.cfg), n, p(img), stream),
+                    'yunet_aug_pixels_photo')
         return self._collate(img, gb, gk, cnt, params, dev)
+
+    def _photometric(self, n, iteration, dev):
+        """yunet_aug_photometric on the current stream, keyed like _decide -> the table [N, PHOTO_WORDS] fp32."""
+        pp = torch.empty(n, L.PHOTO_WORDS, device=dev, dtype=torch.float32)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        L.check(L.load().yunet_aug_photometric(C.byref(self.photo_cfg), self.cfg.seed, int(iteration) & 0xFFFFFFFF, n,
+                                               C.c_void_p(pp.data_ptr()), stream), 'yunet_aug_photometric')
+        self.pparams = pp
+        return pp
 
     def _decide(self, src, iteration, dev):
         """yunet_aug_decide on the current stream -> (padded boxes, padded keypoints, counts, params)."""
@@ -248,8 +314,14 @@ class DevicePipeline:
         gb, gk, cnt, params = self._decide(src, iteration, dev)
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-        L.check(lib.yunet_aug_pixels_window(p(win), p(win_off), p(rect), p(src.src_hw), p(params), C.byref(self.cfg),
-                                            n, p(img), stream), 'yunet_aug_pixels_window')
+        if self.photo is None:
+            L.check(lib.yunet_aug_pixels_window(p(win), p(win_off), p(rect), p(src.src_hw), p(params),
+                                                C.byref(self.cfg), n, p(img), stream), 'yunet_aug_pixels_window')
+        else:
+            pp = self._photometric(n, iteration, dev)
+            L.check(lib.yunet_aug_pixels_window_photo(p(win), p(win_off), p(rect), p(src.src_hw), p(params), p(pp),
+                                                      self.photo_position, C.byref(self.cfg), n, p(img), stream),
+                    'yunet_aug_pixels_window_photo')
         return self._collate(img, gb, gk, cnt, params, dev)
 
     def check(self):

@@ -13,7 +13,10 @@ configs/yunet_n.py (YuNet_n 320 x 320, 256 images per GPU) from three data sourc
   host_window_kernel                the same windows read by the GPU itself from the pinned store (yunet_fetch_windows on
             (+ host_fetch=kernel)   the copy stream, plan from device memory, no host wait)
 
-    python tools/train_e2e.py [--iters 200] [--out profiles/r06_train_e2e.json]
+    python tools/train_e2e.py [--iters 200] [--out profiles/r06_train_e2e.json] [--photometric pre|post]
+
+--photometric inserts the reference's PhotoMetricDistortion (default arguments) into the config's train_pipeline, before
+RandomSquareCrop (pre) or after RandomFlip (post); the modes other than `ready` then run it in the pixel pass.
 
 Prints / writes one JSON object: per mode images/s over the last three logging intervals (150 iterations), the runner's
 time per iteration, and the source's own events (upload ms / GB/s, pipeline ms).  Weights: the trained fixture
@@ -43,9 +46,17 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--modes', default=None,
                     help='comma-separated subset of ready,resident,host_fed,host_window,host_window_kernel')
+    ap.add_argument('--photometric', choices=('pre', 'post'), default=None)
     a = ap.parse_args()
     import torch
     T = load_train_tool()
+    config = a.config
+    if a.photometric:
+        at = {'pre': 2, 'post': 5}[a.photometric]
+        tmp = tempfile.NamedTemporaryFile('w', suffix='.py', delete=False)
+        tmp.write(open(a.config).read() + f"\ntrain_pipeline.insert({at}, dict(type='PhotoMetricDistortion'))\n")
+        tmp.close()
+        config = tmp.name
     fixture = os.path.join(ROOT, 'tests', 'golden', 'yunet_n_synth_trained.pth')
     modes = [('ready', ['data.train.type=SyntheticWiderFace', 'data.train.resident=2']),
              ('resident', ['data.train.type=SyntheticSourceImages', 'data.train.timing=True']),
@@ -56,17 +67,18 @@ def main():
                                      'data.train.host_fed=window', 'data.train.host_fetch=kernel'])]
     if a.modes:
         modes = [m for m in modes if m[0] in a.modes.split(',')]
-    res = {'what': __doc__.split('\n')[0], 'config': os.path.basename(a.config), 'iters': a.iters, 'modes': {}}
+    res = {'what': __doc__.split('\n')[0], 'config': os.path.basename(a.config), 'iters': a.iters,
+           'photometric': a.photometric, 'modes': {}}
     for name, opts in modes:
         with tempfile.TemporaryDirectory() as wd:
-            argv = [a.config, '--work-dir', wd, '--max-iters', str(a.iters), '--no-validate', '--seed', '0',
+            argv = [config, '--work-dir', wd, '--max-iters', str(a.iters), '--no-validate', '--seed', '0',
                     '--cfg-options', 'log_config.interval=50', f'load_from={fixture}'] + opts
             hist = T.main(argv)
             torch.cuda.synchronize()
         rows = [r for r in hist if 'time' in r]
         bs = None
         import yunet_amd
-        bs = yunet_amd.Config.fromfile(a.config).data.samples_per_gpu
+        bs = yunet_amd.Config.fromfile(config).data.samples_per_gpu
         steady = rows[1:] if len(rows) > 1 else rows          # the first interval holds start-up (plan build, first launches)
         t = sum(r['time'] for r in steady) / len(steady)
         m = {'ms_per_iter': round(1000 * t, 3), 'images_per_sec': round(bs / t, 1), 'batch': bs,
@@ -80,6 +92,8 @@ def main():
         del src
         T.main.last_source = None
         torch.cuda.empty_cache()
+    if config != a.config:
+        os.unlink(config)
     line = json.dumps(res)
     print(line)
     if a.out:
