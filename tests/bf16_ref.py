@@ -79,6 +79,21 @@ class BNRef:
         return F.relu(self.xhat(z) * self.gamma + self.beta)
 
 
+class RunningBNRef(BNRef):
+    """a BatchNorm in eval mode, applied directly as nn.BatchNorm2d.eval() does: (z - running_mean) /
+    sqrt(running_var + eps) gamma + beta.  No sums: a kernel that derives its coefficients from synthesised sums is
+    checked against this, not against its own recovery."""
+
+    def __init__(self, running_mean, running_var, gamma, beta, eps=1e-5):
+        self.rm, self.rv = running_mean.double().cpu(), running_var.double().cpu()
+        self.gamma, self.beta = gamma.double().cpu(), beta.double().cpu()
+        self.stats = self.bstats = None
+        self.eps = float(eps)
+
+    def mean_invstd(self):
+        return self.rm, 1.0 / torch.sqrt(self.rv + self.eps)
+
+
 def stats_of(z):
     z = z.double().reshape(-1, z.shape[-1])
     return torch.cat([z.sum(0), (z * z).sum(0)])

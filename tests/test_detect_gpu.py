@@ -99,17 +99,24 @@ def exact_heads(n, P, seed):
     return flat
 
 
-@pytest.mark.parametrize('h,n,seed', [(160, 6, 1), (320, 3, 2), (640, 2, 3), (1024, 2, 4), (1280, 1, 5)])
-def test_detect_kernel_vs_oracle_exact_geometry(h, n, seed):
+@pytest.mark.parametrize('h,w,n,seed', [pytest.param(h, h, n, seed, id=f'{h}-{n}-{seed}')
+                                         for h, n, seed in [(160, 6, 1), (320, 3, 2), (640, 2, 3), (1024, 2, 4),
+                                                            (1280, 1, 5)]] +
+                         [(1120, 1664, 1, 6), (704, 1024, 2, 7), (160, 1024, 2, 8), (1024, 160, 2, 9)])
+def test_detect_kernel_vs_oracle_exact_geometry(h, w, n, seed):
     """Thousands of candidates per image with heavy overlap (K exceeds the LDS box cache at 640):
     the survivors, their order and their boxes must be identical to the oracle's.
     1024: P = 21504 > 16384 priors (origin-size WIDER images, tools/test_widerface.py --mode 2) with
     ~16.1 k candidates -- compacted through the scratch, sorted in LDS; 1280: P = 33600 with ~25 k
-    candidates -- more than the LDS holds, sorted in the global scratch."""
-    sizes = C.featmap_sizes(h, h)
+    candidates -- more than the LDS holds, sorted in the global scratch.  Rectangles, the test-time geometries
+    (tools/test_widerface.py): 1120 x 1664 (--mode 1, P = 38220, the largest), original sizes padded to 32 (--mode 2)
+    with odd stride-32 levels, and a tall and a wide strip."""
+    sizes = C.featmap_sizes(h, w)
     P = sum(a * b for a, b in sizes)
+    if (h, w) == (1120, 1664):
+        assert P == 38220
     flat = exact_heads(n, P, seed)
-    dets, kps, cnt = _run_detect(flat, h, h)
+    dets, kps, cnt = _run_detect(flat, h, w)
     ref = D.get_bboxes(flat, sizes, [8, 16, 32], 0.02, 0.45)
     for i in range(n):
         c = int(cnt[i])

@@ -1,5 +1,7 @@
 """-m gpu: every HIP kernel of libyunet_hip.so, called through the C ABI, against a torch
 fp64 CPU restatement of the same op (floating-point kernels) -- tolerance stated per test."""
+from fractions import Fraction
+
 import numpy as np
 import pytest
 import torch
@@ -702,3 +704,167 @@ def test_add(n, shift):
     k.add(a2, b, a2)
     torch.cuda.synchronize()
     assert torch.equal(a2, a + b)
+
+
+# ------------------------------------------------------------------------------------------------ bn_batch_kernel
+# (C, slots, count) of the layers of one launch: C = 100 runs the 64-thread channel loop twice; counts 1 (no Bessel
+# factor), 2, and 256 * 160 * 160
+BN_LAYERS = [(16, 8, 1), (32, 1, 2), (64, 8, 6553600), (100, 8, 6553600), (100, 1, 2)]
+BN_GAP = 16             # canary elements between the layers' blocks
+CANARY = -12345.6875
+
+
+def _f32_exact(fr):
+    """a Fraction rounded once to fp32 (ties to even)"""
+    x = np.float32(float(fr))
+    cands = [np.nextafter(x, np.float32(-np.inf)), x, np.nextafter(x, np.float32(np.inf))]
+    err = [abs(Fraction(float(c)) - fr) for c in cands]
+    best = min(err)
+    ties = [c for c, e in zip(cands, err) if e == best]
+    return ties[0] if len(ties) == 1 else [c for c in ties if not (c.view(np.int32) & 1)][0]
+
+
+def _bn_sum_np(block, slots, C, i):
+    """common.h bn_sum: the first eight replicas pairwise, the rest in order"""
+    v = [block[k * 2 * C + i] if k < slots else 0.0 for k in range(8)]
+    r = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]))
+    for k in range(8, slots):
+        r += block[k * 2 * C + i]
+    return r
+
+
+def _bn_batch_setup(seed, adversarial=False):
+    """stats / running-stat / gradient buffers with canaries around every layer's region, and a table with one more
+    row than the launch covers (its regions must stay untouched)"""
+    g = np.random.default_rng(seed)
+    layers = BN_LAYERS + [(16, 8, 4)]                     # the last row: outside the launch
+    rows, so, ro, go = [], BN_GAP, BN_GAP, BN_GAP
+    for C, slots, count in layers:
+        rows.append([so, C, count, ro, go, go + C + BN_GAP, slots])
+        so += slots * 2 * C + BN_GAP
+        ro += C + BN_GAP
+        go += 2 * (C + BN_GAP)
+    stats = np.full(so, CANARY)
+    rm, rv, grad = np.full(ro, CANARY, np.float32), np.full(ro, CANARY, np.float32), np.full(go, CANARY, np.float32)
+    for (s0, C, count, r0, _, _, slots) in rows:
+        mean = g.normal(0.3, 2.0, C)
+        var = g.uniform(0.01, 5.0, C)
+        for k in range(slots):       # a batch's sums split over the replicas
+            share = g.dirichlet(np.ones(slots))[k] if slots > 1 else 1.0
+            stats[s0 + k * 2 * C:s0 + k * 2 * C + C] = share * mean * count
+            stats[s0 + k * 2 * C + C:s0 + (k + 1) * 2 * C] = share * (var + mean * mean) * count
+        if count > 1:              # channel 3 all in slot 0, with a variance of -1e-15 mean^2: clamped to 0
+            for k in range(1, slots):
+                stats[s0 + k * 2 * C + 3] = stats[s0 + k * 2 * C + C + 3] = 0.0
+            stats[s0 + C + 3] = stats[s0 + 3] ** 2 / count * (1 - 1e-15)
+        rm[r0:r0 + C] = g.normal(0.0, 1.0, C)
+        rv[r0:r0 + C] = g.uniform(0.1, 3.0, C)
+        if adversarial:
+            rm[r0], rv[r0] = 50.0, 1e-8
+            rm[r0 + 1], rv[r0 + 1] = -50.0, 1e-8
+            rv[r0 + 2] = 1e4
+    return rows, stats, rm, rv, grad
+
+
+def _launch_bn_batch(rows, n, stats, rm, rv, grad, momentum, mode):
+    import yunet_amd._lib as L
+    k = K()
+    t = torch.tensor(rows, dtype=torch.int32).to(DEV)
+    bufs = [torch.from_numpy(a.copy()).to(DEV) for a in (stats, rm, rv, grad)]
+    L.check(L.load().yunet_bn_batch(t.data_ptr(), n, bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(),
+                                    momentum, bufs[3].data_ptr(), mode, k._stream()), 'yunet_bn_batch')
+    torch.cuda.synchronize()
+    assert torch.equal(t.cpu(), torch.tensor(rows, dtype=torch.int32)), 'the table was written'
+    return [b.cpu().numpy() for b in bufs]
+
+
+def _untouched(name, got, want, written):
+    """every element outside `written` (a boolean mask) is bit-identical to what was there before the launch"""
+    keep = ~written
+    assert np.array_equal(got[keep].view(np.uint8), want[keep].view(np.uint8)), f'{name}: written outside the launch'
+
+
+def test_bn_batch_mode0_running_update():
+    """mode 0 (the step's running-statistics update) bit-exact: fp64 slot sums in bn_sum's order, mean and biased
+    variance in fp64 (var = fma(s2, 1/count, -mean^2), as compiled), the clamp, the Bessel factor only for count > 1,
+    then m' = (mom mean) + ((1 - mom) m) and v' = fma(mom, unbiased, (1 - mom) v) in fp32"""
+    rows, stats, rm, rv, grad = _bn_batch_setup(1)
+    n = len(BN_LAYERS)
+    mom = np.float32(0.1)
+    st_g, rm_g, rv_g, grad_g = _launch_bn_batch(rows, n, stats, rm, rv, grad, float(mom), 0)
+    wm, wv = rm.copy(), rv.copy()
+    written = np.zeros(rm.shape, bool)
+    one_m = np.float32(np.float32(1.0) - mom)
+    for (s0, C, count, r0, _, _, slots) in rows[:n]:
+        blk = stats[s0:s0 + slots * 2 * C]
+        inv = 1.0 / float(count)
+        for c in range(C):
+            s1, s2 = _bn_sum_np(blk, slots, C, c), _bn_sum_np(blk, slots, C, C + c)
+            mean = s1 * inv
+            var = float(Fraction(s2) * Fraction(inv) - Fraction(mean * mean))
+            var = max(var, 0.0)
+            unb = var * (float(count) / float(count - 1)) if count > 1 else var
+            wm[r0 + c] = np.float32(np.float32(mom * np.float32(mean)) + np.float32(one_m * rm[r0 + c]))
+            wv[r0 + c] = _f32_exact(Fraction(float(mom)) * Fraction(float(np.float32(unb))) +
+                                    Fraction(float(np.float32(one_m * rv[r0 + c]))))
+        written[r0:r0 + C] = True
+    assert rows[0][2] == 1 and rows[2][2] == 6553600
+    bad = np.nonzero((rm_g.view(np.int32) != wm.view(np.int32)) | (rv_g.view(np.int32) != wv.view(np.int32)))[0]
+    assert bad.size == 0, ('running stats not bit-exact at', bad[:8], rm_g[bad[:4]], wm[bad[:4]], rv_g[bad[:4]],
+                           wv[bad[:4]])
+    _untouched('running_mean', rm_g, rm, written)
+    _untouched('running_var', rv_g, rv, written)
+    assert np.array_equal(st_g.view(np.uint8), stats.view(np.uint8)), 'mode 0 wrote the sums'
+    assert np.array_equal(grad_g.view(np.uint8), grad.view(np.uint8)), 'mode 0 wrote the gradient'
+
+
+def test_bn_batch_mode1_param_grad():
+    """mode 1 (d(beta) = sum dy, d(gamma) = sum dy xhat) bit-exact: the slot sums in bn_sum's order cast to fp32"""
+    rows, stats, rm, rv, grad = _bn_batch_setup(2)
+    n = len(BN_LAYERS)
+    st_g, rm_g, rv_g, grad_g = _launch_bn_batch(rows, n, stats, rm, rv, grad, 0.0, 1)
+    want = grad.copy()
+    written = np.zeros(grad.shape, bool)
+    for (s0, C, count, r0, g_off, b_off, slots) in rows[:n]:
+        blk = stats[s0:s0 + slots * 2 * C]
+        for c in range(C):
+            want[b_off + c] = np.float32(_bn_sum_np(blk, slots, C, c))
+            want[g_off + c] = np.float32(_bn_sum_np(blk, slots, C, C + c))
+        written[b_off:b_off + C] = written[g_off:g_off + C] = True
+    bad = np.nonzero(grad_g.view(np.int32) != want.view(np.int32))[0]
+    assert bad.size == 0, ('parameter gradients not bit-exact at', bad[:8], grad_g[bad[:4]], want[bad[:4]])
+    _untouched('grad', grad_g, grad, written)
+    for name, a, b in (('stats', st_g, stats), ('running_mean', rm_g, rm), ('running_var', rv_g, rv)):
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), f'mode 1 wrote {name}'
+
+
+def test_bn_batch_mode2_synthesised_sums():
+    """mode 2 (eval): slot 0 = [m count | (v + m^2) count] exactly, replicas 1.. zeroed; recovered as common.h does,
+    the mean is running_mean to 1e-12 relative and the variance running_var to a few fp64 ulps of v + m^2 (|m| = 50 at
+    v = 1e-8 cancels to ~5e-13); invstd in fp32 within one ulp of 1 / sqrt(v + eps)"""
+    import eval_ref as E
+    rows, stats, rm, rv, grad = _bn_batch_setup(3, adversarial=True)
+    n = len(BN_LAYERS)
+    st_g, rm_g, rv_g, grad_g = _launch_bn_batch(rows, n, stats, rm, rv, grad, 0.0, 2)
+    written = np.zeros(stats.shape, bool)
+    worst = 0.0
+    for (s0, C, count, r0, _, _, slots) in rows[:n]:
+        m, v = rm[r0:r0 + C].astype(np.float64), rv[r0:r0 + C].astype(np.float64)
+        blk = st_g[s0:s0 + slots * 2 * C].reshape(slots, 2 * C)
+        assert np.array_equal(blk[0, :C], m * count), 'slot 0 sums'
+        assert np.array_equal(blk[0, C:], (v + m * m) * count), 'slot 0 sums of squares'
+        assert not blk[1:].any(), 'replicas 1.. not zeroed'
+        written[s0:s0 + slots * 2 * C] = True
+        mean, var, _ = E.recover(torch.from_numpy(blk.copy()), count)
+        mean, var = mean.numpy(), var.numpy()
+        assert np.all(np.abs(mean - m) <= 1e-12 * np.abs(m)), 'recovered mean'
+        ulps = np.abs(var - v) / (2.0 ** -52 * (v + m * m))
+        worst = max(worst, float(ulps.max()))
+        assert np.all(ulps <= 4), ('recovered variance', float(ulps.max()))
+        inv_k = (1.0 / np.sqrt(var + float(np.float32(1e-5)))).astype(np.float32)
+        inv_d = (1.0 / np.sqrt(v + 1e-5)).astype(np.float32)
+        assert np.all(np.abs(inv_k.astype(np.float64) - inv_d) <= np.spacing(inv_d).astype(np.float64)), 'invstd'
+    print(f'[bn_batch mode 2] worst recovered-variance error {worst:.3g} ulps of v + m^2')
+    _untouched('stats', st_g, stats, written)
+    for name, a, b in (('grad', grad_g, grad), ('running_mean', rm_g, rm), ('running_var', rv_g, rv)):
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), f'mode 2 wrote {name}'
