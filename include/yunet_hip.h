@@ -530,6 +530,39 @@ int yunet_fetch_windows(const uint8_t* host_src, long long store_bytes, const lo
                         const int32_t* rect, const long long* win_off, int N, uint8_t* win, long long win_bytes,
                         int32_t* status, void* stream);
 
+/* ---- custom training hooks (csrc/hooks.hip) -------------------------------------------------------------------------
+ * yunet_ema_update: ExpMomentumEMAHook / LinearMomentumEMAHook (mmdet/core/hook/ema.py) over up to
+ * YUNET_EMA_MAX_SEGMENTS flat fp32 segments in ONE launch:  ema_i[k] = fma(m, src_i[k], ema_i[k] * keep)  -- the
+ * rounding of torch's  ema.mul_(1 - momentum).add_(src, alpha=momentum)  on a ROCm fp32 tensor, with keep =
+ * (float)(1 - momentum) and m = (float)momentum formed on the host in double.  src, ema, n are HOST arrays of nseg
+ * entries (device pointers, 4-byte aligned; n[i] >= 0, n[i] == 0 allows NULL pointers).  16-byte accesses where
+ * src_i and ema_i share their alignment, scalar accesses otherwise.  YUNET_EINVAL (nothing launched) on a bad
+ * argument; nothing is launched when every n[i] is 0. */
+#define YUNET_EMA_MAX_SEGMENTS 3
+int yunet_ema_update(const float* const* src, float* const* ema, const long long* n, int nseg, float keep, float m,
+                     void* stream);
+/* yunet_box_size_hist: YuNetSampleSizeStatisticsHook's per-batch work on the device.  Box g < counts[n] of image n
+ * (boxes [N, Gmax, 4] fp32 xyxy, counts [N] int32, device) falls into bin (w, h) = (trunc(x2 - x1), trunc(y2 - y1))
+ * of a persistent grid [(H + 1) x (W + 1)] (row h, column w):  bin_count += 1  and  bin_first = min(bin_first,
+ * (iteration << 32) | (n * Gmax + g))  (64-bit integer atomics: the result does not depend on arrival order;
+ * bin_first starts at all ones).  totals[YUNET_HIST_TOTAL] counts every box, totals[YUNET_HIST_NOIMG] every image
+ * with counts[n] == 0.  A box whose (w, h) lies outside [0, W] x [0, H] (or is NaN) is not binned: it is appended to
+ * spill [spill_cap, 2] as (key, fp32 bits of w | fp32 bits of h << 32) at slot totals[YUNET_HIST_SPILLED]++ and
+ * YUNET_HIST_SPILL is OR-ed into totals[YUNET_HIST_STATUS]; past spill_cap YUNET_HIST_OVERFLOW is set instead.  A count
+ * outside [0, Gmax] is clamped and sets YUNET_HIST_BAD_COUNT.  All int64 arrays are device memory.  YUNET_EINVAL
+ * (nothing launched) on NULL pointers, N < 0, Gmax < 1, N * Gmax >= 2^31, W or H outside [0, 65535], iteration
+ * outside [0, 2^31), spill_cap < 0 (or spill == NULL with spill_cap > 0).  N == 0 launches nothing. */
+#define YUNET_HIST_TOTAL 0
+#define YUNET_HIST_NOIMG 1
+#define YUNET_HIST_SPILLED 2
+#define YUNET_HIST_STATUS 3
+#define YUNET_HIST_SPILL 1
+#define YUNET_HIST_OVERFLOW 2
+#define YUNET_HIST_BAD_COUNT 4
+int yunet_box_size_hist(const float* boxes, const int32_t* counts, int N, int Gmax, long long iteration, int W, int H,
+                        long long* bin_count, long long* bin_first, long long* totals, long long* spill, int spill_cap,
+                        void* stream);
+
 /* Measurement switches of the dispatchers (ABI 6).  The library reads the environment ONCE, the first time an
  * option is needed (YUNET_NO_PACK, YUNET_BWD_FP32MMA, YUNET_BWD64_NW, YUNET_EW_GRID, YUNET_DP_FWD_BLOCKS_PER_CU);
  * after that only this call changes them -- no launch calls getenv.  Names:

@@ -15,6 +15,9 @@ MAX_LEVELS = 5
 
 EINVAL, EOPCODE = -1, -2            # YUNET_EINVAL / YUNET_EOPCODE (include/yunet_hip.h)
 FETCH_BAD_RECT, FETCH_BAD_SRC, FETCH_BAD_DST = 1, 2, 4      # YUNET_FETCH_BAD_* (yunet_fetch_windows status bits)
+EMA_MAX_SEGMENTS = 3                                        # YUNET_EMA_MAX_SEGMENTS (yunet_ema_update)
+HIST_TOTAL, HIST_NOIMG, HIST_SPILLED, HIST_STATUS = 0, 1, 2, 3   # YUNET_HIST_* (yunet_box_size_hist totals[])
+HIST_SPILL, HIST_OVERFLOW, HIST_BAD_COUNT = 1, 2, 4             # its status bits
 T_IDENTITY, T_BNRELU = 0, 1
 F32, BF16 = 0, 1
 BOX_EIOU, BOX_DIOU, BOX_IOU_LINEAR, BOX_IOU_SQUARE, BOX_IOU_LOG, BOX_GIOU, BOX_CIOU = 0, 1, 2, 3, 4, 5, 6
@@ -145,6 +148,10 @@ _SIGNATURES = {
     'yunet_upload_windows': (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
     'yunet_fetch_windows': (C.c_int, [C.c_void_p, C.c_longlong] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_longlong,
                                                                          C.c_void_p, C.c_void_p]),
+    'yunet_ema_update': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), C.c_int,
+                                   C.c_float, C.c_float, C.c_void_p]),
+    'yunet_box_size_hist': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int] +
+                            [C.c_void_p] * 4 + [C.c_int, C.c_void_p]),
     'yunet_reduce_partials': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                         C.c_void_p]),
     'yunet_assign': (C.c_int, [C.c_void_p] * 5 + [C.POINTER(YunetLevels)] + [C.c_int] * 3 +

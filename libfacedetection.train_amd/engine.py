@@ -174,6 +174,42 @@ class FlatParams:
         for name, c in zip(layout.bn_names, self.bn_channels):
             self.bn_offset[name] = o
             o += c
+        # EMA mirror (the EMA hooks, hooks.py): same layouts, created on request by enable_ema()
+        self.ema_data = self.ema_running_mean = self.ema_running_var = self.ema_num_batches_tracked = None
+
+    def enable_ema(self, buffers=True):
+        """Allocate the EMA mirror: ema_data (the layout of `data`) and, with buffers=True, ema_running_mean /
+        ema_running_var / ema_num_batches_tracked.  Starts as a copy of the live values."""
+        self.ema_data = self.data.clone()
+        if buffers:
+            self.ema_running_mean = self.running_mean.clone()
+            self.ema_running_var = self.running_var.clone()
+            self.ema_num_batches_tracked = self.num_batches_tracked.clone()
+        else:
+            self.ema_running_mean = self.ema_running_var = self.ema_num_batches_tracked = None
+
+    def ema_pairs(self):
+        """(live, ema) flat tensor pairs of the mirror: the fp32 segments the EMA update averages, then (with buffers)
+        num_batches_tracked, which the epoch-end swap exchanges but the update leaves alone."""
+        if self.ema_data is None:
+            return [], []
+        f32 = [(self.data, self.ema_data)]
+        other = []
+        if self.ema_running_mean is not None:
+            f32 += [(self.running_mean, self.ema_running_mean), (self.running_var, self.ema_running_var)]
+            other = [(self.num_batches_tracked, self.ema_num_batches_tracked)]
+        return f32, other
+
+    def ema_view(self, key):
+        """The mirror's tensor for state_dict key `key` (a parameter or a BN running buffer)."""
+        if key in self.layout.entries:
+            return self.view(key, of=self.ema_data)
+        bn, kind = key.rsplit('.', 1)
+        i = self.layout.bn_names.index(bn)
+        if kind == 'num_batches_tracked':
+            return self.ema_num_batches_tracked[i]
+        o, c = self.bn_offset[bn], self.bn_channels[i]
+        return (self.ema_running_mean if kind == 'running_mean' else self.ema_running_var)[o:o + c]
 
     def view(self, key, of=None):
         off, shape = self.layout.entries[key]

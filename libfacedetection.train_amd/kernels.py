@@ -399,3 +399,43 @@ def sgd_step(params, grads, buf, lr_dev, momentum, weight_decay, grad_scale=1.0,
     L.check(L.load().yunet_sgd_step_ex(_p(params), _p(grads), _p(buf), params.numel(), _p(lr_dev),
                                        float(momentum), float(dampening), int(bool(nesterov)), float(weight_decay),
                                        float(grad_scale), int(first), _stream()), 'yunet_sgd_step_ex')
+
+
+def ema_coefficients(momentum):
+    """(keep, m) of the EMA hooks: 1 - momentum in double, as the reference's python does, then both as fp32 -- what
+    torch's  ema.mul_(1 - momentum).add_(src, alpha=momentum)  hands its fp32 kernels."""
+    momentum = float(momentum)
+    return C.c_float(1.0 - momentum).value, C.c_float(momentum).value
+
+
+def ema_update(pairs, momentum):
+    """ema <- ema * (1 - momentum) + momentum * src over up to three (src, ema) pairs of fp32 CUDA tensors (contiguous
+    views of any offset), ONE launch on the current stream (yunet_ema_update)."""
+    if not 1 <= len(pairs) <= L.EMA_MAX_SEGMENTS:
+        raise ValueError(f'ema_update: 1..{L.EMA_MAX_SEGMENTS} segments, got {len(pairs)}')
+    for s, e in pairs:
+        _chk_f32(s, e)
+        if s.numel() != e.numel():
+            raise ValueError('ema_update: src and ema differ in size')
+    k = len(pairs)
+    src = (C.c_void_p * k)(*[s.data_ptr() for s, _ in pairs])
+    ema = (C.c_void_p * k)(*[e.data_ptr() for _, e in pairs])
+    n = (C.c_longlong * k)(*[s.numel() for s, _ in pairs])
+    keep, m = ema_coefficients(momentum)
+    L.check(L.load().yunet_ema_update(src, ema, n, k, keep, m, _stream()), 'yunet_ema_update')
+
+
+def box_size_hist(boxes, counts, iteration, bin_count, bin_first, totals, spill):
+    """One batch of GT boxes into the persistent (w, h) grid of YuNetSampleSizeStatisticsHook (yunet_box_size_hist):
+    boxes [N, Gmax, 4] fp32 and counts [N] int32 on the device; bin_count / bin_first [(H + 1), (W + 1)] int64,
+    totals [4] int64, spill [cap, 2] int64.  One launch on the current stream, no host sync."""
+    _chk_f32(boxes)
+    assert boxes.dim() == 3 and boxes.shape[2] == 4, 'boxes: [N, Gmax, 4]'
+    assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == boxes.shape[0]
+    for t in (bin_count, bin_first, totals, spill):
+        assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous(), 'expected a contiguous int64 CUDA tensor'
+    assert bin_count.shape == bin_first.shape and bin_count.dim() == 2 and totals.numel() == 4
+    h1, w1 = bin_count.shape
+    L.check(L.load().yunet_box_size_hist(_p(boxes), _p(counts), boxes.shape[0], boxes.shape[1], int(iteration), w1 - 1,
+                                         h1 - 1, _p(bin_count), _p(bin_first), _p(totals), _p(spill),
+                                         spill.shape[0], _stream()), 'yunet_box_size_hist')

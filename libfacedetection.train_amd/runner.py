@@ -308,10 +308,22 @@ def save_checkpoint(model, optimizer, path, meta):
     torch.save(dict(meta=meta, state_dict=sd, optimizer=optimizer.state_dict()), path)
 
 
+def load_model_state(target, sd, strict=True):
+    """target.load_state_dict(sd, strict) that skips the EMA hooks' `ema_*` entries only one side has, with a warning
+    (yunet.skip_ema_entries; YuNet registers it on itself, any other module gets it for this call).  Every other key
+    stays strict."""
+    from .yunet import skip_ema_entries
+    handle = target.register_load_state_dict_post_hook(skip_ema_entries)
+    try:
+        return target.load_state_dict(sd, strict=strict)
+    finally:
+        handle.remove()
+
+
 def load_checkpoint(model, path, optimizer=None, strict=True):
     ck = torch.load(path, map_location='cpu', weights_only=False)
     target = model.module if hasattr(model, 'module') else model
-    target.load_state_dict(ck['state_dict'] if 'state_dict' in ck else ck, strict=strict)
+    load_model_state(target, ck['state_dict'] if 'state_dict' in ck else ck, strict=strict)
     if optimizer is not None:
         if isinstance(ck.get('optimizer'), dict):
             optimizer.load_state_dict(ck['optimizer'])
@@ -620,7 +632,7 @@ class EpochBasedRunner:
         self._max_epochs, self._max_iters = max_epochs, max_iters
         self.epoch, self.iter, self.inner_iter = 0, 0, 0
         self.hooks, self.outputs, self.log_buffer = [], None, []
-        self.data_source, self.device = None, 'cuda'
+        self.data_source, self.device, self.data_batch = None, 'cuda', None
 
     @property
     def max_epochs(self):
@@ -693,10 +705,12 @@ class EpochBasedRunner:
         self.call_hook('before_train_epoch')
         for i in range(data_source.iters_per_epoch):
             self.inner_iter = i
+            # mmcv's EpochBasedRunner.train: the batch is runner.data_batch before the before_train_iter hooks run
+            self.data_batch = data_source.batch(self.iter, self.device)
             self.call_hook('before_train_iter')
-            batch = data_source.batch(self.iter, self.device)
-            self.outputs = self.model.train_step(batch, self.optimizer)
+            self.outputs = self.model.train_step(self.data_batch, self.optimizer)
             self.call_hook('after_train_iter')
+            self.data_batch = None
             self.iter += 1
             if self._max_iters is not None and self.iter >= self._max_iters:
                 return False
@@ -839,3 +853,7 @@ def train_detector(model, dataset, cfg, distributed=False, validate=False, times
     elif cfg.get('load_from'):
         runner.load_checkpoint(cfg.load_from)
     return runner.run([dataset], cfg.get('workflow', [('train', 1)]), device=device)
+
+
+# the reference's custom hooks (mmdet/core/hook/: EMA, box-size statistics, loss check) register themselves in HOOKS
+from . import hooks  # noqa: E402,F401

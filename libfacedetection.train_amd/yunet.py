@@ -57,6 +57,24 @@ def bbox_mapping_back(bboxes, meta):
     return b / (sf if sf.numel() == 4 else sf[:1])
 
 
+def skip_ema_entries(module, incompatible_keys):
+    """load_state_dict post-hook: `ema_*` entries (the EMA hooks' buffers, hooks.BaseEMAHook) that only the checkpoint
+    or only the model has are dropped from the unexpected / missing keys, with a warning naming how many -- what mmcv's
+    load_checkpoint(strict=False) gives the reference for an EMA checkpoint loaded into a model without the hook, or a
+    resume that runs before the hook's before_run (which is why the hook has its own resume_from).  Any other mismatch
+    still fails a strict load."""
+    extra = [k for k in incompatible_keys.unexpected_keys if k.startswith('ema_')]
+    missing = [k for k in incompatible_keys.missing_keys if k.startswith('ema_')]
+    if not extra and not missing:
+        return
+    for k in extra:
+        incompatible_keys.unexpected_keys.remove(k)
+    for k in missing:
+        incompatible_keys.missing_keys.remove(k)
+    warnings.warn(f'{type(module).__name__}.load_state_dict: {len(extra)} unexpected and {len(missing)} missing '
+                  f'ema_* entries skipped (EMA hook state)')
+
+
 class LazyScalar:
     """A logged loss value that is copied to the host asynchronously and only waited for
     when somebody reads it (the reference calls .item() five times per iteration,
@@ -133,6 +151,8 @@ class YuNet(nn.Module):
         self._world, self._group = 1, None
         self._anchor = None
         self.init_weights(pretrained)
+        # checkpoints with the EMA hooks' ema_* entries load everywhere a YuNet is loaded (train, test, export tools)
+        self.register_load_state_dict_post_hook(skip_ema_entries)
 
     # ------------------------------------------------------------------ mmdet surface
     @property
@@ -299,12 +319,48 @@ class YuNet(nn.Module):
             mod._buffers['running_var'] = fp.running_var[o:o + c]
             mod._buffers['num_batches_tracked'] = fp.num_batches_tracked[i]
         self.engine = eng
+        self.bind_ema()
         self._maybe_oneshot()
         self._anchor = torch.zeros(1, device=device, requires_grad=True)
         self._log_host = torch.zeros(256, 8, dtype=torch.float32).pin_memory()
         self._log_iter = 0
         self._log_pending = None
         return eng
+
+    @staticmethod
+    def ema_name(key):
+        """Buffer name of the EMA copy of state_dict entry `key` (mmdet/core/hook/ema.py: '.' -> '_')."""
+        return 'ema_' + key.replace('.', '_')
+
+    def bind_ema(self):
+        """Re-point the EMA hooks' `ema_*` buffers (hooks.BaseEMAHook.before_run: one per state_dict entry, or per
+        parameter with skip_buffers=True) into the engine's flat EMA mirror (FlatParams.enable_ema), the way
+        bind_engine re-points the parameters and BN buffers: one fused launch then updates all of them, and
+        state_dict() carries them under the reference's names.  The values the buffers hold -- registered before the
+        engine existed, loaded from a checkpoint, or those of a previous binding -- are copied in.  Returns whether a
+        mirror is bound (False: no engine, or no ema_ buffers)."""
+        eng = self.engine
+        if eng is None:
+            return False
+        fp = eng.params
+        params = [n for n, _ in self.named_parameters()]
+        bufs = [f'{bn}.{k}' for bn in fp.layout.bn_names for k in ('running_mean', 'running_var', 'num_batches_tracked')]
+        hp = [self.ema_name(k) in self._buffers for k in params]
+        hb = [self.ema_name(k) in self._buffers for k in bufs]
+        if not any(hp) and not any(hb):
+            return False
+        if not all(hp) or (any(hb) and not all(hb)):
+            raise RuntimeError('ema_ buffers for a part of the state_dict only: the EMA mirror covers every parameter '
+                               '(and every BatchNorm buffer, or none of them)')
+        keys = params + (bufs if all(hb) else [])
+        old = {k: self._buffers[self.ema_name(k)] for k in keys}
+        fp.enable_ema(buffers=all(hb))
+        with torch.no_grad():
+            for k in keys:
+                v = fp.ema_view(k)
+                v.copy_(old[k].reshape(v.shape))
+                self._buffers[self.ema_name(k)] = v
+        return True
 
     # ------------------------------------------------------------------ logged scalars
     def _log_copy(self, rec, src):
