@@ -19,7 +19,9 @@ The timed window is exactly K = --steps steps after W = --warmup untimed ones; `
 --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64 losses, float32 gradients and
 post-update state): the inputs depend only on the arguments, so two builds can be compared output for output.
 
-Extra objects on that line (N=1 only):
+A plain run does only what the headline needs: set-up, the W warm-up steps, the K timed steps, the dump, the line.
+--full measures the rest after the timed window (nothing it does changes `value`, `ms_per_step` or the dump); the
+--no-* switches leave single parts of it out.  Extra objects on the line with --full (N=1 only):
   roofline     -- the dominant kernel FAMILY of the step (all template instances of one __global__ function, e.g. the
                   four of dp_bwd64_kernel), every launch timed with events on the launch stream; achieved = the family's
                   algorithmic bytes / its time; `instances` keeps the per-instance table; `step_frac` = the whole step's
@@ -27,8 +29,10 @@ Extra objects on that line (N=1 only):
   cpu_baseline -- the reference's own step (oracle/_ref under the mmcv stub; kind "reference") timed on this host's cores
                   over a bounded sample, `gpu_eager` = the same unmodified reference code on the MI355X through stock
                   PyTorch-ROCm ops (the "un-accelerated GPU" row of BASELINE.md)
-N > 1: after the RCCL window the same window runs again through the one-shot all-reduce (csrc/collective.hip) when its
-self-check passes; both are printed under `dist` (`value` stays the RCCL figure -- the default path).
+  exact_fp32_bwd -- the step once more with every backward GEMM on the exact fp32 matrix instruction (fp32 line only)
+  other_configs  -- 50-step windows of BASELINE.json configs[2..4] (after the headline configuration only)
+N > 1 with --full: after the RCCL window the same window runs again through the one-shot all-reduce
+(csrc/collective.hip) when its self-check passes; both are printed under `dist` (`value` stays the RCCL figure).
 """
 import argparse
 import ctypes as C
@@ -63,16 +67,19 @@ def parse():
                    help='accepted for older scripts: the timed window is always exactly --steps steps')
     p.add_argument('--dump-outputs', metavar='DIR', default=None,
                    help='write the last timed step\'s losses, gradients and updated state as DIR/<name>.npy')
-    p.add_argument('--no-cpu-baseline', action='store_true')
+    p.add_argument('--full', action='store_true',
+                   help='after the timed window, also measure roofline + per-kernel tables, exact_fp32_bwd, '
+                        'other_configs and cpu_baseline (N=1) or the one-shot all-reduce window (N>1)')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='--full without cpu_baseline')
     p.add_argument('--cpu-baseline-only', action='store_true', help=argparse.SUPPRESS)
     p.add_argument('--gpu-eager-only', action='store_true', help=argparse.SUPPRESS)
     p.add_argument('--no-gpu-eager', action='store_true',
-                   help='skip the un-accelerated-GPU row (the oracle\'s eager torch ops on cuda:0)')
-    p.add_argument('--no-roofline', action='store_true')
+                   help='--full without the un-accelerated-GPU row (the oracle\'s eager torch ops on cuda:0)')
+    p.add_argument('--no-roofline', action='store_true', help='--full without roofline and the per-kernel tables')
     p.add_argument('--no-other-configs', action='store_true',
-                   help='skip the 50-step windows of BASELINE.json configs[2..4] after the headline')
+                   help='--full without the 50-step windows of BASELINE.json configs[2..4] after the headline')
     p.add_argument('--no-exact-bwd', action='store_true',
-                   help='skip the second timing with the exact-fp32 backward matrix instruction (exact_fp32_bwd)')
+                   help='--full without the second timing with the exact-fp32 backward matrix instruction (exact_fp32_bwd)')
     p.add_argument('--no-live-traffic', action='store_true',
                    help='roofline.traffic from the committed profiles/ table instead of two live rocprofv3 --pmc passes')
     p.add_argument('--weights', default='trained', choices=['trained', 'init'],
@@ -800,7 +807,7 @@ def main():
                                    ('fp32 (64->64 backward GEMMs: two-way bf16 split -- measured against the exact-fp32 instruction: every output '
                                     'within 9e-6 of its tensor maximum, 50 SGD iterations end as far from the exact path as a '
                                     'last-bit perturbation of it does, tests/test_precision_gpu.py + profiles/r05_precision.json; '
-                                    'the strictly-fp32 variant is timed in exact_fp32_bwd)'
+                                    'the strictly-fp32 variant is timed in exact_fp32_bwd with --full)'
                                     if a.dtype == 'f32' else
                                     'bf16 activations + bf16 forward matrix instruction, fp32 gradients / weights') +
                                    ': fwd + SimOTA + losses + bwd + grad all-reduce + SGD, synthetic WIDER-Face-shaped '
@@ -822,7 +829,7 @@ def main():
                      'note': 'num_pos (4 B) | gradient bucket A on a side stream under the backward '
                              'kernels of the early stages | bucket B + the 5 logged scalars'},
         }
-    if world > 1 and os.environ.get('YUNET_BENCH_ONESHOT', '1') != '0':
+    if world > 1 and a.full and os.environ.get('YUNET_BENCH_ONESHOT', '1') != '0':
         # The same window once more with the three collectives on the one-shot all-reduce over peer-mapped inboxes
         # (csrc/collective.hip), so that ONE multi-GPU run answers "RCCL or one-shot for bucket B / num_pos" (VERDICT r4
         # next 8).  `value` above stays the RCCL figure.  Guards: enable_oneshot() self-checks against the process
@@ -868,7 +875,7 @@ def main():
             done.set()
         if rank == 0:
             res['dist']['oneshot'] = one
-    if rank == 0 and world == 1 and not a.no_roofline:
+    if rank == 0 and world == 1 and a.full and not a.no_roofline:
         agg = profile_ops(model.engine)
         tot = sum(v['ms'] for v in agg.values())
         # The dominant kernel is chosen per __global__ FAMILY: one function split over template instances
@@ -946,7 +953,7 @@ def main():
         res['families'] = {k: {'launches': v['launches'], 'ms': round(v['ms'], 4),
                                'frac': round(v['bytes'] / (v['ms'] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if v['ms'] > 0 else 0}
                            for k, v in sorted(fam.items(), key=lambda kv: -kv[1]['ms'])[:8]}
-    if rank == 0 and world == 1 and a.dtype == 'f32' and not a.no_exact_bwd:
+    if rank == 0 and world == 1 and a.full and a.dtype == 'f32' and not a.no_exact_bwd:
         # the same step with the 64->64 backward GEMMs on the EXACT fp32 matrix instruction
         # (the dispatcher option "bwd_fp32mma", include/yunet_hip.h: yunet_set_option): the number the headline
         # would be without the split-bf16 gradient GEMMs
@@ -966,7 +973,7 @@ def main():
                                  'value': round(a.batch * a.steps / dte, 1), 'unit': 'images/sec',
                                  'what': 'same run, option bwd_fp32mma=1: every backward GEMM on v_mfma_f32_16x16x4_f32'}
     headline = (a.kind, a.size, a.batch, a.dtype, a.weights) == (KIND, H, BATCH, 'f32', 'trained')
-    if rank == 0 and world == 1 and headline and not a.no_other_configs:
+    if rank == 0 and world == 1 and a.full and headline and not a.no_other_configs:
         # BASELINE.json configs[2] / [3] / [4] on one GPU, 50-step windows in this same process
         del wrapped, opt, pool
         model.engine.release() if hasattr(model.engine, 'release') else None
@@ -981,7 +988,7 @@ def main():
             except Exception as e:                           # a side measurement must not cost the headline line
                 res['other_configs'][name] = {'error': repr(e)[:200]}
         model = wrapped = opt = pool = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         res['cpu_baseline'] = cpu_baseline(a.kind, a.size)
         if not a.no_gpu_eager:
             model = wrapped = opt = pool = None    # hand the GPU to the child process

@@ -1,6 +1,7 @@
-"""-m gpu: bench.py's timed window and --dump-outputs.  `steps` / `ms_per_step` describe exactly the --steps steps that
-were timed, and the dump holds what the last of them handed its caller (losses, gradients, updated state), with the
-same inputs -- hence the same outputs up to the summation order of the fp64 atomics -- from run to run."""
+"""-m gpu: bench.py's timed window, --dump-outputs and a plain run without --full.  `steps` / `ms_per_step` describe
+exactly the --steps steps that were timed, and the dump holds what the last of them handed its caller (losses,
+gradients, updated state), with the same inputs -- hence the same outputs up to the summation order of the fp64
+atomics -- from run to run."""
 import json
 import os
 import subprocess
@@ -15,8 +16,8 @@ ARGS = ['--steps', '3', '--warmup', '1', '--batch', '32', '--no-cpu-baseline', '
         '--no-exact-bwd', '--no-gpu-eager']
 
 
-def _bench(out_dir):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), *ARGS, '--dump-outputs', str(out_dir)],
+def _bench(out_dir, args=ARGS):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), *args, '--dump-outputs', str(out_dir)],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -54,3 +55,13 @@ def test_bench_times_exactly_the_requested_steps_and_dumps_the_last_one(tmp_path
     for k, v in got.items():
         scale = float(np.abs(v).max()) if v.size else 0.0
         assert np.abs(again[k].astype(np.float64) - v).max(initial=0.0) <= 1e-5 * scale + 1e-9, k
+
+
+def test_plain_run_measures_the_headline_only(tmp_path):
+    """Without --full (and without any --no-* switch) the run is set-up, warm-up, the timed window, the dump and the
+    line: none of the side measurements that --full adds after the window."""
+    res, got = _bench(tmp_path / 'plain', ['--steps', '2', '--warmup', '1', '--batch', '32'])
+    assert {'metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'final_loss'} <= set(res)
+    assert res['steps'] == 2 and res['warmup'] == 1 and res['dtype'] == 'f32' and res['higher_is_better'] is True
+    assert not {'roofline', 'kernels', 'families', 'exact_fp32_bwd', 'other_configs', 'cpu_baseline'} & set(res), res
+    assert float(got['loss']) == pytest.approx(res['final_loss'], abs=1e-4)

@@ -197,7 +197,7 @@ def test_bench_two_ranks_share_one_gpu_over_gloo():
     env = dict(os.environ, YUNET_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0', OMP_NUM_THREADS='2')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node=2', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port_cli()), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '6',
-           '--warmup', '3', '--batch', '64']
+           '--warmup', '3', '--batch', '64', '--full']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]

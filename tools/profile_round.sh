@@ -8,8 +8,8 @@ R=${1:-r05}
 OUT=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-# (the driver's own line: --steps 20 --warmup 5; bench.py extends the timed window to >= 0.5 s itself)
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/${R}_bench.json
+# (the headline line with every side measurement: roofline, exact_fp32_bwd, other_configs, cpu_baseline)
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 > $OUT/${R}_bench.json
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$R -o $R -- \
     python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --exact-steps --no-cpu-baseline --no-roofline --no-exact-bwd --no-other-configs > /tmp/prof_$R.log 2>&1
@@ -54,7 +54,7 @@ python $GRAFT_REPO_ROOT/tools/pmc_mean.py $OUT/${R}_util.json $UT
 fi
 #   5. the second bench line (bf16 activations / bf16 forward matrix instruction, fp32 gradients)
 cd $GRAFT_REPO_ROOT
-timeout 300 python bench.py --dtype bf16 --steps 30 --warmup 10 --no-cpu-baseline --no-gpu-eager 2>/dev/null | tail -1 > $OUT/${R}_bench_bf16.json
+timeout 300 python bench.py --dtype bf16 --steps 30 --warmup 10 --full --no-cpu-baseline --no-gpu-eager 2>/dev/null | tail -1 > $OUT/${R}_bench_bf16.json
 [ -n "$QUICK" ] && exit 0
 #   6. torch-free kernel A/B at sustained clocks (tools/ubench/bwd_ab), every variant a copy of THIS library (the
 #      environment switches are read once per library instance): the exact-fp32 matrix path (= the yardstick),

@@ -7,7 +7,7 @@ SHOW=${SHOW:-"bwd16s stem"}
 for rep in 1 2; do
 for cfg in "$@"; do
   echo "== [$rep] $cfg" >> $L
-  env $cfg timeout 200 python bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-other-configs --no-exact-bwd --no-live-traffic 2>/dev/null | tail -1 | python -c "
+  env $cfg timeout 200 python bench.py --steps 40 --warmup 10 --full --no-cpu-baseline --no-other-configs --no-exact-bwd --no-live-traffic 2>/dev/null | tail -1 | python -c "
 import json,sys
 b=json.loads(sys.stdin.read())
 print(b['ms_per_step'], b['value'])
