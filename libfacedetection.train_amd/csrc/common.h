@@ -72,26 +72,14 @@ __device__ __forceinline__ float act_round(float v) {
 // tensor, nothing of it survives in a cache until its consumer runs) are better kept out of the 4 MB L2 of their XCD, where
 // they push out the halo rows the neighbouring tiles are about to re-read: dp_bwd64 -1.5 .. -3 %, step -0.5 %.  The forward
 // units' z stores are NOT: on the 40 x 40 and smaller maps the next forward kernel finds them in the L2 / infinity cache, and
-// with nt the ten plain 64 -> 64 forward launches got 4 % slower.  YUNET_ST_AUX: forward stores (default policy);
-// YUNET_DX_AUX: backward dx stores on unpacked maps.
-#ifndef YUNET_ST_AUX
-#define YUNET_ST_AUX 0
-#endif
-#ifndef YUNET_DX_AUX
-#define YUNET_DX_AUX 2
-#endif
-// 4 consecutive channels through a buffer descriptor (byte offset; out-of-range offsets read 0 / drop)
-template <typename R>
+// with nt the ten plain 64 -> 64 forward launches got 4 % slower.  ST_AUX: forward stores (default policy);
+// DX_AUX: backward dx stores on unpacked maps.
+constexpr int ST_AUX = 0;
+constexpr int DX_AUX = 2;
+// 4 consecutive channels through a buffer descriptor (byte offset; out-of-range offsets read 0 / drop), with
+// cache-policy bits AUX (2: non-temporal -- a tensor a kernel reads exactly once)
+template <int AUX = 0, typename R>
 __device__ __forceinline__ act_raw4 act_bufld4(R rsrc, unsigned byte_off) {
-#ifdef YUNET_ACT_BF16
-    return __builtin_amdgcn_raw_buffer_load_b64(rsrc, byte_off, 0, 0);
-#else
-    return __builtin_amdgcn_raw_buffer_load_b128(rsrc, byte_off, 0, 0);
-#endif
-}
-// the same load with cache-policy bits (AUX = 2: non-temporal -- a tensor a kernel reads exactly once)
-template <int AUX, typename R>
-__device__ __forceinline__ act_raw4 act_bufld4_aux(R rsrc, unsigned byte_off) {
 #ifdef YUNET_ACT_BF16
     return __builtin_amdgcn_raw_buffer_load_b64(rsrc, byte_off, 0, AUX);
 #else
@@ -101,9 +89,9 @@ __device__ __forceinline__ act_raw4 act_bufld4_aux(R rsrc, unsigned byte_off) {
 template <typename R>
 __device__ __forceinline__ void act_bufst4(R rsrc, unsigned byte_off, const float4 v) {
 #ifdef YUNET_ACT_BF16
-    __builtin_amdgcn_raw_buffer_store_b64(act_pack(v), rsrc, byte_off, 0, YUNET_ST_AUX);
+    __builtin_amdgcn_raw_buffer_store_b64(act_pack(v), rsrc, byte_off, 0, ST_AUX);
 #else
-    __builtin_amdgcn_raw_buffer_store_b128(act_pack(v), rsrc, byte_off, 0, YUNET_ST_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(act_pack(v), rsrc, byte_off, 0, ST_AUX);
 #endif
 }
 // the same through plain pointers (element-wise kernels)
@@ -119,12 +107,9 @@ __device__ __forceinline__ void act_st4(act_t* p, const float4 v) {
 // columns) always run on OTHER XCDs and the halo is fetched once per L2.  first_tile() renumbers the
 // workgroups so that each XCD walks a contiguous run of tiles: neighbours are in flight on the same
 // XCD at the same time and the second reader of a halo line hits that XCD's L2.
-#ifndef YUNET_XCD_REMAP
-#define YUNET_XCD_REMAP 1
-#endif
 __device__ __forceinline__ int first_tile() {
     const int g = (int)gridDim.x, b = (int)blockIdx.x;
-    if (YUNET_XCD_REMAP && (g & 7) == 0) return (b & 7) * (g >> 3) + (b >> 3);
+    if ((g & 7) == 0) return (b & 7) * (g >> 3) + (b >> 3);
     return b;
 }
 

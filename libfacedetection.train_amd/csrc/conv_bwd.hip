@@ -16,50 +16,8 @@
 
 namespace {
 
-// cache-policy bits of the generic tile kernel's x loads on unpacked maps (x is read once: tile interior only; 2 = non-temporal)
-#ifndef YUNET_BWDT_X_AUX
-#define YUNET_BWDT_X_AUX 0
-#endif
 #define BWD_THREADS 512
 #define BWD_WAVES 8
-// Where the split-bf16 variant issues the next tile's global loads: 1 = right after the stage (the
-// loads have the whole tile to land, 64 more live registers in the p GEMM and the VALU phase),
-// 0 = after the VALU phase like the fp32 variant (whose two long GEMMs follow and cover the latency)
-#ifndef DP_BWD_PF_EARLY
-#define DP_BWD_PF_EARLY 0
-#endif
-#ifndef DP_BWD_PF_SPREAD
-#define DP_BWD_PF_SPREAD 1
-#endif
-#ifndef DP_BWD_PF_LATE              // round 6: every piece one issue point later (the last one between the da GEMM and the mask)
-#define DP_BWD_PF_LATE 0
-#endif
-#ifndef DP_BWD_PF_SPREAD_ALL        // also for the exact-fp32 variants (16 / 32-channel units)
-#define DP_BWD_PF_SPREAD_ALL 0
-#endif
-// -DDP_BWD_PROF: per-workgroup phase cycle counters (tools/ubench/bwd_ab: PROF=1).  d.prof then points to
-// [grid][8] uint64: cycles of wave 0 between the barriers that end stage | p GEMM | depthwise | dW1 + da |
-// mask | store, summed over the workgroup's tiles.  Not in the product build (it costs registers).
-#ifdef DP_BWD_PROF
-#define DP_BWD_STAMP(k)                                                        \
-    if (prof_on && threadIdx.x == 0) {                                         \
-        const unsigned long long now_ = __builtin_readcyclecounter();          \
-        prof_acc[k] += now_ - prof_t;                                          \
-        prof_t = now_;                                                         \
-    }
-#else
-#define DP_BWD_STAMP(k)
-#endif
-#ifdef DP_BWD_PROF
-#define DP_BWD64_STAMP(k)                                                      \
-    if (prof_on && threadIdx.x == 0) {                                         \
-        const unsigned long long now_ = __builtin_readcyclecounter();          \
-        s_prof[k] += now_ - s_prof[7];                                         \
-        s_prof[7] = now_;                                                      \
-    }
-#else
-#define DP_BWD64_STAMP(k)
-#endif
 
 // GEMM = 0: the three pointwise GEMMs on the exact-fp32 matrix instruction (v_mfma_f32_16x16x4_f32).
 // GEMM = 1: split-bf16 -- every fp32 operand x is split on the fly into hi = bf16(x) and
@@ -200,9 +158,6 @@ __global__ __launch_bounds__(BWD_THREADS) void dp_bwd_kernel(const YunetDP d, co
     // debug ablation mask (tools/kbench.py --ablate): prof < 4096 is a bit mask, not a pointer
     const unsigned abl = (unsigned long long)d.prof < 4096ull ? (unsigned)(unsigned long long)d.prof : 0u;
 
-#ifdef DP_BWD_PROF
-    const unsigned long long prof_t0 = __builtin_readcyclecounter();
-#endif
     // per-image tiling, or (PACKED) one tile grid over the packed canvas of all images (common.h)
     const int tiles_x = ((PACKED ? pk.CW : W) + TW - 1) / TW, tiles_y = ((PACKED ? pk.CH : H) + TH - 1) / TH;
     const int tiles_img = tiles_x * tiles_y;
@@ -311,7 +266,7 @@ __global__ __launch_bounds__(BWD_THREADS) void dp_bwd_kernel(const YunetDP d, co
             } else {
                 off = (FULL || (y < H && x < W)) ? (unsigned)((y * W + x) * CIN + ich4 * 4) * ACT_B : xbytes;
             }
-            px[i] = PACKED ? act_bufld4(r_x, off) : act_bufld4_aux<YUNET_BWDT_X_AUX>(r_x, off);
+            px[i] = act_bufld4(r_x, off);
             if constexpr (PACKED) __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -402,14 +357,8 @@ __global__ __launch_bounds__(BWD_THREADS) void dp_bwd_kernel(const YunetDP d, co
 
     // next tile's loads in four pieces (measured: -8 % on 16->16 at 160x160, -6 % on 16->64, +2 % on the
     // 64->16 heads, which keep the single issue)
-    constexpr bool SPREAD = DP_BWD_PF_SPREAD && (GEMM == 1 || DP_BWD_PF_SPREAD_ALL || COUT >= 32 || CIN == 16);
+    constexpr bool SPREAD = GEMM == 1 || COUT >= 32 || CIN == 16;
     const bool pf_on = !(abl & 32);
-#ifdef DP_BWD_PROF
-    const bool prof_on = (unsigned long long)d.prof >= 4096ull;
-    unsigned long long prof_acc[6] = {0, 0, 0, 0, 0, 0};
-    unsigned long long prof_t = __builtin_readcyclecounter();
-    const unsigned long long prof_pro = prof_t - prof_t0;       // prologue: weights / coefficients -> LDS
-#endif
     for (; t < ntiles; t += gridDim.x) {
         const int n = PACKED ? 0 : t / tiles_img, rr = t - n * tiles_img;
         const int y0 = (rr / tiles_x) * TH, x0 = (rr % tiles_x) * TW;      // canvas coordinates if PACKED
@@ -464,10 +413,8 @@ __global__ __launch_bounds__(BWD_THREADS) void dp_bwd_kernel(const YunetDP d, co
             }
         }
         __syncthreads();
-        DP_BWD_STAMP(0);
         const bool more = t + (int)gridDim.x < ntiles && pf_on;
-        if (SPREAD) { if (more && !DP_BWD_PF_LATE) issue(t + gridDim.x, std::integral_constant<int, 0>{}); }
-        else if (GEMM == 1 && DP_BWD_PF_EARLY && more) issue(t + gridDim.x, All{});
+        if (SPREAD && more) issue(t + gridDim.x, std::integral_constant<int, 0>{});
 
         // ---- p = a * W1^T + b1 on the interior pixels (one M tile per wave) ---------------------
         if constexpr (GEMM == 1) {
@@ -584,8 +531,7 @@ __global__ __launch_bounds__(BWD_THREADS) void dp_bwd_kernel(const YunetDP d, co
             }
         }
         __syncthreads();
-        DP_BWD_STAMP(1);
-        if (SPREAD && more) issue(t + gridDim.x, std::integral_constant<int, DP_BWD_PF_LATE ? 0 : 1>{});
+        if (SPREAD && more) issue(t + gridDim.x, std::integral_constant<int, 1>{});
 
         // ---- depthwise backward on the VALU; dp overwrites p in place ----------------------------
         // A thread owns a channel quad and a column of PPT rows.  The dz column triple is walked
@@ -642,12 +588,11 @@ __global__ __launch_bounds__(BWD_THREADS) void dp_bwd_kernel(const YunetDP d, co
             }
         }
         __syncthreads();
-        DP_BWD_STAMP(2);
         // prefetch the next tile's global data; issued here (not right after the stage) so that the
         // p GEMM and the VALU phase run without ~64 prefetch registers live -- the two GEMMs, the
         // mask phase and the store that follow are several microseconds, enough for HBM
-        if (SPREAD) { if (more) issue(t + gridDim.x, std::integral_constant<int, DP_BWD_PF_LATE ? 1 : 2>{}); }
-        else if (!(GEMM == 1 && DP_BWD_PF_EARLY) && more) issue(t + gridDim.x, All{});
+        if (SPREAD) { if (more) issue(t + gridDim.x, std::integral_constant<int, 2>{}); }
+        else if (more) issue(t + gridDim.x, All{});
 
         // ---- dW1 += a^T * dp (K = pixels) and da = dp * W1 on the matrix cores -------------------
         if constexpr (GEMM == 1) {
@@ -751,7 +696,7 @@ __global__ __launch_bounds__(BWD_THREADS) void dp_bwd_kernel(const YunetDP d, co
                 for (int r = 0; r < 4; ++r) gw1[0][r] += (part[0][r] + part[1][r]) + (part[2][r] + part[3][r]);
             }
         }
-        if (SPREAD && more) issue(t + gridDim.x, std::integral_constant<int, DP_BWD_PF_LATE ? 2 : 3>{});
+        if (SPREAD && more) issue(t + gridDim.x, std::integral_constant<int, 3>{});
         f32x4 da[G::MPW][G::NTI];
 #pragma unroll
         for (int mi = 0; mi < G::MPW; ++mi)
@@ -816,8 +761,6 @@ __global__ __launch_bounds__(BWD_THREADS) void dp_bwd_kernel(const YunetDP d, co
             }
         }
         __syncthreads();  // every wave is done reading s_a for dW1
-        DP_BWD_STAMP(3);
-        if (SPREAD && DP_BWD_PF_LATE && more) issue(t + gridDim.x, std::integral_constant<int, 3>{});
         if (bn_in) {
 #pragma unroll
             for (int nt = 0; nt < G::NTI; ++nt) {
@@ -860,7 +803,6 @@ __global__ __launch_bounds__(BWD_THREADS) void dp_bwd_kernel(const YunetDP d, co
                         s_a[((wid * G::MPW + mi) * 16 + 4 * g + r) * G::LSI + nt * 16 + l15] = da[mi][nt][r];
         }
         __syncthreads();
-        DP_BWD_STAMP(4);
 
         // ---- dx store (coalesced) + BN-backward sums of the producer ------------------------------
         if (d.dx && !(abl & 16)) {
@@ -894,29 +836,21 @@ __global__ __launch_bounds__(BWD_THREADS) void dp_bwd_kernel(const YunetDP d, co
                     float4 v = *reinterpret_cast<const float4*>(s_a + ip * G::LSI + ich4 * 4);
                     const float4 o = *reinterpret_cast<const float4*>(&old[i]);
                     v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-                    __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&v), r_dx, off[i], 0, PACKED ? 0 : YUNET_DX_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&v), r_dx, off[i], 0, PACKED ? 0 : DX_AUX);
                 }
             } else {
 #pragma unroll
                 for (int i = 0; i < G::NX; ++i) {
                     const int ip = (tid + BWD_THREADS * i) / G::C4I;
                     const float4 v = *reinterpret_cast<const float4*>(s_a + ip * G::LSI + ich4 * 4);
-                    __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&v), r_dx, off[i], 0, PACKED ? 0 : YUNET_DX_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&v), r_dx, off[i], 0, PACKED ? 0 : DX_AUX);
                 }
             }
         }
         __syncthreads();
-        DP_BWD_STAMP(5);
     }
 
     // ============ flush per-workgroup partial sums ==============================================
-#ifdef DP_BWD_PROF
-    if (prof_on && threadIdx.x == 0) {
-        for (int k = 0; k < 6; ++k) d.prof[blockIdx.x * 8 + k] = prof_acc[k];
-        d.prof[blockIdx.x * 8 + 6] = prof_pro;
-    }
-    const unsigned long long prof_t1 = __builtin_readcyclecounter();
-#endif
     float* row = d.wgrad_partials + (size_t)blockIdx.x * G::WROW;
     // Every wave parks its dW1 tiles in the LDS plane of its K slice and every thread its
     // dW2 | db1 | db2 accumulators in a record (two passes of 6 / 5 float4: 11 at once do not fit next to
@@ -964,9 +898,6 @@ __global__ __launch_bounds__(BWD_THREADS) void dp_bwd_kernel(const YunetDP d, co
     reduce_pass(1, 5);
     // (c) BN-backward sums of the producer: one global fp64 atomic per channel
     if (bn_in && d.dx && d.in_bn.bstats && tid < 2 * CIN) atomic_add_f64(bn_slot(d.in_bn.bstats, d.in_bn.slots, CIN) + tid, s_bst[tid]);
-#ifdef DP_BWD_PROF
-    if (prof_on && threadIdx.x == 0) d.prof[blockIdx.x * 8 + 7] = __builtin_readcyclecounter() - prof_t1;
-#endif
 }
 
 template <int CIN, int COUT, int TH, int TW, bool PACKED = false, int GEMM = 0, bool POOLDY = false, bool FULL = false>
@@ -1031,31 +962,16 @@ __device__ __forceinline__ float act_bufld1(R rsrc, unsigned byte_off) {
     return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, byte_off, 0, 0));
 #endif
 }
-#ifndef YUNET_BWD64_ADDR2
-#define YUNET_BWD64_ADDR2 1
-#endif
+namespace bwd64 {
 // Round 6: the two fp32 tiles the matrix-layout phases touch with 4-byte accesses (p / dx writes, x reads of the mask) are
 // XOR-swizzled: a wave's 32-lane group there is 16 channels x 2 pixel groups 4 pixels apart = 256 words = the SAME banks
 // (every such access paid a 2-way conflict); element (pixel, channel) now lives at channel ^ 16 * ((pixel >> 2) & 1).  The
 // row-wise 16-byte accesses of the stage / depthwise / store phases see a wave-uniform flip (a wave's four pixels share
-// pixel bit 2), so nothing else changes.  -DYUNET_BWD64_SWZ=0 = the linear layout.
-#ifndef YUNET_BWD64_SWZ
-#define YUNET_BWD64_SWZ 1
-#endif
-#ifndef YUNET_BWD64_X_AUX        // cache-policy bits of the x loads of the unpacked instances: x is read exactly once (tile interior only),
-                                 // non-temporal keeps it out of the L2 the dy / z halo re-reads live in (step -0.04 ms, profiles/r06_bench_ab_ntx.log)
-#define YUNET_BWD64_X_AUX 2
-#endif
-#ifndef YUNET_BWD64_DY_AUX       // cache-policy bits of the dy loads (measurement switch; 0 = default policy; the dx stores: common.h YUNET_DX_AUX)
-#define YUNET_BWD64_DY_AUX 0
-#endif
-#ifndef YUNET_BWD64_PFMODE      // where the next tile's loads are issued: 0 = four pieces from the p GEMM on (rounds 2-5), 1 = all at
-#define YUNET_BWD64_PFMODE 5    // once after the p GEMM (measurement), 5 = four pieces, each one issue point later (round 6)
-#endif
-namespace bwd64 {
-__device__ __forceinline__ int tile_swz(int pixel) { return YUNET_BWD64_SWZ ? ((pixel >> 2) & 1) << 4 : 0; }
-}
-namespace bwd64 {
+// pixel bit 2), so nothing else changes.
+__device__ __forceinline__ int tile_swz(int pixel) { return ((pixel >> 2) & 1) << 4; }
+// cache-policy bits of the x loads of the unpacked instances: x is read exactly once (tile interior only), non-temporal
+// keeps it out of the L2 the dy / z halo re-reads live in (step -0.04 ms, profiles/r06_bench_ab_ntx.log)
+constexpr int X_AUX = 2;
 constexpr int C = 64, C4 = 16;
 constexpr int PLANE_PX = 128;      // (pixels of the largest tile: plane_off() only needs the row pitch)
 // NW = waves per workgroup: 8 -> 8 x 16 pixel tiles, one workgroup (149 KB of LDS) per CU;
@@ -1081,11 +997,7 @@ struct Geo {
     static constexpr int WORKB = OFF_A + 2 * PLANE;
     static constexpr int PAR_F = 9 * C + 7 * C + 5 * C + C;            // w2 | out-bn | in-bn | b1 (floats)
     static constexpr int MH = NW / 4;                                  // pixel halves (p / da GEMM: 4 pixel tiles per wave)
-#ifdef DP_BWD_PROF
-    static constexpr int SMEM = WORKB + PAR_F * 4 + MH * 2 * C * 8 + IP + 64;
-#else
     static constexpr int SMEM = WORKB + PAR_F * 4 + MH * 2 * C * 8 + IP;   // + fp64 sums per pixel half + validity bytes
-#endif
     static constexpr int KSPLIT = NW / 4;                              // dW1: pixels 64 ks .. 64 ks + 63 per wave quad
     static_assert(2 * PLANE <= HP * C * 4, "dp planes alias the dz halo");
     static_assert((size_t)KSPLIT * C * C * 4 + (size_t)NT * 24 * 4 <= (size_t)WORKB, "flush area");
@@ -1108,15 +1020,12 @@ __device__ __forceinline__ u32x2 tr_read(const unsigned char* p) {
 // bf16(a) with bf16(W1) (conv_fwd64.hip), so the backward that is consistent with it recomputes p as that ONE product,
 // takes dW1 = bf16(a)^T dp as two (dp = hi + lo) and da = dp bf16(W1) as two: 5 matrix products per tile instead of 9,
 // and the low plane of `a` is neither written nor read
-// (round 5; -DYUNET_BWD64_BF16_LEAN=0 builds the earlier variant, which split the fp32 a and W1 as the fp32 build does:
+// (round 5; against the earlier variant, which split the fp32 a and W1 as the fp32 build does:
 // same-box A/B of the bf16 step 4.00 -> 3.89 ms, profiles/r05_bf16_lean_ab.log)
-#ifndef YUNET_BWD64_BF16_LEAN
-#define YUNET_BWD64_BF16_LEAN 1
-#endif
-#if defined(YUNET_ACT_BF16) && YUNET_BWD64_BF16_LEAN
-#define BWD64_LEAN 1
+#ifdef YUNET_ACT_BF16
+constexpr bool BWD64_LEAN = true;
 #else
-#define BWD64_LEAN 0
+constexpr bool BWD64_LEAN = false;
 #endif
 __device__ __forceinline__ f32x4 mfma1r(const u32x4 a, const u32x4 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
@@ -1136,7 +1045,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
     using namespace bwd64;
     using G = Geo<NW>;
-    constexpr bool ADDR2 = !PACKED && (YUNET_BWD64_ADDR2 != 0);      // round 5: shift-only halo addressing (issue2)
+    constexpr bool ADDR2 = !PACKED;      // round 5: shift-only halo addressing (issue2)
     constexpr int NT = G::NT, TH = G::TH, TW = G::TW, HW_ = G::HW_, HP = G::HP, IP = G::IP, NDZ = G::NDZ, NX = G::NX;
     constexpr int PSTEP = G::PSTEP, PLANE = G::PLANE, OFF_DZ = G::OFF_DZ, OFF_X = G::OFF_X, OFF_P = G::OFF_P;
     constexpr int OFF_A = G::OFF_A, WORKB = G::WORKB, KSPLIT = G::KSPLIT, MH = G::MH, XP = G::XP;
@@ -1160,18 +1069,8 @@ void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
     const bool bn_in = d.in_transform == YUNET_T_BNRELU;
     const bool bn_out = d.out_has_bn != 0;
     const float relu_floor = bn_in ? 0.0f : -__builtin_inff();
-    // debug: prof < 4096 is an ablation bit mask; a -DDP_BWD_PROF build also takes the mask from the low 6 bits of
-    // the (256-byte aligned) counter pointer, so that ablated runs can be profiled per phase
-    const unsigned abl = (unsigned long long)d.prof < 4096ull ? (unsigned)(unsigned long long)d.prof
-#ifdef DP_BWD_PROF
-                                                              : (unsigned)((unsigned long long)d.prof & 63ull);
-    unsigned long long* const prof_out = reinterpret_cast<unsigned long long*>((unsigned long long)d.prof & ~63ull);
-#else
-                                                              : 0u;
-#endif
-#ifdef DP_BWD_PROF
-    const unsigned long long prof_t0 = __builtin_readcyclecounter();
-#endif
+    // debug ablation mask (tools/kbench.py --ablate): prof < 4096 is a bit mask, not a pointer
+    const unsigned abl = (unsigned long long)d.prof < 4096ull ? (unsigned)(unsigned long long)d.prof : 0u;
     const int tiles_x = ((PACKED ? pk.CW : W) + TW - 1) / TW, tiles_y = ((PACKED ? pk.CH : H) + TH - 1) / TH;
     const int tiles_img = tiles_x * tiles_y;
     const int ntiles = PACKED ? tiles_img : d.N * tiles_img;
@@ -1332,7 +1231,7 @@ void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
                 pdy[i] = *reinterpret_cast<const float4*>(&vdy);
                 pid[i] = __builtin_amdgcn_raw_buffer_load_b32(r_id, ok ? eq : pooledbytes, 0, 0);
             } else {
-                const u32x4 vdy = __builtin_amdgcn_raw_buffer_load_b128(r_dy, ok ? eo * 4u : dybytes, 0, YUNET_BWD64_DY_AUX);
+                const u32x4 vdy = __builtin_amdgcn_raw_buffer_load_b128(r_dy, ok ? eo * 4u : dybytes, 0, 0);
                 pdy[i] = *reinterpret_cast<const float4*>(&vdy);
             }
             pz[i] = act_raw4{};
@@ -1387,7 +1286,7 @@ void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
 #pragma unroll
             for (int i = 0; i < NX; ++i) {
                 const bool ok = tfull || (y0 + 2 * i + r < H && x0 + hxm < W);
-                px[i] = act_bufld4_aux<YUNET_BWD64_X_AUX>(r_x, ok ? (unsigned)(xb + i * 2 * W * C + tm) * ACT_B : xbytes);
+                px[i] = act_bufld4<X_AUX>(r_x, ok ? (unsigned)(xb + i * 2 * W * C + tm) * ACT_B : xbytes);
             }
         }
     };
@@ -1395,8 +1294,7 @@ void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
     // between the da GEMM and the mask): the requests spend less time queued in a memory system that is already
     // oversubscribed by 256 CUs prefetching a whole tile each -- issuing EARLIER (inside the stage, into the registers it
     // frees: built, +23 %) or all at once (+3 %) is worse, later is neutral at 80 x 80 and -1 .. -3 % on the smaller maps
-    // (profiles/r06_bwd64_pf5.log; -DYUNET_BWD64_PFMODE=0 = the earlier points)
-    constexpr bool LATE = (YUNET_BWD64_PFMODE == 5);
+    // (profiles/r06_bwd64_pf5.log)
     auto issue_any = [&](int t, auto part_c) {
         if constexpr (ADDR2) issue2(t, part_c);
         else issue(t, part_c);
@@ -1473,16 +1371,6 @@ void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
     for (int i = tid; i < MH * 2 * C; i += NT) s_bst[i] = 0.0;
 
     const bool pf_on = !(abl & 32);
-#ifdef DP_BWD_PROF
-    // phase counters live in LDS (as registers they change the allocation of the kernel they measure)
-    const bool prof_on = (unsigned long long)d.prof >= 4096ull;
-    unsigned long long* s_prof = reinterpret_cast<unsigned long long*>(s_in + IP);
-    if (tid == 0) {
-        for (int q = 0; q < 6; ++q) s_prof[q] = 0;
-        s_prof[7] = __builtin_readcyclecounter();
-        s_prof[6] = s_prof[7] - prof_t0;
-    }
-#endif
     for (; t < ntiles; t += gridDim.x) {
         const int n = PACKED ? 0 : t / tiles_img, rr = t - n * tiles_img;
         const int y0 = (rr / tiles_x) * TH, x0 = (rr % tiles_x) * TW;
@@ -1603,7 +1491,6 @@ void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
             }
         }
         __syncthreads();
-        DP_BWD64_STAMP(0);
         const bool more = t + (int)gridDim.x < ntiles && pf_on;
 
         // ---- p = a * W1^T + b1: this wave's 16 output channels on 4 pixel tiles -------------------------------------
@@ -1647,15 +1534,6 @@ void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
             }
         }
         __syncthreads();
-        DP_BWD64_STAMP(1);
-        // next tile's loads go out in four pieces from here on (the p GEMM above runs with no load in flight: a
-        // CU cannot keep a whole tile's 124 KB in flight, and the in-order vector-memory queue would hold any
-        // scratch access behind them)
-#if YUNET_BWD64_PFMODE == 1     // experiment: the whole next tile at once
-        if (more) issue_any(t + gridDim.x, All{});
-#else
-        if (more && !LATE) issue_any(t + gridDim.x, std::integral_constant<int, 0>{});
-#endif
 
         // ---- depthwise backward on the VALU (sliding window over a 4-row column); dp stays in registers -------------
         float4 dp[4];
@@ -1713,9 +1591,10 @@ void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
                 gb1.x += dp[r].x; gb1.y += dp[r].y; gb1.z += dp[r].z; gb1.w += dp[r].w;
             }
         }
-#if YUNET_BWD64_PFMODE != 1
-        if (more) { if (LATE) issue_any(t + gridDim.x, std::integral_constant<int, 0>{}); else issue_any(t + gridDim.x, std::integral_constant<int, 1>{}); }
-#endif
+        // next tile's loads go out in four pieces from here on (the p GEMM and the depthwise phase above run with no
+        // load in flight: a CU cannot keep a whole tile's 124 KB in flight, and the in-order vector-memory queue would
+        // hold any scratch access behind them)
+        if (more) issue_any(t + gridDim.x, std::integral_constant<int, 0>{});
         __syncthreads();      // every dz read is done: the dp planes may overwrite the halo
         {
             const int cq = opaque((int)threadIdx.x) % C4;
@@ -1731,10 +1610,7 @@ void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
             }
         }
         __syncthreads();
-        DP_BWD64_STAMP(2);
-#if YUNET_BWD64_PFMODE != 1
-        if (more) { if (LATE) issue_any(t + gridDim.x, std::integral_constant<int, 1>{}); else issue_any(t + gridDim.x, std::integral_constant<int, 2>{}); }
-#endif
+        if (more) issue_any(t + gridDim.x, std::integral_constant<int, 1>{});
 
         // ---- dW1 += a^T * dp (K = pixels): operands through the transposing LDS read --------------------------------
         // k index of lane group G, element e (0..7): pixel 32 kb + 4 * (4 (G >> 1) + 2 (e >> 2) + (G & 1)) + (e & 3) --
@@ -1775,10 +1651,7 @@ void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
                 }
             }
         }
-        DP_BWD64_STAMP(3);
-#if YUNET_BWD64_PFMODE != 1
-        if (more) { if (LATE) issue_any(t + gridDim.x, std::integral_constant<int, 2>{}); else issue_any(t + gridDim.x, std::integral_constant<int, 3>{}); }
-#endif
+        if (more) issue_any(t + gridDim.x, std::integral_constant<int, 2>{});
 
         // ---- da = dp * W1 (this wave's 16 input channels, 4 pixel tiles) + ReLU mask + BN-backward sums ----------------
         // Everything a step needs is requested before the step that consumes it (operands of both k blocks, then the
@@ -1808,7 +1681,7 @@ void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            if (LATE && more) issue_any(t + gridDim.x, std::integral_constant<int, 3>{});
+            if (more) issue_any(t + gridDim.x, std::integral_constant<int, 3>{});
             if (bn_in) {
                 const float m_mean = s_ci[c], m_scale = s_ci[C + c], m_beta = s_ci[2 * C + c], m_inv = s_ci[3 * C + c];
                 const float m_lo = s_ci[4 * C + c];
@@ -1858,7 +1731,6 @@ void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
             }
         }
         __syncthreads();
-        DP_BWD64_STAMP(4);
 
         // ---- dx store (coalesced rows of s_p) --------------------------------------------------------------------------
         if (d.dx && !(abl & 16)) {
@@ -1890,7 +1762,7 @@ void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
                     float4 v = *reinterpret_cast<const float4*>(s_p + ip * XP + ((ich4 * 4) ^ tile_swz(ip)));
                     const float4 o = *reinterpret_cast<const float4*>(&old[i]);
                     v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-                    __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&v), r_dx, off[i], 0, YUNET_DX_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&v), r_dx, off[i], 0, DX_AUX);
                 }
             } else {
 #pragma unroll
@@ -1899,21 +1771,15 @@ void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
                     const float4 v = *reinterpret_cast<const float4*>(s_p + ip * XP + ((ich4 * 4) ^ tile_swz(ip)));
                     // (non-temporal on the big maps, default policy on the packed 20 x 20 / 10 x 10 levels: common.h)
                     if constexpr (PACKED) __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&v), r_dx, off[i], 0, 0);
-                    else __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&v), r_dx, off[i], 0, YUNET_DX_AUX);
+                    else __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&v), r_dx, off[i], 0, DX_AUX);
                 }
             }
         }
-        DP_BWD64_STAMP(5);
         // no barrier here: the next stage writes the halo / x / a planes (all read before the barrier above) and
         // s_p is next written by the p GEMM, one barrier later
     }
 
     // ============ flush per-workgroup partial sums ================================================================
-#ifdef DP_BWD_PROF
-    if (prof_on && threadIdx.x == 0)
-        for (int q = 0; q < 7; ++q) prof_out[blockIdx.x * 8 + q] = s_prof[q];
-    const unsigned long long prof_t1 = __builtin_readcyclecounter();
-#endif
     __syncthreads();                                     // the last tile's dx rows have been read
     float* row = d.wgrad_partials + (size_t)blockIdx.x * WROW;
     float* sm = reinterpret_cast<float*>(smem_raw);
@@ -1961,9 +1827,6 @@ void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
     my[0] = gw2[6]; my[1] = gw2[7]; my[2] = gw2[8]; my[3] = gb1; my[4] = gb2;
     __syncthreads();
     reduce_pass(1, 5);
-#ifdef DP_BWD_PROF
-    if (prof_on && threadIdx.x == 0) prof_out[blockIdx.x * 8 + 7] = __builtin_readcyclecounter() - prof_t1;
-#endif
 }
 
 template <int NW, bool PACKED, bool POOLDY>

@@ -15,12 +15,6 @@
 
 #include "common.h"
 
-// 1: forward pointwise GEMM of the 32 / 64-channel units as a three-way bf16 split (fp32-accurate);
-// 0: exact-fp32 matrix instruction (A/B builds, tools/ubench)
-#ifndef YUNET_FWD_SPLIT3
-#define YUNET_FWD_SPLIT3 1
-#endif
-
 namespace {
 
 // ------------------------------------------------------------------------------- stem
@@ -287,7 +281,7 @@ __global__ __launch_bounds__(256) void dp_fwd_kernel(const YunetDP d, const Pack
     // fp32 build, 32 / 64 input channels: three-way bf16 split of BOTH operands, x = h + m + l EXACTLY
     // (3 x 8 significand bits), six bf16 MFMAs per product block (hh, hm, mh, mm, hl, lh; the dropped
     // ml, lm, ll terms are <= 2^-24 relative): fp32-accurate at 6/16 of the fp32 matrix time.
-    constexpr bool SPLIT3 = YUNET_ACT_DTYPE == YUNET_F32 && CIN % 32 == 0 && YUNET_FWD_SPLIT3;
+    constexpr bool SPLIT3 = YUNET_ACT_DTYPE == YUNET_F32 && CIN % 32 == 0;
     constexpr int NCH = CIN / 8;                                      // 16-byte chunks per weight row
     __bf16* s_w1p = reinterpret_cast<__bf16*>(s_w1);                  // planes h | m | l, each [COUT][CIN], swizzled
     if constexpr (SPLIT3) {
@@ -545,7 +539,7 @@ __global__ __launch_bounds__(256) void dp_fwd_kernel(const YunetDP d, const Pack
                     if (!(abl & 4)) {
                         const unsigned zoff = (unsigned)(pn * (PACKED ? d.z_img_stride : 0) + (py * W + px) * COUT + cq * 4);
                         if (z_f32)
-                            __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&o), r_z, zoff * 4u, 0, YUNET_ST_AUX);
+                            __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&o), r_z, zoff * 4u, 0, ST_AUX);
                         else
                             act_bufst4(r_z, zoff * ACT_B, o);
                     }
@@ -783,9 +777,6 @@ extern "C" int ACT_SUFFIX(yunet_dp_fwd)(const YunetDP* d, void* stream) {
         return d->cout == 64 ? launch_dp_fwd<64, 64, 8, 16, true>(d, s) : launch_dp_fwd<64, 16, 8, 16, true>(d, s);
     // the plain 64 -> 64 unit: wave-streaming kernel (conv_fwd64.hip); the phase-clock debug mode stays on the
     // tile kernel
-#ifdef F64S_PROF
-    if (d->cin == 64 && d->cout == 64 && yunet_options().fwd64s) return ACT_SUFFIX(launch_dp_fwd64s)(d, s);
-#endif
     if (d->cin == 64 && d->cout == 64 && d->z_dtype == YUNET_ACT_DTYPE && (unsigned long long)d->prof < 64ull && yunet_options().fwd64s)
         return ACT_SUFFIX(launch_dp_fwd64s)(d, s);
     DP_CASE(16, 16)

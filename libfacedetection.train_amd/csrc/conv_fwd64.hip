@@ -31,9 +31,6 @@
 // and bf16(W1) (fp32 accumulation) instead of the exact three-way split -- the arithmetic of the bf16 tile kernel
 // (conv_fwd.hip); depthwise, bias and BN sums (of the unrounded values) stay fp32.
 #include "common.h"
-#ifndef YUNET_FWD64_X_AUX       // cache-policy bits of the x loads (round 6 measurement switch; 2 = non-temporal)
-#define YUNET_FWD64_X_AUX 0
-#endif
 
 namespace {
 namespace f64s {
@@ -46,21 +43,6 @@ constexpr size_t SMEM = W1_BYTES + (WAVES * SLOT_FLOATS + 9 * C + C + C + C + 2 
 }  // namespace f64s
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
-// -DF64S_PROF (tools/ubench/build_ab.sh): s_memtime stamps per image row, summed per wave into YunetDP.prof
-// [(block * 4 + wave) * 4 + i]: i = 0 wait for the row's loads | 1 transform + split | 2 matrix phase + p store |
-// 3 depthwise + z stores.  The stamps serialise the phases (each drains the LDS counter): read them as an upper bound.
-#ifdef F64S_PROF
-#define F64S_STAMP(i)                                                                    \
-    {                                                                                    \
-        if ((i) == 0) { pt = __builtin_readcyclecounter(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); } \
-        const unsigned long long now_ = __builtin_readcyclecounter();                    \
-        pc[i] += now_ - pt;                                                              \
-        pt = now_;                                                                       \
-    }
-#else
-#define F64S_STAMP(i)
-#endif
 
 __device__ __forceinline__ float med3(float a, float b, float c) { return __builtin_amdgcn_fmed3f(a, b, c); }
 
@@ -130,12 +112,7 @@ __device__ __forceinline__ void dp_fwd64s_body(const YunetDP& d, const int R, co
     }
     // prof < 64 is a debug ablation mask (tools/ubench: ABL), not a pointer: 1 skip the matrix instructions,
     // 2 skip the depthwise phase, 4 skip the z stores, 8 skip the input loads (results are then wrong)
-#ifdef F64S_PROF
-    const unsigned abl = 0;
-    unsigned long long pc[4] = {0, 0, 0, 0}, pt = 0;
-#else
     const unsigned abl = (unsigned)(unsigned long long)d.prof;
-#endif
     float* pslot = s_p + wid * SLOT_FLOATS;
     const int strips = (W + TW - 1) / TW, bands = (H + R - 1) / R;
     const int tasks_img = strips * bands, ntasks = d.N * tasks_img;
@@ -186,13 +163,13 @@ __device__ __forceinline__ void dp_fwd64s_body(const YunetDP& d, const int R, co
             if (abl & 8) return;
             const unsigned o = xlane + (unsigned)(y * W * C) * ACT_B;
 #ifdef YUNET_ACT_BF16
-            xr[0] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o, 0, YUNET_FWD64_X_AUX);          // 8 bf16 channels of block 0
-            xr[2] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o + 64, 0, YUNET_FWD64_X_AUX);     // ... of block 1
+            xr[0] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o, 0, 0);          // 8 bf16 channels of block 0
+            xr[2] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o + 64, 0, 0);     // ... of block 1
 #else
-            xr[0] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o, 0, YUNET_FWD64_X_AUX);
-            xr[1] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o + 16, 0, YUNET_FWD64_X_AUX);
-            xr[2] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o + 128, 0, YUNET_FWD64_X_AUX);
-            xr[3] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o + 144, 0, YUNET_FWD64_X_AUX);
+            xr[0] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o, 0, 0);
+            xr[1] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o + 16, 0, 0);
+            xr[2] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o + 128, 0, 0);
+            xr[3] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o + 144, 0, 0);
 #endif
         };
         issue(rs);
@@ -255,7 +232,6 @@ __device__ __forceinline__ void dp_fwd64s_body(const YunetDP& d, const int R, co
 
 #pragma unroll 1
         for (int r = rs; r <= re; ++r) {
-            F64S_STAMP(0)
             // ---- a = T(x), split into three bf16 pieces: the B operands (k = 8 channels of this lane, n = pixel)
             u32x4 bh[2], bm[2], bl[2];
 #pragma unroll
@@ -296,7 +272,6 @@ __device__ __forceinline__ void dp_fwd64s_body(const YunetDP& d, const int R, co
                 }
 #endif
             }
-            F64S_STAMP(1)
             // the registers are free again: the next row is in flight under this row's arithmetic
             if (r < re) issue(r + 1);
 
@@ -356,7 +331,6 @@ __device__ __forceinline__ void dp_fwd64s_body(const YunetDP& d, const int R, co
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
-            F64S_STAMP(2)
             // ---- depthwise, accumulate form: this row is the bottom tap row of output row r - 1 (now complete), the
             //      middle of r, the top of r + 1
             if (abl & 2) continue;
@@ -386,7 +360,6 @@ __device__ __forceinline__ void dp_fwd64s_body(const YunetDP& d, const int R, co
                 }
             }
             if (r - 1 >= y0) emit_row(r - 1, dn);
-            F64S_STAMP(3)
         }
         if (y1 == H) emit_row(H - 1, oa);      // the image's last row has no row below it: complete as it stands
         // ---- BN partial sums of the band: across the four column groups, then fp64 in LDS
@@ -407,10 +380,6 @@ __device__ __forceinline__ void dp_fwd64s_body(const YunetDP& d, const int R, co
             }
         }
     }
-#ifdef F64S_PROF
-    if (d.prof && lane == 0)
-        for (int i = 0; i < 4; ++i) d.prof[(blockIdx.x * 4 + wid) * 4 + i] = pc[i];
-#endif
     if (d.out_has_bn) {
         __syncthreads();
         if (tid < 2 * C) atomic_add_f64(bn_slot(d.out_bn.stats, d.out_bn.slots, C) + tid, s_st[tid]);
@@ -441,7 +410,7 @@ __global__ __launch_bounds__(f64s::NTHR, 3) void dp_fwd64s_group_kernel(const Fw
     // the XCD-contiguous renumbering of first_tile(), inside the unit's own grid (hardware deals workgroup ids to the
     // 8 XCDs round-robin: valid where the grid starts at a multiple of 8 and has a multiple of 8 workgroups)
     const int l = b - base;
-    const int first = (YUNET_XCD_REMAP && (nblk & 7) == 0 && (base & 7) == 0) ? (l & 7) * (nblk >> 3) + (l >> 3) : l;
+    const int first = ((nblk & 7) == 0 && (base & 7) == 0) ? (l & 7) * (nblk >> 3) + (l >> 3) : l;
     dp_fwd64s_body<false>(m.d[u], m.R[u], first, nblk);
 }
 

@@ -414,10 +414,9 @@ __global__ __launch_bounds__(ASSIGN_THREADS) void assign_resolve_kernel(
 // r05_assign_kernels.log): A2 24 us, B2 61 us (11 fixed + 12 walk + 8 evaluation + 28 list merges), C2 13 us.
 #define CCH 256                      // priors per chunk of A2
 #define CCH_SHIFT 8
-#ifndef A2_CQ
-#define A2_CQ 2                       // measured at the bench batch: 1 -> 24.9 us, 2 -> 22.7 us, 4 -> 29.3 us
-#endif
-#define CQ A2_CQ                    // threads per prior of A2 (each takes the GTs q, q + CQ, ...)
+// threads per prior of A2 (each takes the GTs q, q + CQ, ...); measured at the bench batch: 1 -> 24.9 us, 2 -> 22.7 us,
+// 4 -> 29.3 us
+constexpr int CQ = 2;
 #define RB 512                       // records per LDS block of B2 (= capacity of the per-wave candidate list)
 
 __device__ __forceinline__ float overlap_of(float bx1, float by1, float bx2, float by2, const GT& g) {
@@ -599,9 +598,6 @@ __global__ __launch_bounds__(CCH * CQ) void assign_compact2_kernel(
 // block's arithmetic); wave w takes records 128 w .. 128 w + 127 of a block.  Afterwards each wave extracts its own top
 // lists with wave reductions and the four lists are merged from LDS.
 template <int TOPK>
-#ifdef B2_WAVES_PER_EU
-__attribute__((amdgpu_waves_per_eu(B2_WAVES_PER_EU, B2_WAVES_PER_EU)))
-#endif
 __global__ __launch_bounds__(TOPK_WAVES * 64) void assign_topk2_kernel(
     const float* __restrict__ gt_boxes, int P, int Gmax, int nchunk, float radius, int topk, CostW cw, AssignScratch ws) {
     constexpr int NT = TOPK_WAVES * 64, PER = RB / NT, WB = RB / TOPK_WAVES;      // WB: records of a block per wave

@@ -77,13 +77,4 @@ for sl in 8; do
   SLOTS=$sl REPS=500 timeout 200 tools/ubench/bwd_ab.bin /tmp/libyunet_fp32.so:YUNET_BWD_FP32MMA=1 libfacedetection.train_amd/libyunet_hip.so 2>&1 \
       | grep -v yardstick | grep -v "max|" >> $OUT/${R}_bwd_ab.log
 done
-#   7. per-phase cycle counters of dp_bwd64 (a -DDP_BWD_PROF build made by tools/ubench/build_ab.sh prof "-DDP_BWD_PROF"),
-#      whole kernel and with every GEMM / depthwise phase and the global traffic ablated (ABL=63: what staging costs)
-if [ -f tools/ubench/libyunet_prof.so ]; then
-  for a in 0 15 63; do
-    echo "== ABL=$a" >> $OUT/${R}_bwd_phase_cycles.log
-    PROF=1 ABL=$a REPS=50 timeout 200 tools/ubench/bwd_ab.bin /tmp/libyunet_fp32.so:YUNET_BWD_FP32MMA=1 tools/ubench/libyunet_prof.so \
-        2>&1 | grep -v "total 0" >> $OUT/${R}_bwd_phase_cycles.log
-  done
-fi
 ls -la $OUT | tail -8

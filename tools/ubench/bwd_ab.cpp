@@ -310,14 +310,6 @@ int main(int argc, char** argv) {
             // ABL=<mask>: the kernel's debug ablation mask (1 p GEMM, 2 depthwise, 4 dW1, 8 da, 16 dx
             // store, 32 next-tile prefetch are SKIPPED); results are then wrong, only the time matters
             if (getenv("ABL")) d.prof = (unsigned long long*)(uintptr_t)atoll(getenv("ABL"));
-            unsigned long long* dprof = nullptr;
-            if (getenv("PROF")) {     // libraries built with -DDP_BWD_PROF: per-phase cycle counters
-                CK(hipMalloc(&dprof, (size_t)blocks * 64));
-                CK(hipMemset(dprof, 0, (size_t)blocks * 64));
-                d.prof = dprof;
-                if (getenv("ABL"))     // dp_bwd64 profile builds: ablation mask in the low bits of the aligned pointer
-                    d.prof = (unsigned long long*)((uintptr_t)dprof | ((uintptr_t)atoll(getenv("ABL")) & 63));
-            }
             CK(hipMemsetAsync(dbsi, 0, 2 * ci * 8 * slots, st));
             CK(hipMemsetAsync(ddx, 0xff, px * ci * 4, st));       // NaN: a variant that skips a dx element must not inherit the previous one's
             int rc = v.bwd(&d, st);
@@ -365,21 +357,6 @@ int main(int argc, char** argv) {
                        H, W, ci, co, N, v.name.c_str(), ms, gbs, rel(vdx, ref_dx, 0, vdx.size()),
                        rel(vw, ref_w, 0, o1), rel(vw, ref_w, o1, o2), rel(vw, ref_w, o2, o3),
                        rel(vw, ref_w, o3, (size_t)width), rel(hb, ref_b, 0, hb.size()));
-            }
-            if (dprof) {
-                CK(hipMemset(dprof, 0, (size_t)blocks * 64));
-                // d.prof may carry the ablation bits
-                v.bwd(&d, st);
-                CK(hipStreamSynchronize(st));
-                std::vector<unsigned long long> hp2((size_t)blocks * 8);
-                CK(hipMemcpy(hp2.data(), dprof, hp2.size() * 8, hipMemcpyDeviceToHost));
-                double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tot = 0;
-                for (int b = 0; b < blocks; ++b)
-                    for (int k = 0; k < 8; ++k) acc[k] += (double)hp2[(size_t)b * 8 + k] / blocks;
-                for (int k = 0; k < 8; ++k) tot += acc[k];
-                printf("    cycles per workgroup (mean): prologue %.0f | stage %.0f | p %.0f | dw %.0f | dW1+da %.0f | mask %.0f | store %.0f"
-                       " | epilogue %.0f | total %.0f\n", acc[6], acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], acc[7], tot);
-                CK(hipFree(dprof));
             }
             if (!v.env_k.empty()) unsetenv(v.env_k.c_str());
             CK(hipFree(dpart));
