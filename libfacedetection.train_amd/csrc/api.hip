@@ -178,7 +178,7 @@ extern "C" int yunet_set_option(const char* name, int value) {
     return prev;
 }
 
-// the same conv entry points compiled with bf16 activation storage (conv_fwd.hip / conv_bwd.hip -DYUNET_ACT_BF16)
+// the same conv entry points compiled with bf16 activation storage (conv_fwd*.hip / conv_bwd*.hip / conv_stem.hip -DYUNET_ACT_BF16)
 extern "C" {
 int yunet_stem_fwd_bf16(const float*, const float*, const float*, float*, double*, int, int, int, int, void*);
 int yunet_stem_bwd_bf16(const float*, const float*, const float*, const YunetBN*, float*, int, int, int, int, int, void*);

@@ -16,7 +16,8 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // ---- activation storage type of this translation unit ------------------------------------------
-// conv_fwd.hip / conv_bwd.hip are compiled twice: as is (fp32 activations, the headline path) and with
+// The conv_fwd*.hip / conv_bwd*.hip files (all but conv_bwd_host.hip) are compiled twice: as is (fp32 activations, the
+// headline path) and with
 // -DYUNET_ACT_BF16 (BASELINE.json configs[2]: "bf16 fwd / fp32 grads").  In the second build every
 // ACTIVATION tensor a forward kernel writes (raw conv outputs z, pool / upsample-add outputs) is stored
 // as bf16 (round to nearest even) and every kernel that reads one widens it on load; gradients (dy, dx),
@@ -392,6 +393,8 @@ int ACT_SUFFIX(launch_dp_fwd64s)(const YunetDP* d, hipStream_t stream);
 int ACT_SUFFIX(launch_dp_fwd64s_group)(const YunetDP* const* ds, int n, hipStream_t stream);     // independent plain units, one grid
 // conv_bwd16.hip: backward of the fp32 16 -> 16 unit (plain or pooled dy), z recomputed from x
 int ACT_SUFFIX(launch_dp_bwd16s)(const YunetDP* d, hipStream_t stream);
+// conv_bwd64.hip: backward of the 64 -> 64 unit on nw = 4 | 8 waves per workgroup (plain, packed canvas or pooled dy)
+int ACT_SUFFIX(launch_dp_bwd64)(const YunetDP* d, int nw, hipStream_t stream);
 // conv_fwd16.hip: forward of the fp32 16 -> 16 (plain | fused pooling) and 16 -> 64 units
 int ACT_SUFFIX(launch_dp_fwd16s)(const YunetDP* d, hipStream_t stream);
 // conv_stem.hip: the fp32 stem on the matrix cores (forward; weight gradient with z recomputed from the image)

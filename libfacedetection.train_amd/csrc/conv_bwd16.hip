@@ -27,12 +27,14 @@
 // for the load, which serialises the prefetch.)  HBM traffic per pixel: x (read with a 2-pixel halo), dy (full size, or the pooled gradient + 1 position
 // byte per element when the unit feeds max_pool2d: YunetDP.pool_idx) and dx -- z is not read.
 #include "common.h"
+#include "dp_bwd_parts.h"
 
 namespace {
 namespace b16s {
 constexpr int C = 16, PXW = 32, HALO = 2, OUTW = PXW - 2 * HALO;
 constexpr int WAVES = 8, NTHR = 64 * WAVES;
-constexpr int WROW = C * C + C + C * 9 + C;
+using Row = DpWgradRow<C, C>;
+constexpr int WROW = Row::WIDTH;
 constexpr int PST = 20;                            // floats per pixel of a row slot (16 + 4: 16-byte stores without bank conflicts)
 constexpr int SLOT = PXW * PST;
 constexpr int XRING = 3;                           // raw x rows X - 2 .. X (mask / BN sums two steps after the load)
@@ -50,10 +52,6 @@ static_assert((OFF_ST * 4) % 8 == 0, "fp64 alignment");
 
 __device__ __forceinline__ float lane_read(int src_lane, float v) {       // v of lane src_lane (no memory access)
     return __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane << 2, __float_as_int(v)));
-}
-__device__ __forceinline__ int opaque(int v) {        // stops the compiler from hoisting what is derived from v
-    asm volatile("" : "+v"(v));
-    return v;
 }
 
 template <bool POOLDY>
@@ -412,15 +410,15 @@ __global__ __launch_bounds__(b16s::NTHR, 1) void dp_bwd16s_kernel(const YunetDP 
         b1v += __shfl_xor(b1v, 16, 64); b1v += __shfl_xor(b1v, 32, 64);
         b2v += __shfl_xor(b2v, 16, 64); b2v += __shfl_xor(b2v, 32, 64);
         if (g == 0) {
-            red[C * C + l15] = b1v;
-            red[C * C + C + C * 9 + l15] = b2v;
+            red[Row::B1 + l15] = b1v;
+            red[Row::B2 + l15] = b2v;
         }
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
             float v = gw2[k];
             v += __shfl_xor(v, 16, 64);
             v += __shfl_xor(v, 32, 64);
-            if (g == 0) red[C * C + C + l15 * 9 + k] = v;
+            if (g == 0) red[Row::W2 + l15 * 9 + k] = v;
         }
     }
     __syncthreads();

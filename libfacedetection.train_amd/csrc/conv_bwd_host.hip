@@ -1,0 +1,143 @@
+// conv_bwd_host.hip -- the parts of the backward that do not depend on the activation storage type (compiled once):
+// the grid-size queries, the BatchNorm parameter gradient and the reduction of the per-workgroup partial rows.
+#include "common.h"
+#include "bwd_grid.h"
+
+namespace {
+
+__global__ void bn_param_grad_kernel(const double* __restrict__ bstats, float* __restrict__ dgamma,
+                                     float* __restrict__ dbeta, int C, int accumulate) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const float db = (float)bstats[c], dg = (float)bstats[C + c];
+    dbeta[c] = accumulate ? dbeta[c] + db : db;
+    dgamma[c] = accumulate ? dgamma[c] + dg : dg;
+}
+
+// One row slice of a column: rows sl, sl + 16, ... added IN THAT ORDER.  Sixteen (then four) loads are issued before the
+// first addition: written as `v += p[...]` in a plain loop the compiler waits out every load before the next one is issued
+// (s_waitcnt vmcnt(0) per iteration), and a 768-row job -- 48 rows per slice, each an L2 / HBM round trip -- took 40 us
+// at the END of the backward, where nothing overlaps it.  Same additions in the same order: bit-identical sums.
+__device__ __forceinline__ float column_slice_sum(const float* __restrict__ p, int blocks, int width, int sl) {
+    float v = 0.0f;
+    int b = sl;
+    for (; b + 16 * 15 < blocks; b += 16 * 16) {
+        float x[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) x[u] = p[(size_t)(b + 16 * u) * width];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v += x[u];
+    }
+    for (; b + 16 * 3 < blocks; b += 16 * 4) {
+        float x[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) x[u] = p[(size_t)(b + 16 * u) * width];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v += x[u];
+    }
+    for (; b < blocks; b += 16) v += p[(size_t)b * width];
+    return v;
+}
+
+// out[j] (+)= sum_b partials[b][j]: 64 columns x 16 row-slices per workgroup (coalesced 256-byte
+// row segments, 16 x 16 loads in flight per column), combined in a fixed order -> deterministic.
+__global__ __launch_bounds__(1024) void reduce_partials_kernel(const float* __restrict__ partials,
+                                                               int blocks, int width,
+                                                               float* __restrict__ out,
+                                                               int accumulate) {
+    __shared__ float s[16][64];
+    const int lane = threadIdx.x & 63, sl = threadIdx.x >> 6;
+    const int col = blockIdx.x * 64 + lane;
+    float v = 0.0f;
+    if (col < width) v = column_slice_sum(partials + col, blocks, width, sl);
+    s[sl][lane] = v;
+    __syncthreads();
+    if (sl == 0 && col < width) {
+        float t = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) t += s[k][lane];
+        out[col] = accumulate ? out[col] + t : t;
+    }
+}
+
+// table-driven variant: workgroup -> (job, 64-column chunk); same arithmetic and order as above
+__global__ __launch_bounds__(1024) void reduce_partials_batch_kernel(const YunetReduceJob* __restrict__ jobs,
+                                                                     int njobs) {
+    __shared__ float s[16][64];
+    // the last job whose first chunk is <= this workgroup (chunk0 ascends): bisection -- 6 dependent scalar loads
+    // instead of up to njobs
+    int lo = 0, hi = njobs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (jobs[mid].chunk0 <= (int)blockIdx.x) lo = mid;
+        else hi = mid - 1;
+    }
+    const YunetReduceJob job = jobs[lo];
+    const int lane = threadIdx.x & 63, sl = threadIdx.x >> 6;
+    const int col = ((int)blockIdx.x - job.chunk0) * 64 + lane;
+    float v = 0.0f;
+    if (col < job.width) v = column_slice_sum(job.partials + col, job.blocks, job.width, sl);
+    s[sl][lane] = v;
+    __syncthreads();
+    if (sl == 0 && col < job.width) {
+        float t = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) t += s[k][lane];
+        job.out[col] = job.accumulate ? job.out[col] + t : t;
+    }
+}
+
+}  // namespace
+
+extern "C" int yunet_dp_bwd_blocks(int N, int H, int W, int cin, int cout) {
+    const bool two_per_cu = cin == 64 && cout == 64 && bwd64_nw(N, H, W) == 4;      // dp_bwd64 on 8 x 8 tiles
+    const int th = dp_bwd_big_tile(H, W, cin, cout) ? 16 : 8, tw = two_per_cu ? 8 : th * 2;
+    const PackGeom pk = dp_pack_geom(N, H, W);       // small maps: one tile grid over the packed canvas
+    const long long tiles = dp_use_pack_bwd(N, H, W, cin, cout)
+                                ? (long long)((pk.CW + tw - 1) / tw) * ((pk.CH + th - 1) / th)
+                                  : (long long)N * ((W + tw - 1) / tw) * ((H + th - 1) / th);
+    const int cap = two_per_cu ? 2 * DP_BWD_MAX_BLOCKS : DP_BWD_MAX_BLOCKS;
+    return (int)(tiles < cap ? tiles : cap);
+}
+extern "C" int yunet_dp_pool_fusion_ok(int N, int H, int W, int cin, int cout) {
+    if ((H & 1) || (W & 1)) return 0;
+    if (cin == 16 && cout == 16) return dp_bwd_big_tile(H, W, cin, cout) ? 1 : 0;
+    if (cin == 64 && cout == 64) return dp_use_pack_bwd(N, H, W, cin, cout) ? 0 : 1;
+    if (cin == 32 && cout == 64) return 1;       // YuNet_s: the unit in front of its 80x80 -> 40x40 pool
+    return 0;
+}
+extern "C" int yunet_stem_bwd_blocks(int N, int H, int W) {
+    const long long tiles = (long long)N * ((W / 2 + SB_TW - 1) / SB_TW) * ((H / 2 + SB_TH - 1) / SB_TH);
+    return (int)(tiles < STEM_BWD_MAX_BLOCKS ? tiles : STEM_BWD_MAX_BLOCKS);
+}
+
+// the same weight gradient on the matrix cores with z RECOMPUTED from the image (w [16,3,3,3], b [16]: the stem's
+// parameters) instead of read: 112 instead of 176 bytes per output pixel (conv_stem.hip)
+extern "C" int yunet_stem_bwd_rz(const float* img, const float* w, const float* b, const float* dy, const YunetBN* bn,
+                                 float* wgrad_partials, int wgrad_blocks, int N, int H, int W, int cmid, void* stream) {
+    if (cmid != 16 || (H & 1) || (W & 1) || !w || !b || !bn->bstats || wgrad_blocks != yunet_stem_bwd_blocks(N, H, W)) return YUNET_EINVAL;
+    return launch_stem_bwd_mma(img, w, b, dy, bn, wgrad_partials, wgrad_blocks, N, H, W, (hipStream_t)stream);
+}
+
+extern "C" int yunet_bn_param_grad(const double* bstats, float* dgamma, float* dbeta, int C,
+                                   int accumulate, void* stream) {
+    hipLaunchKernelGGL(bn_param_grad_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream,
+                       bstats, dgamma, dbeta, C, accumulate);
+    return hip_status();
+}
+
+extern "C" int yunet_reduce_partials(const float* partials, int blocks, int width, float* out,
+                                     int accumulate, void* stream) {
+    if (blocks < 1 || width < 1) return YUNET_EINVAL;
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3((width + 63) / 64), dim3(1024), 0,
+                       (hipStream_t)stream, partials, blocks, width, out, accumulate);
+    return hip_status();
+}
+
+extern "C" int yunet_reduce_partials_batch(const YunetReduceJob* jobs, int njobs, int total_chunks,
+                                           void* stream) {
+    if (!jobs || njobs < 1 || total_chunks < njobs) return YUNET_EINVAL;
+    hipLaunchKernelGGL(reduce_partials_batch_kernel, dim3(total_chunks), dim3(1024), 0,
+                       (hipStream_t)stream, jobs, njobs);
+    return hip_status();
+}

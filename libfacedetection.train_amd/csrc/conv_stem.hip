@@ -1,7 +1,7 @@
 // conv_stem.hip -- the stem (Conv_head.conv1: 3 x 3, stride 2, 3 -> 16 channels, bias; mmdet/models/utils/
 // yunet_layer.py:51-52,58) forward and its weight gradient on the MATRIX CORES, as wave-streaming kernels.
 //
-// The VALU kernels they replace (conv_fwd.hip: stem_fwd_kernel, conv_bwd.hip: stem_bwd_kernel) run at 3.2 / 3.5 TB/s
+// The VALU kernels they replace (conv_fwd.hip: stem_fwd_kernel, conv_bwd_ew.hip: stem_bwd_kernel) run at 3.2 / 3.5 TB/s
 // of algorithmic bytes with ~430 FMAs and ~100 LDS reads per output pixel; a version of the backward kernel that
 // recomputed z on the VALU instead of reading it (-36 % bytes) was SLOWER (0.30 -> 0.46 ms,
 // profiles/r04_stem_bwd_rz_ab.log): these kernels are instruction-bound.  As a matrix product the convolution is
@@ -274,7 +274,7 @@ int stem_rows(int N, int Ho, int Wo, int waves) {
 
 }  // namespace
 
-// conv_fwd.hip / conv_bwd.hip dispatch here (option stem_mma).  The forward is compiled once per activation storage type (fp32 |
+// conv_fwd.hip (forward) and conv_bwd_host.hip (yunet_stem_bwd_rz) dispatch here (option stem_mma).  The forward is compiled once per activation storage type (fp32 |
 // -DYUNET_ACT_BF16: z stored as bf16, BN sums of the unrounded values); the weight gradient with its recomputed z is fp32-storage
 // only.  Grids: forward 256 CUs x 3 workgroups; backward = the rows of wgrad_partials (yunet_stem_bwd_blocks).
 int ACT_SUFFIX(launch_stem_fwd_mma)(const float* img, const float* w, const float* b, float* z, double* stats, int N, int H, int W,

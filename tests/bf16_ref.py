@@ -10,7 +10,7 @@ The contract, one row per kernel family, as the sources implement it (common.h: 
     product of a = bf16(relu(bn(x))) (a computed in fp32, then rounded) with bf16(W1), fp32 accumulation; depthwise and
     biases fp32; z stored as RNE bf16, BN sums unrounded.  (The fp32 build splits both operands three ways instead.)
   * Heads (64 -> 16, no BatchNorm behind them): the 64-input rule above, z written as fp32.
-  * dp_bwd64 (64 -> 64 backward, conv_bwd.hip, BWD64_LEAN: every bf16 build): p = bf16(a) bf16(W1) as one product;
+  * dp_bwd64 (64 -> 64 backward, conv_bwd64.hip, BWD64_LEAN: every bf16 build): p = bf16(a) bf16(W1) as one product;
     dW1 = bf16(a)^T dp and da = dp bf16(W1), dp fp32-accurate (split hi + lo); everything else fp32.
   * The other backward tile kernels (dp_bwd<...>, including the split-bf16 GEMM = 1 32 -> 64 instance and the packed
     64 -> 16 heads): fp32-accurate arithmetic on the widened stored bf16 x and z (the BN backward's xhat comes from the

@@ -32,8 +32,8 @@ KNOWN = {
     ('loss_step.hip', 'assign_resolve2_kernel'): 2,
     ('loss_step.hip', 'assign_topk2_kernel'): 2,
 }
-FILES = ['api.hip', 'conv_fwd.hip', 'conv_fwd16.hip', 'conv_fwd64.hip', 'conv_bwd.hip', 'conv_bwd16.hip', 'conv_stem.hip',
-         'loss_step.hip']
+FILES = ['api.hip', 'conv_fwd.hip', 'conv_fwd16.hip', 'conv_fwd64.hip', 'conv_bwd.hip', 'conv_bwd64.hip', 'conv_bwd16.hip',
+         'conv_bwd_ew.hip', 'conv_bwd_host.hip', 'conv_stem.hip', 'loss_step.hip']
 
 
 def _scanner():

@@ -1,7 +1,7 @@
 """-m gpu: what the two-way bf16 split of the 64 -> 64 BACKWARD GEMMs costs.
 
 The forward 64-channel units multiply through an exact three-way bf16 split (fp32-accurate, 2.4e-7).  The backward
-64 -> 64 units (dp_bwd64, csrc/conv_bwd.hip) form p, dW1 and da as hi*hi + hi*lo + lo*hi -- every operand carries 16
+64 -> 64 units (dp_bwd64, csrc/conv_bwd64.hip) form p, dW1 and da as hi*hi + hi*lo + lo*hi -- every operand carries 16
 significand bits, a product is good to ~2^-17.  The dispatcher option `bwd_fp32mma` runs the same units on the exact-fp32
 matrix instruction (bench.py's `exact_fp32_bwd` line).  This file PROVES the bound instead of asserting it in prose:
 
