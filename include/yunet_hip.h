@@ -427,7 +427,7 @@ typedef struct YunetAugCfg {
 
 /* Per image: decide scale / window / flip, transform and compact the kept boxes + keypoints.
  *  src_hw [N,2] (h, w); boxes [sum G,4] xyxy; kps [sum G,5,3]; gt_off [N+1] prefix offsets;
- *  params [N,8] int32 = left, top, cw (0 = failed), flip, kept, draws, status, 0
+ *  params [N,8] int32 = left, top, cw (0 = failed), flip, kept, draws, status, 0 (S_n from yunet_aug_decide_ms)
  *      status 0 ok, 1 no window with a box centre inside (or no GT), 2 kept > gmax (truncated);
  *  out_boxes [N,gmax,4], out_kps [N,gmax,5,3] (rows >= count zeroed), out_count [N]. */
 int yunet_aug_decide(const int32_t* src_hw, const float* boxes, const float* kps, const int32_t* gt_off,
@@ -495,6 +495,31 @@ int yunet_aug_pixels_photo(const uint8_t* src, const long long* src_off, const i
 int yunet_aug_pixels_window_photo(const uint8_t* win, const long long* win_off, const int32_t* rect,
                                   const int32_t* src_hw, const int32_t* params, const float* pparams, int position,
                                   const YunetAugCfg* cfg, int N, float* out_img, void* stream);
+
+/* Multi-scale training: Resize(img_scale=(a, b), multiscale_mode='square_range', keep_ratio=False), the reference's
+ * own addition to mmdet's Resize (transforms.py:99, 128-149, 226-228).  Additive to ABI 11: nothing above changes.
+ *
+ * yunet_aug_decide_ms is yunet_aug_decide with one more draw per image, in the reference's position -- after the
+ * crop draws, before the flip draw: edge = scale_lo + floor(u32 / 2^32 * (scale_hi + 1 - scale_lo))
+ * (numpy.random.randint(lo, hi + 1)), S_n = edge / 32 * 32.  Boxes, keypoints, clipping and flip are the arithmetic
+ * of yunet_aug_decide with S_n in place of cfg->out_size (which is ignored); params[n][7] = S_n.  An image with
+ * status 1 makes the draw too (no GT: it is its only draw).  YUNET_EINVAL unless
+ * 32 <= scale_lo <= scale_hi <= YUNET_AUG_MAX_EDGE. */
+#define YUNET_AUG_MAX_EDGE 8192
+int yunet_aug_decide_ms(const int32_t* src_hw, const float* boxes, const float* kps, const int32_t* gt_off,
+                        const YunetAugCfg* cfg, int scale_lo, int scale_hi, uint32_t iteration, int N,
+                        int32_t* params, float* out_boxes, float* out_kps, int32_t* out_count, void* stream);
+/* The pixel pass of a multi-scale batch onto a canvas out_img [N,3,out_hw,out_hw]: image n fills the top-left
+ * S_n x S_n corner (S_n = params[n][7] of yunet_aug_decide_ms) with exactly the floats yunet_aug_pixels* gives at
+ * out_size = S_n; every other canvas pixel is 0.0f -- DefaultFormatBundle's padding_value (formatting.py:202, 231)
+ * as mmcv's collate applies it, bottom and right (the placement is mmcv's rule; mmcv is not part of the reference
+ * tree and is unpinned here).  out_hw is the batch's max S_n; a larger S_n is cut at the canvas, S_n <= 0 gives an
+ * all-zero image.  One entry for the four forms: rect = NULL reads whole sources (yunet_aug_pixels), else the
+ * window buffer of yunet_aug_window_plan, whose rectangles do not depend on the output size; position =
+ * YUNET_PHOTO_NONE (pparams unused) / PRE / POST -- POST distorts the image, never the zero border. */
+int yunet_aug_pixels_canvas(const uint8_t* src, const long long* src_off, const int32_t* rect, const int32_t* src_hw,
+                            const int32_t* params, const float* pparams, int position, const YunetAugCfg* cfg,
+                            int out_hw, int N, float* out_img, void* stream);
 
 /* Decoded-source store (pipelines.SourceStore).  One launch builds a batch's SourceBatch tables from the store's
  * per-image tables (M images: byte offset, (h, w), first GT row, GT count; boxes [*,4], kps [*,5,3]) and a device

@@ -72,6 +72,7 @@ class YunetAugCfg(C.Structure):
 # PhotoMetricDistortion in the pixel pass (YUNET_PHOTO_*): positions, sub-stream salt, per-image table words
 PHOTO_NONE, PHOTO_PRE, PHOTO_POST = 0, 1, 2
 PHOTO_SALT, PHOTO_WORDS = 0x50484D44, 16
+AUG_MAX_EDGE = 8192                  # YUNET_AUG_MAX_EDGE (yunet_aug_decide_ms / yunet_aug_pixels_canvas)
 (PHOTO_BRIGHT, PHOTO_DELTA, PHOTO_MODE, PHOTO_CONTRAST, PHOTO_ALPHA, PHOTO_SAT, PHOTO_SAT_F, PHOTO_HUE, PHOTO_HUE_D,
  PHOTO_SWAP, PHOTO_PERM, PHOTO_DRAWS) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 13
 
@@ -142,6 +143,10 @@ _SIGNATURES = {
                                                             C.c_void_p]),
     'yunet_aug_pixels_window_photo': (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.POINTER(YunetAugCfg), C.c_int,
                                                                    C.c_void_p, C.c_void_p]),
+    'yunet_aug_decide_ms': (C.c_int, [C.c_void_p] * 4 + [C.POINTER(YunetAugCfg), C.c_int, C.c_int, C.c_uint32, C.c_int] +
+                            [C.c_void_p] * 5),
+    'yunet_aug_pixels_canvas': (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.POINTER(YunetAugCfg), C.c_int, C.c_int,
+                                                             C.c_void_p, C.c_void_p]),
     'yunet_aug_gather': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int] +
                          [C.c_void_p] * 6),
     'yunet_aug_window_plan': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

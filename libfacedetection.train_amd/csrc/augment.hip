@@ -11,6 +11,11 @@
 //   aug_pixels_kernel : one thread per output pixel: flip -> bilinear taps in the (virtual) padded
 //       crop -> source uint8 gather, written planar NCHW fp32 (what stem_fwd reads).
 //
+// Multi-scale training (Resize(multiscale_mode='square_range'), transforms.py:128-149): MS = true makes one more
+// bounded draw per image, between the crop draws and the flip draw, and uses S_n = edge / 32 * 32 in place of
+// cfg.out_size; CANVAS = true writes image n into the top-left S_n x S_n corner of an out_hw x out_hw canvas whose
+// remaining pixels are 0 (DefaultFormatBundle's padding_value through mmcv's collate).
+//
 // Built with -ffp-contract=off: every float operation is the single rounded operation numpy
 // performs, so boxes / keypoints are bit-identical to the reference and pixels to the oracle.
 #include <cfloat>
@@ -51,11 +56,15 @@ __device__ __forceinline__ bool centre_inside(const float* b, int p0, int p1, in
 #define AUG_P_KEPT 4
 #define AUG_P_DRAWS 5
 #define AUG_P_STATUS 6
+#define AUG_P_SIZE 7      // MS: S_n of the image; 0 from the fixed-size decide
 
+// MS = false: S = cfg.out_size, scale_lo / scale_hi unused.  MS = true: S = S_n drawn from [scale_lo, scale_hi].
+template <bool MS>
 __global__ __launch_bounds__(64) void aug_decide_kernel(
     const int32_t* __restrict__ src_hw, const float* __restrict__ boxes, const float* __restrict__ kps,
-    const int32_t* __restrict__ gt_off, const YunetAugCfg cfg, uint32_t iteration, int32_t* __restrict__ params,
-    float* __restrict__ out_boxes, float* __restrict__ out_kps, int32_t* __restrict__ out_count) {
+    const int32_t* __restrict__ gt_off, const YunetAugCfg cfg, int scale_lo, int scale_hi, uint32_t iteration,
+    int32_t* __restrict__ params, float* __restrict__ out_boxes, float* __restrict__ out_kps,
+    int32_t* __restrict__ out_count) {
     const int n = blockIdx.x, lane = threadIdx.x;
     const int h = src_hw[2 * n], w = src_hw[2 * n + 1];
     const int g0 = gt_off[n], G = gt_off[n + 1] - g0;
@@ -63,7 +72,7 @@ __global__ __launch_bounds__(64) void aug_decide_kernel(
     const float* kp = kps + (size_t)g0 * 15;
     const uint32_t key = stream_key(cfg.seed, iteration, (uint32_t)n);
     uint32_t ctr = 0;
-    const int S = cfg.out_size, gmax = cfg.gmax;
+    const int gmax = cfg.gmax;
     float* ob = out_boxes + (size_t)n * gmax * 4;
     float* ok = out_kps + (size_t)n * gmax * 15;
 
@@ -87,6 +96,10 @@ __global__ __launch_bounds__(64) void aug_decide_kernel(
             found = __any(any);
         }
     }
+    // ---- Resize._random_scale, square_range: randint(lo, hi + 1) // 32 * 32 (transforms.py:143-149); drawn for a
+    // failed image too, so that its S_n is defined
+    int S = cfg.out_size;
+    if (MS) S = (scale_lo + bounded(rand_u32(key, ctr++), scale_hi + 1 - scale_lo)) / 32 * 32;
     // ---- RandomFlip: one uniform against flip_ratio (transforms.py:514-521) -------------------
     const bool flip = found && ((double)rand_u32(key, ctr++) * (1.0 / 4294967296.0) < cfg.flip_ratio);
 
@@ -133,7 +146,7 @@ __global__ __launch_bounds__(64) void aug_decide_kernel(
         int32_t* p = params + 8 * n;
         p[AUG_P_LEFT] = left; p[AUG_P_TOP] = top; p[AUG_P_CW] = found ? cw : 0;
         p[AUG_P_FLIP] = flip ? 1 : 0; p[AUG_P_KEPT] = kept; p[AUG_P_DRAWS] = (int32_t)ctr;
-        p[AUG_P_STATUS] = found ? (kept > gmax ? 2 : 0) : 1; p[7] = 0;
+        p[AUG_P_STATUS] = found ? (kept > gmax ? 2 : 0) : 1; p[AUG_P_SIZE] = MS ? S : 0;
         out_count[n] = count;
     }
 }
@@ -293,13 +306,16 @@ __device__ __forceinline__ void photo_pixel(const Photo& q, float& b, float& g, 
 //   src + src_off[n] with row pitch cols (yunet_aug_window_plan; the host-store upload).  The float operations are
 //   those of WIN = false, so the output is bit-identical; the extra rectangle test only ever fails when the plan
 //   does not belong to these params, and then it reads pad instead of leaving the window buffer.
+// CANVAS = false: S is the output edge of every image.  CANVAS = true: S is the canvas edge (out_hw) and image n's
+//   edge is params[n][AUG_P_SIZE]; canvas pixels at or beyond it are 0 -- also under PH = POST, which distorts the
+//   image, not the collate padding -- and the pixels inside take the float operations of CANVAS = false at S = S_n.
 // PH = YUNET_PHOTO_NONE: no distortion (yunet_aug_pixels / _window); PRE: each in-image tap pixel is distorted after
 //   its load (pad taps stay pad); POST: the output pixel is distorted after the vertical pass.  `pp` = the table of
 //   yunet_aug_photometric (unused for NONE).
-template <bool WIN, int PH>
+template <bool WIN, int PH, bool CANVAS = false>
 __global__ __launch_bounds__(256) void aug_pixels_kernel(
     const uint8_t* __restrict__ src, const long long* __restrict__ src_off, const int32_t* __restrict__ src_hw,
-    const int32_t* __restrict__ rect, const int32_t* __restrict__ params, const float* __restrict__ pp, int S,
+    const int32_t* __restrict__ rect, const int32_t* __restrict__ params, const float* __restrict__ pp, int C,
     float pad, float* __restrict__ out) {
     const int n = blockIdx.y;
     const int32_t* p = params + 8 * n;
@@ -308,11 +324,18 @@ __global__ __launch_bounds__(256) void aug_pixels_kernel(
     const int ry = WIN ? rect[4 * n + 0] : 0, rx = WIN ? rect[4 * n + 1] : 0;
     const int rh = WIN ? rect[4 * n + 2] : h, rw = WIN ? rect[4 * n + 3] : w;
     const uint8_t* im = src + src_off[n];
-    float* o = out + (size_t)n * 3 * S * S;
+    const int S = CANVAS ? p[AUG_P_SIZE] : C;
+    float* o = out + (size_t)n * 3 * C * C;
     Photo q;
     if (PH != YUNET_PHOTO_NONE) q = load_photo(pp + (size_t)n * YUNET_PHOTO_WORDS);
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < S * S; i += gridDim.x * 256) {
-        const int dy = i / S, dx = i - dy * S;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < C * C; i += gridDim.x * 256) {
+        const int dy = i / C, dx = i - dy * C;
+        if (CANVAS && (dy >= S || dx >= S)) {
+            o[i] = 0.0f;
+            o[(size_t)C * C + i] = 0.0f;
+            o[(size_t)2 * C * C + i] = 0.0f;
+            continue;
+        }
         float v[3] = {pad, pad, pad};
         if (cw > 0) {
             const int dxs = flip ? S - 1 - dx : dx;
@@ -363,8 +386,8 @@ __global__ __launch_bounds__(256) void aug_pixels_kernel(
         }
         if (PH == YUNET_PHOTO_POST) photo_pixel(q, v[0], v[1], v[2]);
         o[i] = v[0];
-        o[(size_t)S * S + i] = v[1];
-        o[(size_t)2 * S * S + i] = v[2];
+        o[(size_t)C * C + i] = v[1];
+        o[(size_t)2 * C * C + i] = v[2];
     }
 }
 
@@ -377,8 +400,20 @@ extern "C" int yunet_aug_decide(const int32_t* src_hw, const float* boxes, const
     if (!cfg || N < 1 || cfg->n_choice < 1 || cfg->n_choice > 8 || cfg->out_size < 1 || cfg->gmax < 1 ||
         cfg->max_attempts < 1 || cfg->max_retries < 1)
         return YUNET_EINVAL;
-    hipLaunchKernelGGL(aug_decide_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, src_hw, boxes, kps,
-                       gt_off, *cfg, iteration, params, out_boxes, out_kps, out_count);
+    hipLaunchKernelGGL(aug_decide_kernel<false>, dim3(N), dim3(64), 0, (hipStream_t)stream, src_hw, boxes, kps,
+                       gt_off, *cfg, 0, 0, iteration, params, out_boxes, out_kps, out_count);
+    return hip_status();
+}
+
+extern "C" int yunet_aug_decide_ms(const int32_t* src_hw, const float* boxes, const float* kps,
+                                   const int32_t* gt_off, const YunetAugCfg* cfg, int scale_lo, int scale_hi,
+                                   uint32_t iteration, int N, int32_t* params, float* out_boxes, float* out_kps,
+                                   int32_t* out_count, void* stream) {
+    if (!cfg || N < 1 || cfg->n_choice < 1 || cfg->n_choice > 8 || cfg->gmax < 1 || cfg->max_attempts < 1 ||
+        cfg->max_retries < 1 || scale_lo < 32 || scale_hi < scale_lo || scale_hi > YUNET_AUG_MAX_EDGE)
+        return YUNET_EINVAL;
+    hipLaunchKernelGGL(aug_decide_kernel<true>, dim3(N), dim3(64), 0, (hipStream_t)stream, src_hw, boxes, kps,
+                       gt_off, *cfg, scale_lo, scale_hi, iteration, params, out_boxes, out_kps, out_count);
     return hip_status();
 }
 
@@ -455,4 +490,38 @@ extern "C" int yunet_aug_pixels_window_photo(const uint8_t* win, const long long
                                              int position, const YunetAugCfg* cfg, int N, float* out_img,
                                              void* stream) {
     return launch_pixels_photo<true>(win, win_off, src_hw, rect, params, pparams, position, cfg, N, out_img, stream);
+}
+
+template <bool WIN>
+static int launch_pixels_canvas(const uint8_t* src, const long long* src_off, const int32_t* src_hw,
+                                const int32_t* rect, const int32_t* params, const float* pparams, int position,
+                                const YunetAugCfg* cfg, int out_hw, int N, float* out_img, void* stream) {
+    int bx = (out_hw * out_hw + 255) / 256;     // the grid covers the canvas, border included
+    if (bx > 64) bx = 64;
+    const dim3 grid(bx, N), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (position == YUNET_PHOTO_NONE)
+        hipLaunchKernelGGL((aug_pixels_kernel<WIN, YUNET_PHOTO_NONE, true>), grid, block, 0, st, src, src_off, src_hw,
+                           rect, params, pparams, out_hw, cfg->pad_value, out_img);
+    else if (position == YUNET_PHOTO_PRE)
+        hipLaunchKernelGGL((aug_pixels_kernel<WIN, YUNET_PHOTO_PRE, true>), grid, block, 0, st, src, src_off, src_hw,
+                           rect, params, pparams, out_hw, cfg->pad_value, out_img);
+    else
+        hipLaunchKernelGGL((aug_pixels_kernel<WIN, YUNET_PHOTO_POST, true>), grid, block, 0, st, src, src_off, src_hw,
+                           rect, params, pparams, out_hw, cfg->pad_value, out_img);
+    return hip_status();
+}
+
+extern "C" int yunet_aug_pixels_canvas(const uint8_t* src, const long long* src_off, const int32_t* rect,
+                                       const int32_t* src_hw, const int32_t* params, const float* pparams,
+                                       int position, const YunetAugCfg* cfg, int out_hw, int N, float* out_img,
+                                       void* stream) {
+    const bool photo = position == YUNET_PHOTO_PRE || position == YUNET_PHOTO_POST;
+    if (!cfg || N < 1 || out_hw < 1 || out_hw > YUNET_AUG_MAX_EDGE || (!photo && position != YUNET_PHOTO_NONE) ||
+        (photo && !pparams))
+        return YUNET_EINVAL;
+    return rect ? launch_pixels_canvas<true>(src, src_off, src_hw, rect, params, pparams, position, cfg, out_hw, N,
+                                             out_img, stream)
+                : launch_pixels_canvas<false>(src, src_off, src_hw, nullptr, params, pparams, position, cfg, out_hw,
+                                              N, out_img, stream);
 }

@@ -188,6 +188,7 @@ class RetinaFaceSource:
         self.cache, self.store, self._feed, self._decoding = cache, None, None, {}
         self.ds, self.bs, self.rank, self.world, self.seed = dataset, samples_per_gpu, rank, world, seed
         self.pipe = DevicePipeline(pipeline, seed=seed + 7919 * rank, gmax=64 if max_gt <= 64 else 128)
+        self.pipe.check_plan_cache()
         from .samplers import DistributedGroupSampler
         self.sampler = DistributedGroupSampler(dataset, samples_per_gpu, world, rank, seed=seed)
         self.iters_per_epoch = max(1, len(self.sampler) // samples_per_gpu)

@@ -68,18 +68,43 @@ class RandomSquareCrop(_Carrier):
 
 @PIPELINES.register_module()
 class Resize(_Carrier):
-    """transforms.py:52-330, the keep_ratio=False / single-scale case of the train configs."""
+    """transforms.py:52-330, the keep_ratio=False cases of the train configs: one square scale, or the reference's own
+    multiscale_mode='square_range' (transforms.py:128-149): per sample one edge from [min(img_scale), max(img_scale)],
+    rounded down to a multiple of 32 (`scale_range` = (lo, hi); None for the fixed size)."""
 
     def __init__(self, img_scale=None, multiscale_mode='range', ratio_range=None, keep_ratio=True,
                  bbox_clip_border=True, backend='cv2', interpolation='bilinear', override=False):
+        square = multiscale_mode == 'square_range' and ratio_range is None
         if isinstance(img_scale, list):
             if len(img_scale) != 1:
-                raise NotImplementedError('multi-scale Resize')
+                if square:      # random_sample_square asserts len(img_scales) == 1
+                    raise ValueError("Resize(multiscale_mode='square_range') takes one img_scale=(a, b), got "
+                                     f'{len(img_scale)}')
+                raise NotImplementedError(f'multi-scale Resize(multiscale_mode={multiscale_mode!r}) with '
+                                          f"{len(img_scale)} scales; implemented: 'square_range' with one (a, b)")
             img_scale = img_scale[0]
-        if keep_ratio or ratio_range is not None or img_scale is None or img_scale[0] != img_scale[1] \
+        if ratio_range is not None:
+            raise NotImplementedError(f'multi-scale Resize(ratio_range={ratio_range!r})')
+        if square:
+            if keep_ratio or img_scale is None or interpolation != 'bilinear' or not bbox_clip_border:
+                raise NotImplementedError("only Resize(img_scale=(a, b), multiscale_mode='square_range', "
+                                          'keep_ratio=False, bilinear)')
+            lo, hi = int(min(img_scale)), int(max(img_scale))
+            if lo < 32:
+                raise ValueError(f"Resize(multiscale_mode='square_range'): the low end {lo} rounds down to an edge of 0 "
+                                 '(edges are multiples of 32)')
+            if hi > L.AUG_MAX_EDGE:
+                raise ValueError(f"Resize(multiscale_mode='square_range'): the high end {hi} exceeds {L.AUG_MAX_EDGE}")
+            super().__init__(img_scale=(int(img_scale[0]), int(img_scale[1])), multiscale_mode=multiscale_mode)
+            self.scale_range = (lo, hi)
+            return
+        if keep_ratio or img_scale is None or img_scale[0] != img_scale[1] \
                 or interpolation != 'bilinear' or not bbox_clip_border:
-            raise NotImplementedError('only Resize(img_scale=(S, S), keep_ratio=False, bilinear)')
+            raise NotImplementedError('only Resize(img_scale=(S, S), keep_ratio=False, bilinear)' + (
+                f'; multiscale_mode={multiscale_mode!r} is not implemented for img_scale={tuple(img_scale)}'
+                if img_scale is not None and img_scale[0] != img_scale[1] else ''))
         super().__init__(img_scale=(int(img_scale[0]), int(img_scale[1])))
+        self.scale_range = None
 
 
 @PIPELINES.register_module()
@@ -217,14 +242,24 @@ class DevicePipeline:
         by = dict(zip(names, steps))
         if not by['LoadAnnotations'].with_keypoints:
             raise NotImplementedError('LoadAnnotations(with_keypoints=True) is required')
-        self.out_size = by['Resize'].img_scale[0]
-        if self.out_size % 32:
-            raise ValueError('Resize img_scale must be a multiple of 32 for the YuNet stack')
+        # fixed size: out_size = S, out_sizes = [S].  square_range: out_size is None (there is no one size) and
+        # out_sizes lists the S_n an image can draw, the multiples of 32 in [lo // 32 * 32, hi // 32 * 32]
+        self.scale_range = by['Resize'].scale_range
+        if self.scale_range is None:
+            self.out_size = by['Resize'].img_scale[0]
+            if self.out_size % 32:
+                raise ValueError('Resize img_scale must be a multiple of 32 for the YuNet stack')
+            self.out_sizes = [self.out_size]
+        else:
+            lo, hi = self.scale_range
+            self.out_size = None
+            self.out_sizes = list(range(lo // 32 * 32, hi // 32 * 32 + 1, 32))
+        self.sizes = None            # square_range: S_n of the last batch (host int32 [N])
         choice = by['RandomSquareCrop'].crop_choice
         if not 1 <= len(choice) <= 8:
             raise NotImplementedError('crop_choice must have 1..8 entries')
         cfg = L.YunetAugCfg()
-        cfg.out_size, cfg.n_choice = self.out_size, len(choice)
+        cfg.out_size, cfg.n_choice = self.out_size or self.out_sizes[-1], len(choice)    # unused by the _ms entry
         for i, c in enumerate(choice):
             cfg.crop_choice[i] = c
         cfg.flip_ratio, cfg.pad_value, cfg.seed = by['RandomFlip'].flip_ratio, pad_value, seed & 0xFFFFFFFF
@@ -234,11 +269,14 @@ class DevicePipeline:
         self.gmax = gmax
         self.params = None
 
-    def __call__(self, src, iteration):
+    def __call__(self, src, iteration, sizes=None):
         lib = L.load()
         n, S, dev = src.n, self.out_size, src.src.device
         if dev.type != 'cuda':
             raise RuntimeError('DevicePipeline needs device-resident sources: HIP kernels only, no CPU fallback')
+        if self.scale_range is not None:
+            gb, gk, cnt, params = self._decide(src, iteration, dev)
+            return self._canvas(src.src, src.src_off, None, src, iteration, gb, gk, cnt, params, sizes, dev)
         img = torch.empty(n, 3, S, S, device=dev, dtype=torch.float32)
         gb, gk, cnt, params = self._decide(src, iteration, dev)
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -272,10 +310,44 @@ class DevicePipeline:
         params = torch.empty(n, 8, device=dev, dtype=torch.int32)
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+        if self.scale_range is not None:
+            lo, hi = self.scale_range
+            L.check(lib.yunet_aug_decide_ms(p(src.src_hw), p(src.boxes), p(src.kps), p(src.gt_off), C.byref(self.cfg),
+                                            lo, hi, int(iteration) & 0xFFFFFFFF, n, p(params), p(gb), p(gk), p(cnt),
+                                            stream), 'yunet_aug_decide_ms')
+            return gb, gk, cnt, params
         L.check(lib.yunet_aug_decide(p(src.src_hw), p(src.boxes), p(src.kps), p(src.gt_off), C.byref(self.cfg),
                                      int(iteration) & 0xFFFFFFFF, n, p(params), p(gb), p(gk), p(cnt), stream),
                 'yunet_aug_decide')
         return gb, gk, cnt, params
+
+    def read_sizes(self, params):
+        """square_range: S_n [N] (params[:, 7]) on the host.  The batch tensor is [N, 3, max S_n, max S_n], so the host
+        has to know the sizes before it can allocate: one N-word copy that waits for the decide kernel on the current
+        stream (and for nothing else on the device).  WindowFeed makes this copy with its plan, iterations ahead, and
+        hands the result to `windowed(sizes=...)`."""
+        return params[:, 7].cpu().numpy()
+
+    def _canvas(self, pix, pix_off, rect, src, iteration, gb, gk, cnt, params, sizes, dev):
+        """square_range: the pixel pass onto the [N, 3, Smax, Smax] canvas and the collate.  Image n sits in the
+        top-left S_n x S_n corner, the rest is 0: DefaultFormatBundle wraps the image with padding_value=0, stack=True
+        (formatting.py:202, 231) and mmcv's collate pads a group's images at the bottom and right up to the largest.
+        The value and the stacking are the reference's; the bottom / right placement is mmcv's rule, restated here
+        without mmcv at hand."""
+        n = src.n
+        sizes = np.asarray(self.read_sizes(params) if sizes is None else sizes, dtype=np.int32)
+        if sizes.shape != (n,) or not all(int(s) in self.out_sizes for s in sizes):
+            raise RuntimeError(f'square_range sizes {sizes.tolist()} are not the S_n of this pipeline ({self.out_sizes})')
+        self.sizes = sizes
+        smax = int(sizes.max())
+        img = torch.empty(n, 3, smax, smax, device=dev, dtype=torch.float32)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        pp = self._photometric(n, iteration, dev) if self.photo is not None else None
+        L.check(L.load().yunet_aug_pixels_canvas(p(pix), p(pix_off), p(rect), p(src.src_hw), p(params), p(pp),
+                                                 self.photo_position, C.byref(self.cfg), smax, n, p(img), stream),
+                'yunet_aug_pixels_canvas')
+        return self._collate(img, gb, gk, cnt, params, dev)
 
     def _collate(self, img, gb, gk, cnt, params, dev):
         n, S = img.shape[0], self.out_size
@@ -284,7 +356,12 @@ class DevicePipeline:
         boxes.padded, boxes.counts = gb, cnt
         kps.padded, kps.counts = gk, cnt
         labels = GTList([torch.zeros(self.gmax, dtype=torch.int64, device=dev)] * n)
-        metas = [dict(img_shape=(S, S, 3), pad_shape=(S, S, 3), batch_input_shape=(S, S)) for _ in range(n)]
+        if self.scale_range is not None:      # mmdet's Resize sets img_shape = pad_shape; collate leaves metas alone
+            smax = int(img.shape[-1])
+            metas = [dict(img_shape=(int(s), int(s), 3), pad_shape=(int(s), int(s), 3), batch_input_shape=(smax, smax))
+                     for s in self.sizes]
+        else:
+            metas = [dict(img_shape=(S, S, 3), pad_shape=(S, S, 3), batch_input_shape=(S, S)) for _ in range(n)]
         return dict(img=img, img_metas=metas, gt_bboxes=boxes, gt_labels=labels, gt_keypointss=kps)
 
     def window_plan(self, src, iteration, dev):
@@ -302,14 +379,18 @@ class DevicePipeline:
                 'yunet_aug_window_plan')
         return params, rect, off
 
-    def windowed(self, src, iteration, win, rect, win_off):
+    def windowed(self, src, iteration, win, rect, win_off, sizes=None):
         """The pipeline on a compact window buffer `win` (uint8, device) holding, at win_off[n], the rectangle
-        rect[n] of image n (window_plan of the same iteration): bit-identical to __call__ on the full sources."""
+        rect[n] of image n (window_plan of the same iteration): bit-identical to __call__ on the full sources.
+        square_range: `sizes` = params[:, 7] of that plan, already on the host (else read_sizes waits here)."""
         lib = L.load()
         dev = win.device
         if dev.type != 'cuda':
             raise RuntimeError('DevicePipeline needs a device-resident window buffer: HIP kernels only')
         n, S = src.n, self.out_size
+        if self.scale_range is not None:
+            gb, gk, cnt, params = self._decide(src, iteration, dev)
+            return self._canvas(win, win_off, rect, src, iteration, gb, gk, cnt, params, sizes, dev)
         img = torch.empty(n, 3, S, S, device=dev, dtype=torch.float32)
         gb, gk, cnt, params = self._decide(src, iteration, dev)
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -323,6 +404,18 @@ class DevicePipeline:
                                                       self.photo_position, C.byref(self.cfg), n, p(img), stream),
                     'yunet_aug_pixels_window_photo')
         return self._collate(img, gb, gk, cnt, params, dev)
+
+    def check_plan_cache(self, max_plans=None):
+        """square_range walks len(out_sizes) batch geometries, one engine plan each; beyond engine.MAX_PLANS every
+        new geometry evicts a plan, and an eviction drains the device (Engine.get_plan)."""
+        if max_plans is None:
+            from . import engine
+            max_plans = engine.MAX_PLANS
+        if len(self.out_sizes) > max_plans:
+            lo, hi = self.scale_range
+            raise ValueError(f"Resize(img_scale=({lo}, {hi}), multiscale_mode='square_range') draws {len(self.out_sizes)} "
+                             f'batch sizes but the engine keeps {max_plans} plans: narrow the range or set '
+                             f'YUNET_MAX_PLANS >= {len(self.out_sizes)} in the environment')
 
     def check(self):
         """Synchronising status check of the last batch: raises like the reference would misbehave

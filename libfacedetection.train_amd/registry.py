@@ -47,15 +47,23 @@ class Config(ConfigDict):
         return cfg
 
     def merge_from_dict(self, options):
-        """--cfg-options key.sub=value overrides (tools/train.py:72-81)."""
+        """--cfg-options key.sub=value overrides (tools/train.py:72-81).  A number after a list-valued key indexes the
+        list, as mmcv's allow_list_keys=True does: data.train.pipeline.3.multiscale_mode=square_range."""
         for key, value in options.items():
             node = self
             parts = key.split('.')
-            for p in parts[:-1]:
-                if p not in node or not isinstance(node[p], dict):
+            for i, p in enumerate(parts[:-1]):
+                if isinstance(node, list):
+                    node = node[int(p)]
+                    continue
+                into_list = p in node and isinstance(node[p], list) and parts[i + 1].isdigit()
+                if not into_list and (p not in node or not isinstance(node[p], dict)):
                     node[p] = ConfigDict()          # mmcv creates the intermediate dicts (e.g. fp16.loss_scale=512.)
                 node = node[p]
-            node[parts[-1]] = value
+            if isinstance(node, list):
+                node[int(parts[-1])] = value
+            else:
+                node[parts[-1]] = value
 
     @property
     def pretty_text(self):

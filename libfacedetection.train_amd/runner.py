@@ -144,6 +144,7 @@ class SyntheticSourceImages:
                  seed=0, host_fed=False, timing=False, host_fetch=None, **_):
         from .pipelines import DevicePipeline
         self.pipe = DevicePipeline(pipeline, seed=seed + 7919 * rank, gmax=64 if max_gt <= 64 else 128)
+        self.pipe.check_plan_cache()
         self.bs, self.iters_per_epoch, self.rank = samples_per_gpu, iters_per_epoch, rank
         self.pool, self.src_hw, self.max_gt, self.seed = pool, src_hw, max_gt, seed
         if host_fed not in (False, True, 'window'):
@@ -583,7 +584,17 @@ class TextLoggerHook(LoggerHook):
     def log(self, runner, rec):
         keys = [k for k in rec if k not in ('iter', 'epoch', 'lr', 'time')]
         runner.logger(f"Epoch [{rec['epoch']}][{rec['iter']}] lr: {rec['lr']:.3e}, time: {rec['time']:.4f}, " +
-                      ', '.join(f'{k}: {rec[k]:.4f}' for k in keys))
+                      ', '.join(f'{k}: {rec[k]}' if isinstance(rec[k], tuple) else f'{k}: {rec[k]:.4f}' for k in keys))
+
+
+class YuNetTextLoggerHook(TextLoggerHook):
+    """mmdet/core/hook/yunet_text_logger_hook.py: TextLoggerHook plus `image_scale`, the (h, w) of the current batch's
+    first image (img_metas[0]['img_shape'][:2], lines 43-44) -- what changes from line to line under
+    Resize(multiscale_mode='square_range').  The key goes into this hook's own line, not into runner.log_buffer."""
+
+    def log(self, runner, rec):
+        shape = runner.data_batch['img_metas'][0]['img_shape'][:2]
+        super().log(runner, dict(rec, image_scale=tuple(int(v) for v in shape)))
 
 
 class TensorboardLoggerHook(LoggerHook):
@@ -614,8 +625,9 @@ class TensorboardLoggerHook(LoggerHook):
             self.writer.close()
 
 
-HOOKS = dict(TextLoggerHook=TextLoggerHook, TensorboardLoggerHook=TensorboardLoggerHook,
-             CheckpointHook=CheckpointHook, OptimizerHook=OptimizerHook, Fp16OptimizerHook=Fp16OptimizerHook)
+HOOKS = dict(TextLoggerHook=TextLoggerHook, YuNetTextLoggerHook=YuNetTextLoggerHook,
+             TensorboardLoggerHook=TensorboardLoggerHook, CheckpointHook=CheckpointHook, OptimizerHook=OptimizerHook,
+             Fp16OptimizerHook=Fp16OptimizerHook)
 
 
 class EpochBasedRunner:

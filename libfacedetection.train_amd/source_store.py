@@ -184,7 +184,11 @@ class WindowFeed:
                      event), yunet_upload_windows queues one hipMemcpy2DAsync per rectangle.
       fetch='kernel' the copy stream waits on the plan event on the GPU and yunet_fetch_windows reads the rectangles
                      from the pinned store itself, with the plan taken from device memory: no host wait, no plan copy.
-                     Invalid plan rows are skipped on the device and flagged in a device status word: check()."""
+                     Invalid plan rows are skipped on the device and flagged in a device status word: check().
+
+    A square_range pipeline (multi-scale training) needs each image's S_n on the host before it can allocate the batch:
+    the plan carries params[:, 7] into a pinned ring with the plan's own copies, and run() hands them to the pipeline
+    once the plan event has passed -- an event made iterations earlier, not a wait on the device."""
 
     RING = 3
 
@@ -201,6 +205,7 @@ class WindowFeed:
         self._status = torch.zeros(1, dtype=torch.int32, device=dev) if fetch == 'kernel' else None
         self._consumed = [None, None]          # event: the pipeline that read buffer b has run
         self._ring = None
+        self._size_ring = None                 # square_range: pinned S_n [N] per plan in flight
         self._nplans = 0
         self._planned = {}                     # it -> plan
         self._uploaded = {}                    # it -> (buffer, e0, e1, bytes)
@@ -211,31 +216,44 @@ class WindowFeed:
     def uploaded(self, it):
         return it in self._uploaded
 
+    def _sizes_to_host(self, params, n):
+        """On the plan stream, before the plan event: S_n of a square_range plan -> a slot of the pinned ring."""
+        if self.pipe.scale_range is None:
+            return None
+        if self._size_ring is None or self._size_ring[0].shape[0] != n:
+            self._size_ring = [torch.empty(n, dtype=torch.int32, pin_memory=True) for _ in range(self.RING)]
+        sizes_h = self._size_ring[self._nplans % self.RING]
+        sizes_h.copy_(params[:, 7], non_blocking=True)
+        return sizes_h
+
     def plan(self, it, idx):
         """Enqueue the plan of iteration it (store images idx) on the plan stream."""
         st = self._plan_stream
+        n = len(idx)
         if self.fetch == 'kernel':
             with torch.cuda.stream(st):
                 sb = self.store.batch(idx)
-                _, rect, off = self.pipe.window_plan(sb, it, self.store.device)
+                params, rect, off = self.pipe.window_plan(sb, it, self.store.device)
+                sizes_h = self._sizes_to_host(params, n)
                 ev = torch.cuda.Event()
                 ev.record(st)
-            self._planned[it] = dict(sb=sb, rect=rect, off=off, ev=ev)
+            self._nplans += 1
+            self._planned[it] = dict(sb=sb, rect=rect, off=off, ev=ev, sizes_h=sizes_h)
             return
-        n = len(idx)
         if self._ring is None or self._ring[0][0].shape[0] != n:
             self._ring = [(torch.empty(n, 4, dtype=torch.int32, pin_memory=True),
                            torch.empty(n + 1, dtype=torch.int64, pin_memory=True)) for _ in range(self.RING)]
         rect_h, off_h = self._ring[self._nplans % self.RING]
-        self._nplans += 1
         with torch.cuda.stream(st):
             sb = self.store.batch(idx)
-            _, rect, off = self.pipe.window_plan(sb, it, self.store.device)
+            params, rect, off = self.pipe.window_plan(sb, it, self.store.device)
             rect_h.copy_(rect, non_blocking=True)
             off_h.copy_(off, non_blocking=True)
+            sizes_h = self._sizes_to_host(params, n)
             ev = torch.cuda.Event()
             ev.record(st)
-        self._planned[it] = dict(sb=sb, rect=rect, off=off, rect_h=rect_h, off_h=off_h, ev=ev)
+        self._nplans += 1
+        self._planned[it] = dict(sb=sb, rect=rect, off=off, rect_h=rect_h, off_h=off_h, ev=ev, sizes_h=sizes_h)
 
     def upload(self, it):
         """Issue the copies of iteration it's windows (its plan must have been enqueued)."""
@@ -313,7 +331,11 @@ class WindowFeed:
         sb = P['sb']
         for t in (sb.src_off, sb.src_hw, sb.boxes, sb.kps, sb.gt_off, P['rect'], P['off']):
             t.record_stream(cur)
-        out = self.pipe.windowed(sb, it, self._bufs[b], P['rect'], P['off'])
+        sizes = None
+        if P['sizes_h'] is not None:
+            P['ev'].synchronize()               # fetch='dma': upload() has waited on it already
+            sizes = P['sizes_h'].numpy().copy()
+        out = self.pipe.windowed(sb, it, self._bufs[b], P['rect'], P['off'], sizes=sizes)
         done = torch.cuda.Event(enable_timing=self.timing)
         done.record(cur)
         self._consumed[b] = done

@@ -14,9 +14,14 @@ configs/yunet_n.py (YuNet_n 320 x 320, 256 images per GPU) from three data sourc
             (+ host_fetch=kernel)   the copy stream, plan from device memory, no host wait)
 
     python tools/train_e2e.py [--iters 200] [--out profiles/r06_train_e2e.json] [--photometric pre|post]
+                              [--multiscale LO,HI | --size S] [--samples-per-gpu N]
 
 --photometric inserts the reference's PhotoMetricDistortion (default arguments) into the config's train_pipeline, before
 RandomSquareCrop (pre) or after RandomFlip (post); the modes other than `ready` then run it in the pixel pass.
+
+--multiscale LO,HI rewrites the config's Resize entry to Resize(img_scale=(LO, HI), multiscale_mode='square_range',
+keep_ratio=False) (multi-scale training: the batch geometry changes from step to step); --size S to the fixed
+img_scale=(S, S); --samples-per-gpu N sets data.samples_per_gpu.  `ready` feeds finished batches and ignores the pipeline.
 
 Prints / writes one JSON object: per mode images/s over the last three logging intervals (150 iterations), the runner's
 time per iteration, and the source's own events (upload ms / GB/s, pipeline ms).  Weights: the trained fixture
@@ -47,14 +52,29 @@ def main():
     ap.add_argument('--modes', default=None,
                     help='comma-separated subset of ready,resident,host_fed,host_window,host_window_kernel')
     ap.add_argument('--photometric', choices=('pre', 'post'), default=None)
+    ap.add_argument('--multiscale', default=None, metavar='LO,HI')
+    ap.add_argument('--size', type=int, default=None)
+    ap.add_argument('--samples-per-gpu', type=int, default=None)
     a = ap.parse_args()
+    if a.multiscale and a.size:
+        ap.error('--multiscale and --size both rewrite the Resize entry')
     import torch
     T = load_train_tool()
     config = a.config
+    edits = []
+    if a.multiscale or a.size:
+        lo, hi = [int(v) for v in a.multiscale.split(',')] if a.multiscale else (a.size, a.size)
+        resize = (f"dict(type='Resize', img_scale=({lo}, {hi}), multiscale_mode='square_range', keep_ratio=False)"
+                  if a.multiscale else f"dict(type='Resize', img_scale=({lo}, {hi}), keep_ratio=False)")
+        edits.append(f"train_pipeline[[p['type'] for p in train_pipeline].index('Resize')] = {resize}")
     if a.photometric:
         at = {'pre': 2, 'post': 5}[a.photometric]
+        edits.append(f"train_pipeline.insert({at}, dict(type='PhotoMetricDistortion'))")
+    if a.samples_per_gpu:
+        edits.append(f"data['samples_per_gpu'] = {a.samples_per_gpu}")
+    if edits:
         tmp = tempfile.NamedTemporaryFile('w', suffix='.py', delete=False)
-        tmp.write(open(a.config).read() + f"\ntrain_pipeline.insert({at}, dict(type='PhotoMetricDistortion'))\n")
+        tmp.write(open(a.config).read() + '\n' + '\n'.join(edits) + '\n')
         tmp.close()
         config = tmp.name
     fixture = os.path.join(ROOT, 'tests', 'golden', 'yunet_n_synth_trained.pth')
@@ -68,7 +88,7 @@ def main():
     if a.modes:
         modes = [m for m in modes if m[0] in a.modes.split(',')]
     res = {'what': __doc__.split('\n')[0], 'config': os.path.basename(a.config), 'iters': a.iters,
-           'photometric': a.photometric, 'modes': {}}
+           'photometric': a.photometric, 'multiscale': a.multiscale, 'size': a.size, 'modes': {}}
     for name, opts in modes:
         with tempfile.TemporaryDirectory() as wd:
             argv = [config, '--work-dir', wd, '--max-iters', str(a.iters), '--no-validate', '--seed', '0',
