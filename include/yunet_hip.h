@@ -521,6 +521,86 @@ int yunet_aug_pixels_canvas(const uint8_t* src, const long long* src_off, const 
                             const int32_t* params, const float* pparams, int position, const YunetAugCfg* cfg,
                             int out_hw, int N, float* out_img, void* stream);
 
+/* Mosaic(use_kps=True) (transforms.py:2218-2519) under MultiImageMixDataset (dataset_wrappers.py:338-444), in front of
+ * RandomSquareCrop.  Additive to ABI 11: nothing above changes.
+ *
+ * Draws of image n come from a SUB-STREAM of the generator: key mix32(stream_key(seed, iteration, n) ^
+ * YUNET_MOSAIC_SALT), counter from 0, in the reference's call order:
+ *   3 x partner index  floor(u32 / 2^32 * M) over the M images of the store  (get_indexes: transforms.py imports
+ *                      numpy's `random`, whose randint(0, len(dataset)) is [0, M) as well)
+ *   1 x uniform(0, 1)  > prob: the image passes through unchanged (geom[YUNET_MOSAIC_APPLIED] = 0)
+ *   2 x uniform(lo, hi) = lo + (hi - lo) * (u32 / 2^32) in double: center_x = int(. * S), then center_y
+ * so the crop / size / flip / photometric draws are the same numbers with Mosaic present or absent.
+ *
+ * geom [N, YUNET_MOSAIC_WORDS] int32 per image: the header words below, then from word YUNET_MOSAIC_QUAD one block
+ * of YUNET_MOSAIC_QWORDS words per sub-image in the order top-left (the image itself), top-right, bottom-left,
+ * bottom-right. */
+#define YUNET_MOSAIC_SALT 0x4D4F5341u  /* "MOSA" */
+#define YUNET_MOSAIC_WORDS 80
+#define YUNET_MOSAIC_APPLIED 0   /* 1: mosaic made, 0: skipped by prob */
+#define YUNET_MOSAIC_CX 1        /* centre (0 when skipped) */
+#define YUNET_MOSAIC_CY 2
+#define YUNET_MOSAIC_DRAWS 3     /* u32 draws consumed from the sub-stream (6; 4 when skipped) */
+#define YUNET_MOSAIC_KEPT 4      /* merged GT rows before the truncation to gmax */
+#define YUNET_MOSAIC_STATUS 5    /* 0 ok, 2 kept > gmax (truncated), | 4 a sub-image resized to an empty size (not pasted) */
+#define YUNET_MOSAIC_QUAD 16
+#define YUNET_MOSAIC_QWORDS 16
+#define YUNET_MOSAIC_Q_IDX 0     /* store index of the sub-image */
+#define YUNET_MOSAIC_Q_H 1       /* its source size */
+#define YUNET_MOSAIC_Q_W 2
+#define YUNET_MOSAIC_Q_RW 3      /* resized size int(w * r), int(h * r), r = min(S / h, S / w) */
+#define YUNET_MOSAIC_Q_RH 4
+#define YUNET_MOSAIC_Q_PX1 5     /* paste rectangle on the canvas (_mosaic_combine) */
+#define YUNET_MOSAIC_Q_PY1 6
+#define YUNET_MOSAIC_Q_PX2 7
+#define YUNET_MOSAIC_Q_PY2 8
+#define YUNET_MOSAIC_Q_CX1 9     /* top-left corner of the crop rectangle in the resized sub-image */
+#define YUNET_MOSAIC_Q_CY1 10
+#define YUNET_MOSAIC_Q_SX 12     /* 12-13, 14-15: double 1 / (rw / w), 1 / (rh / h), the cv2 coordinate scales */
+#define YUNET_MOSAIC_Q_SY 14
+typedef struct YunetMosaicCfg {
+    int32_t img_scale;           /* S of Mosaic(img_scale=(S, S)): the canvas is 2S x 2S */
+    int32_t gmax;                /* rows of the merged GT outputs */
+    double center_lo, center_hi; /* center_ratio_range, 0 <= lo <= hi <= 2 */
+    double prob;
+    float min_bbox_size;         /* used when skip_filter == 0 */
+    float pad_val;               /* canvas fill (114) */
+    uint32_t seed;
+    int32_t bbox_clip_border;
+    int32_t skip_filter;
+    int32_t reserved_;
+} YunetMosaicCfg;
+/* One wavefront per image.  idx [N]: the batch's store indices (an index outside [0, M) is an empty image); store_*:
+ * the tables of yunet_aug_gather.  Writes geom, out_hw [N,2] (2S x 2S, or the image's own size when skipped) and the
+ * merged GT -- boxes / keypoints r * v + pad in fp32, clipped to the canvas (bbox_clip_border), filtered by
+ * min_bbox_size (skip_filter == 0) and by find_inside_bboxes, compacted in the four-image order; the third keypoint
+ * column travels untouched -- into out_boxes [N,gmax,4], out_kps [N,gmax,5,3] (rows >= count zeroed), out_count [N]:
+ * the input of yunet_aug_decide_padded.  A skipped image's own GT is copied through.  YUNET_EINVAL unless
+ * 1 <= S <= YUNET_AUG_MAX_EDGE / 2, M >= 1, 0 <= lo <= hi <= 2, 0 <= prob <= 1. */
+int yunet_aug_mosaic_decide(const int32_t* idx, int N, int M, const int32_t* store_hw, const int32_t* store_goff,
+                            const int32_t* store_gcnt, const float* store_boxes, const float* store_kps,
+                            const YunetMosaicCfg* cfg, uint32_t iteration, int32_t* geom, int32_t* out_hw,
+                            float* out_boxes, float* out_kps, int32_t* out_count, void* stream);
+/* yunet_aug_decide / yunet_aug_decide_ms (scale_lo > 0) on padded input GT: image n's rows are boxes + n * in_gmax * 4,
+ * kps + n * in_gmax * 15, counts[n] of them (clamped to [0, in_gmax]).  Same draws and arithmetic. */
+int yunet_aug_decide_padded(const int32_t* src_hw, const float* boxes, const float* kps, const int32_t* counts,
+                            int in_gmax, const YunetAugCfg* cfg, int scale_lo, int scale_hi, uint32_t iteration, int N,
+                            int32_t* params, float* out_boxes, float* out_kps, int32_t* out_count, void* stream);
+/* The pixel pass over the mosaic canvas, which is never materialised: each tap of the crop's bilinear resolves
+ * through geom -- outside the canvas cfg->pad_value, quadrant by the centre, outside the paste rectangle
+ * mcfg->pad_val, else the inner bilinear tap of the uint8 sub-image (store + store_off[idx]), rounded to fp32 as the
+ * reference's resized sub-image is, before the outer interpolation reads it.  A skipped image reads its own source as
+ * yunet_aug_pixels does.  hw / params: out_hw of yunet_aug_mosaic_decide and the params yunet_aug_decide_padded made
+ * from it.  out_hw = 0: fixed size cfg->out_size; out_hw > 0: the canvas form of yunet_aug_pixels_canvas.
+ * position: YUNET_PHOTO_NONE or YUNET_PHOTO_POST (PRE would distort the canvas, pad included: not built, EINVAL). */
+int yunet_aug_pixels_mosaic(const uint8_t* store, const long long* store_off, const int32_t* geom, const int32_t* hw,
+                            const int32_t* params, const float* pparams, int position, const YunetAugCfg* cfg,
+                            const YunetMosaicCfg* mcfg, int out_hw, int N, float* out_img, void* stream);
+/* Test entry: the canvas itself through the tap function of yunet_aug_pixels_mosaic, canvas [N, 2S, 2S, 3] fp32 HWC
+ * (a skipped image's canvas is all pad_val). */
+int yunet_aug_mosaic_canvas(const uint8_t* store, const long long* store_off, const int32_t* geom,
+                            const YunetMosaicCfg* mcfg, int N, float* canvas, void* stream);
+
 /* Decoded-source store (pipelines.SourceStore).  One launch builds a batch's SourceBatch tables from the store's
  * per-image tables (M images: byte offset, (h, w), first GT row, GT count; boxes [*,4], kps [*,5,3]) and a device
  * index vector idx [N] (repeats allowed, 1 <= N <= 8192): src_off [N], src_hw [N,2], gt_off [N+1] (exclusive scan of

@@ -83,6 +83,21 @@ class YunetPhotoCfg(C.Structure):
                 ('position', C.c_int32), ('reserved_', C.c_int32)]
 
 
+# Mosaic (YUNET_MOSAIC_*): sub-stream salt, geometry table words per image, header words, per-sub-image block
+MOSAIC_SALT, MOSAIC_WORDS = 0x4D4F5341, 80
+MOSAIC_APPLIED, MOSAIC_CX, MOSAIC_CY, MOSAIC_DRAWS, MOSAIC_KEPT, MOSAIC_STATUS = 0, 1, 2, 3, 4, 5
+MOSAIC_QUAD, MOSAIC_QWORDS = 16, 16
+(MOSAIC_Q_IDX, MOSAIC_Q_H, MOSAIC_Q_W, MOSAIC_Q_RW, MOSAIC_Q_RH, MOSAIC_Q_PX1, MOSAIC_Q_PY1, MOSAIC_Q_PX2, MOSAIC_Q_PY2,
+ MOSAIC_Q_CX1, MOSAIC_Q_CY1) = range(11)
+MOSAIC_Q_SX, MOSAIC_Q_SY = 12, 14      # two doubles: the cv2 coordinate scales of the inner resize
+
+
+class YunetMosaicCfg(C.Structure):
+    _fields_ = [('img_scale', C.c_int32), ('gmax', C.c_int32), ('center_lo', C.c_double), ('center_hi', C.c_double),
+                ('prob', C.c_double), ('min_bbox_size', C.c_float), ('pad_val', C.c_float), ('seed', C.c_uint32),
+                ('bbox_clip_border', C.c_int32), ('skip_filter', C.c_int32), ('reserved_', C.c_int32)]
+
+
 MAX_RANKS, IPC_HANDLE_BYTES, COMM_HEADER_BYTES = 8, 64, 20480
 
 
@@ -147,6 +162,13 @@ _SIGNATURES = {
                             [C.c_void_p] * 5),
     'yunet_aug_pixels_canvas': (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.POINTER(YunetAugCfg), C.c_int, C.c_int,
                                                              C.c_void_p, C.c_void_p]),
+    'yunet_aug_mosaic_decide': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 +
+                                [C.POINTER(YunetMosaicCfg), C.c_uint32] + [C.c_void_p] * 6),
+    'yunet_aug_decide_padded': (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.POINTER(YunetAugCfg), C.c_int, C.c_int, C.c_uint32,
+                                                             C.c_int] + [C.c_void_p] * 5),
+    'yunet_aug_pixels_mosaic': (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.POINTER(YunetAugCfg), C.POINTER(YunetMosaicCfg),
+                                                             C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'yunet_aug_mosaic_canvas': (C.c_int, [C.c_void_p] * 3 + [C.POINTER(YunetMosaicCfg), C.c_int, C.c_void_p, C.c_void_p]),
     'yunet_aug_gather': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int] +
                          [C.c_void_p] * 6),
     'yunet_aug_window_plan': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -59,15 +59,18 @@ __device__ __forceinline__ bool centre_inside(const float* b, int p0, int p1, in
 #define AUG_P_SIZE 7      // MS: S_n of the image; 0 from the fixed-size decide
 
 // MS = false: S = cfg.out_size, scale_lo / scale_hi unused.  MS = true: S = S_n drawn from [scale_lo, scale_hi].
-template <bool MS>
+// PAD = false: image n's GT rows are [gt_off[n], gt_off[n + 1]).  PAD = true (the merged GT of mosaic_decide_kernel):
+// rows [n * in_gmax, n * in_gmax + gt_off[n]), gt_off holding the counts.
+template <bool MS, bool PAD = false>
 __global__ __launch_bounds__(64) void aug_decide_kernel(
     const int32_t* __restrict__ src_hw, const float* __restrict__ boxes, const float* __restrict__ kps,
     const int32_t* __restrict__ gt_off, const YunetAugCfg cfg, int scale_lo, int scale_hi, uint32_t iteration,
     int32_t* __restrict__ params, float* __restrict__ out_boxes, float* __restrict__ out_kps,
-    int32_t* __restrict__ out_count) {
+    int32_t* __restrict__ out_count, int in_gmax) {
     const int n = blockIdx.x, lane = threadIdx.x;
     const int h = src_hw[2 * n], w = src_hw[2 * n + 1];
-    const int g0 = gt_off[n], G = gt_off[n + 1] - g0;
+    const int g0 = PAD ? n * in_gmax : gt_off[n];
+    const int G = PAD ? (gt_off[n] < 0 ? 0 : gt_off[n] > in_gmax ? in_gmax : gt_off[n]) : gt_off[n + 1] - g0;
     const float* bx = boxes + (size_t)g0 * 4;
     const float* kp = kps + (size_t)g0 * 15;
     const uint32_t key = stream_key(cfg.seed, iteration, (uint32_t)n);
@@ -164,6 +167,210 @@ __device__ __forceinline__ void lin_coef(int d, int dst, int src, int& s0, int& 
     s1 = s + 1 < src ? s + 1 : src - 1;
     w0 = 1.0f - f;
     w1 = f;
+}
+
+// lin_coef with the coordinate scale 1 / (dst / src) handed in (mosaic_decide_kernel forms it once per sub-image with
+// the same double operations): the same s0 / s1 / w0 / w1.
+__device__ __forceinline__ void lin_coef_s(int d, double scale, int src, int& s0, int& s1, float& w0, float& w1) {
+    float f = (float)(((double)d + 0.5) * scale - 0.5);
+    int s = (int)floorf(f);
+    f -= (float)s;
+    if (s < 0) { f = 0.0f; s = 0; }
+    if (s >= src - 1) { f = 0.0f; s = src - 1; }
+    s0 = s;
+    s1 = s + 1 < src ? s + 1 : src - 1;
+    w0 = 1.0f - f;
+    w1 = f;
+}
+
+// ---- Mosaic(use_kps=True) (transforms.py:2218-2519; include/yunet_hip.h YUNET_MOSAIC_*) --------------------------------
+__device__ __forceinline__ uint32_t mosaic_key(uint32_t seed, uint32_t iteration, uint32_t image) {
+    return mix32(stream_key(seed, iteration, image) ^ YUNET_MOSAIC_SALT);
+}
+
+// One wavefront per image: the draws, the four sub-images' geometry (all wave-uniform integer / double arithmetic, as
+// the Python code has it) and the merged GT, compacted order-preserving like aug_decide_kernel's.
+__global__ __launch_bounds__(64) void mosaic_decide_kernel(
+    const int32_t* __restrict__ idx, int M, const int32_t* __restrict__ store_hw, const int32_t* __restrict__ store_goff,
+    const int32_t* __restrict__ store_gcnt, const float* __restrict__ store_boxes, const float* __restrict__ store_kps,
+    const YunetMosaicCfg cfg, uint32_t iteration, int32_t* __restrict__ geom, int32_t* __restrict__ out_hw,
+    float* __restrict__ out_boxes, float* __restrict__ out_kps, int32_t* __restrict__ out_count) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    const uint32_t key = mosaic_key(cfg.seed, iteration, (uint32_t)n);
+    uint32_t ctr = 0;
+    const int S = cfg.img_scale, gmax = cfg.gmax;
+    int32_t* gm = geom + (size_t)n * YUNET_MOSAIC_WORDS;
+    float* ob = out_boxes + (size_t)n * gmax * 4;
+    float* ok = out_kps + (size_t)n * gmax * 15;
+    for (int i = lane; i < YUNET_MOSAIC_WORDS; i += 64) gm[i] = 0;
+    __syncthreads();      // one wavefront: orders the zero fill before the words written below
+
+    int qi[4];
+    qi[0] = idx[n];
+#pragma unroll
+    for (int k = 1; k < 4; ++k) qi[k] = bounded(rand_u32(key, ctr++), M);                       // get_indexes
+    const bool applied = !((double)rand_u32(key, ctr++) * (1.0 / 4294967296.0) > cfg.prob);     // transforms.py:2304
+    int cx = 0, cy = 0;
+    if (applied) {      // random.uniform(a, b) = a + (b - a) * random()
+        const double span = cfg.center_hi - cfg.center_lo;
+        cx = (int)((cfg.center_lo + span * ((double)rand_u32(key, ctr++) * (1.0 / 4294967296.0))) * (double)S);
+        cy = (int)((cfg.center_lo + span * ((double)rand_u32(key, ctr++) * (1.0 / 4294967296.0))) * (double)S);
+    }
+    const float lim = (float)(2 * S);
+    int kept = 0, status = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (!applied && q > 0) break;
+        const int i = qi[q];
+        const bool ok_i = i >= 0 && i < M;
+        const int h = ok_i ? store_hw[2 * i] : 0, w = ok_i ? store_hw[2 * i + 1] : 0;
+        const int G = ok_i ? store_gcnt[i] : 0;
+        const size_t g0 = ok_i ? (size_t)store_goff[i] : 0;
+        float r = 1.0f, padw = 0.0f, padh = 0.0f;
+        if (applied) {
+            int rw = 0, rh = 0, x1 = 0, y1 = 0, x2 = 0, y2 = 0, c1 = 0, c2 = 0;
+            double sx = 0.0, sy = 0.0, ratio = 1.0;
+            if (h > 0 && w > 0) {
+                const double rh_ = (double)S / (double)h, rw_ = (double)S / (double)w;
+                ratio = rh_ < rw_ ? rh_ : rw_;                                                // min(S / h, S / w)
+                rw = (int)((double)w * ratio);
+                rh = (int)((double)h * ratio);
+            }
+            if (rw > 0 && rh > 0) {       // _mosaic_combine, transforms.py:2442-2501
+                if (q == 0) {
+                    x1 = cx - rw > 0 ? cx - rw : 0; y1 = cy - rh > 0 ? cy - rh : 0; x2 = cx; y2 = cy;
+                    c1 = rw - (x2 - x1); c2 = rh - (y2 - y1);
+                } else if (q == 1) {
+                    x1 = cx; y1 = cy - rh > 0 ? cy - rh : 0; x2 = cx + rw < 2 * S ? cx + rw : 2 * S; y2 = cy;
+                    c1 = 0; c2 = rh - (y2 - y1);
+                } else if (q == 2) {
+                    x1 = cx - rw > 0 ? cx - rw : 0; y1 = cy; x2 = cx; y2 = cy + rh < 2 * S ? cy + rh : 2 * S;
+                    c1 = rw - (x2 - x1); c2 = 0;
+                } else {
+                    x1 = cx; y1 = cy; x2 = cx + rw < 2 * S ? cx + rw : 2 * S; y2 = cy + rh < 2 * S ? cy + rh : 2 * S;
+                    c1 = 0; c2 = 0;
+                }
+                sx = 1.0 / ((double)rw / (double)w);
+                sy = 1.0 / ((double)rh / (double)h);
+            } else {
+                status |= 4;
+            }
+            r = (float)ratio; padw = (float)(x1 - c1); padh = (float)(y1 - c2);
+            if (lane == 0) {
+                int32_t* gq = gm + YUNET_MOSAIC_QUAD + q * YUNET_MOSAIC_QWORDS;
+                gq[YUNET_MOSAIC_Q_IDX] = ok_i ? i : 0; gq[YUNET_MOSAIC_Q_H] = h; gq[YUNET_MOSAIC_Q_W] = w;
+                gq[YUNET_MOSAIC_Q_RW] = rw; gq[YUNET_MOSAIC_Q_RH] = rh;
+                gq[YUNET_MOSAIC_Q_PX1] = x1; gq[YUNET_MOSAIC_Q_PY1] = y1; gq[YUNET_MOSAIC_Q_PX2] = x2;
+                gq[YUNET_MOSAIC_Q_PY2] = y2; gq[YUNET_MOSAIC_Q_CX1] = c1; gq[YUNET_MOSAIC_Q_CY1] = c2;
+                *reinterpret_cast<double*>(gq + YUNET_MOSAIC_Q_SX) = sx;
+                *reinterpret_cast<double*>(gq + YUNET_MOSAIC_Q_SY) = sy;
+            }
+        } else if (lane == 0) {
+            int32_t* gq = gm + YUNET_MOSAIC_QUAD;
+            gq[YUNET_MOSAIC_Q_IDX] = ok_i ? i : 0; gq[YUNET_MOSAIC_Q_H] = h; gq[YUNET_MOSAIC_Q_W] = w;
+        }
+        if (q == 0 && lane == 0) {
+            out_hw[2 * n] = applied ? 2 * S : h;
+            out_hw[2 * n + 1] = applied ? 2 * S : w;
+        }
+        const float* bx = store_boxes + g0 * 4;
+        const float* kp = store_kps + g0 * 15;
+        for (int base = 0; base < G; base += 64) {
+            const int g = base + lane;
+            float b[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            bool keep = g < G;
+            if (keep) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) b[e] = bx[4 * g + e];
+                if (applied) {
+                    b[0] = r * b[0] + padw; b[2] = r * b[2] + padw;       // transforms.py:2388-2391, fp32
+                    b[1] = r * b[1] + padh; b[3] = r * b[3] + padh;
+                    if (cfg.bbox_clip_border) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) b[e] = fminf(fmaxf(b[e], 0.0f), lim);
+                    }
+                    if (!cfg.skip_filter)
+                        keep = (b[2] - b[0] > cfg.min_bbox_size) && (b[3] - b[1] > cfg.min_bbox_size);
+                    keep = keep && b[0] < lim && b[2] > 0.0f && b[1] < lim && b[3] > 0.0f;     // find_inside_bboxes
+                }
+            }
+            const unsigned long long m = __ballot(keep);
+            const int at = kept + __popcll(m & ((1ull << lane) - 1ull));
+            if (keep && at < gmax) {
+                float* o = ob + 4 * at;
+                o[0] = b[0]; o[1] = b[1]; o[2] = b[2]; o[3] = b[3];
+                const float* k = kp + 15 * g;
+                float* t = ok + 15 * at;
+#pragma unroll
+                for (int j = 0; j < 5; ++j) {
+                    float x = k[3 * j], y = k[3 * j + 1];
+                    if (applied) {
+                        x = r * x + padw; y = r * y + padh;
+                        if (cfg.bbox_clip_border) { x = fminf(fmaxf(x, 0.0f), lim); y = fminf(fmaxf(y, 0.0f), lim); }
+                    }
+                    t[3 * j] = x; t[3 * j + 1] = y; t[3 * j + 2] = k[3 * j + 2];
+                }
+            }
+            kept += __popcll(m);
+        }
+    }
+    const int count = kept < gmax ? kept : gmax;
+    for (int i = count * 4 + lane; i < gmax * 4; i += 64) ob[i] = 0.0f;
+    for (int i = count * 15 + lane; i < gmax * 15; i += 64) ok[i] = 0.0f;
+    if (lane == 0) {
+        gm[YUNET_MOSAIC_APPLIED] = applied ? 1 : 0; gm[YUNET_MOSAIC_CX] = cx; gm[YUNET_MOSAIC_CY] = cy;
+        gm[YUNET_MOSAIC_DRAWS] = (int32_t)ctr; gm[YUNET_MOSAIC_KEPT] = kept;
+        gm[YUNET_MOSAIC_STATUS] = status | (kept > gmax ? 2 : 0);
+        out_count[n] = count;
+    }
+}
+
+// One pixel (X, Y) of the mosaic canvas of the image whose table is g: quadrant by the centre, pad_val outside the
+// paste rectangle, else the pixel of the resized sub-image -- cv2's float bilinear of the uint8 source, horizontal pass
+// then vertical pass, each product and sum rounded to fp32 (the file is built without contraction).  lin_coef_s clamps
+// both taps to the source, so whatever the table holds nothing outside sub-image idx is read.
+__device__ __forceinline__ void mosaic_tap(const int32_t* __restrict__ g, const uint8_t* __restrict__ store,
+                                           const long long* __restrict__ store_off, int cx, int cy, int X, int Y,
+                                           float mpad, float* __restrict__ o) {
+    const int q = (X >= cx ? 1 : 0) + (Y >= cy ? 2 : 0);
+    const int32_t* gq = g + YUNET_MOSAIC_QUAD + q * YUNET_MOSAIC_QWORDS;
+    const int4 A = *reinterpret_cast<const int4*>(gq);          // idx, h, w, rw
+    const int4 B = *reinterpret_cast<const int4*>(gq + 4);      // rh, px1, py1, px2
+    const int4 D = *reinterpret_cast<const int4*>(gq + 8);      // py2, cx1, cy1, -
+    if (X < B.y || X >= B.w || Y < B.z || Y >= D.x || A.y < 1 || A.z < 1) {
+        o[0] = mpad; o[1] = mpad; o[2] = mpad;
+        return;
+    }
+    const double2 sc = *reinterpret_cast<const double2*>(gq + YUNET_MOSAIC_Q_SX);
+    int sx0, sx1, sy0, sy1;
+    float a0, a1, b0, b1;
+    lin_coef_s(X - B.y + D.y, sc.x, A.z, sx0, sx1, a0, a1);
+    lin_coef_s(Y - B.z + D.z, sc.y, A.y, sy0, sy1, b0, b1);
+    const uint8_t* im = store + store_off[A.x];
+    const uint8_t* r0 = im + (size_t)sy0 * A.z * 3;
+    const uint8_t* r1 = im + (size_t)sy1 * A.z * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float t0 = (float)r0[3 * sx0 + c] * a0 + (float)r0[3 * sx1 + c] * a1;
+        const float t1 = (float)r1[3 * sx0 + c] * a0 + (float)r1[3 * sx1 + c] * a1;
+        o[c] = t0 * b0 + t1 * b1;
+    }
+}
+
+// Test entry: every canvas pixel through mosaic_tap, written HWC fp32 as the reference holds its canvas.
+__global__ __launch_bounds__(256) void mosaic_canvas_kernel(const uint8_t* __restrict__ store,
+                                                            const long long* __restrict__ store_off,
+                                                            const int32_t* __restrict__ geom, int S, float mpad,
+                                                            float* __restrict__ canvas) {
+    const int n = blockIdx.y, E = 2 * S;
+    const int32_t* g = geom + (size_t)n * YUNET_MOSAIC_WORDS;
+    const int applied = g[YUNET_MOSAIC_APPLIED], cx = g[YUNET_MOSAIC_CX], cy = g[YUNET_MOSAIC_CY];
+    float* o = canvas + (size_t)n * E * E * 3;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < E * E; i += gridDim.x * 256) {
+        float v[3] = {mpad, mpad, mpad};
+        if (applied) mosaic_tap(g, store, store_off, cx, cy, i % E, i / E, mpad, v);
+        o[3 * (size_t)i] = v[0]; o[3 * (size_t)i + 1] = v[1]; o[3 * (size_t)i + 2] = v[2];
+    }
 }
 
 // ---- PhotoMetricDistortion (transforms.py:1211-1312; include/yunet_hip.h YUNET_PHOTO_*) ------------------------
@@ -312,18 +519,26 @@ __device__ __forceinline__ void photo_pixel(const Photo& q, float& b, float& g, 
 // PH = YUNET_PHOTO_NONE: no distortion (yunet_aug_pixels / _window); PRE: each in-image tap pixel is distorted after
 //   its load (pad taps stay pad); POST: the output pixel is distorted after the vertical pass.  `pp` = the table of
 //   yunet_aug_photometric (unused for NONE).
-template <bool WIN, int PH, bool CANVAS = false>
+// MOSAIC = false: the code as it stands.  MOSAIC = true (WIN = false, PH = NONE / POST): `src` is the whole store,
+//   src_hw the out_hw of mosaic_decide_kernel and geom its table.  An image whose mosaic was made reads the four taps
+//   of the crop's bilinear through mosaic_tap (the canvas is never materialised; `mpad` fills it outside the paste
+//   rectangles, `pad` lies outside the canvas); a skipped image is image store_off[its index] through the plain code.
+template <bool WIN, int PH, bool CANVAS = false, bool MOSAIC = false>
 __global__ __launch_bounds__(256) void aug_pixels_kernel(
     const uint8_t* __restrict__ src, const long long* __restrict__ src_off, const int32_t* __restrict__ src_hw,
     const int32_t* __restrict__ rect, const int32_t* __restrict__ params, const float* __restrict__ pp, int C,
-    float pad, float* __restrict__ out) {
+    float pad, float* __restrict__ out, const int32_t* __restrict__ geom, const long long* __restrict__ store_off,
+    float mpad) {
     const int n = blockIdx.y;
     const int32_t* p = params + 8 * n;
     const int left = p[AUG_P_LEFT], top = p[AUG_P_TOP], cw = p[AUG_P_CW], flip = p[AUG_P_FLIP];
     const int h = src_hw[2 * n], w = src_hw[2 * n + 1];
     const int ry = WIN ? rect[4 * n + 0] : 0, rx = WIN ? rect[4 * n + 1] : 0;
     const int rh = WIN ? rect[4 * n + 2] : h, rw = WIN ? rect[4 * n + 3] : w;
-    const uint8_t* im = src + src_off[n];
+    const int32_t* gm = MOSAIC ? geom + (size_t)n * YUNET_MOSAIC_WORDS : nullptr;
+    const bool mosaic = MOSAIC && gm[YUNET_MOSAIC_APPLIED] != 0;
+    const int mcx = MOSAIC ? gm[YUNET_MOSAIC_CX] : 0, mcy = MOSAIC ? gm[YUNET_MOSAIC_CY] : 0;
+    const uint8_t* im = MOSAIC ? src + (mosaic ? 0 : store_off[gm[YUNET_MOSAIC_QUAD + YUNET_MOSAIC_Q_IDX]]) : src + src_off[n];
     const int S = CANVAS ? p[AUG_P_SIZE] : C;
     float* o = out + (size_t)n * 3 * C * C;
     Photo q;
@@ -352,7 +567,20 @@ __global__ __launch_bounds__(256) void aug_pixels_kernel(
             }
             const uint8_t* r0 = im + ((size_t)(Y0 - ry) * rw) * 3 - (size_t)rx * 3;
             const uint8_t* r1 = im + ((size_t)(Y1 - ry) * rw) * 3 - (size_t)rx * 3;
-            if (PH == YUNET_PHOTO_PRE) {
+            if (MOSAIC && mosaic) {
+                float t00[3] = {pad, pad, pad}, t01[3] = {pad, pad, pad}, t10[3] = {pad, pad, pad},
+                      t11[3] = {pad, pad, pad};
+                if (y0in && x0in) mosaic_tap(gm, src, store_off, mcx, mcy, X0, Y0, mpad, t00);
+                if (y0in && x1in) mosaic_tap(gm, src, store_off, mcx, mcy, X1, Y0, mpad, t01);
+                if (y1in && x0in) mosaic_tap(gm, src, store_off, mcx, mcy, X0, Y1, mpad, t10);
+                if (y1in && x1in) mosaic_tap(gm, src, store_off, mcx, mcy, X1, Y1, mpad, t11);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float t0 = t00[c] * a0 + t01[c] * a1;    // horizontal pass
+                    const float t1 = t10[c] * a0 + t11[c] * a1;
+                    v[c] = t0 * b0 + t1 * b1;                      // vertical pass
+                }
+            } else if (PH == YUNET_PHOTO_PRE) {
                 float t00[3], t01[3], t10[3], t11[3];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
@@ -401,7 +629,7 @@ extern "C" int yunet_aug_decide(const int32_t* src_hw, const float* boxes, const
         cfg->max_attempts < 1 || cfg->max_retries < 1)
         return YUNET_EINVAL;
     hipLaunchKernelGGL(aug_decide_kernel<false>, dim3(N), dim3(64), 0, (hipStream_t)stream, src_hw, boxes, kps,
-                       gt_off, *cfg, 0, 0, iteration, params, out_boxes, out_kps, out_count);
+                       gt_off, *cfg, 0, 0, iteration, params, out_boxes, out_kps, out_count, 0);
     return hip_status();
 }
 
@@ -413,7 +641,7 @@ extern "C" int yunet_aug_decide_ms(const int32_t* src_hw, const float* boxes, co
         cfg->max_retries < 1 || scale_lo < 32 || scale_hi < scale_lo || scale_hi > YUNET_AUG_MAX_EDGE)
         return YUNET_EINVAL;
     hipLaunchKernelGGL(aug_decide_kernel<true>, dim3(N), dim3(64), 0, (hipStream_t)stream, src_hw, boxes, kps,
-                       gt_off, *cfg, scale_lo, scale_hi, iteration, params, out_boxes, out_kps, out_count);
+                       gt_off, *cfg, scale_lo, scale_hi, iteration, params, out_boxes, out_kps, out_count, 0);
     return hip_status();
 }
 
@@ -425,7 +653,7 @@ extern "C" int yunet_aug_pixels(const uint8_t* src, const long long* src_off, co
     int bx = (S * S + 255) / 256;
     if (bx > 64) bx = 64;                       // grid-stride over the pixels of one image
     hipLaunchKernelGGL((aug_pixels_kernel<false, YUNET_PHOTO_NONE>), dim3(bx, N), dim3(256), 0, (hipStream_t)stream, src,
-                       src_off, src_hw, nullptr, params, nullptr, S, cfg->pad_value, out_img);
+                       src_off, src_hw, nullptr, params, nullptr, S, cfg->pad_value, out_img, nullptr, nullptr, 0.0f);
     return hip_status();
 }
 
@@ -437,7 +665,7 @@ extern "C" int yunet_aug_pixels_window(const uint8_t* win, const long long* win_
     int bx = (S * S + 255) / 256;
     if (bx > 64) bx = 64;
     hipLaunchKernelGGL((aug_pixels_kernel<true, YUNET_PHOTO_NONE>), dim3(bx, N), dim3(256), 0, (hipStream_t)stream, win,
-                       win_off, src_hw, rect, params, nullptr, S, cfg->pad_value, out_img);
+                       win_off, src_hw, rect, params, nullptr, S, cfg->pad_value, out_img, nullptr, nullptr, 0.0f);
     return hip_status();
 }
 
@@ -469,10 +697,10 @@ static int launch_pixels_photo(const uint8_t* src, const long long* src_off, con
     if (bx > 64) bx = 64;
     if (position == YUNET_PHOTO_PRE)
         hipLaunchKernelGGL((aug_pixels_kernel<WIN, YUNET_PHOTO_PRE>), dim3(bx, N), dim3(256), 0, (hipStream_t)stream,
-                           src, src_off, src_hw, rect, params, pparams, S, cfg->pad_value, out_img);
+                           src, src_off, src_hw, rect, params, pparams, S, cfg->pad_value, out_img, nullptr, nullptr, 0.0f);
     else if (position == YUNET_PHOTO_POST)
         hipLaunchKernelGGL((aug_pixels_kernel<WIN, YUNET_PHOTO_POST>), dim3(bx, N), dim3(256), 0, (hipStream_t)stream,
-                           src, src_off, src_hw, rect, params, pparams, S, cfg->pad_value, out_img);
+                           src, src_off, src_hw, rect, params, pparams, S, cfg->pad_value, out_img, nullptr, nullptr, 0.0f);
     else
         return YUNET_EINVAL;
     return hip_status();
@@ -502,13 +730,13 @@ static int launch_pixels_canvas(const uint8_t* src, const long long* src_off, co
     hipStream_t st = (hipStream_t)stream;
     if (position == YUNET_PHOTO_NONE)
         hipLaunchKernelGGL((aug_pixels_kernel<WIN, YUNET_PHOTO_NONE, true>), grid, block, 0, st, src, src_off, src_hw,
-                           rect, params, pparams, out_hw, cfg->pad_value, out_img);
+                           rect, params, pparams, out_hw, cfg->pad_value, out_img, nullptr, nullptr, 0.0f);
     else if (position == YUNET_PHOTO_PRE)
         hipLaunchKernelGGL((aug_pixels_kernel<WIN, YUNET_PHOTO_PRE, true>), grid, block, 0, st, src, src_off, src_hw,
-                           rect, params, pparams, out_hw, cfg->pad_value, out_img);
+                           rect, params, pparams, out_hw, cfg->pad_value, out_img, nullptr, nullptr, 0.0f);
     else
         hipLaunchKernelGGL((aug_pixels_kernel<WIN, YUNET_PHOTO_POST, true>), grid, block, 0, st, src, src_off, src_hw,
-                           rect, params, pparams, out_hw, cfg->pad_value, out_img);
+                           rect, params, pparams, out_hw, cfg->pad_value, out_img, nullptr, nullptr, 0.0f);
     return hip_status();
 }
 
@@ -524,4 +752,87 @@ extern "C" int yunet_aug_pixels_canvas(const uint8_t* src, const long long* src_
                                              out_img, stream)
                 : launch_pixels_canvas<false>(src, src_off, src_hw, nullptr, params, pparams, position, cfg, out_hw,
                                               N, out_img, stream);
+}
+
+static bool aug_cfg_ok(const YunetAugCfg* cfg) {
+    return cfg && cfg->n_choice >= 1 && cfg->n_choice <= 8 && cfg->gmax >= 1 && cfg->max_attempts >= 1 &&
+           cfg->max_retries >= 1;
+}
+
+static bool mosaic_cfg_ok(const YunetMosaicCfg* c) {
+    return c && c->img_scale >= 1 && c->img_scale <= YUNET_AUG_MAX_EDGE / 2 && c->gmax >= 1 &&
+           std::isfinite(c->center_lo) && std::isfinite(c->center_hi) && c->center_lo >= 0.0 &&
+           c->center_lo <= c->center_hi && c->center_hi <= 2.0 && c->prob >= 0.0 && c->prob <= 1.0 &&
+           std::isfinite(c->min_bbox_size) && std::isfinite(c->pad_val);
+}
+
+extern "C" int yunet_aug_mosaic_decide(const int32_t* idx, int N, int M, const int32_t* store_hw,
+                                       const int32_t* store_goff, const int32_t* store_gcnt, const float* store_boxes,
+                                       const float* store_kps, const YunetMosaicCfg* cfg, uint32_t iteration,
+                                       int32_t* geom, int32_t* out_hw, float* out_boxes, float* out_kps,
+                                       int32_t* out_count, void* stream) {
+    if (!mosaic_cfg_ok(cfg) || N < 1 || M < 1 || !idx || !store_hw || !store_goff || !store_gcnt || !store_boxes ||
+        !store_kps || !geom || !out_hw || !out_boxes || !out_kps || !out_count)
+        return YUNET_EINVAL;
+    hipLaunchKernelGGL(mosaic_decide_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, idx, M, store_hw, store_goff,
+                       store_gcnt, store_boxes, store_kps, *cfg, iteration, geom, out_hw, out_boxes, out_kps,
+                       out_count);
+    return hip_status();
+}
+
+extern "C" int yunet_aug_decide_padded(const int32_t* src_hw, const float* boxes, const float* kps,
+                                       const int32_t* counts, int in_gmax, const YunetAugCfg* cfg, int scale_lo,
+                                       int scale_hi, uint32_t iteration, int N, int32_t* params, float* out_boxes,
+                                       float* out_kps, int32_t* out_count, void* stream) {
+    if (!aug_cfg_ok(cfg) || N < 1 || in_gmax < 1) return YUNET_EINVAL;
+    if (scale_lo > 0) {
+        if (scale_lo < 32 || scale_hi < scale_lo || scale_hi > YUNET_AUG_MAX_EDGE) return YUNET_EINVAL;
+        hipLaunchKernelGGL((aug_decide_kernel<true, true>), dim3(N), dim3(64), 0, (hipStream_t)stream, src_hw, boxes,
+                           kps, counts, *cfg, scale_lo, scale_hi, iteration, params, out_boxes, out_kps, out_count,
+                           in_gmax);
+    } else {
+        if (cfg->out_size < 1) return YUNET_EINVAL;
+        hipLaunchKernelGGL((aug_decide_kernel<false, true>), dim3(N), dim3(64), 0, (hipStream_t)stream, src_hw, boxes,
+                           kps, counts, *cfg, 0, 0, iteration, params, out_boxes, out_kps, out_count, in_gmax);
+    }
+    return hip_status();
+}
+
+extern "C" int yunet_aug_pixels_mosaic(const uint8_t* store, const long long* store_off, const int32_t* geom,
+                                       const int32_t* hw, const int32_t* params, const float* pparams, int position,
+                                       const YunetAugCfg* cfg, const YunetMosaicCfg* mcfg, int out_hw, int N,
+                                       float* out_img, void* stream) {
+    const bool post = position == YUNET_PHOTO_POST;
+    if (!cfg || !mosaic_cfg_ok(mcfg) || N < 1 || !store || !store_off || !geom || !hw || !params || !out_img ||
+        (!post && position != YUNET_PHOTO_NONE) || (post && !pparams) || out_hw < 0 || out_hw > YUNET_AUG_MAX_EDGE ||
+        (out_hw == 0 && cfg->out_size < 1))
+        return YUNET_EINVAL;
+    const int C = out_hw ? out_hw : cfg->out_size;
+    int bx = (C * C + 255) / 256;
+    if (bx > 64) bx = 64;
+    const dim3 grid(bx, N), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define YUNET_LAUNCH_MOSAIC(PH, CANVAS)                                                                              \
+    hipLaunchKernelGGL((aug_pixels_kernel<false, PH, CANVAS, true>), grid, block, 0, st, store, nullptr, hw, nullptr, \
+                       params, pparams, C, cfg->pad_value, out_img, geom, store_off, mcfg->pad_val)
+    if (out_hw) {
+        if (post) YUNET_LAUNCH_MOSAIC(YUNET_PHOTO_POST, true);
+        else YUNET_LAUNCH_MOSAIC(YUNET_PHOTO_NONE, true);
+    } else {
+        if (post) YUNET_LAUNCH_MOSAIC(YUNET_PHOTO_POST, false);
+        else YUNET_LAUNCH_MOSAIC(YUNET_PHOTO_NONE, false);
+    }
+#undef YUNET_LAUNCH_MOSAIC
+    return hip_status();
+}
+
+extern "C" int yunet_aug_mosaic_canvas(const uint8_t* store, const long long* store_off, const int32_t* geom,
+                                       const YunetMosaicCfg* mcfg, int N, float* canvas, void* stream) {
+    if (!mosaic_cfg_ok(mcfg) || N < 1 || !store || !store_off || !geom || !canvas) return YUNET_EINVAL;
+    const int E = 2 * mcfg->img_scale;
+    int bx = (E * E + 255) / 256;
+    if (bx > 256) bx = 256;
+    hipLaunchKernelGGL(mosaic_canvas_kernel, dim3(bx, N), dim3(256), 0, (hipStream_t)stream, store, store_off, geom,
+                       mcfg->img_scale, mcfg->pad_val, canvas);
+    return hip_status();
 }

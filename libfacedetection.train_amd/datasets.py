@@ -159,6 +159,45 @@ class RetinaFaceDataset:
                     gt_bboxes_ignore=ann['bboxes_ignore'])
 
 
+@DATASETS.register_module()
+class MultiImageMixDataset:
+    """mmdet/datasets/dataset_wrappers.py:338-444 as a configuration carrier: `dataset` (its pipeline loads: LoadImageFromFile,
+    LoadAnnotations) wrapped with the mixing `pipeline` (Mosaic, then the usual train transforms).  The device pipeline runs
+    the two lists as one (`flat_pipeline`); the wrapper itself moves no data."""
+
+    def __init__(self, dataset, pipeline, dynamic_scale=None, skip_type_keys=None, max_refetch=15):
+        if dynamic_scale is not None:
+            raise RuntimeError('dynamic_scale is deprecated. Please use Resize pipeline to achieve similar functions')
+        if skip_type_keys is not None:
+            raise NotImplementedError('MultiImageMixDataset(skip_type_keys=...) is not implemented')
+        self.dataset = DATASETS.build(dataset) if isinstance(dataset, dict) else dataset
+        self.pipeline_cfg, self.max_refetch = list(pipeline), max_refetch
+        self.CLASSES = getattr(self.dataset, 'CLASSES', None)
+        if hasattr(self.dataset, 'flag'):
+            self.flag = self.dataset.flag
+
+    def __len__(self):
+        return len(self.dataset)
+
+
+def flatten_multi_image_mix(dcfg):
+    """data.train = dict(type='MultiImageMixDataset', dataset=dict(...), pipeline=[...]) -> the inner dataset's
+    configuration with pipeline = its own loading steps + the wrapper's list (the flat list DevicePipeline takes); the
+    wrapper's other keys (cache, host_fed, ... given with --cfg-options) travel to the inner configuration."""
+    if dcfg.get('dynamic_scale') is not None:
+        raise RuntimeError('dynamic_scale is deprecated. Please use Resize pipeline to achieve similar functions')
+    if dcfg.get('skip_type_keys') is not None:
+        raise NotImplementedError('MultiImageMixDataset(skip_type_keys=...) is not implemented')
+    inner = dict(dcfg['dataset'])
+    if inner.get('type') == 'MultiImageMixDataset':
+        raise NotImplementedError('nested MultiImageMixDataset')
+    inner['pipeline'] = list(inner.get('pipeline') or []) + list(dcfg['pipeline'])
+    for k, v in dcfg.items():
+        if k not in ('type', 'dataset', 'pipeline', 'dynamic_scale', 'skip_type_keys', 'max_refetch'):
+            inner[k] = v
+    return inner
+
+
 class RetinaFaceSource:
     """Training data source over a RetinaFaceDataset: iteration `it` of rank r is batch it % iters_per_epoch of the
     reference's DistributedGroupSampler(dataset, samples_per_gpu, world, r, seed) in epoch it // iters_per_epoch
@@ -189,6 +228,8 @@ class RetinaFaceSource:
         self.ds, self.bs, self.rank, self.world, self.seed = dataset, samples_per_gpu, rank, world, seed
         self.pipe = DevicePipeline(pipeline, seed=seed + 7919 * rank, gmax=64 if max_gt <= 64 else 128)
         self.pipe.check_plan_cache()
+        if cache != 'device':
+            self.pipe.require_resident(f'RetinaFaceSource(cache={cache!r})')
         from .samplers import DistributedGroupSampler
         self.sampler = DistributedGroupSampler(dataset, samples_per_gpu, world, rank, seed=seed)
         self.iters_per_epoch = max(1, len(self.sampler) // samples_per_gpu)
@@ -222,17 +263,27 @@ class RetinaFaceSource:
             del self._ahead[k]
         return [f.result() for f in futs]
 
+    def _partners(self, it, n):
+        """Mosaic: the store indices iteration it's kernel will draw as partners of its n images -- a pure function of
+        (seed, it, image), computed here so that they are decoded before the batch that reads them."""
+        if self.pipe.mosaic is None:
+            return []
+        from .pipelines import mosaic_partners
+        m = len(self.ds.data_infos)
+        return [j for k in range(n) for j in mosaic_partners(self.pipe.cfg.seed, it, k, m)]
+
     def _fill(self, it):
         """Decode the images of iteration it that the store lacks (and queue those of it + 1), store them; -> indices."""
         idx = self._indices(it)
-        ahead = self._indices(it + 1) if self.workers else []
+        need = idx + self._partners(it, len(idx))
+        ahead = (self._indices(it + 1) + self._partners(it + 1, len(idx))) if self.workers else []
         if self.workers and self._pool is None:
             from concurrent.futures import ThreadPoolExecutor
             self._pool = ThreadPoolExecutor(self.workers)
-        for i in list(dict.fromkeys(idx)) + [i for i in ahead if i not in idx]:
+        for i in list(dict.fromkeys(need)) + [i for i in ahead if i not in need]:
             if not self.store.has(i) and i not in self._decoding and self.workers:
                 self._decoding[i] = self._pool.submit(self.ds.load_image, i)
-        for i in dict.fromkeys(idx):
+        for i in dict.fromkeys(need):
             if not self.store.has(i):
                 fut = self._decoding.pop(i, None)
                 img = fut.result() if fut is not None else self.ds.load_image(i)

@@ -150,6 +150,65 @@ class PhotoMetricDistortion(_Carrier):
 
 
 @PIPELINES.register_module()
+class Mosaic(_Carrier):
+    """transforms.py:2218-2519 with the reference's constructor, under MultiImageMixDataset
+    (dataset_wrappers.py:338-444).  Runs as yunet_aug_mosaic_decide + the MOSAIC form of the pixel pass; its draws come
+    from a sub-stream of the pipeline's generator (include/yunet_hip.h YUNET_MOSAIC_SALT).  Partner indices are drawn
+    from [0, len(dataset)), as by the reference: its `random` is numpy's (transforms.py:10), whose randint excludes the
+    upper end."""
+
+    def __init__(self, img_scale=(640, 640), center_ratio_range=(0.5, 1.5), min_bbox_size=0, bbox_clip_border=True,
+                 skip_filter=True, pad_val=114, prob=1.0, use_kps=False):
+        if not use_kps:
+            raise NotImplementedError('Mosaic(use_kps=False): the device pipeline always carries the five landmarks '
+                                      '(LoadAnnotations(with_keypoints=True)); write use_kps=True')
+        if len(img_scale) != 2 or int(img_scale[0]) != int(img_scale[1]):
+            raise NotImplementedError(f'Mosaic(img_scale={tuple(img_scale)}): only the square canvas '
+                                      '(img_scale=(S, S)) is built; the rectangular one is not')
+        S = int(img_scale[0])
+        if not 1 <= S <= L.AUG_MAX_EDGE // 2:
+            raise ValueError(f'Mosaic(img_scale=({S}, {S})): S must lie in [1, {L.AUG_MAX_EDGE // 2}]')
+        lo, hi = (float(v) for v in center_ratio_range)
+        if not 0.0 <= lo <= hi <= 2.0:
+            raise ValueError(f'Mosaic(center_ratio_range={tuple(center_ratio_range)}): the centre must lie on the '
+                             'canvas, 0 <= lo <= hi <= 2')
+        if not 0 <= prob <= 1.0:
+            raise ValueError(f'Mosaic: the probability should be in range [0, 1], got {prob}')
+        if isinstance(pad_val, (list, tuple)) or not math.isfinite(float(pad_val)) \
+                or not math.isfinite(float(min_bbox_size)):
+            raise ValueError('Mosaic: one finite pad_val and a finite min_bbox_size')
+        super().__init__(img_scale=(S, S), center_ratio_range=(lo, hi), min_bbox_size=min_bbox_size,
+                         bbox_clip_border=bool(bbox_clip_border), skip_filter=bool(skip_filter), pad_val=pad_val,
+                         prob=float(prob), use_kps=True)
+
+    def c_cfg(self, seed, gmax):
+        c = L.YunetMosaicCfg()
+        c.img_scale, c.gmax = self.img_scale[0], gmax
+        c.center_lo, c.center_hi = self.center_ratio_range
+        c.prob, c.min_bbox_size, c.pad_val = self.prob, float(self.min_bbox_size), float(self.pad_val)
+        c.seed, c.bbox_clip_border, c.skip_filter = seed & 0xFFFFFFFF, int(self.bbox_clip_border), int(self.skip_filter)
+        return c
+
+
+def _mix32(x):
+    x &= 0xFFFFFFFF
+    x ^= x >> 16
+    x = (x * 0x7FEB352D) & 0xFFFFFFFF
+    x ^= x >> 15
+    x = (x * 0x846CA68B) & 0xFFFFFFFF
+    return x ^ (x >> 16)
+
+
+def mosaic_partners(seed, iteration, n, m):
+    """The three partner indices yunet_aug_mosaic_decide draws for image n of `iteration` over a store of m images: the
+    draws are a pure function of (seed, iteration, n), so the host computes them ahead (a lazily decoding source
+    decodes the partners before the batch that uses them) instead of waiting for the device."""
+    k = _mix32((seed & 0xFFFFFFFF) ^ ((iteration * 0x27D4EB2F) & 0xFFFFFFFF))
+    k = _mix32(_mix32(k ^ ((n * 0x9E3779B9) & 0xFFFFFFFF)) ^ L.MOSAIC_SALT)
+    return [(_mix32(k ^ ((c * 0x85EBCA6B + 0xC2B2AE35) & 0xFFFFFFFF)) * m) >> 32 for c in range(3)]
+
+
+@PIPELINES.register_module()
 class Normalize(_Carrier):
     def __init__(self, mean, std, to_rgb=True):
         if any(float(m) != 0.0 for m in mean) or any(float(s) != 1.0 for s in std) or to_rgb:
@@ -175,15 +234,37 @@ class DeviceGT(GTList):
     or beyond counts[i] are zero."""
 
 
+class StoreView:
+    """Device tables of a decoded-source store of m images (what yunet_aug_gather reads): byte offsets int64 [m],
+    (h, w) int32 [m,2], first GT row / GT count int32 [m], boxes fp32 [*,4], kps fp32 [*,15]."""
+
+    def __init__(self, m, off, hw, goff, gcnt, boxes, kps):
+        self.m, self.off, self.hw, self.goff, self.gcnt, self.boxes, self.kps = int(m), off, hw, goff, gcnt, boxes, kps
+
+
 class SourceBatch:
     """A batch of decoded source images and their annotations, resident on the device:
     src uint8 (concatenated HWC images), src_off int64 [N], src_hw int32 [N,2],
-    boxes fp32 [sum G,4], kps fp32 [sum G,5,3], gt_off int32 [N+1]."""
+    boxes fp32 [sum G,4], kps fp32 [sum G,5,3], gt_off int32 [N+1].
+    `view` / `idx` (Mosaic): the tables of the whole store the batch was picked from (StoreView, every image in `src`)
+    and the batch's store indices, int32 [N] on the device; a batch made by from_lists is its own store."""
 
-    def __init__(self, src, src_off, src_hw, boxes, kps, gt_off):
+    def __init__(self, src, src_off, src_hw, boxes, kps, gt_off, view=None, idx=None):
         self.src, self.src_off, self.src_hw = src, src_off, src_hw
         self.boxes, self.kps, self.gt_off = boxes, kps, gt_off
         self.n = int(src_hw.shape[0])
+        self.view, self.idx = view, idx
+
+    def store_view(self):
+        """-> (StoreView, idx) addressing any image of the store.  Without a store: the batch itself, M = N."""
+        if self.view is None:
+            if self.src.device.type != 'cuda':
+                return None, None
+            goff = self.gt_off[:-1].contiguous()
+            self.view = StoreView(self.n, self.src_off, self.src_hw, goff, (self.gt_off[1:] - goff).contiguous(),
+                                  self.boxes, self.kps.reshape(-1, 15))
+            self.idx = torch.arange(self.n, dtype=torch.int32, device=self.src.device)
+        return self.view, self.idx
 
     @classmethod
     def from_lists(cls, images, gt_bboxes, gt_keypointss, device):
@@ -211,6 +292,9 @@ class SourceBatch:
         return cls(src.to(d), torch.from_numpy(off).to(d), hw.to(d), boxes.to(d), kps.to(d), goff.to(d))
 
 
+MOSAIC_MAX_GT = 1024        # GT rows per image the engine's assign kernels are tested to
+
+
 class DevicePipeline:
     """Builds from the reference's pipeline list and runs it as two kernel launches per batch."""
 
@@ -223,6 +307,26 @@ class DevicePipeline:
     def __init__(self, pipeline, seed=0, gmax=64, pad_value=128.0, max_attempts=250, max_retries=64):
         steps = [build_from_cfg(p, PIPELINES) if isinstance(p, dict) else p for p in pipeline]
         names = [type(s).__name__ for s in steps]
+        self.mosaic, self.mosaic_cfg, self.geom = None, None, None
+        if 'Mosaic' in names:
+            at = names.index('Mosaic')
+            if names.count('Mosaic') > 1:
+                raise NotImplementedError(f'DevicePipeline runs one Mosaic, got {names.count("Mosaic")} in {names}')
+            if at == 0 or at + 1 >= len(names) or names[at - 1] != 'LoadAnnotations' \
+                    or names[at + 1] not in ('RandomSquareCrop', 'PhotoMetricDistortion'):
+                raise NotImplementedError('DevicePipeline runs Mosaic at one place, between LoadAnnotations and '
+                                          f'RandomSquareCrop; got {names}')
+            if names[at + 1] == 'PhotoMetricDistortion':
+                raise NotImplementedError(
+                    'PhotoMetricDistortion between Mosaic and RandomSquareCrop would distort the mosaic canvas, its '
+                    'pad pixels included; that form is not built -- place it between RandomFlip and Normalize')
+            if 4 * gmax > MOSAIC_MAX_GT:
+                raise ValueError(f'Mosaic merges four images: gmax={gmax} gives {4 * gmax} GT rows per image, more than '
+                                 f'the {MOSAIC_MAX_GT} the assignment kernels are tested to')
+            self.mosaic = steps[at]
+            steps, names = steps[:at] + steps[at + 1:], names[:at] + names[at + 1:]
+            gmax = 4 * gmax                     # rows of the merged GT and of the batch's padded GT
+            self.mosaic_cfg = self.mosaic.c_cfg(seed, gmax)
         self.photo, self.photo_position, self.pparams = None, L.PHOTO_NONE, None
         if 'PhotoMetricDistortion' in names:
             at = names.index('PhotoMetricDistortion')
@@ -237,7 +341,8 @@ class DevicePipeline:
             names = rest
         if names != self.ORDER:
             raise NotImplementedError(f'DevicePipeline implements exactly {self.ORDER} (with an optional '
-                                      f'PhotoMetricDistortion before RandomSquareCrop or after RandomFlip); got {names}')
+                                      'PhotoMetricDistortion before RandomSquareCrop or after RandomFlip and an '
+                                      f'optional Mosaic before RandomSquareCrop); got {names}')
         self.steps = steps
         by = dict(zip(names, steps))
         if not by['LoadAnnotations'].with_keypoints:
@@ -274,6 +379,8 @@ class DevicePipeline:
         n, S, dev = src.n, self.out_size, src.src.device
         if dev.type != 'cuda':
             raise RuntimeError('DevicePipeline needs device-resident sources: HIP kernels only, no CPU fallback')
+        if self.mosaic is not None:
+            return self._mosaic(src, iteration, sizes, dev)
         if self.scale_range is not None:
             gb, gk, cnt, params = self._decide(src, iteration, dev)
             return self._canvas(src.src, src.src_off, None, src, iteration, gb, gk, cnt, params, sizes, dev)
@@ -289,6 +396,48 @@ class DevicePipeline:
             L.check(lib.yunet_aug_pixels_photo(p(src.src), p(src.src_off), p(src.src_hw), p(params), p(pp),
                                                self.photo_position, C.byref(self.cfg), n, p(img), stream),
                     'yunet_aug_pixels_photo')
+        return self._collate(img, gb, gk, cnt, params, dev)
+
+    def _mosaic(self, src, iteration, sizes, dev):
+        """Mosaic: yunet_aug_mosaic_decide (partners, geometry, merged GT) -> the existing decide on the merged GT with
+        the canvas as its source image -> the pixel pass that resolves its taps through the geometry table."""
+        lib = L.load()
+        view, idx = src.store_view()
+        if view is None or idx is None:
+            raise NotImplementedError('Mosaic needs sources that are resident on the device')
+        n, gm, it = src.n, self.gmax, int(iteration) & 0xFFFFFFFF
+        geom = torch.empty(n, L.MOSAIC_WORDS, device=dev, dtype=torch.int32)
+        hw = torch.empty(n, 2, device=dev, dtype=torch.int32)
+        mb = torch.empty(n, gm, 4, device=dev, dtype=torch.float32)
+        mk = torch.empty(n, gm, 5, 3, device=dev, dtype=torch.float32)
+        mc = torch.empty(n, device=dev, dtype=torch.int32)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        L.check(lib.yunet_aug_mosaic_decide(p(idx), n, view.m, p(view.hw), p(view.goff), p(view.gcnt), p(view.boxes),
+                                            p(view.kps), C.byref(self.mosaic_cfg), it, p(geom), p(hw), p(mb), p(mk),
+                                            p(mc), stream), 'yunet_aug_mosaic_decide')
+        self.geom, self.merged = geom, (mb, mk, mc, hw)
+        gb = torch.empty(n, gm, 4, device=dev, dtype=torch.float32)
+        gk = torch.empty(n, gm, 5, 3, device=dev, dtype=torch.float32)
+        cnt = torch.empty(n, device=dev, dtype=torch.int32)
+        params = torch.empty(n, 8, device=dev, dtype=torch.int32)
+        lo, hi = self.scale_range or (0, 0)
+        L.check(lib.yunet_aug_decide_padded(p(hw), p(mb), p(mk), p(mc), gm, C.byref(self.cfg), lo, hi, it, n, p(params),
+                                            p(gb), p(gk), p(cnt), stream), 'yunet_aug_decide_padded')
+        out_hw = 0
+        if self.scale_range is not None:
+            sizes = np.asarray(self.read_sizes(params) if sizes is None else sizes, dtype=np.int32)
+            if sizes.shape != (n,) or not all(int(s) in self.out_sizes for s in sizes):
+                raise RuntimeError(f'square_range sizes {sizes.tolist()} are not the S_n of this pipeline '
+                                   f'({self.out_sizes})')
+            self.sizes = sizes
+            out_hw = int(sizes.max())
+        edge = out_hw or self.out_size
+        img = torch.empty(n, 3, edge, edge, device=dev, dtype=torch.float32)
+        pp = self._photometric(n, iteration, dev) if self.photo is not None else None
+        L.check(lib.yunet_aug_pixels_mosaic(p(src.src), p(view.off), p(geom), p(hw), p(params), p(pp),
+                                            self.photo_position, C.byref(self.cfg), C.byref(self.mosaic_cfg), out_hw, n,
+                                            p(img), stream), 'yunet_aug_pixels_mosaic')
         return self._collate(img, gb, gk, cnt, params, dev)
 
     def _photometric(self, n, iteration, dev):
@@ -370,6 +519,7 @@ class DevicePipeline:
         (row0, col0, rows, cols), win_off [N+1] int64 byte offsets of a compact window buffer, win_off[N] = total).
         Runs on the current stream; `src` needs only src_hw / boxes / kps / gt_off on the device."""
         lib = L.load()
+        self.require_resident('a window plan')
         _, _, _, params = self._decide(src, iteration, dev)
         rect = torch.empty(src.n, 4, device=dev, dtype=torch.int32)
         off = torch.empty(src.n + 1, device=dev, dtype=torch.int64)
@@ -384,6 +534,7 @@ class DevicePipeline:
         rect[n] of image n (window_plan of the same iteration): bit-identical to __call__ on the full sources.
         square_range: `sizes` = params[:, 7] of that plan, already on the host (else read_sizes waits here)."""
         lib = L.load()
+        self.require_resident('a window buffer')
         dev = win.device
         if dev.type != 'cuda':
             raise RuntimeError('DevicePipeline needs a device-resident window buffer: HIP kernels only')
@@ -405,6 +556,13 @@ class DevicePipeline:
                     'yunet_aug_pixels_window_photo')
         return self._collate(img, gb, gk, cnt, params, dev)
 
+    def require_resident(self, what):
+        """Mosaic reads four images of the store per output image; a feed that brings only the batch's own pixels (or
+        windows of them) to the device cannot serve it."""
+        if self.mosaic is not None:
+            raise NotImplementedError(f'Mosaic over {what}: the partner images\' pixels are not on the device; use '
+                                      "resident sources (SourceStore(placement='device'), cache='device')")
+
     def check_plan_cache(self, max_plans=None):
         """square_range walks len(out_sizes) batch geometries, one engine plan each; beyond engine.MAX_PLANS every
         new geometry evicts a plan, and an eviction drains the device (Engine.get_plan)."""
@@ -421,6 +579,13 @@ class DevicePipeline:
         """Synchronising status check of the last batch: raises like the reference would misbehave
         (it loops forever on an image whose boxes no crop window can contain)."""
         st = self.params[:, 6].cpu()
+        if self.mosaic is not None:         # merged GT beyond gmax is truncated like the crop's: the same status
+            ms = self.geom[:, L.MOSAIC_STATUS].cpu()
+            empty = ((ms & 4) != 0).nonzero().flatten().tolist()
+            if empty:
+                raise ValueError(f'Mosaic: a sub-image of images {empty} resizes to an empty size (img_scale too small '
+                                 'for its aspect ratio)')
+            st = torch.where((st == 0) & ((ms & 2) != 0), torch.full_like(st, 2), st)
         bad = (st == 1).nonzero().flatten().tolist()
         if bad:
             raise ValueError(f'RandomSquareCrop found no window containing a box centre for images {bad} '

@@ -155,6 +155,8 @@ class SyntheticSourceImages:
         if host_fetch is not None and self.host_fed != 'window':
             raise ValueError(f"host_fetch applies to host_fed='window' only, not host_fed={host_fed!r}")
         self.host_fetch = host_fetch
+        if self.host_fed:
+            self.pipe.require_resident(f'host-fed sources (host_fed={host_fed!r})')
         self._src = None
         self._ev = []
 
@@ -174,6 +176,12 @@ class SyntheticSourceImages:
     def _build(self, device):
         from .pipelines import SourceBatch
         imgs, boxes, kps, idx = self._pool_sources()
+        if self.pipe.mosaic is not None:        # the dataset Mosaic draws its partners from is the pool, not the batch
+            from .source_store import SourceStore
+            store = SourceStore([im.shape[:2] for im in imgs], placement='device', device=device)
+            for i, im in enumerate(imgs):
+                store.put(i, im, boxes[i], kps[i])
+            return store.batch(idx)
         return SourceBatch.from_lists([imgs[i] for i in idx], [boxes[i] for i in idx],
                                       [kps[i] for i in idx], 'cpu' if self.host_fed else device)
 

@@ -142,7 +142,7 @@ class SourceStore:
         """SourceBatch of the stored images idx (repeats allowed) via yunet_aug_gather on the current stream.  Device
         placement: `src` is the store itself; host placement: `src` is the pinned host store (for WindowFeed; the
         plain pipeline refuses it).  The batch also carries `host_off` / `host_hw` (numpy) of the picked images."""
-        from .pipelines import SourceBatch
+        from .pipelines import SourceBatch, StoreView
         idx = np.asarray(idx.cpu() if torch.is_tensor(idx) else idx, dtype=np.int64).reshape(-1)
         n = idx.shape[0]
         if not 1 <= n <= GATHER_MAX_N:
@@ -169,7 +169,9 @@ class SourceStore:
         L.check(L.load().yunet_aug_gather(p(d_idx), n, len(self.hw), p(t['off']), p(t['hw']), p(t['goff']),
                                           p(t['gcnt']), p(t['boxes']), p(t['kps']), g, p(src_off), p(src_hw),
                                           p(gt_off), p(boxes), p(kps), stream), 'yunet_aug_gather')
-        sb = SourceBatch(self.data, src_off, src_hw, boxes, kps, gt_off)
+        view = StoreView(len(self.hw), t['off'], t['hw'], t['goff'], t['gcnt'], t['boxes'], t['kps'])
+        sb = SourceBatch(self.data, src_off, src_hw, boxes, kps, gt_off,
+                         view=view if self.placement == 'device' else None, idx=d_idx)
         sb.host_off, sb.host_hw = self.offsets[idx], self.hw[idx]
         return sb
 
@@ -197,6 +199,7 @@ class WindowFeed:
             raise ValueError('WindowFeed feeds from a host-placement SourceStore')
         if fetch not in ('dma', 'kernel'):
             raise ValueError(f"WindowFeed fetch must be 'dma' or 'kernel', got {fetch!r}")
+        pipe.require_resident('a window feed')
         dev = store.device
         self.pipe, self.store, self.timing, self.fetch = pipe, store, bool(timing), fetch
         self._plan_stream = torch.cuda.Stream(device=dev)

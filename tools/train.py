@@ -99,6 +99,9 @@ def prepare_config(args):
 def build_source(cfg, rank, world, seed):
     """The training data source named by data.train.type (the role of build_dataset + build_dataloader)."""
     dcfg = cfg.data.train
+    if dcfg.get('type') == 'MultiImageMixDataset':      # Mosaic: the wrapped dataset with the two pipeline lists as one
+        from yunet_amd.datasets import flatten_multi_image_mix
+        dcfg = type(dcfg)(flatten_multi_image_mix(dcfg))
     kw = {k: v for k, v in dcfg.items() if k != 'type'}
     if dcfg.get('type') == 'SyntheticWiderFace':
         return R.SyntheticWiderFace(samples_per_gpu=cfg.data.samples_per_gpu, rank=rank, **kw)
@@ -113,7 +116,8 @@ def build_source(cfg, rank, world, seed):
         dataset = yunet_amd.build_dataset(dcfg)
         return RetinaFaceSource(dataset, dcfg['pipeline'], samples_per_gpu=cfg.data.samples_per_gpu, rank=rank,
                                 world=world, seed=seed, cache=cache, host_fetch=host_fetch)
-    raise SystemExit('data sources: RetinaFaceDataset (labelv2 + image files, augmented on the GPU), '
+    raise SystemExit('data sources: RetinaFaceDataset (labelv2 + image files, augmented on the GPU; also wrapped in '
+                     'MultiImageMixDataset for Mosaic), '
                      'SyntheticWiderFace (ready batches) or SyntheticSourceImages (decoded synthetic '
                      'sources + the reference train pipeline on the GPU)')
 

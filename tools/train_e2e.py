@@ -54,6 +54,8 @@ def main():
     ap.add_argument('--photometric', choices=('pre', 'post'), default=None)
     ap.add_argument('--multiscale', default=None, metavar='LO,HI')
     ap.add_argument('--size', type=int, default=None)
+    ap.add_argument('--mosaic', type=int, default=None, metavar='S',
+                    help="Mosaic(img_scale=(S, S), use_kps=True) in front of RandomSquareCrop (resident mode only)")
     ap.add_argument('--samples-per-gpu', type=int, default=None)
     a = ap.parse_args()
     if a.multiscale and a.size:
@@ -70,6 +72,8 @@ def main():
     if a.photometric:
         at = {'pre': 2, 'post': 5}[a.photometric]
         edits.append(f"train_pipeline.insert({at}, dict(type='PhotoMetricDistortion'))")
+    if a.mosaic:
+        edits.append(f"train_pipeline.insert(2, dict(type='Mosaic', img_scale=({a.mosaic}, {a.mosaic}), use_kps=True))")
     if a.samples_per_gpu:
         edits.append(f"data['samples_per_gpu'] = {a.samples_per_gpu}")
     if edits:
@@ -88,7 +92,7 @@ def main():
     if a.modes:
         modes = [m for m in modes if m[0] in a.modes.split(',')]
     res = {'what': __doc__.split('\n')[0], 'config': os.path.basename(a.config), 'iters': a.iters,
-           'photometric': a.photometric, 'multiscale': a.multiscale, 'size': a.size, 'modes': {}}
+           'photometric': a.photometric, 'multiscale': a.multiscale, 'size': a.size, 'mosaic': a.mosaic, 'modes': {}}
     for name, opts in modes:
         with tempfile.TemporaryDirectory() as wd:
             argv = [config, '--work-dir', wd, '--max-iters', str(a.iters), '--no-validate', '--seed', '0',
