@@ -601,6 +601,22 @@ int yunet_aug_pixels_mosaic(const uint8_t* store, const long long* store_off, co
 int yunet_aug_mosaic_canvas(const uint8_t* store, const long long* store_off, const int32_t* geom,
                             const YunetMosaicCfg* mcfg, int N, float* canvas, void* stream);
 
+/* The TEST pipeline of a batch (test_pipeline.DeviceTestPipeline; csrc/test_pipeline.hip), one launch: decoded uint8
+ * HWC sources addressed as for yunet_aug_pixels (src, src_off [N], src_hw [N,2]) -> out_img [N, 3, Hc, Wc] fp32 planar.
+ * table [N,4] int32 (device, written by the host) = (nh, nw, flip, 0) per image.  Inside the top-left nh x nw corner:
+ * cv2.resize(uint8, INTER_LINEAR) of the source to nw x nh in OpenCV's 11-bit fixed point (same size: copy; exactly
+ * 2 x down in both directions: (a + b + c + d + 2) >> 2), column nw - 1 - x when flip != 0, as fp32; everywhere else
+ * 0.0f.  The corner is clipped to the canvas; an image with a non-positive size writes zeros.  Every source index is
+ * clamped into the image's own src_hw.  1 <= N <= 65535, 1 <= Hc, 4 <= Wc <= YUNET_AUG_MAX_EDGE, Wc % 4 == 0,
+ * out_img 16-byte aligned; otherwise YUNET_EINVAL and nothing is launched. */
+int yunet_test_pixels(const uint8_t* src, const long long* src_off, const int32_t* src_hw, const int32_t* table, int N,
+                      int Hc, int Wc, float* out_img, void* stream);
+/* get_bboxes(rescale=True) for a batch, in place: dets [N, max_out, 5] rows r < count[n]: columns 0..3 divided by
+ * scale_factor[n][0..3]; kps [N, max_out, 10] (or NULL): x by scale_factor[n][0], y by scale_factor[n][1] -- the
+ * correctly rounded fp32 division.  scale_factor [N,4] fp32 on the device. */
+int yunet_rescale_dets(float* dets, float* kps, const int32_t* count, const float* scale_factor, int N, int max_out,
+                       void* stream);
+
 /* Decoded-source store (pipelines.SourceStore).  One launch builds a batch's SourceBatch tables from the store's
  * per-image tables (M images: byte offset, (h, w), first GT row, GT count; boxes [*,4], kps [*,5,3]) and a device
  * index vector idx [N] (repeats allowed, 1 <= N <= 8192): src_off [N], src_hw [N,2], gt_off [N+1] (exclusive scan of

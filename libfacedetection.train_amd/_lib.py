@@ -169,6 +169,8 @@ _SIGNATURES = {
     'yunet_aug_pixels_mosaic': (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.POINTER(YunetAugCfg), C.POINTER(YunetMosaicCfg),
                                                              C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'yunet_aug_mosaic_canvas': (C.c_int, [C.c_void_p] * 3 + [C.POINTER(YunetMosaicCfg), C.c_int, C.c_void_p, C.c_void_p]),
+    'yunet_test_pixels': (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p]),
+    'yunet_rescale_dets': (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]),
     'yunet_aug_gather': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int] +
                          [C.c_void_p] * 6),
     'yunet_aug_window_plan': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -108,6 +108,13 @@ class RetinaFaceDataset:
 
     def __init__(self, ann_file, img_prefix='', pipeline=None, min_size=None, test_mode=False,
                  gt_path=None, **_):
+        if int(_.get('samples_per_gpu') or 1) > 1:
+            # the reference's tools pop data.test.samples_per_gpu before they build the dataset; one that arrives here
+            # was not read by whoever built the dataset, and the images will be evaluated one at a time
+            import warnings
+            warnings.warn(f"RetinaFaceDataset: samples_per_gpu={_['samples_per_gpu']} reached the dataset unread -- this "
+                          f'caller evaluates one image at a time; tools/widerface_batched.py and evaluation.'
+                          f'single_gpu_test(samples_per_gpu=...) run the batched device test pipeline')
         self.ann_file, self.img_prefix, self.pipeline_cfg = ann_file, img_prefix, pipeline
         self.min_size, self.test_mode, self.gt_path = min_size, test_mode, gt_path
         self.NK = NK

@@ -78,6 +78,31 @@ def write_predictions(pred_dir, event, image_name, boxes_xyxy_score):
             f.write('%.5f %.5f %.5f %.5f %g\n' % (r[0], r[1], r[2] - r[0], r[3] - r[1], r[4]))
 
 
+def collect_wider_results(dets, dataset, pred_dir=None):
+    """Per-image results of single_gpu_test ([[dets [n, 5]]] in dataset order) -> the `pred` dict of wider_evaluation
+    ({event: {image stem: x y w h score}}); with pred_dir also the protocol's text files (write_predictions)."""
+    pred = {}
+    for i, res in enumerate(dets):
+        name = dataset.data_infos[i]['filename']
+        res = res[0] if isinstance(res, (list, tuple)) else res
+        event, fn = name.split('/')[-2], name.split('/')[-1]
+        stem = fn[:-4] if fn.endswith('.jpg') else os.path.splitext(fn)[0]
+        xywh = np.array(res, copy=True)
+        xywh[:, 2] -= xywh[:, 0]
+        xywh[:, 3] -= xywh[:, 1]
+        pred.setdefault(event, {})[stem] = xywh.astype(np.float64)
+        if pred_dir is not None:
+            write_predictions(pred_dir, event, stem, res)
+    return pred
+
+
+def write_aps(out_dir, aps):
+    """The `aps` file of tools/test_widerface.py: easy,medium,hard on one line."""
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, 'aps'), 'w') as f:
+        f.write('%f,%f,%f\n' % (aps[0], aps[1], aps[2]))
+
+
 def norm_score(pred):
     """Min-max normalisation of every score over the WHOLE prediction set, in place
     (widerface.py:152-174)."""
@@ -302,28 +327,54 @@ def prepare_test_image(img_bgr, scale, device, resize='cv2'):
     return x, meta
 
 
-def single_gpu_test(model, dataset, device, scale=(640, 640), max_images=None):
+def _batched(samples_per_gpu, pipeline, cache):
+    """True when single_gpu_test / multi_gpu_test are asked for the batched device path (test_pipeline.run_test);
+    the defaults keep the per-image path."""
+    if int(samples_per_gpu) < 1:
+        raise ValueError(f'samples_per_gpu must be >= 1, got {samples_per_gpu}')
+    return int(samples_per_gpu) > 1 or pipeline is not None or cache is not None
+
+
+def _run_batched(model, dataset, device, indices, scale, samples_per_gpu, pipeline, cache, log):
+    from . import test_pipeline as TP
+    pipe = pipeline if isinstance(pipeline, TP.DeviceTestPipeline) else TP.DeviceTestPipeline(pipeline, scale=scale)
+    source = TP.source_for(dataset, cache, device)
+    return TP.run_test(model, dataset, device, indices, pipe, source, samples_per_gpu, log=log)
+
+
+def single_gpu_test(model, dataset, device, scale=(640, 640), max_images=None, samples_per_gpu=1, pipeline=None,
+                    cache=None, log=None):
     """mmdet/apis/test.py single_gpu_test for this path: eval-mode forward + get_bboxes(rescale=True) per image
-    of a test-mode RetinaFaceDataset -> [[dets [n, 5]]] per image (boxes in original-image coordinates)."""
+    of a test-mode RetinaFaceDataset -> [[dets [n, 5]]] per image (boxes in original-image coordinates).
+
+    samples_per_gpu > 1, pipeline (the config's test pipeline list, or a DeviceTestPipeline) or cache ('device':
+    the decoded images stay in a device store kept on the dataset) select the batched device path
+    (test_pipeline.run_test): consecutive images in batches of samples_per_gpu, the last batch short, results in
+    dataset order.  `scale` is the view when the pipeline names none."""
     import torch
     was_training = model.training
     model.eval()
     out = []
     n = len(dataset) if max_images is None else min(len(dataset), max_images)
     with torch.no_grad():
-        for i in range(n):
-            img, meta = prepare_test_image(dataset.load_image(i), scale, device)
-            meta['ori_filename'] = dataset.data_infos[i]['filename']
-            out.append(model(return_loss=False, rescale=True, img=[img], img_metas=[[meta]])[0])
+        if _batched(samples_per_gpu, pipeline, cache):
+            out = _run_batched(model, dataset, device, list(range(n)), scale, samples_per_gpu, pipeline, cache, log)
+        else:
+            for i in range(n):
+                img, meta = prepare_test_image(dataset.load_image(i), scale, device)
+                meta['ori_filename'] = dataset.data_infos[i]['filename']
+                out.append(model(return_loss=False, rescale=True, img=[img], img_metas=[[meta]])[0])
     if was_training:
         model.train()
     return out
 
 
-def multi_gpu_test(model, dataset, device, scale=(640, 640), max_images=None, group=None):
+def multi_gpu_test(model, dataset, device, scale=(640, 640), max_images=None, group=None, samples_per_gpu=1,
+                   pipeline=None, cache=None, log=None):
     """mmdet/apis/test.py multi_gpu_test for this path (what the reference's DistEvalHook runs): rank r takes the
     images r, r + world, r + 2 world, ...; the per-image results are gathered and put back in dataset order
-    (collect_results).  Returns the full list on rank 0 and None on the other ranks."""
+    (collect_results).  Returns the full list on rank 0 and None on the other ranks.  samples_per_gpu / pipeline /
+    cache: as single_gpu_test, over the rank's own list."""
     import torch
     import torch.distributed as dist
     rank, world = dist.get_rank(group), dist.get_world_size(group)
@@ -332,10 +383,14 @@ def multi_gpu_test(model, dataset, device, scale=(640, 640), max_images=None, gr
     n = len(dataset) if max_images is None else min(len(dataset), max_images)
     part = []
     with torch.no_grad():
-        for i in range(rank, n, world):
-            img, meta = prepare_test_image(dataset.load_image(i), scale, device)
-            meta['ori_filename'] = dataset.data_infos[i]['filename']
-            part.append(model(return_loss=False, rescale=True, img=[img], img_metas=[[meta]])[0])
+        if _batched(samples_per_gpu, pipeline, cache):
+            part = _run_batched(model, dataset, device, list(range(rank, n, world)), scale, samples_per_gpu, pipeline,
+                                cache, log)
+        else:
+            for i in range(rank, n, world):
+                img, meta = prepare_test_image(dataset.load_image(i), scale, device)
+                meta['ori_filename'] = dataset.data_infos[i]['filename']
+                part.append(model(return_loss=False, rescale=True, img=[img], img_metas=[[meta]])[0])
     if was_training:
         model.train()
     parts = [None] * world
@@ -347,4 +402,3 @@ def multi_gpu_test(model, dataset, device, scale=(640, 640), max_images=None, gr
         for k, res in enumerate(p):
             out[r + k * world] = res
     return out
-

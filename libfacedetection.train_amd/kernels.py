@@ -303,6 +303,17 @@ def detect(flat, sizes, strides, score_thr=0.02, iou_thr=0.45, max_out=None, wit
     return dets, kps, count
 
 
+def rescale_dets(dets, kps, count, scale_factor):
+    """get_bboxes(rescale=True) of a batch, in place (yunet_rescale_dets): dets [N,M,5] rows below count[n] divided by
+    scale_factor[n] ([N,4] fp32 on the device), kps [N,M,10] (or None) by its first two entries."""
+    _chk_f32(dets, kps, scale_factor)
+    n, m = dets.shape[0], dets.shape[1]
+    assert kps is None or kps.shape[:2] == (n, m), 'kps: [N, M, 10] or None'
+    assert scale_factor.shape == (n, 4) and count.dtype == torch.int32 and count.numel() == n
+    L.check(L.load().yunet_rescale_dets(_p(dets), _p(kps) if kps is not None else None, _p(count), _p(scale_factor), n, m, _stream()),
+            'yunet_rescale_dets')
+
+
 def nms(boxes, scores, iou_thr=0.45, score_thr=float('-inf'), max_out=None, counts=None):
     """Greedy single-class NMS of explicit candidates: boxes [N,K,4], scores [N,K] (fp32 CUDA),
     optional counts [N] int32 -> (dets [N,max_out,5], keep [N,max_out] int32, count [N])."""

@@ -489,9 +489,18 @@ class EvalHook(Hook):
     on rank 0 (evaluation.multi_gpu_test), as the reference does -- no rank idles behind a barrier."""
 
     def __init__(self, dataset, interval=1, by_epoch=True, metric='mAP', start=None, scale=(640, 640),
-                 max_images=None, save_best=None, distributed=False, **eval_kwargs):
+                 max_images=None, save_best=None, distributed=False, samples_per_gpu=1, pipeline=None, cache=None,
+                 **eval_kwargs):
         self.dataset, self.interval, self.by_epoch, self.metric = dataset, int(interval), by_epoch, metric
         self.start, self.scale, self.max_images, self.distributed = start, scale, max_images, distributed
+        # the batched device test pipeline (evaluation.single_gpu_test): data.val_dataloader.samples_per_gpu, the
+        # data.val.pipeline list (parsed once, here, so that an unsupported form raises before training starts) and
+        # data.val.cache; the defaults keep the per-image path
+        self.samples_per_gpu, self.cache = int(samples_per_gpu), cache
+        if pipeline is not None:
+            from .test_pipeline import DeviceTestPipeline
+            pipeline = DeviceTestPipeline(pipeline, scale=scale)
+        self.pipeline = pipeline
         self.eval_kwargs = {k: v for k, v in eval_kwargs.items() if k in ('iou_thr',)}
         dropped = sorted(k for k in eval_kwargs if k not in self.eval_kwargs)
         if save_best is not None:
@@ -520,15 +529,16 @@ class EvalHook(Hook):
         if dev.type == 'cuda' and dev.index is None:
             dev = torch.device('cuda', torch.cuda.current_device())
         sharded = self.distributed and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
+        how = dict(samples_per_gpu=self.samples_per_gpu, pipeline=self.pipeline, cache=self.cache, log=runner.logger)
         if sharded:
             # BatchNorm running statistics are per rank (no SyncBN, broadcast_buffers=False): the reference's
             # DistEvalHook broadcasts rank 0's running_var / running_mean before multi_gpu_test
             # (mmdet/core/evaluation/eval_hooks.py:101-107) so that every shard is evaluated by the SAME model --
             # the one rank 0 checkpoints.  Here the buffers of all layers are two flat tensors.
             broadcast_bn_buffers(target)
-            dets = multi_gpu_test(target, self.dataset, dev, self.scale, self.max_images)      # None off rank 0
+            dets = multi_gpu_test(target, self.dataset, dev, self.scale, self.max_images, **how)      # None off rank 0
         else:
-            dets = single_gpu_test(target, self.dataset, dev, self.scale, self.max_images) if runner.rank == 0 else None
+            dets = single_gpu_test(target, self.dataset, dev, self.scale, self.max_images, **how) if runner.rank == 0 else None
         if dets is not None:
             res = self.dataset.evaluate(dets, metric=self.metric, **self.eval_kwargs)
             done = runner.iter if self.by_epoch else runner.iter + 1          # iterations completed so far
@@ -858,11 +868,20 @@ def train_detector(model, dataset, cfg, distributed=False, validate=False, times
         eval_cfg['by_epoch'] = dict(cfg.runner).get('type', 'EpochBasedRunner') != 'IterBasedRunner'
         scale = None
         for t in val_cfg.get('pipeline') or []:
-            if t.get('type') == 'MultiScaleFlipAug':
+            if t.get('type') == 'MultiScaleFlipAug' and t.get('img_scale') is not None:      # (scale_factor lists: the parser)
                 scale = tuple(t['img_scale']) if not isinstance(t['img_scale'], list) else tuple(t['img_scale'][0])
+        # mmdet/apis/train.py:206-222: data.val_dataloader.samples_per_gpu (default 1).  A value above 1, a
+        # data.val.cache, or a val pipeline that spells its transforms out runs the batched device test pipeline,
+        # built from that list; otherwise (the shipped configs) the per-image path, which reads img_scale only
+        val_spg = int((cfg.get('data').get('val_dataloader') or {}).get('samples_per_gpu', 1))
+        val_cache = val_cfg.pop('cache', None)
+        val_pipe = val_cfg.get('pipeline') or []
+        spelled = any(t.get('type') == 'MultiScaleFlipAug' and t.get('transforms') for t in val_pipe)
+        batched = dict(samples_per_gpu=val_spg, cache=val_cache,
+                       pipeline=list(val_pipe) if (spelled or val_spg > 1 or val_cache is not None) else None)
         if os.path.exists(val_cfg.get('ann_file', '')):
             runner.register_hook(EvalHook(build_dataset(val_cfg), scale=scale or (640, 640), distributed=distributed,
-                                          **eval_cfg), 'LOW')
+                                          **batched, **eval_cfg), 'LOW')
         else:
             log(f"validate: {val_cfg.get('ann_file')} not found -- no EvalHook registered")
     resume_from = cfg.get('resume_from')

@@ -247,9 +247,9 @@ class YuNet(nn.Module):
             raise RuntimeError('YuNet.simple_test needs a CUDA (ROCm) tensor: HIP kernels only, no CPU fallback')
         eng = self._ensure_engine(img.device)
         flat = eng.forward_eval(img.float().contiguous())
-        res, lmk = self.bbox_head.get_bboxes_flat(flat, eng.plan.sizes, img_metas, rescale=rescale)
-        out = [[d.cpu().numpy()] for d, _ in res]                  # bbox2result, num_classes = 1
-        return (out, [k.cpu().numpy() for k in lmk]) if with_landmarks else out
+        dets, lmk = self.bbox_head.get_bboxes_batch(flat, eng.plan.sizes, img_metas, rescale=rescale)
+        out = [[d] for d in dets]                                  # bbox2result, num_classes = 1
+        return (out, lmk) if with_landmarks else out
 
     # ------------------------------------------------------------------ engine binding
     def arch(self):

@@ -217,16 +217,20 @@ class YuNet_Head(nn.Module):
         flat = torch.cat(per_level, dim=1).contiguous()
         return self.get_bboxes_flat(flat, sizes, img_metas, cfg, rescale)[0]
 
-    def get_bboxes_flat(self, flat, sizes, img_metas=None, cfg=None, rescale=False):
-        """flat [N,P,16] (eval-mode engine output) -> (result list, decoded landmark list)."""
+    def _detect_flat(self, flat, sizes, cfg=None):
+        """test_cfg -> one csrc/detect.hip launch: (dets [N,M,5], kps [N,M,10], count [N]) on the device."""
         cfg = self.test_cfg if cfg is None else cfg
         if cfg is None:
             raise ValueError('test_cfg (score_thr, nms.iou_threshold, max_per_img) is required')
         nms = cfg.get('nms', dict(type='nms', iou_threshold=0.45))
         if nms.get('type', 'nms') != 'nms':
             raise NotImplementedError(f"nms type {nms.get('type')!r}")
-        dets, kps, count = K.detect(flat, sizes, self.strides, cfg.get('score_thr', 0.02),
-                                    nms.get('iou_threshold', 0.45), cfg.get('max_per_img', -1))
+        return K.detect(flat, sizes, self.strides, cfg.get('score_thr', 0.02),
+                        nms.get('iou_threshold', 0.45), cfg.get('max_per_img', -1))
+
+    def get_bboxes_flat(self, flat, sizes, img_metas=None, cfg=None, rescale=False):
+        """flat [N,P,16] (eval-mode engine output) -> (result list, decoded landmark list)."""
+        dets, kps, count = self._detect_flat(flat, sizes, cfg)
         cnt = count.cpu().tolist()
         results, landmarks = [], []
         for i, c in enumerate(cnt):
@@ -238,3 +242,26 @@ class YuNet_Head(nn.Module):
             results.append((d, torch.zeros(c, dtype=torch.int64, device=d.device)))
             landmarks.append(k)
         return results, landmarks
+
+    def get_bboxes_batch(self, flat, sizes, img_metas=None, cfg=None, rescale=False):
+        """get_bboxes_flat for a batch, ending on the host: the rescale of all images is one launch
+        (kernels.rescale_dets, the fp32 division get_bboxes_flat does per image) and the batch leaves the device in two
+        copies -- the counts, then one block of the dets / landmark rows up to the largest count -- instead of three
+        per image.  -> ([dets [n,5] numpy], [kps [n,10] numpy]), the values of get_bboxes_flat."""
+        import numpy as np
+        dets, kps, count = self._detect_flat(flat, sizes, cfg)
+        n = dets.shape[0]
+        if rescale:
+            sf = np.empty((n, 4), dtype=np.float32)
+            for i in range(n):
+                v = np.asarray(img_metas[i]['scale_factor'], dtype=np.float32).reshape(-1)
+                if v.size not in (1, 4):
+                    raise ValueError(f'img_metas[{i}].scale_factor must have 4 entries, got {v.size}')
+                sf[i] = v
+            K.rescale_dets(dets, kps, count, torch.from_numpy(sf).pin_memory().to(dets.device, non_blocking=True))
+        cnt = count.cpu().tolist()
+        top = max(cnt) if cnt else 0
+        if top == 0:
+            return [np.zeros((0, 5), np.float32) for _ in cnt], [np.zeros((0, 10), np.float32) for _ in cnt]
+        block = torch.cat([dets[:, :top], kps[:, :top]], dim=2).cpu().numpy()
+        return [block[i, :c, :5].copy() for i, c in enumerate(cnt)], [block[i, :c, 5:].copy() for i, c in enumerate(cnt)]

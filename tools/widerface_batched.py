@@ -1,0 +1,90 @@
+#!/usr/bin/env python
+"""tools/test_widerface.py through the batched device test pipeline (yunet_amd/test_pipeline.py): the same command line
+(CONFIG CHECKPOINT [--out DIR] [--save-preds] [--thr T] [--mode M] [--gt-path D] [--max-images N]) plus `--cache device`.
+
+`data.test.samples_per_gpu` is read as the reference's tool reads it (default 1) and `data.test.pipeline` is rewritten
+for --mode as the reference's tool does (img_scale of the MultiScaleFlipAug, the size of its Pad; an empty list is the
+pipeline evaluation.prepare_test_image hard-codes).  One kernel launch prepares a batch and the detections of a batch
+leave the device together; `--cache device` decodes into a device store first.  Origin size (--mode 2) has more batch
+geometries than the engine keeps plans and runs one image per batch, with the reason printed.  The prediction files and
+the `aps` file are those of tools/test_widerface.py (at one image per batch, text for text); use that tool for
+`--eval-only`.
+"""
+import argparse
+import copy
+import importlib.util
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def per_image_tool():
+    """tools/test_widerface.py as a module: its argument parser and its --mode table are used as they are."""
+    spec = importlib.util.spec_from_file_location('widerface_per_image', os.path.join(ROOT, 'tools', 'test_widerface.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def mode_pipeline(pipeline, scale):
+    """The reference's rewrite of data.test.pipeline for --mode (tools/test_widerface.py:77-96 there): img_scale of the
+    MultiScaleFlipAug and the size of its Pad; origin size = scale_factor 1.0 and Pad(size_divisor=32).  A copy."""
+    out = copy.deepcopy([dict(t) for t in (pipeline or [])])
+    for t in out:
+        if t.get('type') == 'MultiScaleFlipAug':
+            t['img_scale'] = scale
+            t.pop('scale_factor', None)
+            if scale is None:
+                t['scale_factor'] = 1.0
+            t['transforms'] = [dict(x) for x in t.get('transforms') or []]
+            for x in t['transforms']:
+                if x.get('type') == 'Pad':
+                    x['size'], x['size_divisor'] = (scale, None) if scale is not None else (None, 32)
+    return out
+
+
+def main():
+    tool = per_image_tool()
+    own = argparse.ArgumentParser(add_help=False)
+    own.add_argument('--cache', default=None, choices=['device'],
+                     help="'device': decode into a device store and feed the batches from it")
+    b, rest = own.parse_known_args()
+    if '-h' in rest or '--help' in rest:
+        own.print_help()
+    sys.argv = [sys.argv[0]] + rest
+    a = tool.parse_args()
+    if a.eval_only:
+        raise SystemExit('--eval-only scores saved files: use tools/test_widerface.py')
+    if not a.checkpoint:
+        raise SystemExit('a checkpoint is required')
+    import torch
+    import yunet_amd
+    from yunet_amd import evaluation as E
+    from yunet_amd.test_pipeline import DeviceTestPipeline
+    cfg = yunet_amd.Config.fromfile(a.config)
+    tcfg = dict(cfg.data.test)
+    gt_path = a.gt_path or os.path.join(os.path.dirname(tcfg['ann_file']), 'gt')
+    if a.thr != -1.:
+        cfg.model.test_cfg.score_thr = a.thr
+    dev = torch.device('cuda', 0)
+    model = yunet_amd.build_detector(cfg.model)
+    ck = torch.load(a.checkpoint, map_location='cpu', weights_only=False)
+    model.load_state_dict(ck['state_dict'] if 'state_dict' in ck else ck, strict=True)
+    model.to(dev).eval()
+    tcfg['test_mode'] = True
+    spg = int(tcfg.pop('samples_per_gpu', 1))          # as the reference reads it (tools/test_widerface.py:101-104 there)
+    ds = yunet_amd.build_dataset(tcfg)
+    scale = tool.target_scale(a.mode)
+    pipe = DeviceTestPipeline(mode_pipeline(tcfg.get('pipeline') or [], scale), scale=scale)
+    dets = E.single_gpu_test(model, ds, dev, scale, a.max_images, samples_per_gpu=spg, pipeline=pipe, cache=b.cache,
+                             log=print)
+    results = E.collect_wider_results(dets, ds, a.out if a.save_preds else None)
+    aps = E.wider_evaluation(results, gt_path, 0.5)
+    E.write_aps(a.out, aps)
+    print('APS:', aps)
+
+
+if __name__ == '__main__':
+    main()
