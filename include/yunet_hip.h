@@ -617,6 +617,42 @@ int yunet_test_pixels(const uint8_t* src, const long long* src_off, const int32_
 int yunet_rescale_dets(float* dets, float* kps, const int32_t* count, const float* scale_factor, int N, int max_out,
                        void* stream);
 
+/* ---- scoring a detection set (evaluation.py with device=...; csrc/score.hip) ------------------------------------------
+ * The integer stages of the two protocols; every table is device memory, offsets are int64 [I + 1] (exclusive scans of
+ * the per-image row counts, checked on the device against the totals P / G / D before they address anything).
+ * Totals above INT_MAX, a negative count or a missing pointer: YUNET_EINVAL, nothing launched.
+ *
+ * yunet_score_wider: widerface.py norm_score + image_eval + img_pr_info summed over the images.
+ *   pred [P,5] fp64 x y w h score, gt [G,4] fp64 x y w h, gt_bits [G] (bit s: the box is in subset s = easy, medium,
+ *   hard), thr [n_thr] fp64 the score thresholds in non-increasing order (1 <= n_thr <= YUNET_SCORE_MAX_THRESH).
+ *   minmax [2] <- min(2.0, scores), max(-1.0, scores) (the reference's starting values); a row's score is
+ *   (s - min) / (max - min) in fp64.  Per prediction the fp64 inclusive-pixel IoU against every box of its image, best =
+ *   first index of the maximum, hit = IoU >= iou_thresh; a row is its box's first hit when no earlier row of the image
+ *   hit that box.  counts [3, n_thr, 2] uint64 <- sum over the images that have predictions and boxes of
+ *   (cumsum(proposal_s)[last], cumsum(first_s)[last]), last = the LAST row index whose score passes thr[t] (nothing is
+ *   added when no row does), first_s = hit & in_s(best) & first hit, proposal_s = !(hit & !in_s(best)).
+ *   Scratch the caller allocates: best [P] int32, hit [P] uint8, first [G] int32, keys [2] uint64.
+ * yunet_score_wider_match: the matching stage alone (best, hit and first as above). */
+#define YUNET_SCORE_BLOCK 256       /* threads of a scoring workgroup = rows of a prediction tile */
+#define YUNET_SCORE_GT_CHUNK 256    /* ground truths staged in LDS at a time (any count per image) */
+#define YUNET_SCORE_MAX_THRESH 1024
+int yunet_score_wider(const double* pred, const long long* pred_off, const double* gt, const long long* gt_off,
+                      const uint8_t* gt_bits, int I, long long P, long long G, double iou_thresh, const double* thr,
+                      int n_thr, int32_t* best, uint8_t* hit, int32_t* first, unsigned long long* keys,
+                      unsigned long long* counts, double* minmax, void* stream);
+int yunet_score_wider_match(const double* pred, const long long* pred_off, const double* gt, const long long* gt_off,
+                            int I, long long P, long long G, double iou_thresh, int32_t* best, uint8_t* hit,
+                            int32_t* first, void* stream);
+/* yunet_score_map_tpfp: mean_ap.py tpfp_default for one class without area ranges.  dets [D,5] fp32 x1 y1 x2 y2 score;
+ * per image its kept boxes followed by its ignored ones in gts [G,4] fp32 (gt_off), kept [I] int32 the kept count;
+ * order [D] int32: per image, the row (relative to the image) visited k-th.  fp32 IoU (no +1, union >= 1e-6f), first
+ * index of the maximum over kept and ignored boxes together; a best IoU below iou_thr: fp; a best box that is ignored:
+ * neither; the first visit of a kept box: tp, a later one: fp; an image with no box at all: fp for every row.
+ * tp, fp [D] fp32 in row order.  Scratch: code [D] int32, first [G] int32. */
+int yunet_score_map_tpfp(const float* dets, const long long* det_off, const float* gts, const long long* gt_off,
+                         const int32_t* kept, const int32_t* order, int I, long long D, long long G, float iou_thr,
+                         int32_t* code, int32_t* first, float* tp, float* fp, void* stream);
+
 /* Decoded-source store (pipelines.SourceStore).  One launch builds a batch's SourceBatch tables from the store's
  * per-image tables (M images: byte offset, (h, w), first GT row, GT count; boxes [*,4], kps [*,5,3]) and a device
  * index vector idx [N] (repeats allowed, 1 <= N <= 8192): src_off [N], src_hw [N,2], gt_off [N+1] (exclusive scan of

@@ -18,6 +18,7 @@ FETCH_BAD_RECT, FETCH_BAD_SRC, FETCH_BAD_DST = 1, 2, 4      # YUNET_FETCH_BAD_* 
 EMA_MAX_SEGMENTS = 3                                        # YUNET_EMA_MAX_SEGMENTS (yunet_ema_update)
 HIST_TOTAL, HIST_NOIMG, HIST_SPILLED, HIST_STATUS = 0, 1, 2, 3   # YUNET_HIST_* (yunet_box_size_hist totals[])
 HIST_SPILL, HIST_OVERFLOW, HIST_BAD_COUNT = 1, 2, 4             # its status bits
+SCORE_BLOCK, SCORE_GT_CHUNK, SCORE_MAX_THRESH = 256, 256, 1024   # YUNET_SCORE_* (csrc/score.hip)
 T_IDENTITY, T_BNRELU = 0, 1
 F32, BF16 = 0, 1
 BOX_EIOU, BOX_DIOU, BOX_IOU_LINEAR, BOX_IOU_SQUARE, BOX_IOU_LOG, BOX_GIOU, BOX_CIOU = 0, 1, 2, 3, 4, 5, 6
@@ -171,6 +172,12 @@ _SIGNATURES = {
     'yunet_aug_mosaic_canvas': (C.c_int, [C.c_void_p] * 3 + [C.POINTER(YunetMosaicCfg), C.c_int, C.c_void_p, C.c_void_p]),
     'yunet_test_pixels': (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p]),
     'yunet_rescale_dets': (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]),
+    'yunet_score_wider': (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_longlong, C.c_longlong, C.c_double, C.c_void_p, C.c_int] +
+                          [C.c_void_p] * 7),
+    'yunet_score_wider_match': (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_longlong, C.c_longlong, C.c_double] +
+                                [C.c_void_p] * 4),
+    'yunet_score_map_tpfp': (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_longlong, C.c_longlong, C.c_float] +
+                             [C.c_void_p] * 5),
     'yunet_aug_gather': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int] +
                          [C.c_void_p] * 6),
     'yunet_aug_window_plan': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -136,9 +136,10 @@ class RetinaFaceDataset:
     def load_image(self, idx):
         return imread_bgr(os.path.join(self.img_prefix, self.data_infos[idx]['filename']))
 
-    def evaluate(self, results, metric='mAP', logger=None, iou_thr=0.5, **_):
+    def evaluate(self, results, metric='mAP', logger=None, iou_thr=0.5, device=None, **_):
         """CustomDataset.evaluate (mmdet/datasets/custom.py:310-367) for the metric the shipped configs ask
-        for (`evaluation = dict(interval=..., metric='mAP')`): AP of the face class at each IoU threshold."""
+        for (`evaluation = dict(interval=..., metric='mAP')`): AP of the face class at each IoU threshold.
+        device: a CUDA device scores tp / fp there (evaluation.eval_map_single_class); None: on the host."""
         from collections import OrderedDict
         from .evaluation import eval_map_single_class
         if not isinstance(metric, str):
@@ -150,7 +151,7 @@ class RetinaFaceDataset:
         thrs = [iou_thr] if isinstance(iou_thr, float) else list(iou_thr)
         res, aps = OrderedDict(), []
         for t in thrs:
-            ap, _ = eval_map_single_class(results, anns, t)
+            ap, _ = eval_map_single_class(results, anns, t, device=device)
             aps.append(ap)
             res[f'AP{int(t * 100):02d}'] = round(ap, 3)
         res['mAP'] = sum(aps) / len(aps)

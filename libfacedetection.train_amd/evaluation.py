@@ -16,8 +16,12 @@ of the reference's per-prediction Python loop over a multiprocessing pool:
 
 `pred` is {event: {image name: float array [n, 5] = x, y, w, h, score}} (rows in descending
 score, as get_bboxes delivers them); `gt_path` holds the four protocol files
-wider_{face,easy,medium,hard}_val.mat.  Host side only (numpy): evaluation is not part of the
-training hot path.
+wider_{face,easy,medium,hard}_val.mat.
+
+Both protocols have an integer stage (matching, first hits, prefix sums, counting) and a short floating-point
+tail (precision / recall / area).  The integer stage is `wider_pr_counts` / `tpfp_default`; the default runs it on the
+host in numpy, `device=<a CUDA device>` runs it in csrc/score.hip (kernels.score_wider / kernels.score_map_tpfp) on
+the packed set and reads the counters back -- the same integers, so the same APs.  The tail stays on the host.
 """
 import os
 
@@ -111,6 +115,10 @@ def norm_score(pred):
         for v in ev.values():
             if len(v):
                 lo, hi = min(lo, float(np.min(v[:, -1]))), max(hi, float(np.max(v[:, -1])))
+    return _apply_norm(pred, lo, hi)
+
+
+def _apply_norm(pred, lo, hi):
     diff = hi - lo
     for ev in pred.values():
         for v in ev.values():
@@ -182,21 +190,104 @@ def voc_ap(rec, prec):
 
 
 # ----------------------------------------------------------------------------------- dataset
-def wider_evaluation(pred, gt_path, iou_thresh=0.5, return_curves=False):
-    """-> [AP_easy, AP_medium, AP_hard] (widerface.py:271-347).  `pred` scores are normalised in
-    place, as in the reference."""
+SUBSETS = ('easy', 'medium', 'hard')
+
+
+def _score_device(device):
+    """The torch device of the device scorer; anything but a usable GPU raises (no silent host path)."""
+    import torch
+    dev = torch.device(device)
+    if dev.type != 'cuda' or not torch.cuda.is_available():
+        raise RuntimeError(f'scoring on device {device!r} needs a GPU: HIP kernels only, no CPU fallback')
+    if dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    return dev
+
+
+def _upload(dev, arrays):
+    """Host arrays -> device tensors of the same dtypes and shapes through ONE copy (8-byte aligned sections of one
+    byte buffer)."""
+    import torch
+    arrays = [np.ascontiguousarray(a) for a in arrays]
+    offs, total = [], 0
+    for a in arrays:
+        offs.append(total)
+        total += (a.nbytes + 7) // 8 * 8
+    buf = np.zeros(max(total, 8), dtype=np.uint8)
+    for a, o in zip(arrays, offs):
+        buf[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+    d = torch.from_numpy(buf).to(dev)
+    return [d[o:o + a.nbytes].view(getattr(torch, a.dtype.name)).view(a.shape) for a, o in zip(arrays, offs)]
+
+
+def pack_wider(pred, events):
+    """The packed form the device scorer takes: (pred [P,5] fp64, pred_off int64 [I+1], gt [G,4] fp64, gt_off int64
+    [I+1], gt_bits uint8 [G], count_face int64 [3]), images in protocol order.  Predictions of images no event lists
+    follow as images without ground truths: they take part in the score range, as in norm_score, and in nothing else."""
+    rows, boxes, bits, pn, gn, used = [], [], [], [], [], set()
+    count_face = np.zeros(3, dtype=np.int64)
+
+    def rows_of(info, where):
+        a = np.asarray(info)
+        if len(a) == 0:
+            return np.zeros((0, 5))
+        if a.dtype != np.float64 or a.ndim != 2 or a.shape[1] != 5:
+            raise TypeError(f'device scorer: predictions of {where} are {a.dtype} {a.shape}; it takes float64 [n, 5] '
+                            '(what collect_wider_results and read_predictions deliver)')
+        return a
+
+    for ev in events:
+        plist = pred[ev['name']]
+        for im in ev['images']:
+            a = rows_of(plist[im['name']], im['name'])
+            used.add((ev['name'], im['name']))
+            g = np.asarray(im['boxes'], dtype=np.float64).reshape(-1, 4)
+            b = np.zeros(g.shape[0], dtype=np.uint8)
+            for s, setting in enumerate(SUBSETS):
+                keep = im['keep'][setting]
+                count_face[s] += len(keep)
+                if len(keep):
+                    b[keep - 1] |= np.uint8(1 << s)
+            rows.append(a)
+            boxes.append(g)
+            bits.append(b)
+            pn.append(len(a))
+            gn.append(len(g))
+    for en, plist in pred.items():
+        for name, info in plist.items():
+            if (en, name) not in used and len(info):
+                rows.append(rows_of(info, name))
+                pn.append(len(info))
+                gn.append(0)
+    cat = lambda parts, width, dt: np.concatenate(parts).astype(dt, copy=False) if parts else np.zeros((0, width), dt)
+    off = lambda n: np.concatenate([[0], np.cumsum(np.asarray(n, dtype=np.int64))]).astype(np.int64)
+    return (cat(rows, 5, np.float64), off(pn), cat(boxes, 4, np.float64), off(gn),
+            np.concatenate(bits) if bits else np.zeros(0, np.uint8), count_face)
+
+
+def _thresholds(thresh_num=THRESH_NUM):
+    return np.array([1 - (t + 1) / thresh_num for t in range(thresh_num)])
+
+
+def wider_pr_counts(pred, events, iou_thresh=0.5, device=None):
+    """The integer stage of the protocol -> (counts int64 [3, 1000, 2], count_face int64 [3]): per subset (easy,
+    medium, hard) and score threshold, (#counted predictions, #recalled GTs) summed over the images, and the number of
+    GTs of the subset.  `pred` scores are normalised in place (norm_score).  device=None: numpy on the host; a CUDA
+    device: csrc/score.hip on the packed set (one upload, the counters read back) -- the same integers."""
+    events = load_wider_gt(events) if isinstance(events, (str, os.PathLike)) else events
+    if device is not None:
+        return _wider_pr_counts_device(pred, events, iou_thresh, _score_device(device))
     pred = norm_score(pred)
-    events = load_wider_gt(gt_path) if isinstance(gt_path, (str, os.PathLike)) else gt_path
-    aps, curves = [], []
-    for setting in ('easy', 'medium', 'hard'):
-        count_face = 0
+    counts = np.zeros((3, THRESH_NUM, 2), dtype=np.int64)
+    count_face = np.zeros(3, dtype=np.int64)
+    for s, setting in enumerate(SUBSETS):
         pr = np.zeros((THRESH_NUM, 2))
         for ev in events:
             plist = pred[ev['name']]
             for im in ev['images']:
                 info = plist[im['name']]
                 keep = im['keep'][setting]
-                count_face += len(keep)
+                count_face[s] += len(keep)
                 if len(im['boxes']) == 0 or len(info) == 0:
                     continue
                 flag = np.zeros(im['boxes'].shape[0], dtype=np.int64)
@@ -205,12 +296,40 @@ def wider_evaluation(pred, gt_path, iou_thresh=0.5, return_curves=False):
                 info = np.asarray(info, dtype=np.float64)
                 rec, prop = image_eval(info, im['boxes'], flag, iou_thresh)
                 pr += img_pr_info(info[:, 4], prop, rec)
+        counts[s] = pr                    # sums of 0 / 1 flags: integers far below 2^53, exact in either type
+    return counts, count_face
+
+
+def _wider_pr_counts_device(pred, events, iou_thresh, dev):
+    import torch
+    from . import kernels as K
+    rows, poff, boxes, goff, bits, count_face = pack_wider(pred, events)
+    with torch.cuda.device(dev):
+        d = _upload(dev, [rows, poff, boxes, goff, _thresholds(), bits])
+        counts, minmax = K.score_wider(d[0], d[1], d[2], d[3], d[5], d[4], iou_thresh)
+        counts, minmax = counts.cpu().numpy(), minmax.cpu().numpy()
+    _apply_norm(pred, float(minmax[0]), float(minmax[1]))      # the caller sees the host path's side effect
+    return counts, count_face
+
+
+def wider_aps_from_counts(counts, count_face, return_curves=False):
+    """The floating-point tail: precision / recall per threshold and the area under the envelope, per subset."""
+    aps, curves = [], []
+    for s in range(3):
+        pr = np.asarray(counts[s], dtype=np.float64)
         with np.errstate(divide='ignore', invalid='ignore'):
             precision = pr[:, 1] / pr[:, 0]
-            recall = pr[:, 1] / count_face
+            recall = pr[:, 1] / int(count_face[s])
         aps.append(float(voc_ap(recall, precision)))
         curves.append(np.stack([precision, recall], 1))
     return (aps, curves) if return_curves else aps
+
+
+def wider_evaluation(pred, gt_path, iou_thresh=0.5, return_curves=False, device=None):
+    """-> [AP_easy, AP_medium, AP_hard] (widerface.py:271-347).  `pred` scores are normalised in
+    place, as in the reference.  device: where the integer stage runs (wider_pr_counts)."""
+    counts, count_face = wider_pr_counts(pred, gt_path, iou_thresh, device=device)
+    return wider_aps_from_counts(counts, count_face, return_curves)
 
 
 # ============================================================================ mAP (EvalHook during training)
@@ -269,21 +388,48 @@ def average_precision_area(recalls, precisions):
     return np.float32(np.sum((mrec[ind + 1] - mrec[ind]) * mpre[ind + 1]))
 
 
-def eval_map_single_class(det_results, annotations, iou_thr=0.5):
+def tpfp_device(dets, gts, igns, iou_thr, device):
+    """tpfp_default of every image in one pass of csrc/score.hip: dets / gts / igns are per-image lists of float32
+    [n, 5] / [g, 4] / [k, 4] -> (tp, fp) float32 [sum n] in row order.  The visiting order of an image is the host's
+    np.argsort(-score), so ties fall as they do in tpfp_default; iou_thr is compared as float32, as numpy compares a
+    float32 array with a Python float."""
+    import torch
+    from . import kernels as K
+    dev = _score_device(device)
+    off = lambda n: np.concatenate([[0], np.cumsum(np.asarray(n, dtype=np.int64))]).astype(np.int64)
+    alld = np.concatenate(dets) if dets else np.zeros((0, 5), np.float32)
+    if alld.shape[0] == 0:
+        return np.zeros(0, np.float32), np.zeros(0, np.float32)
+    allg = np.concatenate([np.vstack([g, k]) for g, k in zip(gts, igns)])
+    order = np.concatenate([np.argsort(-d[:, -1]) for d in dets]).astype(np.int32)
+    kept = np.asarray([g.shape[0] for g in gts], dtype=np.int32)
+    with torch.cuda.device(dev):
+        d = _upload(dev, [off([x.shape[0] for x in dets]), off([g.shape[0] + k.shape[0] for g, k in zip(gts, igns)]),
+                          alld, allg, kept, order])
+        tp, fp = K.score_map_tpfp(d[2], d[0], d[3], d[1], d[4], d[5], float(np.float32(iou_thr)))
+        both = torch.stack([tp, fp]).cpu().numpy()
+    return both[0], both[1]
+
+
+def eval_map_single_class(det_results, annotations, iou_thr=0.5, device=None):
     """eval_map (mean_ap.py:522-686) for one class.  det_results: per image [[n, 5] array] (the per-class
     list of a detector's simple_test) or the [n, 5] array itself; annotations: per image dict(bboxes, labels,
     bboxes_ignore, labels_ignore) as RetinaFaceDataset.get_ann_info returns.  -> (mAP, dict(num_gts, num_dets,
-    recall, precision, ap))."""
+    recall, precision, ap)).  device: a CUDA device takes tp / fp from the device scorer (tpfp_device) instead of
+    tpfp_default; the ranking, the cumulative sums and the area stay on the host."""
     assert len(det_results) == len(annotations)
     dets = [np.asarray(d[0] if isinstance(d, (list, tuple)) else d, dtype=np.float32).reshape(-1, 5) for d in det_results]
-    tps, fps, num_gts = [], [], 0
-    for d, ann in zip(dets, annotations):
-        gts = np.asarray(ann['bboxes'], dtype=np.float32).reshape(-1, 4)
-        ign = np.asarray(ann.get('bboxes_ignore', np.zeros((0, 4))), dtype=np.float32).reshape(-1, 4)
-        t, f = tpfp_default(d, gts, ign, iou_thr)
-        tps.append(t)
-        fps.append(f)
-        num_gts += gts.shape[0]
+    gtl = [np.asarray(ann['bboxes'], dtype=np.float32).reshape(-1, 4) for ann in annotations]
+    ignl = [np.asarray(ann.get('bboxes_ignore', np.zeros((0, 4))), dtype=np.float32).reshape(-1, 4) for ann in annotations]
+    num_gts = sum(g.shape[0] for g in gtl)
+    if device is not None:
+        tps, fps = [[v] for v in tpfp_device(dets, gtl, ignl, iou_thr, device)]
+    else:
+        tps, fps = [], []
+        for d, gts, ign in zip(dets, gtl, ignl):
+            t, f = tpfp_default(d, gts, ign, iou_thr)
+            tps.append(t)
+            fps.append(f)
     alld = np.vstack(dets) if dets else np.zeros((0, 5), dtype=np.float32)
     order = np.argsort(-alld[:, -1])
     tp = np.cumsum(np.hstack(tps)[order]) if alld.shape[0] else np.zeros(0, dtype=np.float32)

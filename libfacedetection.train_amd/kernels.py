@@ -330,6 +330,83 @@ def nms(boxes, scores, iou_thr=0.45, score_thr=float('-inf'), max_out=None, coun
     return dets, keep, count
 
 
+# csrc/score.hip: threads of a scoring workgroup (= rows of a prediction tile) and ground truths staged in LDS at a time
+SCORE_BLOCK, SCORE_GT_CHUNK = L.SCORE_BLOCK, L.SCORE_GT_CHUNK
+
+
+def _chk_table(t, dtype, rows, what):
+    assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.shape[0] == rows, f'{what}: {dtype} [{rows}, ...] on the GPU'
+
+
+def _chk_offsets(off, n_img, total, what):
+    assert off.is_cuda and off.dtype == torch.int64 and off.shape == (n_img + 1,), f'{what}: int64 [I + 1] on the GPU'
+    assert 0 <= total < 2 ** 31, f'{what}: at most 2^31 - 1 rows'
+
+
+def score_wider_match(pred, pred_off, gt, gt_off, iou_thresh=0.5):
+    """The matching stage of the WIDER scorer (yunet_score_wider_match): pred [P,5] fp64 xywh+score, gt [G,4] fp64 xywh,
+    int64 offsets [I+1] -> (best int32 [P] relative to the image's first box, hit uint8 [P], first int32 [G]: the first
+    row of the image that hit the box, INT_MAX when none).  Rows of images without boxes are unspecified."""
+    n_img, P, G = pred_off.numel() - 1, pred.shape[0], gt.shape[0]
+    _chk_table(pred.view(-1, 5), torch.float64, P, 'pred')
+    _chk_table(gt.view(-1, 4), torch.float64, G, 'gt')
+    _chk_offsets(pred_off, n_img, P, 'pred_off')
+    _chk_offsets(gt_off, n_img, G, 'gt_off')
+    dev = pred.device
+    best = torch.empty(P, device=dev, dtype=torch.int32)
+    hit = torch.empty(P, device=dev, dtype=torch.uint8)
+    first = torch.empty(G, device=dev, dtype=torch.int32)
+    L.check(L.load().yunet_score_wider_match(_p(pred), _p(pred_off), _p(gt), _p(gt_off), n_img, P, G, float(iou_thresh),
+                                             _p(best), _p(hit), _p(first), _stream()), 'yunet_score_wider_match')
+    return best, hit, first
+
+
+def score_wider(pred, pred_off, gt, gt_off, gt_bits, thr, iou_thresh=0.5):
+    """yunet_score_wider: the packed prediction / ground-truth set of the WIDER protocol (as score_wider_match, plus
+    gt_bits uint8 [G] and the fp64 threshold table thr [T]) -> (counts int64 [3, T, 2], minmax fp64 [2]), on the device."""
+    n_img, P, G, T = pred_off.numel() - 1, pred.shape[0], gt.shape[0], thr.numel()
+    _chk_table(pred.view(-1, 5), torch.float64, P, 'pred')
+    _chk_table(gt.view(-1, 4), torch.float64, G, 'gt')
+    _chk_table(gt_bits, torch.uint8, G, 'gt_bits')
+    _chk_table(thr, torch.float64, T, 'thr')
+    _chk_offsets(pred_off, n_img, P, 'pred_off')
+    _chk_offsets(gt_off, n_img, G, 'gt_off')
+    assert 1 <= T <= L.SCORE_MAX_THRESH
+    dev = pred.device
+    best = torch.empty(P, device=dev, dtype=torch.int32)
+    hit = torch.empty(P, device=dev, dtype=torch.uint8)
+    first = torch.empty(G, device=dev, dtype=torch.int32)
+    keys = torch.empty(2, device=dev, dtype=torch.int64)
+    counts = torch.empty(3, T, 2, device=dev, dtype=torch.int64)          # (written as uint64; every count is < 2^63)
+    minmax = torch.empty(2, device=dev, dtype=torch.float64)
+    L.check(L.load().yunet_score_wider(_p(pred), _p(pred_off), _p(gt), _p(gt_off), _p(gt_bits), n_img, P, G,
+                                       float(iou_thresh), _p(thr), T, _p(best), _p(hit), _p(first), _p(keys), _p(counts),
+                                       _p(minmax), _stream()), 'yunet_score_wider')
+    return counts, minmax
+
+
+def score_map_tpfp(dets, det_off, gts, gt_off, kept, order, iou_thr):
+    """yunet_score_map_tpfp: dets [D,5] fp32 xyxy+score, per image its kept then its ignored boxes in gts [G,4] fp32,
+    kept int32 [I], order int32 [D] (per image: the row visited k-th) -> (tp, fp) fp32 [D] in row order.  iou_thr is
+    compared as fp32."""
+    n_img, D, G = det_off.numel() - 1, dets.shape[0], gts.shape[0]
+    _chk_table(dets.view(-1, 5), torch.float32, D, 'dets')
+    _chk_table(gts.view(-1, 4), torch.float32, G, 'gts')
+    _chk_table(kept, torch.int32, n_img, 'kept')
+    _chk_table(order, torch.int32, D, 'order')
+    _chk_offsets(det_off, n_img, D, 'det_off')
+    _chk_offsets(gt_off, n_img, G, 'gt_off')
+    dev = dets.device
+    code = torch.empty(D, device=dev, dtype=torch.int32)
+    first = torch.empty(G, device=dev, dtype=torch.int32)
+    tp = torch.empty(D, device=dev, dtype=torch.float32)
+    fp = torch.empty(D, device=dev, dtype=torch.float32)
+    L.check(L.load().yunet_score_map_tpfp(_p(dets), _p(det_off), _p(gts), _p(gt_off), _p(kept), _p(order), n_img, D, G,
+                                          float(iou_thr), _p(code), _p(first), _p(tp), _p(fp), _stream()),
+            'yunet_score_map_tpfp')
+    return tp, fp
+
+
 def box_loss_code(box_loss, mode=None):
     """YUNET_BOX_* of a loss class name of mmdet/models/losses/iou_loss.py (+ IoULoss's `mode`)."""
     if box_loss == 'IoULoss':

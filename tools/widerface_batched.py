@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """tools/test_widerface.py through the batched device test pipeline (yunet_amd/test_pipeline.py): the same command line
-(CONFIG CHECKPOINT [--out DIR] [--save-preds] [--thr T] [--mode M] [--gt-path D] [--max-images N]) plus `--cache device`.
+(CONFIG CHECKPOINT [--out DIR] [--save-preds] [--thr T] [--mode M] [--gt-path D] [--max-images N]) plus `--cache device`
+and `--score {host,device}`.
 
 `data.test.samples_per_gpu` is read as the reference's tool reads it (default 1) and `data.test.pipeline` is rewritten
 for --mode as the reference's tool does (img_scale of the MultiScaleFlipAug, the size of its Pad; an empty list is the
@@ -45,11 +46,19 @@ def mode_pipeline(pipeline, scale):
     return out
 
 
-def main():
-    tool = per_image_tool()
+def own_parser():
+    """The options this tool adds to those of tools/test_widerface.py."""
     own = argparse.ArgumentParser(add_help=False)
     own.add_argument('--cache', default=None, choices=['device'],
                      help="'device': decode into a device store and feed the batches from it")
+    own.add_argument('--score', default='host', choices=['host', 'device'],
+                     help="where the WIDER APs are scored: numpy on the host, or the HIP scorer on the GPU (same APs)")
+    return own
+
+
+def main():
+    tool = per_image_tool()
+    own = own_parser()
     b, rest = own.parse_known_args()
     if '-h' in rest or '--help' in rest:
         own.print_help()
@@ -81,7 +90,7 @@ def main():
     dets = E.single_gpu_test(model, ds, dev, scale, a.max_images, samples_per_gpu=spg, pipeline=pipe, cache=b.cache,
                              log=print)
     results = E.collect_wider_results(dets, ds, a.out if a.save_preds else None)
-    aps = E.wider_evaluation(results, gt_path, 0.5)
+    aps = E.wider_evaluation(results, gt_path, 0.5, device=dev if b.score == 'device' else None)
     E.write_aps(a.out, aps)
     print('APS:', aps)
 
