@@ -317,6 +317,39 @@ int yunet_sgd_step_ex(float* params, const float* grads, float* momentum_buf, in
                       const float* lr_dev, float momentum, float dampening, int nesterov,
                       float weight_decay, float grad_scale, int first_step, void* stream);
 
+/* ---- optimizer surface: gradient clipping, parameter groups, Adam / AdamW (csrc/optim.hip) ---------------------------
+ * The calls above stay the default path (one group, no clipping).  These serve optimizer.paramwise_cfg,
+ * optimizer_config.grad_clip and optimizer.type = 'Adam' | 'AdamW'. */
+#define YUNET_NORM_BLOCK 256          /* threads per block of yunet_grad_norm */
+#define YUNET_NORM_TILE 4096          /* floats one block folds per trip */
+#define YUNET_NORM_MAX_BLOCKS 256     /* its grid is min(ceil(n / TILE), MAX_BLOCKS): beyond that a block takes several tiles */
+#define YUNET_NORM_SCRATCH_BYTES (8 + 8 * YUNET_NORM_MAX_BLOCKS)
+enum { YUNET_NORM_INF = 0, YUNET_NORM_L1 = 1, YUNET_NORM_L2 = 2 };
+#define YUNET_OPT_ROW 4               /* doubles per group: lr, weight_decay, momentum (SGD) | beta1 (Adam), beta2 */
+#define YUNET_OPT_MAX_GROUPS 255
+
+/* torch.nn.utils.clip_grad_norm_ without its host side: out[0] = || grads * grad_scale ||_p  (norm_type YUNET_NORM_*),
+ * out[1] = min(1, max_norm / (out[0] + 1e-6)), both written by the one launch, nothing read back.  The sum runs in fp64 in
+ * a fixed order (no float atomics): the same input gives the same bits, whatever the alignment of `grads`.
+ * `scratch`: YUNET_NORM_SCRATCH_BYTES of device memory, 8-byte aligned, ZERO when first used and owned by these calls
+ * afterwards (a launch leaves it ready for the next one: no memset in between); one scratch per stream. */
+int yunet_grad_norm(const float* grads, int64_t n, float grad_scale, int norm_type, float max_norm, void* scratch,
+                    float* out, void* stream);
+/* yunet_sgd_step_ex with lr / weight_decay / momentum per parameter group: element i belongs to group group_of_elem[i]
+ * (< n_groups <= YUNET_OPT_MAX_GROUPS) and reads row group_of_elem[i] of `table` ([n_groups, YUNET_OPT_ROW] doubles in
+ * device memory, rounded to fp32 the way torch rounds its python scalars).  The gradient is multiplied by
+ * grad_scale * clip_coef[0]; clip_coef is out + 1 of yunet_grad_norm, or NULL for no clipping.  A group with momentum 0
+ * leaves its part of momentum_buf alone.  One group and clip_coef = NULL give the bits of yunet_sgd_step_ex. */
+int yunet_sgd_step_grouped(float* params, const float* grads, float* momentum_buf, int64_t n,
+                           const uint8_t* group_of_elem, const double* table, int n_groups, float dampening,
+                           int nesterov, float grad_scale, const float* clip_coef, int first_step, void* stream);
+/* torch.optim.Adam (decoupled = 0: weight decay added to the gradient) / AdamW (decoupled = 1: p *= 1 - lr * wd), the
+ * single-tensor form without amsgrad / maximize / capturable; `step` >= 1 counts this update (bias corrections
+ * 1 - beta^step are formed in fp64 on the device).  exp_avg / exp_avg_sq are flat like params, zero before step 1. */
+int yunet_adam_step_grouped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                            const uint8_t* group_of_elem, const double* table, int n_groups, float eps, int decoupled,
+                            int step, float grad_scale, const float* clip_coef, void* stream);
+
 /* ---- op-list executor ---------------------------------------------------------------- */
 /* A training step is a fixed sequence of the calls above; the host builds it once as an
  * array of YunetOp and replays it with one FFI call per phase. */

@@ -19,6 +19,9 @@ EMA_MAX_SEGMENTS = 3                                        # YUNET_EMA_MAX_SEGM
 HIST_TOTAL, HIST_NOIMG, HIST_SPILLED, HIST_STATUS = 0, 1, 2, 3   # YUNET_HIST_* (yunet_box_size_hist totals[])
 HIST_SPILL, HIST_OVERFLOW, HIST_BAD_COUNT = 1, 2, 4             # its status bits
 SCORE_BLOCK, SCORE_GT_CHUNK, SCORE_MAX_THRESH = 256, 256, 1024   # YUNET_SCORE_* (csrc/score.hip)
+NORM_BLOCK, NORM_TILE, NORM_MAX_BLOCKS, NORM_SCRATCH_BYTES = 256, 4096, 256, 8 + 8 * 256   # YUNET_NORM_* (csrc/optim.hip)
+NORM_INF, NORM_L1, NORM_L2 = 0, 1, 2
+OPT_ROW, OPT_MAX_GROUPS = 4, 255                                  # YUNET_OPT_* (the group table of csrc/optim.hip)
 T_IDENTITY, T_BNRELU = 0, 1
 F32, BF16 = 0, 1
 BOX_EIOU, BOX_DIOU, BOX_IOU_LINEAR, BOX_IOU_SQUARE, BOX_IOU_LOG, BOX_GIOU, BOX_CIOU = 0, 1, 2, 3, 4, 5, 6
@@ -205,6 +208,11 @@ _SIGNATURES = {
     'yunet_sgd_step_ex': (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_float,
                                     C.c_float, C.c_int, C.c_void_p]),
     'yunet_add': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'yunet_grad_norm': (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_int, C.c_float] + [C.c_void_p] * 3),
+    'yunet_sgd_step_grouped': (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int,
+                                         C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
+    'yunet_adam_step_grouped': (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int,
+                                          C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     'yunet_sgd_step': (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_float, C.c_float,
                                                     C.c_float, C.c_int, C.c_void_p]),
     'yunet_exec': (C.c_int, [C.POINTER(YunetOp), C.c_int, C.c_void_p]),

@@ -489,6 +489,72 @@ def sgd_step(params, grads, buf, lr_dev, momentum, weight_decay, grad_scale=1.0,
                                        float(grad_scale), int(first), _stream()), 'yunet_sgd_step_ex')
 
 
+NORM_TYPES = {2: L.NORM_L2, 1: L.NORM_L1, float('inf'): L.NORM_INF}
+
+
+def norm_type_code(norm_type):
+    """clip_grad_norm_'s norm_type -> YUNET_NORM_*; anything but 1, 2 and inf is refused here, on the host."""
+    try:
+        key = float(norm_type)
+    except (TypeError, ValueError):
+        key = None
+    if key not in NORM_TYPES:
+        raise ValueError(f'grad_clip: norm_type {norm_type!r} is not implemented on the device (only 1, 2 and inf are: '
+                         'one pass of sums or maxima over the flat gradient)')
+    return NORM_TYPES[key]
+
+
+def grad_norm_scratch(device):
+    """The zeroed scratch yunet_grad_norm needs once; its launches keep it ready for the next one."""
+    return torch.zeros(L.NORM_SCRATCH_BYTES // 8, device=device, dtype=torch.float64)
+
+
+def grad_norm(grads, max_norm, norm_type=2, grad_scale=1.0, scratch=None, out=None):
+    """out[0] = ||grads * grad_scale||_p, out[1] = min(1, max_norm / (out[0] + 1e-6)) in one launch, no host sync
+    (yunet_grad_norm).  `grads`: any contiguous run of fp32 elements (4-byte aligned is enough)."""
+    _chk_f32(grads)
+    code = norm_type_code(norm_type)
+    if scratch is None:
+        scratch = grad_norm_scratch(grads.device)
+    if out is None:
+        out = torch.empty(2, device=grads.device, dtype=torch.float32)
+    assert scratch.is_cuda and scratch.numel() * scratch.element_size() >= L.NORM_SCRATCH_BYTES
+    _chk_f32(out)
+    L.check(L.load().yunet_grad_norm(_p(grads), grads.numel(), float(grad_scale), code, float(max_norm), _p(scratch),
+                                     _p(out), _stream()), 'yunet_grad_norm')
+    return out
+
+
+def _chk_groups(params, group_of, table):
+    assert group_of.is_cuda and group_of.dtype == torch.uint8 and group_of.is_contiguous() and \
+        group_of.numel() == params.numel(), 'group map: one uint8 per parameter element'
+    assert table.is_cuda and table.dtype == torch.float64 and table.is_contiguous() and table.dim() == 2 and \
+        table.shape[1] == L.OPT_ROW and 1 <= table.shape[0] <= L.OPT_MAX_GROUPS, 'group table: [groups, 4] float64'
+
+
+def sgd_step_grouped(params, grads, buf, group_of, table, grad_scale=1.0, clip_coef=None, first=False, dampening=0.0,
+                     nesterov=False):
+    """torch.optim.SGD over parameter groups: table rows {lr, weight_decay, momentum, -}, group_of[i] the row of element
+    i; the gradient is multiplied by grad_scale * clip_coef[0] (a device float, None = 1)  (yunet_sgd_step_grouped)."""
+    _chk_f32(params, grads, buf, clip_coef)
+    _chk_groups(params, group_of, table)
+    L.check(L.load().yunet_sgd_step_grouped(_p(params), _p(grads), _p(buf), params.numel(), _p(group_of), _p(table),
+                                            table.shape[0], float(dampening), int(bool(nesterov)), float(grad_scale),
+                                            _p(clip_coef), int(first), _stream()), 'yunet_sgd_step_grouped')
+
+
+def adam_step_grouped(params, grads, exp_avg, exp_avg_sq, group_of, table, step, eps=1e-8, decoupled=False,
+                      grad_scale=1.0, clip_coef=None):
+    """torch.optim.Adam (decoupled=False) / AdamW (True) over parameter groups: table rows {lr, weight_decay, beta1,
+    beta2}; `step` counts this update from 1  (yunet_adam_step_grouped)."""
+    _chk_f32(params, grads, exp_avg, exp_avg_sq, clip_coef)
+    _chk_groups(params, group_of, table)
+    L.check(L.load().yunet_adam_step_grouped(_p(params), _p(grads), _p(exp_avg), _p(exp_avg_sq), params.numel(),
+                                             _p(group_of), _p(table), table.shape[0], float(eps), int(bool(decoupled)),
+                                             int(step), float(grad_scale), _p(clip_coef), _stream()),
+            'yunet_adam_step_grouped')
+
+
 def ema_coefficients(momentum):
     """(keep, m) of the EMA hooks: 1 - momentum in double, as the reference's python does, then both as fp32 -- what
     torch's  ema.mul_(1 - momentum).add_(src, alpha=momentum)  hands its fp32 kernels."""

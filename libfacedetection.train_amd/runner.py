@@ -385,31 +385,60 @@ class StepLrUpdaterHook(Hook):
 
     def __init__(self, base_lr=None, **cfg):
         self.cfg, self.base_lr, self.sched = cfg, base_lr, None
+        self._scheds = {}
 
     def before_run(self, runner):
         base = self.base_lr if self.base_lr is not None else runner.optimizer.param_groups[0].get(
             'initial_lr', runner.optimizer.param_groups[0]['lr'])
         self.sched = LrSchedule(base, **self.cfg)
+        self._scheds = {base: self.sched}
+
+    def _sched_of(self, group):
+        """mmcv: every group follows the schedule from its OWN initial_lr (a min_lr or a warm-up is no plain multiple of
+        the base schedule); an explicit base_lr of the hook overrides that for all groups."""
+        base = self.base_lr if self.base_lr is not None else group.get('initial_lr', group['lr'])
+        if base not in self._scheds:
+            self._scheds[base] = LrSchedule(base, **self.cfg)
+        return self._scheds[base]
 
     def before_train_iter(self, runner):
-        lr = self.sched.lr_at(runner.epoch, runner.iter, getattr(runner, 'max_epochs', None), getattr(runner, 'max_iters', None))
+        args = (runner.epoch, runner.iter, getattr(runner, 'max_epochs', None), getattr(runner, 'max_iters', None))
         for g in runner.optimizer.param_groups:
-            g['lr'] = lr
+            g['lr'] = self._sched_of(g).lr_at(*args)
 
 
 class OptimizerHook(Hook):
-    """optimizer_config = dict(grad_clip=None): zero_grad -> backward -> step (mmcv OptimizerHook)."""
+    """optimizer_config = dict(grad_clip=None | dict(max_norm=, norm_type=2)): zero_grad -> backward -> [clip] -> step
+    (mmcv OptimizerHook).  With a fused optimizer (optim.py) clipping is the norm kernel in front of the update kernel,
+    two launches and no host sync; `grad_norm` joins the iteration's log_vars as a device scalar that a logger reads when
+    it fires.  Any other optimizer goes through torch.nn.utils.clip_grad_norm_."""
 
     def __init__(self, grad_clip=None, **_):
         self.grad_clip = grad_clip
 
+    def before_run(self, runner):
+        if hasattr(runner.optimizer, 'set_grad_clip'):
+            runner.optimizer.set_grad_clip(self.grad_clip)
+
+    def _fused_clip(self, runner):
+        return self.grad_clip is not None and getattr(runner.optimizer, 'grad_clip', None) is not None
+
+    def _log_grad_norm(self, runner):
+        log_vars = runner.outputs.get('log_vars')
+        if log_vars is not None:
+            log_vars['grad_norm'] = runner.optimizer.grad_norm
+
     def after_train_iter(self, runner):
         runner.optimizer.zero_grad()
         runner.outputs['loss'].backward()
-        if self.grad_clip is not None:
+        if self.grad_clip is not None and not self._fused_clip(runner):
             params = [p for p in runner.model.parameters() if p.requires_grad and p.grad is not None]
-            torch.nn.utils.clip_grad_norm_(params, **self.grad_clip)
+            norm = torch.nn.utils.clip_grad_norm_(params, **self.grad_clip)
+            if runner.outputs.get('log_vars') is not None:
+                runner.outputs['log_vars']['grad_norm'] = norm
         runner.optimizer.step()
+        if self._fused_clip(runner):
+            self._log_grad_norm(runner)
 
 
 class Fp16OptimizerHook(OptimizerHook):
@@ -429,6 +458,7 @@ class Fp16OptimizerHook(OptimizerHook):
         self.scale, self.growth_interval, self._good = float(init), 2000, 0
 
     def before_run(self, runner):
+        super().before_run(runner)
         target = runner.model.module if hasattr(runner.model, 'module') else runner.model
         target.set_precision('bf16')
 
@@ -445,18 +475,23 @@ class Fp16OptimizerHook(OptimizerHook):
                 self.scale = max(self.scale / 2.0, 1.0)
                 self._good = 0
             return                                             # skip the step, like LossScaler
-        if hasattr(opt, 'grad_scale') and self.grad_clip is None:
-            opt.grad_scale = 1.0 / self.scale                  # FusedSGD: folded into the update kernel
+        fused_clip = self._fused_clip(runner)
+        if hasattr(opt, 'grad_scale') and (self.grad_clip is None or fused_clip):
+            # fused optimizers: folded into the update kernel, and into the norm kernel, which therefore measures the
+            # UNSCALED gradient
+            opt.grad_scale = 1.0 / self.scale
         else:
             # clipping measures the norm of the UNSCALED gradient (max_norm must not shrink by the loss
             # scale): remove the scale in place first
             grad.mul_(1.0 / self.scale)
             if hasattr(opt, 'grad_scale'):
                 opt.grad_scale = 1.0
-        if self.grad_clip is not None:
+        if self.grad_clip is not None and not fused_clip:
             params = [p for p in runner.model.parameters() if p.requires_grad and p.grad is not None]
             torch.nn.utils.clip_grad_norm_(params, **self.grad_clip)
         opt.step()
+        if fused_clip:
+            self._log_grad_norm(runner)
         if self.dynamic:
             self._good += 1
             if self._good % self.growth_interval == 0:
