@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define YUNET_ABI_VERSION 11
+#define YUNET_ABI_VERSION 12
 
 #define YUNET_EINVAL (-1)   /* bad argument / unsupported channel count */
 #define YUNET_EOPCODE (-2)  /* unknown opcode in an op list            */
@@ -458,23 +458,26 @@ typedef struct YunetAugCfg {
     int32_t gmax;            /* rows of the padded GT outputs */
 } YunetAugCfg;
 
-/* Per image: decide scale / window / flip, transform and compact the kept boxes + keypoints.
- *  src_hw [N,2] (h, w); boxes [sum G,4] xyxy; kps [sum G,5,3]; gt_off [N+1] prefix offsets;
- *  params [N,8] int32 = left, top, cw (0 = failed), flip, kept, draws, status, 0 (S_n from yunet_aug_decide_ms)
+/* Per image: decide scale / window / flip, transform and compact the kept boxes + keypoints.  One wavefront per image.
+ *  src_hw [N,2] (h, w); boxes [*,4] xyxy; kps [*,5,3]; the GT rows of image n, by in_gmax:
+ *      in_gmax == 0: ragged GT, gt_idx [N+1] prefix offsets -- rows [gt_idx[n], gt_idx[n+1]);
+ *      in_gmax  > 0: padded GT [N, in_gmax, .] (the merged GT of yunet_aug_mosaic_decide), gt_idx [N] counts -- rows
+ *                    [n * in_gmax, n * in_gmax + gt_idx[n]), the count clamped to [0, in_gmax].
+ *  multiscale == 0: Resize(img_scale=(S, S)), S = cfg->out_size >= 1; scale_lo / scale_hi are ignored.
+ *  multiscale != 0: Resize(img_scale=(a, b), multiscale_mode='square_range', keep_ratio=False), the reference's own
+ *      addition to mmdet's Resize (transforms.py:99, 128-149, 226-228): one more draw per image, in the reference's
+ *      position -- after the crop draws, before the flip draw: edge = scale_lo + floor(u32 / 2^32 * (scale_hi + 1 -
+ *      scale_lo)) (numpy.random.randint(lo, hi + 1)), S_n = edge / 32 * 32.  Boxes, keypoints, clipping and flip are the
+ *      fixed-size arithmetic with S_n in place of cfg->out_size (which is ignored).  An image with status 1 makes the
+ *      draw too (no GT: it is its only draw).  YUNET_EINVAL unless 32 <= scale_lo <= scale_hi <= YUNET_AUG_MAX_EDGE.
+ *  params [N,8] int32 = left, top, cw (0 = failed), flip, kept, draws, status, S_n (0 when multiscale == 0)
  *      status 0 ok, 1 no window with a box centre inside (or no GT), 2 kept > gmax (truncated);
- *  out_boxes [N,gmax,4], out_kps [N,gmax,5,3] (rows >= count zeroed), out_count [N]. */
-int yunet_aug_decide(const int32_t* src_hw, const float* boxes, const float* kps, const int32_t* gt_off,
-                     const YunetAugCfg* cfg, uint32_t iteration, int N, int32_t* params,
-                     float* out_boxes, float* out_kps, int32_t* out_count, void* stream);
-/* Crop (pad 128 outside the source) -> bilinear resize to S x S -> flip, uint8 HWC sources
- * (src + src_off[n], BGR as loaded) to planar fp32 [N,3,S,S]; `params` from yunet_aug_decide. */
-int yunet_aug_pixels(const uint8_t* src, const long long* src_off, const int32_t* src_hw,
-                     const int32_t* params, const YunetAugCfg* cfg, int N, float* out_img, void* stream);
-/* yunet_aug_pixels on a compact window buffer: image n is the source rectangle rect[n] = (row0, col0, rows, cols)
- * stored at win + win_off[n] with row pitch cols * 3 (yunet_aug_window_plan, yunet_upload_windows); src_hw are the
- * FULL source sizes.  Same float operations as yunet_aug_pixels: bit-identical output for the plan of `params`. */
-int yunet_aug_pixels_window(const uint8_t* win, const long long* win_off, const int32_t* rect, const int32_t* src_hw,
-                            const int32_t* params, const YunetAugCfg* cfg, int N, float* out_img, void* stream);
+ *  out_boxes [N,gmax,4], out_kps [N,gmax,5,3] (rows >= count zeroed), out_count [N].
+ * The draws and the arithmetic do not depend on the GT layout: the same GT ragged or padded gives the same outputs. */
+#define YUNET_AUG_MAX_EDGE 8192
+int yunet_aug_decide(const int32_t* src_hw, const float* boxes, const float* kps, const int32_t* gt_idx, int in_gmax,
+                     const YunetAugCfg* cfg, int multiscale, int scale_lo, int scale_hi, uint32_t iteration, int N,
+                     int32_t* params, float* out_boxes, float* out_kps, int32_t* out_count, void* stream);
 
 /* PhotoMetricDistortion (transforms.py:1211-1312) inside the pixel pass.  Positions in the pipeline list:
  *   PRE : between LoadAnnotations and RandomSquareCrop -- each in-image source tap is distorted after its uint8 ->
@@ -520,42 +523,8 @@ typedef struct YunetPhotoCfg {
  * a negative or non-finite delta, hue_delta > 360, position not PRE / POST) or N < 1. */
 int yunet_aug_photometric(const YunetPhotoCfg* cfg, uint32_t seed, uint32_t iteration, int N, float* pparams,
                           void* stream);
-/* yunet_aug_pixels / yunet_aug_pixels_window with the distortion of pparams (yunet_aug_photometric of the same
- * iteration) at `position` (PRE / POST).  Same crop / resize / flip float operations as the plain entry points. */
-int yunet_aug_pixels_photo(const uint8_t* src, const long long* src_off, const int32_t* src_hw,
-                           const int32_t* params, const float* pparams, int position, const YunetAugCfg* cfg, int N,
-                           float* out_img, void* stream);
-int yunet_aug_pixels_window_photo(const uint8_t* win, const long long* win_off, const int32_t* rect,
-                                  const int32_t* src_hw, const int32_t* params, const float* pparams, int position,
-                                  const YunetAugCfg* cfg, int N, float* out_img, void* stream);
-
-/* Multi-scale training: Resize(img_scale=(a, b), multiscale_mode='square_range', keep_ratio=False), the reference's
- * own addition to mmdet's Resize (transforms.py:99, 128-149, 226-228).  Additive to ABI 11: nothing above changes.
- *
- * yunet_aug_decide_ms is yunet_aug_decide with one more draw per image, in the reference's position -- after the
- * crop draws, before the flip draw: edge = scale_lo + floor(u32 / 2^32 * (scale_hi + 1 - scale_lo))
- * (numpy.random.randint(lo, hi + 1)), S_n = edge / 32 * 32.  Boxes, keypoints, clipping and flip are the arithmetic
- * of yunet_aug_decide with S_n in place of cfg->out_size (which is ignored); params[n][7] = S_n.  An image with
- * status 1 makes the draw too (no GT: it is its only draw).  YUNET_EINVAL unless
- * 32 <= scale_lo <= scale_hi <= YUNET_AUG_MAX_EDGE. */
-#define YUNET_AUG_MAX_EDGE 8192
-int yunet_aug_decide_ms(const int32_t* src_hw, const float* boxes, const float* kps, const int32_t* gt_off,
-                        const YunetAugCfg* cfg, int scale_lo, int scale_hi, uint32_t iteration, int N,
-                        int32_t* params, float* out_boxes, float* out_kps, int32_t* out_count, void* stream);
-/* The pixel pass of a multi-scale batch onto a canvas out_img [N,3,out_hw,out_hw]: image n fills the top-left
- * S_n x S_n corner (S_n = params[n][7] of yunet_aug_decide_ms) with exactly the floats yunet_aug_pixels* gives at
- * out_size = S_n; every other canvas pixel is 0.0f -- DefaultFormatBundle's padding_value (formatting.py:202, 231)
- * as mmcv's collate applies it, bottom and right (the placement is mmcv's rule; mmcv is not part of the reference
- * tree and is unpinned here).  out_hw is the batch's max S_n; a larger S_n is cut at the canvas, S_n <= 0 gives an
- * all-zero image.  One entry for the four forms: rect = NULL reads whole sources (yunet_aug_pixels), else the
- * window buffer of yunet_aug_window_plan, whose rectangles do not depend on the output size; position =
- * YUNET_PHOTO_NONE (pparams unused) / PRE / POST -- POST distorts the image, never the zero border. */
-int yunet_aug_pixels_canvas(const uint8_t* src, const long long* src_off, const int32_t* rect, const int32_t* src_hw,
-                            const int32_t* params, const float* pparams, int position, const YunetAugCfg* cfg,
-                            int out_hw, int N, float* out_img, void* stream);
-
 /* Mosaic(use_kps=True) (transforms.py:2218-2519) under MultiImageMixDataset (dataset_wrappers.py:338-444), in front of
- * RandomSquareCrop.  Additive to ABI 11: nothing above changes.
+ * RandomSquareCrop.
  *
  * Draws of image n come from a SUB-STREAM of the generator: key mix32(stream_key(seed, iteration, n) ^
  * YUNET_MOSAIC_SALT), counter from 0, in the reference's call order:
@@ -608,28 +577,63 @@ typedef struct YunetMosaicCfg {
  * merged GT -- boxes / keypoints r * v + pad in fp32, clipped to the canvas (bbox_clip_border), filtered by
  * min_bbox_size (skip_filter == 0) and by find_inside_bboxes, compacted in the four-image order; the third keypoint
  * column travels untouched -- into out_boxes [N,gmax,4], out_kps [N,gmax,5,3] (rows >= count zeroed), out_count [N]:
- * the input of yunet_aug_decide_padded.  A skipped image's own GT is copied through.  YUNET_EINVAL unless
+ * the input of yunet_aug_decide (in_gmax = gmax).  A skipped image's own GT is copied through.  YUNET_EINVAL unless
  * 1 <= S <= YUNET_AUG_MAX_EDGE / 2, M >= 1, 0 <= lo <= hi <= 2, 0 <= prob <= 1. */
 int yunet_aug_mosaic_decide(const int32_t* idx, int N, int M, const int32_t* store_hw, const int32_t* store_goff,
                             const int32_t* store_gcnt, const float* store_boxes, const float* store_kps,
                             const YunetMosaicCfg* cfg, uint32_t iteration, int32_t* geom, int32_t* out_hw,
                             float* out_boxes, float* out_kps, int32_t* out_count, void* stream);
-/* yunet_aug_decide / yunet_aug_decide_ms (scale_lo > 0) on padded input GT: image n's rows are boxes + n * in_gmax * 4,
- * kps + n * in_gmax * 15, counts[n] of them (clamped to [0, in_gmax]).  Same draws and arithmetic. */
-int yunet_aug_decide_padded(const int32_t* src_hw, const float* boxes, const float* kps, const int32_t* counts,
-                            int in_gmax, const YunetAugCfg* cfg, int scale_lo, int scale_hi, uint32_t iteration, int N,
-                            int32_t* params, float* out_boxes, float* out_kps, int32_t* out_count, void* stream);
-/* The pixel pass over the mosaic canvas, which is never materialised: each tap of the crop's bilinear resolves
- * through geom -- outside the canvas cfg->pad_value, quadrant by the centre, outside the paste rectangle
- * mcfg->pad_val, else the inner bilinear tap of the uint8 sub-image (store + store_off[idx]), rounded to fp32 as the
- * reference's resized sub-image is, before the outer interpolation reads it.  A skipped image reads its own source as
- * yunet_aug_pixels does.  hw / params: out_hw of yunet_aug_mosaic_decide and the params yunet_aug_decide_padded made
- * from it.  out_hw = 0: fixed size cfg->out_size; out_hw > 0: the canvas form of yunet_aug_pixels_canvas.
- * position: YUNET_PHOTO_NONE or YUNET_PHOTO_POST (PRE would distort the canvas, pad included: not built, EINVAL). */
-int yunet_aug_pixels_mosaic(const uint8_t* store, const long long* store_off, const int32_t* geom, const int32_t* hw,
-                            const int32_t* params, const float* pparams, int position, const YunetAugCfg* cfg,
-                            const YunetMosaicCfg* mcfg, int out_hw, int N, float* out_img, void* stream);
-/* Test entry: the canvas itself through the tap function of yunet_aug_pixels_mosaic, canvas [N, 2S, 2S, 3] fp32 HWC
+/* The pixel pass, one launch per batch: crop (cfg->pad_value, 128, outside the source) -> bilinear resize -> flip, from
+ * uint8 HWC sources (BGR as loaded) to planar fp32 out_img [N,3,E,E]; `params` from yunet_aug_decide.  Four independent
+ * axes select the form; the crop / resize / flip float operations are the same in every form, so two forms that
+ * describe the same pixels give bit-identical output.
+ *
+ *  rect     NULL: image n is the whole source at src + src_off[n], row pitch w * 3.
+ *           else: a compact window buffer -- image n is the source rectangle rect[n] = (row0, col0, rows, cols) stored
+ *                 at src + src_off[n] with row pitch cols * 3 (yunet_aug_window_plan, yunet_upload_windows /
+ *                 yunet_fetch_windows); src_hw are the FULL source sizes.  Bit-identical to rect == NULL for the plan
+ *                 of `params`; the rectangles do not depend on the output size.  A tap outside its rectangle (a plan
+ *                 that does not belong to these params) reads pad instead of leaving the buffer.
+ *  position YUNET_PHOTO_NONE: no distortion, pparams unused.  PRE / POST: PhotoMetricDistortion with the table pparams
+ *           (yunet_aug_photometric of the same iteration).  PRE distorts each in-image source tap after its uint8 ->
+ *           float load: the crop's pad fill is not distorted.  POST distorts every output pixel of the image (pad
+ *           pixels included) after the vertical pass, never the zero border of a canvas.
+ *  out_hw   0: E = cfg->out_size for every image (yunet_aug_decide with multiscale == 0).
+ *           > 0: a multi-scale batch on a canvas, E = out_hw (the batch's max S_n): image n fills the top-left
+ *                S_n x S_n corner, S_n = params[n][7], with exactly the floats out_hw == 0 gives at out_size = S_n;
+ *                every other canvas pixel is 0.0f -- DefaultFormatBundle's padding_value (formatting.py:202, 231) as
+ *                mmcv's collate applies it, bottom and right (the placement is mmcv's rule; mmcv is not part of the
+ *                reference tree and is unpinned here).  A larger S_n is cut at the canvas, S_n <= 0 gives an all-zero
+ *                image.  cfg->out_size is ignored.
+ *  geom     NULL: no mosaic.
+ *           else: Mosaic in front of the crop, geom / src_hw = the table and out_hw of yunet_aug_mosaic_decide, params
+ *                 made from them by yunet_aug_decide (in_gmax > 0), `mosaic` its configuration, src the whole store and
+ *                 src_off the STORE's offset table [M].  The mosaic canvas is never materialised: each tap of the
+ *                 crop's bilinear resolves through geom -- outside the canvas cfg->pad_value, quadrant by the centre,
+ *                 outside the paste rectangle mosaic->pad_val, else the inner bilinear tap of the uint8 sub-image
+ *                 (src + src_off[idx]), rounded to fp32 as the reference's resized sub-image is, before the outer
+ *                 interpolation reads it.  A skipped image reads its own source as geom == NULL does.
+ *
+ * Built: every combination of rect, position and out_hw without geom; with geom, rect == NULL and position NONE / POST
+ * (a window buffer does not hold the partner images; PRE would distort the mosaic canvas, pad included).
+ * YUNET_EINVAL, nothing launched: a NULL a, cfg, src, src_off, src_hw, params or out_img; N < 1; a position other than
+ * the three; PRE / POST without pparams; out_hw < 0 or > YUNET_AUG_MAX_EDGE; out_hw == 0 with cfg->out_size < 1; geom
+ * without mosaic or mosaic without geom; a bad mosaic configuration (yunet_aug_mosaic_decide); geom with rect or with
+ * PRE. */
+typedef struct YunetAugPixels {
+    const uint8_t* src;            /* whole sources | window buffer | the whole store (mosaic) */
+    const long long* src_off;      /* [N] byte offset of image n in src; mosaic: the store's offset table */
+    const int32_t* src_hw;         /* [N,2] full source sizes; mosaic: out_hw of yunet_aug_mosaic_decide */
+    const int32_t* rect;           /* NULL: whole images; else [N,4] of yunet_aug_window_plan */
+    const int32_t* params;         /* [N,8] of yunet_aug_decide */
+    const float* pparams;          /* table of yunet_aug_photometric; required unless position == YUNET_PHOTO_NONE */
+    const int32_t* geom;           /* NULL: no mosaic; else the table of yunet_aug_mosaic_decide */
+    const YunetMosaicCfg* mosaic;  /* non-NULL iff geom */
+    int32_t position;              /* YUNET_PHOTO_NONE | PRE | POST */
+    int32_t out_hw;                /* 0: every image cfg->out_size; > 0: canvas edge, image n = params[n][7] */
+} YunetAugPixels;
+int yunet_aug_pixels(const YunetAugPixels* a, const YunetAugCfg* cfg, int N, float* out_img, void* stream);
+/* Test entry: the canvas itself through the tap function of yunet_aug_pixels' mosaic form, canvas [N, 2S, 2S, 3] fp32 HWC
  * (a skipped image's canvas is all pad_val). */
 int yunet_aug_mosaic_canvas(const uint8_t* store, const long long* store_off, const int32_t* geom,
                             const YunetMosaicCfg* mcfg, int N, float* canvas, void* stream);

@@ -76,7 +76,7 @@ class YunetAugCfg(C.Structure):
 # PhotoMetricDistortion in the pixel pass (YUNET_PHOTO_*): positions, sub-stream salt, per-image table words
 PHOTO_NONE, PHOTO_PRE, PHOTO_POST = 0, 1, 2
 PHOTO_SALT, PHOTO_WORDS = 0x50484D44, 16
-AUG_MAX_EDGE = 8192                  # YUNET_AUG_MAX_EDGE (yunet_aug_decide_ms / yunet_aug_pixels_canvas)
+AUG_MAX_EDGE = 8192                  # YUNET_AUG_MAX_EDGE (yunet_aug_decide's scale_hi, yunet_aug_pixels' out_hw)
 (PHOTO_BRIGHT, PHOTO_DELTA, PHOTO_MODE, PHOTO_CONTRAST, PHOTO_ALPHA, PHOTO_SAT, PHOTO_SAT_F, PHOTO_HUE, PHOTO_HUE_D,
  PHOTO_SWAP, PHOTO_PERM, PHOTO_DRAWS) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 13
 
@@ -100,6 +100,13 @@ class YunetMosaicCfg(C.Structure):
     _fields_ = [('img_scale', C.c_int32), ('gmax', C.c_int32), ('center_lo', C.c_double), ('center_hi', C.c_double),
                 ('prob', C.c_double), ('min_bbox_size', C.c_float), ('pad_val', C.c_float), ('seed', C.c_uint32),
                 ('bbox_clip_border', C.c_int32), ('skip_filter', C.c_int32), ('reserved_', C.c_int32)]
+
+
+class YunetAugPixels(C.Structure):
+    """The pixel pass of yunet_aug_pixels: rect / position / out_hw / geom select the form (include/yunet_hip.h)."""
+    _fields_ = [('src', C.c_void_p), ('src_off', C.c_void_p), ('src_hw', C.c_void_p), ('rect', C.c_void_p),
+                ('params', C.c_void_p), ('pparams', C.c_void_p), ('geom', C.c_void_p),
+                ('mosaic', C.POINTER(YunetMosaicCfg)), ('position', C.c_int32), ('out_hw', C.c_int32)]
 
 
 MAX_RANKS, IPC_HANDLE_BYTES, COMM_HEADER_BYTES = 8, 64, 20480
@@ -151,27 +158,13 @@ _SIGNATURES = {
                               C.c_int] + [C.c_void_p] * 5),
     'yunet_detect_scratch_bytes': (C.c_size_t, [C.c_int, C.c_int]),
     'yunet_nms': (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 5),
-    'yunet_aug_decide': (C.c_int, [C.c_void_p] * 4 + [C.POINTER(YunetAugCfg), C.c_uint32, C.c_int] +
-                         [C.c_void_p] * 5),
-    'yunet_aug_pixels': (C.c_int, [C.c_void_p] * 4 + [C.POINTER(YunetAugCfg), C.c_int, C.c_void_p, C.c_void_p]),
-    'yunet_aug_pixels_window': (C.c_int, [C.c_void_p] * 5 + [C.POINTER(YunetAugCfg), C.c_int, C.c_void_p,
-                                                             C.c_void_p]),
+    'yunet_aug_decide': (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.POINTER(YunetAugCfg), C.c_int, C.c_int, C.c_int, C.c_uint32,
+                                                      C.c_int] + [C.c_void_p] * 5),
+    'yunet_aug_pixels': (C.c_int, [C.POINTER(YunetAugPixels), C.POINTER(YunetAugCfg), C.c_int, C.c_void_p, C.c_void_p]),
     'yunet_aug_photometric': (C.c_int, [C.POINTER(YunetPhotoCfg), C.c_uint32, C.c_uint32, C.c_int, C.c_void_p,
                                         C.c_void_p]),
-    'yunet_aug_pixels_photo': (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.POINTER(YunetAugCfg), C.c_int, C.c_void_p,
-                                                            C.c_void_p]),
-    'yunet_aug_pixels_window_photo': (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.POINTER(YunetAugCfg), C.c_int,
-                                                                   C.c_void_p, C.c_void_p]),
-    'yunet_aug_decide_ms': (C.c_int, [C.c_void_p] * 4 + [C.POINTER(YunetAugCfg), C.c_int, C.c_int, C.c_uint32, C.c_int] +
-                            [C.c_void_p] * 5),
-    'yunet_aug_pixels_canvas': (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.POINTER(YunetAugCfg), C.c_int, C.c_int,
-                                                             C.c_void_p, C.c_void_p]),
     'yunet_aug_mosaic_decide': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 +
                                 [C.POINTER(YunetMosaicCfg), C.c_uint32] + [C.c_void_p] * 6),
-    'yunet_aug_decide_padded': (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.POINTER(YunetAugCfg), C.c_int, C.c_int, C.c_uint32,
-                                                             C.c_int] + [C.c_void_p] * 5),
-    'yunet_aug_pixels_mosaic': (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.POINTER(YunetAugCfg), C.POINTER(YunetMosaicCfg),
-                                                             C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'yunet_aug_mosaic_canvas': (C.c_int, [C.c_void_p] * 3 + [C.POINTER(YunetMosaicCfg), C.c_int, C.c_void_p, C.c_void_p]),
     'yunet_test_pixels': (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p]),
     'yunet_rescale_dets': (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]),
@@ -255,7 +248,7 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    if lib.yunet_abi_version() != 11:
+    if lib.yunet_abi_version() != 12:
         raise YunetHipError('libyunet_hip.so ABI version mismatch; rebuild it')
     _lib = lib
     return lib

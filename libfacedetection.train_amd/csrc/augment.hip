@@ -20,6 +20,7 @@
 // performs, so boxes / keypoints are bit-identical to the reference and pixels to the oracle.
 #include <cfloat>
 #include <cmath>
+#include <type_traits>
 
 #include "common.h"
 
@@ -621,52 +622,9 @@ __global__ __launch_bounds__(256) void aug_pixels_kernel(
 
 }  // namespace
 
-extern "C" int yunet_aug_decide(const int32_t* src_hw, const float* boxes, const float* kps,
-                                const int32_t* gt_off, const YunetAugCfg* cfg, uint32_t iteration, int N,
-                                int32_t* params, float* out_boxes, float* out_kps, int32_t* out_count,
-                                void* stream) {
-    if (!cfg || N < 1 || cfg->n_choice < 1 || cfg->n_choice > 8 || cfg->out_size < 1 || cfg->gmax < 1 ||
-        cfg->max_attempts < 1 || cfg->max_retries < 1)
-        return YUNET_EINVAL;
-    hipLaunchKernelGGL(aug_decide_kernel<false>, dim3(N), dim3(64), 0, (hipStream_t)stream, src_hw, boxes, kps,
-                       gt_off, *cfg, 0, 0, iteration, params, out_boxes, out_kps, out_count, 0);
-    return hip_status();
-}
-
-extern "C" int yunet_aug_decide_ms(const int32_t* src_hw, const float* boxes, const float* kps,
-                                   const int32_t* gt_off, const YunetAugCfg* cfg, int scale_lo, int scale_hi,
-                                   uint32_t iteration, int N, int32_t* params, float* out_boxes, float* out_kps,
-                                   int32_t* out_count, void* stream) {
-    if (!cfg || N < 1 || cfg->n_choice < 1 || cfg->n_choice > 8 || cfg->gmax < 1 || cfg->max_attempts < 1 ||
-        cfg->max_retries < 1 || scale_lo < 32 || scale_hi < scale_lo || scale_hi > YUNET_AUG_MAX_EDGE)
-        return YUNET_EINVAL;
-    hipLaunchKernelGGL(aug_decide_kernel<true>, dim3(N), dim3(64), 0, (hipStream_t)stream, src_hw, boxes, kps,
-                       gt_off, *cfg, scale_lo, scale_hi, iteration, params, out_boxes, out_kps, out_count, 0);
-    return hip_status();
-}
-
-extern "C" int yunet_aug_pixels(const uint8_t* src, const long long* src_off, const int32_t* src_hw,
-                                const int32_t* params, const YunetAugCfg* cfg, int N, float* out_img,
-                                void* stream) {
-    if (!cfg || N < 1 || cfg->out_size < 1) return YUNET_EINVAL;
-    const int S = cfg->out_size;
-    int bx = (S * S + 255) / 256;
-    if (bx > 64) bx = 64;                       // grid-stride over the pixels of one image
-    hipLaunchKernelGGL((aug_pixels_kernel<false, YUNET_PHOTO_NONE>), dim3(bx, N), dim3(256), 0, (hipStream_t)stream, src,
-                       src_off, src_hw, nullptr, params, nullptr, S, cfg->pad_value, out_img, nullptr, nullptr, 0.0f);
-    return hip_status();
-}
-
-extern "C" int yunet_aug_pixels_window(const uint8_t* win, const long long* win_off, const int32_t* rect,
-                                       const int32_t* src_hw, const int32_t* params, const YunetAugCfg* cfg, int N,
-                                       float* out_img, void* stream) {
-    if (!cfg || N < 1 || cfg->out_size < 1) return YUNET_EINVAL;
-    const int S = cfg->out_size;
-    int bx = (S * S + 255) / 256;
-    if (bx > 64) bx = 64;
-    hipLaunchKernelGGL((aug_pixels_kernel<true, YUNET_PHOTO_NONE>), dim3(bx, N), dim3(256), 0, (hipStream_t)stream, win,
-                       win_off, src_hw, rect, params, nullptr, S, cfg->pad_value, out_img, nullptr, nullptr, 0.0f);
-    return hip_status();
+static bool aug_cfg_ok(const YunetAugCfg* cfg) {
+    return cfg && cfg->n_choice >= 1 && cfg->n_choice <= 8 && cfg->gmax >= 1 && cfg->max_attempts >= 1 &&
+           cfg->max_retries >= 1;
 }
 
 static bool photo_cfg_ok(const YunetPhotoCfg* c) {
@@ -679,6 +637,44 @@ static bool photo_cfg_ok(const YunetPhotoCfg* c) {
            (c->position == YUNET_PHOTO_PRE || c->position == YUNET_PHOTO_POST);
 }
 
+static bool mosaic_cfg_ok(const YunetMosaicCfg* c) {
+    return c && c->img_scale >= 1 && c->img_scale <= YUNET_AUG_MAX_EDGE / 2 && c->gmax >= 1 &&
+           std::isfinite(c->center_lo) && std::isfinite(c->center_hi) && c->center_lo >= 0.0 &&
+           c->center_lo <= c->center_hi && c->center_hi <= 2.0 && c->prob >= 0.0 && c->prob <= 1.0 &&
+           std::isfinite(c->min_bbox_size) && std::isfinite(c->pad_val);
+}
+
+// A run-time choice as a template argument: f(std::bool_constant<b>{}), f(std::integral_constant<int, position>{}).
+template <class F>
+static void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class F>
+static void with_position(int position, F&& f) {
+    if (position == YUNET_PHOTO_PRE) f(std::integral_constant<int, YUNET_PHOTO_PRE>{});
+    else if (position == YUNET_PHOTO_POST) f(std::integral_constant<int, YUNET_PHOTO_POST>{});
+    else f(std::integral_constant<int, YUNET_PHOTO_NONE>{});
+}
+
+extern "C" int yunet_aug_decide(const int32_t* src_hw, const float* boxes, const float* kps, const int32_t* gt_idx,
+                                int in_gmax, const YunetAugCfg* cfg, int multiscale, int scale_lo, int scale_hi,
+                                uint32_t iteration, int N, int32_t* params, float* out_boxes, float* out_kps,
+                                int32_t* out_count, void* stream) {
+    if (!aug_cfg_ok(cfg) || N < 1 || in_gmax < 0) return YUNET_EINVAL;
+    if (multiscale ? (scale_lo < 32 || scale_hi < scale_lo || scale_hi > YUNET_AUG_MAX_EDGE) : cfg->out_size < 1)
+        return YUNET_EINVAL;
+    if (!multiscale) scale_lo = scale_hi = 0;
+    with_bool(multiscale != 0, [&](auto ms) {
+        with_bool(in_gmax > 0, [&](auto pad) {
+            hipLaunchKernelGGL((aug_decide_kernel<decltype(ms)::value, decltype(pad)::value>), dim3(N), dim3(64), 0,
+                               (hipStream_t)stream, src_hw, boxes, kps, gt_idx, *cfg, scale_lo, scale_hi, iteration,
+                               params, out_boxes, out_kps, out_count, in_gmax);
+        });
+    });
+    return hip_status();
+}
+
 extern "C" int yunet_aug_photometric(const YunetPhotoCfg* cfg, uint32_t seed, uint32_t iteration, int N,
                                      float* pparams, void* stream) {
     if (!cfg || !photo_cfg_ok(cfg) || N < 1 || !pparams) return YUNET_EINVAL;
@@ -687,83 +683,41 @@ extern "C" int yunet_aug_photometric(const YunetPhotoCfg* cfg, uint32_t seed, ui
     return hip_status();
 }
 
-template <bool WIN>
-static int launch_pixels_photo(const uint8_t* src, const long long* src_off, const int32_t* src_hw,
-                               const int32_t* rect, const int32_t* params, const float* pparams, int position,
-                               const YunetAugCfg* cfg, int N, float* out_img, void* stream) {
-    if (!cfg || N < 1 || cfg->out_size < 1 || !pparams) return YUNET_EINVAL;
-    const int S = cfg->out_size;
-    int bx = (S * S + 255) / 256;
-    if (bx > 64) bx = 64;
-    if (position == YUNET_PHOTO_PRE)
-        hipLaunchKernelGGL((aug_pixels_kernel<WIN, YUNET_PHOTO_PRE>), dim3(bx, N), dim3(256), 0, (hipStream_t)stream,
-                           src, src_off, src_hw, rect, params, pparams, S, cfg->pad_value, out_img, nullptr, nullptr, 0.0f);
-    else if (position == YUNET_PHOTO_POST)
-        hipLaunchKernelGGL((aug_pixels_kernel<WIN, YUNET_PHOTO_POST>), dim3(bx, N), dim3(256), 0, (hipStream_t)stream,
-                           src, src_off, src_hw, rect, params, pparams, S, cfg->pad_value, out_img, nullptr, nullptr, 0.0f);
-    else
-        return YUNET_EINVAL;
+// Every refusal of the pixel pass, before any launch.  The two forms that are not built -- mosaic over a window buffer,
+// mosaic with the distortion in the PRE position -- are refused here, so the dispatch below never meets them.
+static bool aug_pixels_ok(const YunetAugPixels* a, const YunetAugCfg* cfg, int N, const float* out_img) {
+    if (!a || !cfg || N < 1 || !out_img || !a->src || !a->src_off || !a->src_hw || !a->params) return false;
+    const bool photo = a->position == YUNET_PHOTO_PRE || a->position == YUNET_PHOTO_POST;
+    if ((!photo && a->position != YUNET_PHOTO_NONE) || (photo && !a->pparams)) return false;
+    if (a->out_hw < 0 || a->out_hw > YUNET_AUG_MAX_EDGE || (a->out_hw == 0 && cfg->out_size < 1)) return false;
+    if ((a->geom != nullptr) != (a->mosaic != nullptr)) return false;
+    if (a->geom && (!mosaic_cfg_ok(a->mosaic) || a->rect || a->position == YUNET_PHOTO_PRE)) return false;
+    return true;
+}
+
+extern "C" int yunet_aug_pixels(const YunetAugPixels* a, const YunetAugCfg* cfg, int N, float* out_img, void* stream) {
+    if (!aug_pixels_ok(a, cfg, N, out_img)) return YUNET_EINVAL;
+    const int C = a->out_hw ? a->out_hw : cfg->out_size;      // the grid covers the canvas, border included
+    int bx = (C * C + 255) / 256;
+    if (bx > 64) bx = 64;                                     // grid-stride over the pixels of one image
+    with_bool(a->rect != nullptr, [&](auto win) {
+        with_position(a->position, [&](auto ph) {
+            with_bool(a->out_hw > 0, [&](auto canvas) {
+                with_bool(a->geom != nullptr, [&](auto mosaic) {
+                    constexpr bool WIN = decltype(win)::value, CANVAS = decltype(canvas)::value,
+                                   MOSAIC = decltype(mosaic)::value;
+                    constexpr int PH = decltype(ph)::value;
+                    // the kernel's mosaic form takes the store's offset table apart from src_off
+                    if constexpr (!(MOSAIC && (WIN || PH == YUNET_PHOTO_PRE)))
+                        hipLaunchKernelGGL((aug_pixels_kernel<WIN, PH, CANVAS, MOSAIC>), dim3(bx, N), dim3(256), 0,
+                                           (hipStream_t)stream, a->src, MOSAIC ? nullptr : a->src_off, a->src_hw,
+                                           a->rect, a->params, a->pparams, C, cfg->pad_value, out_img, a->geom,
+                                           MOSAIC ? a->src_off : nullptr, MOSAIC ? a->mosaic->pad_val : 0.0f);
+                });
+            });
+        });
+    });
     return hip_status();
-}
-
-extern "C" int yunet_aug_pixels_photo(const uint8_t* src, const long long* src_off, const int32_t* src_hw,
-                                      const int32_t* params, const float* pparams, int position,
-                                      const YunetAugCfg* cfg, int N, float* out_img, void* stream) {
-    return launch_pixels_photo<false>(src, src_off, src_hw, nullptr, params, pparams, position, cfg, N, out_img,
-                                      stream);
-}
-
-extern "C" int yunet_aug_pixels_window_photo(const uint8_t* win, const long long* win_off, const int32_t* rect,
-                                             const int32_t* src_hw, const int32_t* params, const float* pparams,
-                                             int position, const YunetAugCfg* cfg, int N, float* out_img,
-                                             void* stream) {
-    return launch_pixels_photo<true>(win, win_off, src_hw, rect, params, pparams, position, cfg, N, out_img, stream);
-}
-
-template <bool WIN>
-static int launch_pixels_canvas(const uint8_t* src, const long long* src_off, const int32_t* src_hw,
-                                const int32_t* rect, const int32_t* params, const float* pparams, int position,
-                                const YunetAugCfg* cfg, int out_hw, int N, float* out_img, void* stream) {
-    int bx = (out_hw * out_hw + 255) / 256;     // the grid covers the canvas, border included
-    if (bx > 64) bx = 64;
-    const dim3 grid(bx, N), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    if (position == YUNET_PHOTO_NONE)
-        hipLaunchKernelGGL((aug_pixels_kernel<WIN, YUNET_PHOTO_NONE, true>), grid, block, 0, st, src, src_off, src_hw,
-                           rect, params, pparams, out_hw, cfg->pad_value, out_img, nullptr, nullptr, 0.0f);
-    else if (position == YUNET_PHOTO_PRE)
-        hipLaunchKernelGGL((aug_pixels_kernel<WIN, YUNET_PHOTO_PRE, true>), grid, block, 0, st, src, src_off, src_hw,
-                           rect, params, pparams, out_hw, cfg->pad_value, out_img, nullptr, nullptr, 0.0f);
-    else
-        hipLaunchKernelGGL((aug_pixels_kernel<WIN, YUNET_PHOTO_POST, true>), grid, block, 0, st, src, src_off, src_hw,
-                           rect, params, pparams, out_hw, cfg->pad_value, out_img, nullptr, nullptr, 0.0f);
-    return hip_status();
-}
-
-extern "C" int yunet_aug_pixels_canvas(const uint8_t* src, const long long* src_off, const int32_t* rect,
-                                       const int32_t* src_hw, const int32_t* params, const float* pparams,
-                                       int position, const YunetAugCfg* cfg, int out_hw, int N, float* out_img,
-                                       void* stream) {
-    const bool photo = position == YUNET_PHOTO_PRE || position == YUNET_PHOTO_POST;
-    if (!cfg || N < 1 || out_hw < 1 || out_hw > YUNET_AUG_MAX_EDGE || (!photo && position != YUNET_PHOTO_NONE) ||
-        (photo && !pparams))
-        return YUNET_EINVAL;
-    return rect ? launch_pixels_canvas<true>(src, src_off, src_hw, rect, params, pparams, position, cfg, out_hw, N,
-                                             out_img, stream)
-                : launch_pixels_canvas<false>(src, src_off, src_hw, nullptr, params, pparams, position, cfg, out_hw,
-                                              N, out_img, stream);
-}
-
-static bool aug_cfg_ok(const YunetAugCfg* cfg) {
-    return cfg && cfg->n_choice >= 1 && cfg->n_choice <= 8 && cfg->gmax >= 1 && cfg->max_attempts >= 1 &&
-           cfg->max_retries >= 1;
-}
-
-static bool mosaic_cfg_ok(const YunetMosaicCfg* c) {
-    return c && c->img_scale >= 1 && c->img_scale <= YUNET_AUG_MAX_EDGE / 2 && c->gmax >= 1 &&
-           std::isfinite(c->center_lo) && std::isfinite(c->center_hi) && c->center_lo >= 0.0 &&
-           c->center_lo <= c->center_hi && c->center_hi <= 2.0 && c->prob >= 0.0 && c->prob <= 1.0 &&
-           std::isfinite(c->min_bbox_size) && std::isfinite(c->pad_val);
 }
 
 extern "C" int yunet_aug_mosaic_decide(const int32_t* idx, int N, int M, const int32_t* store_hw,
@@ -777,52 +731,6 @@ extern "C" int yunet_aug_mosaic_decide(const int32_t* idx, int N, int M, const i
     hipLaunchKernelGGL(mosaic_decide_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, idx, M, store_hw, store_goff,
                        store_gcnt, store_boxes, store_kps, *cfg, iteration, geom, out_hw, out_boxes, out_kps,
                        out_count);
-    return hip_status();
-}
-
-extern "C" int yunet_aug_decide_padded(const int32_t* src_hw, const float* boxes, const float* kps,
-                                       const int32_t* counts, int in_gmax, const YunetAugCfg* cfg, int scale_lo,
-                                       int scale_hi, uint32_t iteration, int N, int32_t* params, float* out_boxes,
-                                       float* out_kps, int32_t* out_count, void* stream) {
-    if (!aug_cfg_ok(cfg) || N < 1 || in_gmax < 1) return YUNET_EINVAL;
-    if (scale_lo > 0) {
-        if (scale_lo < 32 || scale_hi < scale_lo || scale_hi > YUNET_AUG_MAX_EDGE) return YUNET_EINVAL;
-        hipLaunchKernelGGL((aug_decide_kernel<true, true>), dim3(N), dim3(64), 0, (hipStream_t)stream, src_hw, boxes,
-                           kps, counts, *cfg, scale_lo, scale_hi, iteration, params, out_boxes, out_kps, out_count,
-                           in_gmax);
-    } else {
-        if (cfg->out_size < 1) return YUNET_EINVAL;
-        hipLaunchKernelGGL((aug_decide_kernel<false, true>), dim3(N), dim3(64), 0, (hipStream_t)stream, src_hw, boxes,
-                           kps, counts, *cfg, 0, 0, iteration, params, out_boxes, out_kps, out_count, in_gmax);
-    }
-    return hip_status();
-}
-
-extern "C" int yunet_aug_pixels_mosaic(const uint8_t* store, const long long* store_off, const int32_t* geom,
-                                       const int32_t* hw, const int32_t* params, const float* pparams, int position,
-                                       const YunetAugCfg* cfg, const YunetMosaicCfg* mcfg, int out_hw, int N,
-                                       float* out_img, void* stream) {
-    const bool post = position == YUNET_PHOTO_POST;
-    if (!cfg || !mosaic_cfg_ok(mcfg) || N < 1 || !store || !store_off || !geom || !hw || !params || !out_img ||
-        (!post && position != YUNET_PHOTO_NONE) || (post && !pparams) || out_hw < 0 || out_hw > YUNET_AUG_MAX_EDGE ||
-        (out_hw == 0 && cfg->out_size < 1))
-        return YUNET_EINVAL;
-    const int C = out_hw ? out_hw : cfg->out_size;
-    int bx = (C * C + 255) / 256;
-    if (bx > 64) bx = 64;
-    const dim3 grid(bx, N), block(256);
-    hipStream_t st = (hipStream_t)stream;
-#define YUNET_LAUNCH_MOSAIC(PH, CANVAS)                                                                              \
-    hipLaunchKernelGGL((aug_pixels_kernel<false, PH, CANVAS, true>), grid, block, 0, st, store, nullptr, hw, nullptr, \
-                       params, pparams, C, cfg->pad_value, out_img, geom, store_off, mcfg->pad_val)
-    if (out_hw) {
-        if (post) YUNET_LAUNCH_MOSAIC(YUNET_PHOTO_POST, true);
-        else YUNET_LAUNCH_MOSAIC(YUNET_PHOTO_NONE, true);
-    } else {
-        if (post) YUNET_LAUNCH_MOSAIC(YUNET_PHOTO_POST, false);
-        else YUNET_LAUNCH_MOSAIC(YUNET_PHOTO_NONE, false);
-    }
-#undef YUNET_LAUNCH_MOSAIC
     return hip_status();
 }
 

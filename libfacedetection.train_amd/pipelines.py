@@ -295,6 +295,15 @@ class SourceBatch:
 MOSAIC_MAX_GT = 1024        # GT rows per image the engine's assign kernels are tested to
 
 
+def _ptr(t):
+    """Device address of a tensor (None: NULL), as a c_void_p argument or descriptor field takes it."""
+    return t.data_ptr() if t is not None else None
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
 class DevicePipeline:
     """Builds from the reference's pipeline list and runs it as two kernel launches per batch."""
 
@@ -364,7 +373,7 @@ class DevicePipeline:
         if not 1 <= len(choice) <= 8:
             raise NotImplementedError('crop_choice must have 1..8 entries')
         cfg = L.YunetAugCfg()
-        cfg.out_size, cfg.n_choice = self.out_size or self.out_sizes[-1], len(choice)    # unused by the _ms entry
+        cfg.out_size, cfg.n_choice = self.out_size or self.out_sizes[-1], len(choice)    # out_size: unused under square_range
         for i, c in enumerate(choice):
             cfg.crop_choice[i] = c
         cfg.flip_ratio, cfg.pad_value, cfg.seed = by['RandomFlip'].flip_ratio, pad_value, seed & 0xFFFFFFFF
@@ -373,57 +382,35 @@ class DevicePipeline:
         self.photo_cfg = self.photo.c_cfg(self.photo_position) if self.photo is not None else None
         self.gmax = gmax
         self.params = None
+        self._pixels = L.YunetAugPixels()       # the pixel pass's descriptor: the per-batch fields are filled in place
+        self._pixels.position = self.photo_position
+        if self.mosaic is not None:
+            self._pixels.mosaic = C.pointer(self.mosaic_cfg)
 
     def __call__(self, src, iteration, sizes=None):
-        lib = L.load()
-        n, S, dev = src.n, self.out_size, src.src.device
+        dev = src.src.device
         if dev.type != 'cuda':
             raise RuntimeError('DevicePipeline needs device-resident sources: HIP kernels only, no CPU fallback')
-        if self.mosaic is not None:
-            return self._mosaic(src, iteration, sizes, dev)
-        if self.scale_range is not None:
-            gb, gk, cnt, params = self._decide(src, iteration, dev)
-            return self._canvas(src.src, src.src_off, None, src, iteration, gb, gk, cnt, params, sizes, dev)
-        img = torch.empty(n, 3, S, S, device=dev, dtype=torch.float32)
-        gb, gk, cnt, params = self._decide(src, iteration, dev)
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-        if self.photo is None:
-            L.check(lib.yunet_aug_pixels(p(src.src), p(src.src_off), p(src.src_hw), p(params), C.byref(self.cfg), n,
-                                         p(img), stream), 'yunet_aug_pixels')
-        else:
-            pp = self._photometric(n, iteration, dev)
-            L.check(lib.yunet_aug_pixels_photo(p(src.src), p(src.src_off), p(src.src_hw), p(params), p(pp),
-                                               self.photo_position, C.byref(self.cfg), n, p(img), stream),
-                    'yunet_aug_pixels_photo')
-        return self._collate(img, gb, gk, cnt, params, dev)
-
-    def _mosaic(self, src, iteration, sizes, dev):
-        """Mosaic: yunet_aug_mosaic_decide (partners, geometry, merged GT) -> the existing decide on the merged GT with
-        the canvas as its source image -> the pixel pass that resolves its taps through the geometry table."""
-        lib = L.load()
+        if self.mosaic is None:
+            return self._run(src, iteration, dev, (src.src, src.src_off, None), sizes)
         view, idx = src.store_view()
         if view is None or idx is None:
             raise NotImplementedError('Mosaic needs sources that are resident on the device')
-        n, gm, it = src.n, self.gmax, int(iteration) & 0xFFFFFFFF
-        geom = torch.empty(n, L.MOSAIC_WORDS, device=dev, dtype=torch.int32)
-        hw = torch.empty(n, 2, device=dev, dtype=torch.int32)
-        mb = torch.empty(n, gm, 4, device=dev, dtype=torch.float32)
-        mk = torch.empty(n, gm, 5, 3, device=dev, dtype=torch.float32)
-        mc = torch.empty(n, device=dev, dtype=torch.int32)
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
-        L.check(lib.yunet_aug_mosaic_decide(p(idx), n, view.m, p(view.hw), p(view.goff), p(view.gcnt), p(view.boxes),
-                                            p(view.kps), C.byref(self.mosaic_cfg), it, p(geom), p(hw), p(mb), p(mk),
-                                            p(mc), stream), 'yunet_aug_mosaic_decide')
-        self.geom, self.merged = geom, (mb, mk, mc, hw)
-        gb = torch.empty(n, gm, 4, device=dev, dtype=torch.float32)
-        gk = torch.empty(n, gm, 5, 3, device=dev, dtype=torch.float32)
-        cnt = torch.empty(n, device=dev, dtype=torch.int32)
-        params = torch.empty(n, 8, device=dev, dtype=torch.int32)
-        lo, hi = self.scale_range or (0, 0)
-        L.check(lib.yunet_aug_decide_padded(p(hw), p(mb), p(mk), p(mc), gm, C.byref(self.cfg), lo, hi, it, n, p(params),
-                                            p(gb), p(gk), p(cnt), stream), 'yunet_aug_decide_padded')
+        return self._run(src, iteration, dev, (src.src, view.off, None), sizes, store=(view, idx))
+
+    def _run(self, src, iteration, dev, pix, sizes, store=None):
+        """One batch on the current stream: decide -> sizes -> allocate -> photometric table -> pixel pass -> collate.
+        `pix` = (buffer, offsets, rect), where the pixel pass reads: whole sources (rect None), a window buffer with its
+        plan, or -- Mosaic, `store` = (StoreView, the batch's store indices) -- the whole store with its offset table.
+        Mosaic: yunet_aug_mosaic_decide (partners, geometry, merged GT) comes first; the decide then runs on the merged
+        GT with the canvas as its source image and the pixel pass resolves its taps through the geometry table.
+        square_range: the batch is the [N, 3, Smax, Smax] canvas.  Image n sits in the top-left S_n x S_n corner, the
+        rest is 0: DefaultFormatBundle wraps the image with padding_value=0, stack=True (formatting.py:202, 231) and
+        mmcv's collate pads a group's images at the bottom and right up to the largest.  The value and the stacking are
+        the reference's; the bottom / right placement is mmcv's rule, restated here without mmcv at hand."""
+        n = src.n
+        merged = self._mosaic_decide(store, n, iteration, dev) if store is not None else None
+        gb, gk, cnt, params = self._decide(src, iteration, dev, merged)
         out_hw = 0
         if self.scale_range is not None:
             sizes = np.asarray(self.read_sizes(params) if sizes is None else sizes, dtype=np.int32)
@@ -435,39 +422,54 @@ class DevicePipeline:
         edge = out_hw or self.out_size
         img = torch.empty(n, 3, edge, edge, device=dev, dtype=torch.float32)
         pp = self._photometric(n, iteration, dev) if self.photo is not None else None
-        L.check(lib.yunet_aug_pixels_mosaic(p(src.src), p(view.off), p(geom), p(hw), p(params), p(pp),
-                                            self.photo_position, C.byref(self.cfg), C.byref(self.mosaic_cfg), out_hw, n,
-                                            p(img), stream), 'yunet_aug_pixels_mosaic')
+        a = self._pixels            # position / mosaic were set with the configuration
+        a.src, a.src_off, a.rect = (_ptr(t) for t in pix)
+        a.src_hw, a.params, a.pparams = _ptr(src.src_hw if merged is None else merged[3]), _ptr(params), _ptr(pp)
+        a.geom, a.out_hw = _ptr(self.geom if merged is not None else None), out_hw
+        L.check(L.load().yunet_aug_pixels(C.byref(a), C.byref(self.cfg), n, _ptr(img), _stream()), 'yunet_aug_pixels')
         return self._collate(img, gb, gk, cnt, params, dev)
+
+    def _mosaic_decide(self, store, n, iteration, dev):
+        """yunet_aug_mosaic_decide on the current stream -> merged = (boxes, keypoints, counts, hw): the merged GT,
+        padded to gmax rows, and the size of each image's canvas (its own size when the mosaic was skipped)."""
+        view, idx = store
+        gm = self.gmax
+        geom = torch.empty(n, L.MOSAIC_WORDS, device=dev, dtype=torch.int32)
+        hw = torch.empty(n, 2, device=dev, dtype=torch.int32)
+        mb = torch.empty(n, gm, 4, device=dev, dtype=torch.float32)
+        mk = torch.empty(n, gm, 5, 3, device=dev, dtype=torch.float32)
+        mc = torch.empty(n, device=dev, dtype=torch.int32)
+        L.check(L.load().yunet_aug_mosaic_decide(
+            _ptr(idx), n, view.m, _ptr(view.hw), _ptr(view.goff), _ptr(view.gcnt), _ptr(view.boxes), _ptr(view.kps),
+            C.byref(self.mosaic_cfg), int(iteration) & 0xFFFFFFFF, _ptr(geom), _ptr(hw), _ptr(mb), _ptr(mk), _ptr(mc),
+            _stream()), 'yunet_aug_mosaic_decide')
+        self.geom, self.merged = geom, (mb, mk, mc, hw)
+        return self.merged
 
     def _photometric(self, n, iteration, dev):
         """yunet_aug_photometric on the current stream, keyed like _decide -> the table [N, PHOTO_WORDS] fp32."""
         pp = torch.empty(n, L.PHOTO_WORDS, device=dev, dtype=torch.float32)
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         L.check(L.load().yunet_aug_photometric(C.byref(self.photo_cfg), self.cfg.seed, int(iteration) & 0xFFFFFFFF, n,
-                                               C.c_void_p(pp.data_ptr()), stream), 'yunet_aug_photometric')
+                                               _ptr(pp), _stream()), 'yunet_aug_photometric')
         self.pparams = pp
         return pp
 
-    def _decide(self, src, iteration, dev):
-        """yunet_aug_decide on the current stream -> (padded boxes, padded keypoints, counts, params)."""
-        lib = L.load()
+    def _decide(self, src, iteration, dev, merged=None):
+        """yunet_aug_decide on the current stream -> (padded boxes, padded keypoints, counts, params).  The GT is src's
+        ragged lists, or `merged` of _mosaic_decide: padded to gmax rows, its hw taking the place of the source sizes."""
         n = src.n
         gb = torch.empty(n, self.gmax, 4, device=dev, dtype=torch.float32)
         gk = torch.empty(n, self.gmax, 5, 3, device=dev, dtype=torch.float32)
         cnt = torch.empty(n, device=dev, dtype=torch.int32)
         params = torch.empty(n, 8, device=dev, dtype=torch.int32)
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-        if self.scale_range is not None:
-            lo, hi = self.scale_range
-            L.check(lib.yunet_aug_decide_ms(p(src.src_hw), p(src.boxes), p(src.kps), p(src.gt_off), C.byref(self.cfg),
-                                            lo, hi, int(iteration) & 0xFFFFFFFF, n, p(params), p(gb), p(gk), p(cnt),
-                                            stream), 'yunet_aug_decide_ms')
-            return gb, gk, cnt, params
-        L.check(lib.yunet_aug_decide(p(src.src_hw), p(src.boxes), p(src.kps), p(src.gt_off), C.byref(self.cfg),
-                                     int(iteration) & 0xFFFFFFFF, n, p(params), p(gb), p(gk), p(cnt), stream),
-                'yunet_aug_decide')
+        if merged is None:
+            boxes, kps, idx, hw, in_gmax = src.boxes, src.kps, src.gt_off, src.src_hw, 0
+        else:
+            boxes, kps, idx, hw, in_gmax = *merged, self.gmax
+        lo, hi = self.scale_range or (0, 0)
+        L.check(L.load().yunet_aug_decide(_ptr(hw), _ptr(boxes), _ptr(kps), _ptr(idx), in_gmax, C.byref(self.cfg),
+                                          int(self.scale_range is not None), lo, hi, int(iteration) & 0xFFFFFFFF, n,
+                                          _ptr(params), _ptr(gb), _ptr(gk), _ptr(cnt), _stream()), 'yunet_aug_decide')
         return gb, gk, cnt, params
 
     def read_sizes(self, params):
@@ -476,27 +478,6 @@ class DevicePipeline:
         stream (and for nothing else on the device).  WindowFeed makes this copy with its plan, iterations ahead, and
         hands the result to `windowed(sizes=...)`."""
         return params[:, 7].cpu().numpy()
-
-    def _canvas(self, pix, pix_off, rect, src, iteration, gb, gk, cnt, params, sizes, dev):
-        """square_range: the pixel pass onto the [N, 3, Smax, Smax] canvas and the collate.  Image n sits in the
-        top-left S_n x S_n corner, the rest is 0: DefaultFormatBundle wraps the image with padding_value=0, stack=True
-        (formatting.py:202, 231) and mmcv's collate pads a group's images at the bottom and right up to the largest.
-        The value and the stacking are the reference's; the bottom / right placement is mmcv's rule, restated here
-        without mmcv at hand."""
-        n = src.n
-        sizes = np.asarray(self.read_sizes(params) if sizes is None else sizes, dtype=np.int32)
-        if sizes.shape != (n,) or not all(int(s) in self.out_sizes for s in sizes):
-            raise RuntimeError(f'square_range sizes {sizes.tolist()} are not the S_n of this pipeline ({self.out_sizes})')
-        self.sizes = sizes
-        smax = int(sizes.max())
-        img = torch.empty(n, 3, smax, smax, device=dev, dtype=torch.float32)
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
-        pp = self._photometric(n, iteration, dev) if self.photo is not None else None
-        L.check(L.load().yunet_aug_pixels_canvas(p(pix), p(pix_off), p(rect), p(src.src_hw), p(params), p(pp),
-                                                 self.photo_position, C.byref(self.cfg), smax, n, p(img), stream),
-                'yunet_aug_pixels_canvas')
-        return self._collate(img, gb, gk, cnt, params, dev)
 
     def _collate(self, img, gb, gk, cnt, params, dev):
         n, S = img.shape[0], self.out_size
@@ -518,14 +499,11 @@ class DevicePipeline:
         (seed, iteration, image), so this can run ahead of the iteration): -> (params [N,8], rect [N,4] int32
         (row0, col0, rows, cols), win_off [N+1] int64 byte offsets of a compact window buffer, win_off[N] = total).
         Runs on the current stream; `src` needs only src_hw / boxes / kps / gt_off on the device."""
-        lib = L.load()
         self.require_resident('a window plan')
         _, _, _, params = self._decide(src, iteration, dev)
         rect = torch.empty(src.n, 4, device=dev, dtype=torch.int32)
         off = torch.empty(src.n + 1, device=dev, dtype=torch.int64)
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-        L.check(lib.yunet_aug_window_plan(p(params), p(src.src_hw), src.n, p(rect), p(off), stream),
+        L.check(L.load().yunet_aug_window_plan(_ptr(params), _ptr(src.src_hw), src.n, _ptr(rect), _ptr(off), _stream()),
                 'yunet_aug_window_plan')
         return params, rect, off
 
@@ -533,28 +511,11 @@ class DevicePipeline:
         """The pipeline on a compact window buffer `win` (uint8, device) holding, at win_off[n], the rectangle
         rect[n] of image n (window_plan of the same iteration): bit-identical to __call__ on the full sources.
         square_range: `sizes` = params[:, 7] of that plan, already on the host (else read_sizes waits here)."""
-        lib = L.load()
         self.require_resident('a window buffer')
         dev = win.device
         if dev.type != 'cuda':
             raise RuntimeError('DevicePipeline needs a device-resident window buffer: HIP kernels only')
-        n, S = src.n, self.out_size
-        if self.scale_range is not None:
-            gb, gk, cnt, params = self._decide(src, iteration, dev)
-            return self._canvas(win, win_off, rect, src, iteration, gb, gk, cnt, params, sizes, dev)
-        img = torch.empty(n, 3, S, S, device=dev, dtype=torch.float32)
-        gb, gk, cnt, params = self._decide(src, iteration, dev)
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-        if self.photo is None:
-            L.check(lib.yunet_aug_pixels_window(p(win), p(win_off), p(rect), p(src.src_hw), p(params),
-                                                C.byref(self.cfg), n, p(img), stream), 'yunet_aug_pixels_window')
-        else:
-            pp = self._photometric(n, iteration, dev)
-            L.check(lib.yunet_aug_pixels_window_photo(p(win), p(win_off), p(rect), p(src.src_hw), p(params), p(pp),
-                                                      self.photo_position, C.byref(self.cfg), n, p(img), stream),
-                    'yunet_aug_pixels_window_photo')
-        return self._collate(img, gb, gk, cnt, params, dev)
+        return self._run(src, iteration, dev, (win, win_off, rect), sizes)
 
     def require_resident(self, what):
         """Mosaic reads four images of the store per output image; a feed that brings only the batch's own pixels (or

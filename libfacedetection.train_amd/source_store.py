@@ -9,7 +9,7 @@ Two placements:
   device  the decoded images live in HBM; a batch is a gather of store indices (csrc/source.hip aug_gather_kernel).
   host    the decoded images live in PINNED host memory (their bytes, per rank); per batch only the rectangle of each
           image that the pixel pass can read travels (WindowFeed: yunet_aug_window_plan -> yunet_upload_windows or,
-          with fetch='kernel', yunet_fetch_windows -> yunet_aug_pixels_window).
+          with fetch='kernel', yunet_fetch_windows -> yunet_aug_pixels with the plan's rect).
 Annotations and the per-image tables always live on the device.
 """
 import ctypes as C

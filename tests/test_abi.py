@@ -25,7 +25,16 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(lib, n), f'{n} is declared in include/yunet_hip.h but not exported'
     assert sorted(L.EXPORTED) == names, 'ctypes signature table and header disagree'
-    assert lib.yunet_abi_version() == 11
+    assert lib.yunet_abi_version() == 12
+    # ABI 12: one pixel-pass entry and one decide entry; the nine names they replace are in neither header nor library
+    gone = [('pixels', s) for s in ('window', 'photo', 'window_photo', 'canvas', 'mosaic')] + [('decide', 'ms'),
+                                                                                                 ('decide', 'padded')]
+    for old in (f'yunet_aug_{entry}_{suffix}' for entry, suffix in gone):
+        assert old not in names and old not in open(HEADER).read(), f'{old} is still declared'
+        assert not hasattr(lib, old), f'{old} is still exported'
+    # the two names that stay carry the new signatures: the descriptor and the explicit multiscale / in_gmax arguments
+    assert L._SIGNATURES['yunet_aug_pixels'][1][0] is C.POINTER(L.YunetAugPixels)
+    assert len(L._SIGNATURES['yunet_aug_pixels'][1]) == 5 and len(L._SIGNATURES['yunet_aug_decide'][1]) == 16
     assert lib.yunet_conv_blocks() >= 256
     assert lib.yunet_loss_blocks(256, 2100) >= 1
 
@@ -42,17 +51,21 @@ def test_ctypes_structs_match_c_layout(tmp_path):
     import yunet_amd._lib as L
     src = tmp_path / 'sz.c'
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "yunet_hip.h"\n'
-                   'int main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n",'
+                   'int main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n",'
                    'sizeof(YunetOp),sizeof(YunetDP),sizeof(YunetBN),sizeof(YunetLevels),'
                    'sizeof(YunetLossCfg),offsetof(YunetOp,p),offsetof(YunetOp,bn),'
                    'offsetof(YunetOp,dp),offsetof(YunetOp,lv),offsetof(YunetDP,prof),sizeof(YunetComm),'
-                   'offsetof(YunetComm,status));return 0;}')
+                   'offsetof(YunetComm,status),sizeof(YunetAugPixels),offsetof(YunetAugPixels,pparams),'
+                   'offsetof(YunetAugPixels,mosaic),offsetof(YunetAugPixels,position),offsetof(YunetAugPixels,out_hw));'
+                   'return 0;}')
     exe = tmp_path / 'sz'
     subprocess.check_call(['gcc', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)])
     got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
     want = [C.sizeof(L.YunetOp), C.sizeof(L.YunetDP), C.sizeof(L.YunetBN), C.sizeof(L.YunetLevels),
             C.sizeof(L.YunetLossCfg), L.YunetOp.p.offset, L.YunetOp.bn.offset, L.YunetOp.dp.offset,
-            L.YunetOp.lv.offset, L.YunetDP.prof.offset, C.sizeof(L.YunetComm), L.YunetComm.status.offset]
+            L.YunetOp.lv.offset, L.YunetDP.prof.offset, C.sizeof(L.YunetComm), L.YunetComm.status.offset,
+            C.sizeof(L.YunetAugPixels), L.YunetAugPixels.pparams.offset, L.YunetAugPixels.mosaic.offset,
+            L.YunetAugPixels.position.offset, L.YunetAugPixels.out_hw.offset]
     assert got == want
 
 

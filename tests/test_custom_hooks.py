@@ -250,7 +250,7 @@ def test_library_exports_hook_entry_points():
     import yunet_amd._lib as L
     lib = L.load()
     assert hasattr(lib, 'yunet_ema_update') and hasattr(lib, 'yunet_box_size_hist')
-    assert lib.yunet_abi_version() == 11
+    assert lib.yunet_abi_version() == 12
 
 
 def test_ema_update_rejects_bad_arguments_without_launching():

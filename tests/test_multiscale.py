@@ -227,15 +227,22 @@ def test_new_entry_points_are_declared_and_bound():
     import yunet_amd._lib as L
     txt = open(os.path.join(ROOT, 'include', 'yunet_hip.h')).read()
     txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
-    for name in ('yunet_aug_decide_ms', 'yunet_aug_pixels_canvas'):
+    for name in ('yunet_aug_decide', 'yunet_aug_pixels'):
         m = re.search(r'\bint\s+' + name + r'\s*\(([^)]*)\)\s*;', txt)
         assert m, f'{name} is not declared in include/yunet_hip.h'
         assert name in L.EXPORTED
         assert len(m.group(1).split(',')) == len(L._SIGNATURES[name][1]), f'{name}: argument counts differ'
     lib = L.load()
-    assert hasattr(lib, 'yunet_aug_decide_ms') and hasattr(lib, 'yunet_aug_pixels_canvas')
-    assert lib.yunet_abi_version() == 11
+    assert hasattr(lib, 'yunet_aug_decide') and hasattr(lib, 'yunet_aug_pixels')
+    assert lib.yunet_abi_version() == 12
     assert int(re.search(r'#define\s+YUNET_AUG_MAX_EDGE\s+(\d+)', txt).group(1)) == L.AUG_MAX_EDGE
+
+
+def _aug_cfg():
+    import yunet_amd._lib as L
+    cfg = L.YunetAugCfg()
+    cfg.out_size, cfg.n_choice, cfg.gmax, cfg.max_attempts, cfg.max_retries = 320, 1, 64, 250, 64
+    return cfg
 
 
 def test_entry_points_reject_bad_arguments_without_a_gpu():
@@ -243,14 +250,81 @@ def test_entry_points_reject_bad_arguments_without_a_gpu():
     import ctypes as C
     import yunet_amd._lib as L
     lib = L.load()
-    cfg = L.YunetAugCfg()
-    cfg.out_size, cfg.n_choice, cfg.gmax, cfg.max_attempts, cfg.max_retries = 320, 1, 64, 250, 64
+    cfg = _aug_cfg()
     for lo, hi in ((31, 320), (0, 0), (320, 319), (320, L.AUG_MAX_EDGE + 1)):
-        assert lib.yunet_aug_decide_ms(None, None, None, None, C.byref(cfg), lo, hi, 0, 1, None, None, None, None,
-                                       None) == L.EINVAL
+        assert lib.yunet_aug_decide(None, None, None, None, 0, C.byref(cfg), 1, lo, hi, 0, 1, None, None, None, None,
+                                    None) == L.EINVAL
     for hw, pos in ((0, L.PHOTO_NONE), (L.AUG_MAX_EDGE + 1, L.PHOTO_NONE), (320, 7), (320, L.PHOTO_POST)):
-        assert lib.yunet_aug_pixels_canvas(None, None, None, None, None, None, pos, C.byref(cfg), hw, 1, None,
-                                           None) == L.EINVAL
+        a = L.YunetAugPixels(position=pos, out_hw=hw)
+        assert lib.yunet_aug_pixels(C.byref(a), C.byref(cfg), 1, None, None) == L.EINVAL
+
+
+def test_pixel_pass_refusal_table_without_a_gpu():
+    """yunet_aug_pixels: every refusal of include/yunet_hip.h, one cause at a time.  The pointers of a case are non-NULL
+    wherever its cause is not a NULL pointer (they address host memory: a refusal comes before any launch and nothing
+    reads them), so a case cannot pass on account of another check; the descriptor without a fault is not called."""
+    import ctypes as C
+    import yunet_amd._lib as L
+    lib = L.load()
+    cfg = _aug_cfg()
+    mem = (C.c_char * 64)()
+    ptr = C.addressof(mem)
+    mcfg = L.YunetMosaicCfg(img_scale=32, gmax=8, center_lo=0.5, center_hi=1.5, prob=1.0, pad_val=114.0)
+    bad_mcfg = L.YunetMosaicCfg.from_buffer_copy(mcfg)
+    bad_mcfg.img_scale = 0
+    ok = dict(src=ptr, src_off=ptr, src_hw=ptr, params=ptr)
+    mosaic = dict(ok, geom=ptr, mosaic=C.pointer(mcfg))
+    cases = {
+        'geom with rect': dict(mosaic, rect=ptr),
+        'geom with PRE': dict(mosaic, position=L.PHOTO_PRE, pparams=ptr),
+        'geom without mosaic': dict(ok, geom=ptr),
+        'mosaic without geom': dict(ok, mosaic=C.pointer(mcfg)),
+        'geom with a bad mosaic configuration': dict(mosaic, mosaic=C.pointer(bad_mcfg)),
+        'PRE without pparams': dict(ok, position=L.PHOTO_PRE),
+        'POST without pparams': dict(ok, position=L.PHOTO_POST),
+        'POST without pparams, mosaic': dict(mosaic, position=L.PHOTO_POST),
+        'position 7': dict(ok, position=7, pparams=ptr),
+        'out_hw -1': dict(ok, out_hw=-1),
+        'out_hw above the largest edge': dict(ok, out_hw=L.AUG_MAX_EDGE + 1),
+        'NULL src': dict(ok, src=None),
+        'NULL src_off': dict(ok, src_off=None),
+        'NULL src_hw': dict(ok, src_hw=None),
+        'NULL params': dict(ok, params=None),
+    }
+    for what, fields in cases.items():
+        a = L.YunetAugPixels(**fields)
+        assert lib.yunet_aug_pixels(C.byref(a), C.byref(cfg), 1, ptr, None) == L.EINVAL, what
+    a = L.YunetAugPixels(**ok)
+    assert lib.yunet_aug_pixels(C.byref(a), C.byref(cfg), 0, ptr, None) == L.EINVAL, 'N < 1'
+    assert lib.yunet_aug_pixels(C.byref(a), C.byref(cfg), 1, None, None) == L.EINVAL, 'NULL out_img'
+    assert lib.yunet_aug_pixels(C.byref(a), None, 1, ptr, None) == L.EINVAL, 'NULL cfg'
+    assert lib.yunet_aug_pixels(None, C.byref(cfg), 1, ptr, None) == L.EINVAL, 'NULL a'
+    cfg.out_size = 0
+    assert lib.yunet_aug_pixels(C.byref(a), C.byref(cfg), 1, ptr, None) == L.EINVAL, 'out_hw == 0 with out_size < 1'
+
+
+def test_decide_refusals_without_a_gpu():
+    """yunet_aug_decide: multiscale = 0 needs cfg->out_size >= 1 and ignores the scale arguments; a negative in_gmax and
+    a bad configuration are refused in every form (one check, aug_cfg_ok)."""
+    import ctypes as C
+    import yunet_amd._lib as L
+    lib = L.load()
+
+    def call(cfg, in_gmax, ms, lo, hi, n=1):
+        return lib.yunet_aug_decide(None, None, None, None, in_gmax, C.byref(cfg) if cfg else None, ms, lo, hi, 0, n,
+                                    None, None, None, None, None)
+    for in_gmax in (0, 8):
+        cfg = _aug_cfg()
+        cfg.out_size = 0
+        assert call(cfg, in_gmax, 0, 320, 640) == L.EINVAL
+        assert call(_aug_cfg(), in_gmax, 0, 320, 640, n=0) == L.EINVAL
+        assert call(None, in_gmax, 1, 320, 640) == L.EINVAL
+        for field, value in (('n_choice', 0), ('n_choice', 9), ('gmax', 0), ('max_attempts', 0), ('max_retries', 0)):
+            for ms in (0, 1):
+                cfg = _aug_cfg()
+                setattr(cfg, field, value)
+                assert call(cfg, in_gmax, ms, 320, 640) == L.EINVAL, (field, ms)
+    assert call(_aug_cfg(), -1, 0, 0, 0) == L.EINVAL
 
 
 def test_cfg_options_reach_the_resize_entry_and_the_logger_hook():

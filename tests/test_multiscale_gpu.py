@@ -1,7 +1,7 @@
-"""-m gpu: multi-scale training on the device -- yunet_aug_decide_ms / yunet_aug_pixels_canvas (csrc/augment.hip) and
+"""-m gpu: multi-scale training on the device -- yunet_aug_decide (multiscale = 1) / yunet_aug_pixels (out_hw > 0) and
 DevicePipeline with Resize(multiscale_mode='square_range') against (a) the fixture made by the unmodified reference
 transforms, (b) the numpy restatement tests/multiscale_ref.py (everything bit-exact, zero border included), (c) the
-existing fixed-size pixel entry points at out_size = S_n, and (d) the engine fed with the same tensors as a ready batch.
+fixed-size form of the pixel entry (out_hw = 0) at out_size = S_n, and (d) the engine fed with the same tensors as a ready batch.
 Every case is one bounded pass: no retries."""
 import ctypes as C
 import os
@@ -129,14 +129,24 @@ def _window_buffer(pipe, sb, it):
     return torch.from_numpy(win).to(DEV), rect, off
 
 
+def pixel_pass(cfg, n, out, *, src, src_off, src_hw, params, rect=None, pparams=None, position=0, out_hw=0):
+    """One direct yunet_aug_pixels call on the current stream."""
+    import yunet_amd._lib as L
+    p = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    a = L.YunetAugPixels(src=p(src), src_off=p(src_off), src_hw=p(src_hw), rect=p(rect), params=p(params),
+                         pparams=p(pparams), position=position, out_hw=out_hw)
+    return L.load().yunet_aug_pixels(C.byref(a), C.byref(cfg), n, C.c_void_p(out.data_ptr()),
+                                     C.c_void_p(torch.cuda.current_stream().cuda_stream))
+
+
 @pytest.mark.parametrize('photo', [None, 'pre', 'post'])
 @pytest.mark.parametrize('window', [False, True])
 def test_canvas_corner_equals_fixed_size_pass_and_border_is_zero(photo, window):
-    """For every image the S_n x S_n corner of yunet_aug_pixels_canvas is bit-identical to the existing fixed-size entry
-    point (plain / window / photo / window+photo) run at out_size = S_n on the SAME params, and every other canvas pixel
-    is exactly 0.0 -- PhotoMetricDistortion in the post position included.  The canvas is pre-filled with NaN."""
+    """For every image the S_n x S_n corner of yunet_aug_pixels at out_hw = Smax (the CANVAS = true instance) is
+    bit-identical to the same entry at out_hw = 0 (the CANVAS = false instance; plain / window / photo / window+photo)
+    run at out_size = S_n on the SAME params, and every other canvas pixel is exactly 0.0 -- PhotoMetricDistortion in
+    the post position included.  The canvas is pre-filled with NaN."""
     import yunet_amd._lib as L
-    lib = L.load()
     lo, hi, seed, it, n = 160, 320, 13, 4, 12
     rng = np.random.default_rng(77)
     srcs = random_sources(rng, n)
@@ -150,29 +160,17 @@ def test_canvas_corner_equals_fixed_size_pass_and_border_is_zero(photo, window):
     sizes = params[:, 7].cpu().numpy()
     assert len(set(sizes.tolist())) >= 3 and set(sizes.tolist()) <= set(pipe.out_sizes)
     smax = int(sizes.max())
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
     canvas = torch.full((n, 3, smax, smax), float('nan'), device=DEV)
     pix, pix_off = (win, off) if window else (sb.src, sb.src_off)
-    L.check(lib.yunet_aug_pixels_canvas(p(pix), p(pix_off), p(rect), p(sb.src_hw), p(params), p(pp),
-                                        pipe.photo_position, C.byref(pipe.cfg), smax, n, p(canvas), stream), 'canvas')
+    form = dict(src=pix, src_off=pix_off, src_hw=sb.src_hw, params=params, rect=rect, pparams=pp,
+                position=pipe.photo_position)
+    L.check(pixel_pass(pipe.cfg, n, canvas, out_hw=smax, **form), 'canvas')
     torch.cuda.synchronize()
     for S in sorted(set(sizes.tolist())):
         cfg = L.YunetAugCfg.from_buffer_copy(pipe.cfg)
         cfg.out_size = int(S)
         fixed = torch.full((n, 3, S, S), float('nan'), device=DEV)
-        if photo is None and not window:
-            rc = lib.yunet_aug_pixels(p(sb.src), p(sb.src_off), p(sb.src_hw), p(params), C.byref(cfg), n, p(fixed), stream)
-        elif photo is None:
-            rc = lib.yunet_aug_pixels_window(p(win), p(off), p(rect), p(sb.src_hw), p(params), C.byref(cfg), n, p(fixed),
-                                             stream)
-        elif not window:
-            rc = lib.yunet_aug_pixels_photo(p(sb.src), p(sb.src_off), p(sb.src_hw), p(params), p(pp), pipe.photo_position,
-                                            C.byref(cfg), n, p(fixed), stream)
-        else:
-            rc = lib.yunet_aug_pixels_window_photo(p(win), p(off), p(rect), p(sb.src_hw), p(params), p(pp),
-                                                   pipe.photo_position, C.byref(cfg), n, p(fixed), stream)
-        L.check(rc, 'fixed-size pass')
+        L.check(pixel_pass(cfg, n, fixed, out_hw=0, **form), 'fixed-size pass')
         torch.cuda.synchronize()
         for i in np.nonzero(sizes == S)[0].tolist():
             a, b = canvas[i, :, :S, :S], fixed[i]
@@ -190,7 +188,6 @@ def test_canvas_entry_cuts_a_mismatched_size_at_the_canvas():
     """params whose S_n exceeds the canvas (a caller's mistake) never write outside it; S_n = 0 (params of the fixed-size
     decide) gives an all-zero image.  A guard band after the canvas stays untouched."""
     import yunet_amd._lib as L
-    lib = L.load()
     rng = np.random.default_rng(3)
     srcs = random_sources(rng, 3)
     sb = source_batch(srcs)
@@ -200,10 +197,8 @@ def test_canvas_entry_cuts_a_mismatched_size_at_the_canvas():
     params[1, 7] = 0
     hw = 160
     buf = torch.full((3 * 3 * hw * hw + 4096,), -7.0, device=DEV)
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-    L.check(lib.yunet_aug_pixels_canvas(p(sb.src), p(sb.src_off), None, p(sb.src_hw), p(params), None, L.PHOTO_NONE,
-                                        C.byref(pipe.cfg), hw, 3, p(buf), stream), 'canvas')
+    L.check(pixel_pass(pipe.cfg, 3, buf, src=sb.src, src_off=sb.src_off, src_hw=sb.src_hw, params=params, out_hw=hw),
+            'canvas')
     torch.cuda.synchronize()
     assert float(buf[3 * 3 * hw * hw:].min()) == -7.0 == float(buf[3 * 3 * hw * hw:].max())
     img = buf[:3 * 3 * hw * hw].view(3, 3, hw, hw)

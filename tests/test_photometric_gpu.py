@@ -163,7 +163,7 @@ def test_gt_and_decisions_identical_absent_pre_post():
 
 
 def test_shipped_list_equals_a_direct_pixel_launch():
-    """Regression guard: without the transform DevicePipeline launches yunet_aug_pixels as before."""
+    """Regression guard: without the transform DevicePipeline launches the plain pass (position = NONE) as before."""
     import yunet_amd._lib as L
     from yunet_amd.pipelines import SourceBatch
     srcs = _random_sources(16, 2)
@@ -172,8 +172,10 @@ def test_shipped_list_equals_a_direct_pixel_launch():
     out = pipe(sb, 4)
     assert pipe.pparams is None
     img = torch.empty_like(out['img'])
-    L.check(L.load().yunet_aug_pixels(_p(sb.src), _p(sb.src_off), _p(sb.src_hw), _p(pipe.params), C.byref(pipe.cfg),
-                                      sb.n, _p(img), C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'pixels')
+    a = L.YunetAugPixels(src=sb.src.data_ptr(), src_off=sb.src_off.data_ptr(), src_hw=sb.src_hw.data_ptr(),
+                         params=pipe.params.data_ptr(), position=L.PHOTO_NONE)
+    L.check(L.load().yunet_aug_pixels(C.byref(a), C.byref(pipe.cfg), sb.n, _p(img),
+                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'pixels')
     torch.cuda.synchronize()
     assert torch.equal(out['img'], img)
 

@@ -227,7 +227,7 @@ def test_wider_result_helpers(tmp_path):
 def test_abi_carries_the_new_entries():
     import yunet_amd._lib as L
     lib = L.load()
-    assert lib.yunet_abi_version() == 11
+    assert lib.yunet_abi_version() == 12
     txt = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'yunet_hip.h')).read(), flags=re.S)
     declared = set(re.findall(r'\b(?:int|size_t)\s+(yunet_\w+)\s*\(', txt))
     for name in ('yunet_test_pixels', 'yunet_rescale_dets'):
