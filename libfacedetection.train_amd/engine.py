@@ -35,6 +35,22 @@ BN_SLOTS = max(1, int(os.environ.get('YUNET_BN_SLOTS', '8')))
 MAX_PLANS = max(2, int(os.environ.get('YUNET_MAX_PLANS', '16')))     # plans kept per engine (see get_plan)
 LOG_HEAD = 8          # floats in front of the flat gradient: cls, bbox, obj, kps, total, 3 spare
 
+# Host-side switches: environment variables YUNET_<NAME>, every one of them listed here and read through
+# read_switch() at the time given -- never at import, so a process can set one and then build an engine or a plan.
+# Set = any non-empty value, except overlap_reduce (on unless '0').
+#   lanes                 plan build    head chains of the coarser levels on executor lanes (also eng.use_lanes)
+#   no_head_group         plan build    share convs of the levels as launches of their own, not as one OP_GROUP
+#   no_pool_fusion        plan build    max_pool2d as kernels of its own, not inside the producing ConvDPUnit
+#   no_upadd_pool_fusion  plan build    a tap's gradient written by the merge backward AND the pool backward
+#   overlap_reduce        engine init   one GPU: reduction of segment A on the side stream (YuNetEngine.backward)
+#   copy_gt               every step    padded GT copied into the plan's buffers instead of read in place (stage_gt)
+PLAN_SWITCHES = ('lanes', 'no_head_group', 'no_pool_fusion', 'no_upadd_pool_fusion')
+
+
+def read_switch(name):
+    v = os.environ.get('YUNET_' + name.upper())
+    return v != '0' if name == 'overlap_reduce' else bool(v)
+
 
 # ============================================================================ parameters
 class ParamLayout:
@@ -271,11 +287,12 @@ _NULL_BN = L.YunetBN(None, None, None, None, 1, BN_EPS)
 
 
 class Plan:
-    """Buffers + op lists for one (N, H, W, Gmax) shape."""
+    """Buffers + op lists for one (N, H, W, Gmax) shape, built in the phases __init__ lists (each phase's docstring: what
+    it needs from the earlier ones, what it leaves on `self`)."""
 
     def __init__(self, eng, n, h, w, gmax):
         self.eng, self.n, self.h, self.w, self.gmax = eng, n, h, w, gmax
-        arch, lay, fp, dev = eng.arch, eng.layout, eng.params, eng.device
+        self.sw = {name: read_switch(name) for name in PLAN_SWITCHES}      # the environment as it is NOW
         # activation storage of this plan: fp32, or bf16 ("bf16 fwd / fp32 grads", BASELINE configs[2]):
         # every tensor a forward kernel writes except the head output; gradients stay fp32
         self.act_dtype = torch.bfloat16 if eng.precision == 'bf16' else torch.float32
@@ -288,49 +305,88 @@ class Plan:
         self._lane = 0          # executor lane of the ops being appended (0 = the caller's stream)
         self._join_before = None
         self.tensors = {}       # unit name -> (input _T, output _T): introspection / debugging
-        f32 = dict(device=dev, dtype=torch.float32)
+        self.bn_count = {}      # BN name -> elements per channel: filled as the forward is emitted (_bn_struct), read after
+        self.img_ptr_ops = []   # (list, index) of the ops that take the image pointer (set_img)
+        self._f32 = dict(device=eng.device, dtype=torch.float32)
+        self._alloc_bn_stats()
+        self._alloc_head_outputs()
+        self._emit_neck_and_heads(self._emit_conv_stack())
+        self._alloc_loss_buffers()
+        self._emit_loss_step()
+        kernels_bwd, marks = self._emit_backward()
+        self.c_fwd_a = self._carray(self.fwd_a)
+        self.c_fwd_b = self._carray(self.fwd_b)
+        self.c_bwd = self._carray(self.bwd)
+        self._build_deferred()
+        self._split_backward(kernels_bwd, marks)
+        self._build_eval()
 
-        # ---- BN statistic buffers: one fp64 block, zeroed by a single memset per step
-        # (every layer's sums are BN_SLOTS replicas [BN_SLOTS, 2c]: YunetBN::slots)
+    # ------------------------------------------------------------------ phases
+    def _bn_layers(self):
+        """The one walk over the BatchNorm layers -> (name, c, offset in doubles of the [BN_SLOTS, 2c] block in the forward
+        half of `stats`, offsets of gamma / beta in the flat parameters, elements per channel | None before its producer)."""
+        lay = self.eng.layout
+        so = 0
+        for name, c in zip(lay.bn_names, self.eng.params.bn_channels):
+            yield name, c, so, lay.entries[name + '.weight'][0], lay.entries[name + '.bias'][0], self.bn_count.get(name)
+            so += 2 * c * BN_SLOTS
+
+    def _bn_table(self, backward, pick=None):
+        """Device table of the bn_batch kernel over the forward | backward sum blocks of the layers with pick(g_off)."""
+        base = self.stats.numel() // 2 if backward else 0
+        bn_offset = self.eng.params.bn_offset
+        rows = [[base + so, c, cnt, bn_offset[name], g_off, b_off, BN_SLOTS]
+                for name, c, so, g_off, b_off, cnt in self._bn_layers() if pick is None or pick(g_off)]
+        return torch.tensor(rows, dtype=torch.int32).to(self.eng.device)
+
+    def _bn_batch_op(self, table, mode, momentum=0.0):
+        """One launch over the layers of `table`: mode 0 updates the running statistics, 1 writes d(gamma) / d(beta)
+        into the flat gradient, 2 fills the sums from the running statistics (eval)."""
+        fp = self.eng.params
+        ptrs = [None, None, fp.grad.data_ptr()] if mode == 1 else [fp.running_mean.data_ptr(), fp.running_var.data_ptr(), None]
+        return self._op(L.OP_BN_BATCH, p=[table.data_ptr(), self.stats.data_ptr()] + ptrs, i=[table.shape[0], mode],
+                        f=[momentum])
+
+    def _alloc_bn_stats(self):
+        """Leaves `stats`, `bn` and the memset that opens fwd_a.
+        BN statistic buffers: one fp64 block, zeroed by a single memset per step
+        (every layer's sums are BN_SLOTS replicas [BN_SLOTS, 2c]: YunetBN::slots)"""
+        fp = self.eng.params
         tot_c = sum(fp.bn_channels) * BN_SLOTS
-        self.stats = torch.zeros(4 * tot_c, device=dev, dtype=torch.float64)
+        self.stats = torch.zeros(4 * tot_c, device=self.eng.device, dtype=torch.float64)
         self.bn = {}
-        o = 0
-        for name, c in zip(lay.bn_names, fp.bn_channels):
-            g_off = lay.entries[name + '.weight'][0]
-            b_off = lay.entries[name + '.bias'][0]
+        for name, c, o, g_off, b_off, _ in self._bn_layers():
             c2 = 2 * c * BN_SLOTS
             self.bn[name] = dict(c=c, stats=self.stats[o:o + c2].view(BN_SLOTS, 2 * c),
                                  bstats=self.stats[2 * tot_c + o:2 * tot_c + o + c2].view(BN_SLOTS, 2 * c),
-                                 gamma=fp.data.data_ptr() + 4 * g_off,
-                                 beta=fp.data.data_ptr() + 4 * b_off,
-                                 dgamma=fp.grad.data_ptr() + 4 * g_off,
-                                 dbeta=fp.grad.data_ptr() + 4 * b_off)
-            o += c2
-        self.ops_memset_stats = self._op(L.OP_MEMSET, p=[self.stats.data_ptr()],
-                                         i=self._split64(self.stats.numel() * 8))
+                                 gamma=fp.data.data_ptr() + 4 * g_off, beta=fp.data.data_ptr() + 4 * b_off,
+                                 dgamma=fp.grad.data_ptr() + 4 * g_off, dbeta=fp.grad.data_ptr() + 4 * b_off)
+        self.ops_memset_stats = self._op(L.OP_MEMSET, p=[self.stats.data_ptr()], i=self._split64(self.stats.numel() * 8))
         self.fwd_a.append(self.ops_memset_stats)
 
-        # ---- loss-step geometry
-        strides = arch['strides']
-        self.sizes = [(h // s, w // s) for s in strides]
+    def _alloc_head_outputs(self):
+        """Loss-step geometry (`sizes`, `P`, `levels`, `level_base`) and the [N,P,16] buffers the heads write and
+        the loss differentiates (`flat`, `dflat`, towers: `flat_c` and the masked dy_scale vectors)."""
+        n, strides = self.n, self.eng.arch['strides']
+        self.sizes = [(self.h // s, self.w // s) for s in strides]
         self.P = sum(a * b for a, b in self.sizes)
         self.levels = K.make_levels(self.sizes, strides)
-        self.flat = torch.empty(n, self.P, 16, **f32)
-        self.dflat = torch.empty(n, self.P, 16, **f32)
+        self.level_base = [sum(a * b for a, b in self.sizes[:l]) for l in range(len(self.sizes))]   # first row of a level in [P]
+        self.flat = torch.empty(n, self.P, 16, **self._f32)
+        self.dflat = torch.empty(n, self.P, 16, **self._f32)
         # towers (stacked_convs > 0): the cls tower's head unit writes its own [N,P,16] (zeros outside the cls channel)
-        self.towers = lay.towers
-        self.flat_c = torch.empty(n, self.P, 16, **f32) if self.towers else None
+        self.towers = self.eng.layout.towers
+        self.flat_c = torch.empty(n, self.P, 16, **self._f32) if self.towers else None
         # ... and each tower's unit takes dy_scale masked to its own channels (engine.backward refreshes them)
-        self.mask_cls = torch.tensor([1.0] + [0.0] * 15, **f32)
+        self.mask_cls = torch.tensor([1.0] + [0.0] * 15, **self._f32)
         self.dy_scale_cls = self.mask_cls.clone()
         self.dy_scale_reg = 1.0 - self.mask_cls
 
-        # ---- conv stack
-        self.img_ptr_ops = []
+    def _emit_conv_stack(self):
+        """Stem, backbone stages and pools into fwd_a / bwd_nodes; returns the pyramid taps, finest first."""
+        arch, n, h, w = self.eng.arch, self.n, self.h, self.w
         st = arch['stage_channels']
-        cmid = st[0][1]
-        z0 = self._new_t(n, h // 2, w // 2, cmid, bn_name='backbone.model0.bn1')
+        z0 = self._new_t(n, h // 2, w // 2, st[0][1], bn_name='backbone.model0.bn1')
         self._stem(z0)
         cur = self._dp(z0, 'backbone.model0.conv2')
         taps = []
@@ -343,6 +399,12 @@ class Plan:
             if i in arch['downsample_idx']:
                 # the pool is the stage output's only consumer unless the stage is also tapped by the neck
                 cur = self._pool(cur, sole_consumer=i not in arch['out_idx'])
+        return taps
+
+    def _emit_neck_and_heads(self, taps):
+        """Lateral convs, top-down merges and head chains of `taps` (per level inside the top-down loop | all levels
+        after it, share convs grouped), the JOIN of the lanes, the towers' add.  Leaves `lanes_ok`, `lanes_used`."""
+        arch = self.eng.arch
         # The head chain of a pyramid level (share convs -> fused head) depends on that level's lateral conv only,
         # and the levels are mutually independent (yunet_head.py:175-247 loops over them): the chains of the coarser
         # levels CAN run on executor lanes (side streams) next to the rest of the top-down pathway; level 0 stays on
@@ -352,84 +414,82 @@ class Plan:
         # 149 KB of LDS admits one workgroup per CU, so concurrent launches queue instead of sharing CUs.
         feats = list(taps)
         level_of = {i: l for l, i in enumerate(arch['neck_out_idx'])}
-        bases, b0 = [], 0
-        for hh, ww in self.sizes:
-            bases.append(b0)
-            b0 += hh * ww
-        lanes_ok = (bool(os.environ.get('YUNET_LANES')) or bool(getattr(eng, 'use_lanes', False))) and not self.towers
+        self.lanes_ok = (self.sw['lanes'] or bool(getattr(self.eng, 'use_lanes', False))) and not self.towers
         self.lanes_used = 0
-
-        def head_chain(i):
-            l = level_of.get(i)
-            if l is None:
-                return
-            f = feats[i]
-            assert (f.h, f.w) == self.sizes[l], 'feature sizes vs strides'
-            lane = l if (lanes_ok and 0 < l <= L.MAX_LANES) else 0
-            if lane:
-                self.fwd_a.append(self._op(L.OP_FORK, i=[1 << lane]))
-                self.lanes_used |= 1 << lane
-                f.head_lane = lane
-            self._lane = lane
-            for j in range(arch['shared_stacked_convs']):
-                f = self._dp(f, f'bbox_head.multi_level_share_convs.{l}.{j}')
-            if self.towers:
-                # yunet_head.py:191-207: two towers on the same feature; cls from one, bbox / obj / kps from the other
-                fc_, fr_ = f, f
-                for j in range(arch['stacked_convs']):
-                    fc_ = self._dp(fc_, f'bbox_head.multi_level_cls_convs.{l}.{j}')
-                for j in range(arch['stacked_convs']):
-                    fr_ = self._dp(fr_, f'bbox_head.multi_level_reg_convs.{l}.{j}')
-                self._head(fr_, l, bases[l])
-                self._head(fc_, l, bases[l], cls_tower=True)
-            else:
-                self._head(f, l, bases[l])
-            self._lane = 0
         # Round 5: the head chains wait until the whole top-down pathway is built, and the share convs of the levels --
         # mutually independent plain 64 -> 64 units -- are emitted next to each other as ONE group
         # (YunetOp.i[OP_GROUP]): the executor launches them as one grid (yunet_dp_fwd_group).  On the 20 x 20 / 10 x 10
         # levels a launch of their own is a prologue, one or two bands per wave and a drain (27 / 13 us for 13 + 3 MB).
         # Needs no lanes (one stream); the tower head (stacked_convs > 0) keeps the per-level order.
-        grouped = (not lanes_ok and not self.towers and not os.environ.get('YUNET_NO_HEAD_GROUP')
+        grouped = (not self.lanes_ok and not self.towers and not self.sw['no_head_group']
                    and arch['shared_stacked_convs'] >= 1)
+
+        def heads(idxs):
+            self._emit_heads([(level_of[i], feats[i]) for i in idxs if i in level_of], grouped)
         for i in range(len(feats) - 1, 0, -1):
             feats[i] = self._dp(feats[i], f'neck.lateral_convs.{i}')
             if not grouped:
-                head_chain(i)
+                heads([i])
             # the backward of this merge ACCUMULATES into feats[i]'s gradient after the level's head chain (on its
             # lane) has written it: the executor joins that lane first
             self._join_before = getattr(feats[i], 'head_lane', None)
             feats[i - 1] = self._upadd(feats[i - 1], feats[i])
             self._join_before = None
         feats[0] = self._dp(feats[0], 'neck.lateral_convs.0')
-        if not grouped:
-            head_chain(0)
-        else:
-            order = [i for i in range(len(feats)) if level_of.get(i) is not None]        # finest (largest) map first
-            cur = {}
-            for i in order:
-                assert (feats[i].h, feats[i].w) == self.sizes[level_of[i]], 'feature sizes vs strides'
-                cur[i] = feats[i]
-            for j in range(arch['shared_stacked_convs']):
-                for s0 in range(0, len(order), L.DP_GROUP_MAX):
-                    part = order[s0:s0 + L.DP_GROUP_MAX]
-                    first = len(self.fwd_a)
-                    for i in part:
-                        cur[i] = self._dp(cur[i], f'bbox_head.multi_level_share_convs.{level_of[i]}.{j}')
-                    if len(part) >= 2:
-                        assert len(self.fwd_a) == first + len(part)
-                        self.fwd_a[first].i[L.OP_GROUP] = len(part)
-            for i in order:
-                self._head(cur[i], level_of[i], bases[level_of[i]])
+        heads(range(len(feats)) if grouped else [0])                # grouped: finest (largest) map first
         if self.lanes_used:
             self.fwd_a.append(self._op(L.OP_JOIN, i=[self.lanes_used]))
         if self.towers:      # flat = (reg tower's bbox | obj | kps channels) + (cls tower's cls channel): exact zeros elsewhere
-            nel = n * self.P * 16
+            # _split64 masks the high word with 0x7fffffff where this op's hand-written split did not: the two agree
+            # for every element count below 2^63
             self.fwd_a.append(self._op(L.OP_ADD, p=[self.flat.data_ptr(), self.flat_c.data_ptr(), self.flat.data_ptr()],
-                                       i=[nel & 0xffffffff if (nel & 0xffffffff) < 2 ** 31 else (nel & 0xffffffff) - 2 ** 32,
-                                          nel >> 32]))
+                                       i=self._split64(self.n * self.P * 16)))
 
-        # ---- loss step
+    def _emit_heads(self, chains, grouped):
+        """chains = [(level, lateral output)]: their share convs -- round by round, as OP_GROUP runs of at most
+        DP_GROUP_MAX when `grouped` -- then their tower convs and fused heads.  A level with a lane (lanes_ok; never
+        with `grouped`) is forked first: `lanes_used` / the feature's `head_lane` tell the merges and the backward walk."""
+        arch = self.eng.arch
+        cur, lane_of = {}, {}
+        for l, f in chains:
+            assert (f.h, f.w) == self.sizes[l], 'feature sizes vs strides'
+            cur[l], lane_of[l] = f, l if (self.lanes_ok and 0 < l <= L.MAX_LANES) else 0
+            if lane_of[l]:
+                self.fwd_a.append(self._op(L.OP_FORK, i=[1 << l]))
+                self.lanes_used |= 1 << l
+                f.head_lane = l
+
+        def dp(x, l, kind, j):
+            self._lane = lane_of[l]
+            return self._dp(x, f'bbox_head.multi_level_{kind}_convs.{l}.{j}')
+        run = L.DP_GROUP_MAX if grouped else 1
+        for j in range(arch['shared_stacked_convs']):
+            for s0 in range(0, len(chains), run):
+                part = [l for l, _ in chains[s0:s0 + run]]
+                first = len(self.fwd_a)
+                for l in part:
+                    cur[l] = dp(cur[l], l, 'share', j)
+                if len(part) >= 2:
+                    assert len(self.fwd_a) == first + len(part)
+                    self.fwd_a[first].i[L.OP_GROUP] = len(part)
+        for l, _ in chains:
+            self._lane = lane_of[l]
+            if self.towers:
+                # yunet_head.py:191-207: two towers on the same feature; cls from one, bbox / obj / kps from the other
+                fc_, fr_ = cur[l], cur[l]
+                for j in range(arch['stacked_convs']):
+                    fc_ = dp(fc_, l, 'cls', j)
+                for j in range(arch['stacked_convs']):
+                    fr_ = dp(fr_, l, 'reg', j)
+                self._head(fr_, l, self.level_base[l])
+                self._head(fc_, l, self.level_base[l], cls_tower=True)
+            else:
+                self._head(cur[l], l, self.level_base[l])
+        self._lane = 0
+
+    def _alloc_loss_buffers(self):
+        """GT staging buffers (`gt_*`), the assignment's and the loss's outputs and work arrays, the dy_scale vectors."""
+        n, gmax, dev, f32 = self.n, self.gmax, self.eng.device, self._f32
         self.gt_boxes = torch.zeros(n, gmax, 4, **f32)
         self.gt_kps = torch.zeros(n, gmax, 5, 3, **f32)
         self.gt_count = torch.zeros(n, device=dev, dtype=torch.int32)
@@ -439,66 +499,53 @@ class Plan:
         self.scratch = torch.empty(n, self.P, 12, **f32)     # yunet_assign work arrays
         self.norm = torch.zeros(4, **f32)
         self.losses = torch.zeros(8, **f32)        # cls, bbox, obj, kps, total (3 spare)
-        lib = L.load()
-        self.loss_blocks = lib.yunet_loss_blocks(n, self.P)
+        self.loss_blocks = L.load().yunet_loss_blocks(n, self.P)
         self.loss_partials = torch.empty(self.loss_blocks, 4, **f32)
         self.dy_scale = torch.ones(16, **f32)
         self.dy_norm = torch.ones(16, **f32)      # deferred normaliser: per-channel 1 / num_total (loss_finalize_ex)
         self.dy_up = torch.ones(16, **f32)        # deferred mode: the upstream loss scales; dy_scale = dy_up * dy_norm
         self.deferred = False
+
+    def _emit_loss_step(self):
+        """Assignment + loss_norm close fwd_a; fwd_b = loss, loss_finalize and the BN running-stat update.  Leaves
+        `assign_idx`, `bn_table_f`, `bn_table_b` (the conv stack and heads are complete: every BN count is known)."""
+        arch, n, gmax = self.eng.arch, self.n, self.gmax
         op = self._op(L.OP_ASSIGN,
-                      p=[self.flat.data_ptr(), self.gt_boxes.data_ptr(), self.gt_kps.data_ptr(),
-                         None, self.gt_count.data_ptr(), self.gt_inds.data_ptr(), None,
-                         self.max_overlaps.data_ptr(), self.img_stats.data_ptr(),
+                      p=[self.flat.data_ptr(), self.gt_boxes.data_ptr(), self.gt_kps.data_ptr(), None, self.gt_count.data_ptr(),
+                         self.gt_inds.data_ptr(), None, self.max_overlaps.data_ptr(), self.img_stats.data_ptr(),
                          self.scratch.data_ptr()],
                       i=[n, self.P, gmax, int(arch.get('candidate_topk', 10))],
                       f=[arch['center_radius'], float(arch.get('iou_weight', 3.0)), float(arch.get('cls_weight', 1.0))])
         op.lv = self.levels
         self.assign_idx = len(self.fwd_a)
         self.fwd_a.append(op)
-        self.fwd_a.append(self._op(L.OP_LOSS_NORM, p=[self.img_stats.data_ptr(),
-                                                     self.norm.data_ptr()],
-                                   i=[n], f=[1.0 / eng.world_size]))
+        self.fwd_a.append(self._op(L.OP_LOSS_NORM, p=[self.img_stats.data_ptr(), self.norm.data_ptr()],
+                                   i=[n], f=[1.0 / self.eng.world_size]))
         op = self._op(L.OP_LOSS,
-                      p=[self.flat.data_ptr(), self.gt_inds.data_ptr(),
-                         self.max_overlaps.data_ptr(), self.gt_boxes.data_ptr(),
-                         self.gt_kps.data_ptr(), self.norm.data_ptr(), self.dflat.data_ptr(),
-                         self.loss_partials.data_ptr()],
+                      p=[self.flat.data_ptr(), self.gt_inds.data_ptr(), self.max_overlaps.data_ptr(), self.gt_boxes.data_ptr(),
+                         self.gt_kps.data_ptr(), self.norm.data_ptr(), self.dflat.data_ptr(), self.loss_partials.data_ptr()],
                       i=[n, self.P, gmax, self.loss_blocks])
         op.lv = self.levels
-        op.loss = K.make_loss_cfg(arch['loss_bbox'], arch['loss_cls_weight'],
-                                  arch['loss_bbox_weight'], arch['loss_obj_weight'],
+        op.loss = K.make_loss_cfg(arch['loss_bbox'], arch['loss_cls_weight'], arch['loss_bbox_weight'], arch['loss_obj_weight'],
                                   arch['loss_kps_weight'], float(arch.get('loss_bbox_eps', 1e-6)),
-                                  float(arch.get('loss_bbox_smooth_point', 0.1)), arch['kps_beta'],
-                                  arch.get('loss_bbox_mode'))
+                                  float(arch.get('loss_bbox_smooth_point', 0.1)), arch['kps_beta'], arch.get('loss_bbox_mode'))
         self.fwd_b.append(op)
-        self.fwd_b.append(self._op(L.OP_LOSS_FINALIZE, p=[self.loss_partials.data_ptr(),
-                                                         self.losses.data_ptr(),
-                                                         fp.log_head.data_ptr()],
-                                   i=[self.loss_blocks]))
+        self.fwd_b.append(self._op(L.OP_LOSS_FINALIZE, p=[self.loss_partials.data_ptr(), self.losses.data_ptr(),
+                                                         self.eng.params.log_head.data_ptr()], i=[self.loss_blocks]))
         # BN running statistics (nn.BatchNorm2d momentum 0.1) and, in backward, d(gamma)/d(beta)
         # of ALL BatchNorm layers: one launch each, driven by a small device table
-        rows_f, rows_b = [], []
-        so = 0
-        for name, c in zip(lay.bn_names, fp.bn_channels):
-            cnt = self.bn_count[name]
-            g_off = lay.entries[name + '.weight'][0]
-            b_off = lay.entries[name + '.bias'][0]
-            rows_f.append([so, c, cnt, fp.bn_offset[name], g_off, b_off, BN_SLOTS])
-            rows_b.append([2 * tot_c + so, c, cnt, fp.bn_offset[name], g_off, b_off, BN_SLOTS])
-            so += 2 * c * BN_SLOTS
-        self.bn_table_f = torch.tensor(rows_f, dtype=torch.int32).to(dev)
-        self.bn_table_b = torch.tensor(rows_b, dtype=torch.int32).to(dev)
-        self.fwd_b.append(self._op(
-            L.OP_BN_BATCH, p=[self.bn_table_f.data_ptr(), self.stats.data_ptr(),
-                              fp.running_mean.data_ptr(), fp.running_var.data_ptr(), None],
-            i=[len(rows_f), 0], f=[BN_MOMENTUM]))
+        self.bn_table_f = self._bn_table(backward=False)
+        self.bn_table_b = self._bn_table(backward=True)
+        self.fwd_b.append(self._bn_batch_op(self.bn_table_f, 0, BN_MOMENTUM))
 
-        # ---- backward: reverse of the forward nodes; the head chains of the lanes first (their gradients exist
-        # from the start), each on its lane, then the caller's stream walks the rest and joins a lane right before
-        # the first op that accumulates into a gradient that lane wrote
+    def _emit_backward(self):
+        """bwd_nodes -> `bwd`, `reduce_jobs`, `reduce_table`.  Returns (the kernel ops alone, marks) for _split_backward;
+        marks = after each backward node: (#ops, #reduce jobs).
+        Reverse of the forward nodes; the head chains of the lanes first (their gradients exist from the start),
+        each on its lane, then the caller's stream walks the rest and joins a lane right before the first op that
+        accumulates into a gradient that lane wrote"""
         self.reduce_jobs = []   # (partials ptr, grad ptr, rows, width, accumulate) of every unit
-        marks = []              # after each backward node: (#ops, #reduce jobs)
+        marks = []
         if self.lanes_used:
             self.bwd.append(self._op(L.OP_FORK, i=[self.lanes_used]))
         joined = 0
@@ -515,24 +562,20 @@ class Plan:
             self.bwd.append(self._op(L.OP_JOIN, i=[self.lanes_used & ~joined]))
         kernels_bwd = list(self.bwd)
         # all weight-gradient partial reductions in ONE launch (table lives on the device)
-        self.reduce_table, chunk = K.reduce_job_table(self.reduce_jobs, dev)
-        self.bwd.append(self._op(L.OP_REDUCE_BATCH, p=[self.reduce_table.data_ptr()],
-                                 i=[len(self.reduce_jobs), chunk]))
-        self.bwd.append(self._op(
-            L.OP_BN_BATCH, p=[self.bn_table_b.data_ptr(), self.stats.data_ptr(), None, None,
-                              fp.grad.data_ptr()], i=[len(rows_b), 1], f=[0.0]))
-        self.c_fwd_a = self._carray(self.fwd_a)
-        self.c_fwd_b = self._carray(self.fwd_b)
-        self.c_bwd = self._carray(self.bwd)
-        # N > 1: the same two phases with the num_pos normaliser DEFERRED -- the loss kernel leaves the cls / bbox /
-        # obj terms un-normalised and does not read norm[0], so its all-reduce runs on the side stream BESIDE the
-        # loss kernel; loss_finalize applies 1 / max(num_total, 1) to the logged losses and writes the per-channel
-        # factor the fused head units take as dy_scale (engine.forward / backward).  x 1.0 is exact: the gradients
-        # are bit-identical to the undeferred form.
+        self.reduce_table, chunk = K.reduce_job_table(self.reduce_jobs, self.eng.device)
+        self.bwd.append(self._op(L.OP_REDUCE_BATCH, p=[self.reduce_table.data_ptr()], i=[len(self.reduce_jobs), chunk]))
+        self.bwd.append(self._bn_batch_op(self.bn_table_b, 1))
+        return kernels_bwd, marks
+
+    def _build_deferred(self):
+        """`c_fwd_b_loss` / `c_fwd_b_rest` from fwd_b, and the GT binding state (`own_gt`, `_gt_bound`).
+        N > 1: the same two phases with the num_pos normaliser DEFERRED -- the loss kernel leaves the cls / bbox /
+        obj terms un-normalised and does not read norm[0], so its all-reduce runs on the side stream BESIDE the
+        loss kernel; loss_finalize applies 1 / max(num_total, 1) to the logged losses and writes the per-channel
+        factor the fused head units take as dy_scale (engine.forward / backward).  x 1.0 is exact: the gradients
+        are bit-identical to the undeferred form."""
         assert self.fwd_b[0].opcode == L.OP_LOSS and self.fwd_b[1].opcode == L.OP_LOSS_FINALIZE
-        loss_def, fin_def = L.YunetOp(), L.YunetOp()
-        C.memmove(C.byref(loss_def), C.byref(self.fwd_b[0]), C.sizeof(L.YunetOp))
-        C.memmove(C.byref(fin_def), C.byref(self.fwd_b[1]), C.sizeof(L.YunetOp))
+        loss_def, fin_def = self._clone_op(self.fwd_b[0]), self._clone_op(self.fwd_b[1])
         loss_def.loss.defer_num_total = 1
         fin_def.p[3] = self.norm.data_ptr()
         fin_def.p[4] = self.dy_norm.data_ptr()
@@ -541,58 +584,56 @@ class Plan:
         self.own_gt = (self.gt_boxes, self.gt_kps, self.gt_count)     # the plan's own staging buffers (bind_gt)
         self._gt_bound = tuple(t.data_ptr() for t in self.own_gt)
 
-        # ---- world > 1: the same backward in TWO segments so that the gradient all-reduce of the
-        # first bucket (head, neck and the backbone stages from the first pyramid tap on: the tail
-        # of the flat buffer, ~85 % of the parameters) runs on a side stream underneath the backward
-        # kernels of the early, high-resolution stages (stem .. model2: most of the backward time).
-        # The reference gets this overlap from the DDP reducer (mmdet/apis/train.py:156-161).
-        # A unit's weight-gradient partials and the d(gamma)/d(beta) of its BatchNorm are final once
-        # its own backward kernel has run (the BN sums come from its consumers, which ran earlier).
+    def _split_backward(self, kernels_bwd, marks):
+        """Leaves `split_off` (None = no split), else also `split_ops`, `bwd_a` / `bwd_b`, `bn_table_ba` / `bn_table_bb`, `c_*`.
+        world > 1: the same backward in TWO segments so that the gradient all-reduce of the
+        first bucket (head, neck and the backbone stages from the first pyramid tap on: the tail
+        of the flat buffer, ~85 % of the parameters) runs on a side stream underneath the backward
+        kernels of the early, high-resolution stages (stem .. model2: most of the backward time).
+        The reference gets this overlap from the DDP reducer (mmdet/apis/train.py:156-161).
+        A unit's weight-gradient partials and the d(gamma)/d(beta) of its BatchNorm are final once
+        its own backward kernel has run (the BN sums come from its consumers, which ran earlier)."""
+        lay, dev = self.eng.layout, self.eng.device
         self.split_off = None
-        split_unit = f"backbone.model{min(arch['out_idx'])}.conv1"
-        if split_unit in lay.units and lay.units[split_unit]['off'] > 0:
-            split_off = lay.units[split_unit]['off']
-            gbase = fp.grad.data_ptr()
-            done = [j for j in self.reduce_jobs if j[1] - gbase >= 4 * split_off]
-            # the jobs of bucket A must be a prefix of the execution order
-            n_a = len(done)
-            if n_a and all(j[1] - gbase >= 4 * split_off for j in self.reduce_jobs[:n_a]):
-                ops_a = max(m[0] for m in marks if m[1] <= n_a)
-                tab_a, chunk_a = K.reduce_job_table(self.reduce_jobs[:n_a], dev)
-                tab_b, chunk_b = K.reduce_job_table(self.reduce_jobs[n_a:], dev)
-                rb_a = [r for r in rows_b if r[4] >= split_off]
-                rb_b = [r for r in rows_b if r[4] < split_off]
-                self.bn_table_ba = torch.tensor(rb_a, dtype=torch.int32).to(dev)
-                self.bn_table_bb = torch.tensor(rb_b, dtype=torch.int32).to(dev)
-                self.keep += [tab_a, tab_b]
+        split_unit = f"backbone.model{min(self.eng.arch['out_idx'])}.conv1"
+        if split_unit not in lay.units or lay.units[split_unit]['off'] <= 0:
+            return
+        split_off = lay.units[split_unit]['off']
+        gbase = self.eng.params.grad.data_ptr()
+        n_a = len([j for j in self.reduce_jobs if j[1] - gbase >= 4 * split_off])
+        # the jobs of bucket A must be a prefix of the execution order
+        if not n_a or not all(j[1] - gbase >= 4 * split_off for j in self.reduce_jobs[:n_a]):
+            return
+        ops_a = max(m[0] for m in marks if m[1] <= n_a)
+        tab_a, chunk_a = K.reduce_job_table(self.reduce_jobs[:n_a], dev)
+        tab_b, chunk_b = K.reduce_job_table(self.reduce_jobs[n_a:], dev)
+        self.bn_table_ba = self._bn_table(backward=True, pick=lambda g_off: g_off >= split_off)
+        self.bn_table_bb = self._bn_table(backward=True, pick=lambda g_off: g_off < split_off)
+        self.keep += [tab_a, tab_b]
 
-                def tail_ops(tab, nj, ch, bnt, nb):
-                    return [self._op(L.OP_REDUCE_BATCH, p=[tab.data_ptr()], i=[nj, ch]),
-                            self._op(L.OP_BN_BATCH, p=[bnt.data_ptr(), self.stats.data_ptr(), None, None,
-                                                       fp.grad.data_ptr()], i=[nb, 1], f=[0.0])]
-                self.bwd_a = kernels_bwd[:ops_a] + tail_ops(tab_a, n_a, chunk_a, self.bn_table_ba, len(rb_a))
-                self.bwd_b = kernels_bwd[ops_a:] + tail_ops(tab_b, len(self.reduce_jobs) - n_a, chunk_b,
-                                                            self.bn_table_bb, len(rb_b))
-                self.c_bwd_a = self._carray(self.bwd_a)
-                self.c_bwd_b = self._carray(self.bwd_b)
-                # one GPU: segment A's kernels alone + its reduction as a list of its own, which then runs on the side
-                # stream under the kernels of segment B (engine.backward)
-                self.c_bwd_a_k = self._carray(self.bwd_a[:ops_a])
-                self.c_tail_a = self._carray(self.bwd_a[ops_a:])
-                self.split_off, self.split_ops = split_off, ops_a
+        def tail_ops(tab, nj, ch, bnt):
+            return [self._op(L.OP_REDUCE_BATCH, p=[tab.data_ptr()], i=[nj, ch]), self._bn_batch_op(bnt, 1)]
+        self.bwd_a = kernels_bwd[:ops_a] + tail_ops(tab_a, n_a, chunk_a, self.bn_table_ba)
+        self.bwd_b = kernels_bwd[ops_a:] + tail_ops(tab_b, len(self.reduce_jobs) - n_a, chunk_b, self.bn_table_bb)
+        self.c_bwd_a = self._carray(self.bwd_a)
+        self.c_bwd_b = self._carray(self.bwd_b)
+        # one GPU: segment A's kernels alone + its reduction as a list of its own, which then runs on the side
+        # stream under the kernels of segment B (engine.backward)
+        self.c_bwd_a_k = self._carray(self.bwd_a[:ops_a])
+        self.c_tail_a = self._carray(self.bwd_a[ops_a:])
+        self.split_off, self.split_ops = split_off, ops_a
 
-        # ---- eval(): the same conv-stack launches with BatchNorm on the running statistics
-        # (op 0 fills the sums from running_mean / running_var instead of zeroing them; producers
-        # do not accumulate: ConvDPUnits get out_has_bn = 0, the stem sums into a scratch block)
-        self.eval_scratch = torch.zeros(64, device=dev, dtype=torch.float64)
-        self.fwd_eval = [self._op(L.OP_BN_BATCH, p=[self.bn_table_f.data_ptr(), self.stats.data_ptr(),
-                                                    fp.running_mean.data_ptr(), fp.running_var.data_ptr(), None],
-                                  i=[len(rows_f), 2], f=[0.0])]
+    def _build_eval(self):
+        """`fwd_eval` / `c_fwd_eval` from fwd_a and `bn_table_f`, and `eval_scratch`.
+        eval(): the same conv-stack launches with BatchNorm on the running statistics
+        (op 0 fills the sums from running_mean / running_var instead of zeroing them; producers
+        do not accumulate: ConvDPUnits get out_has_bn = 0, the stem sums into a scratch block)"""
+        self.eval_scratch = torch.zeros(64, device=self.eng.device, dtype=torch.float64)
+        self.fwd_eval = [self._bn_batch_op(self.bn_table_f, 2)]
         for op in self.fwd_a[1:]:
             if op.opcode in (L.OP_ASSIGN, L.OP_LOSS_NORM):
                 continue          # test time: no SimOTA on stale GT, gt_inds / norm stay untouched
-            cp = L.YunetOp()
-            C.memmove(C.byref(cp), C.byref(op), C.sizeof(L.YunetOp))
+            cp = self._clone_op(op)
             if cp.opcode == L.OP_DP_FWD:
                 cp.dp.out_has_bn = 0
             elif cp.opcode == L.OP_STEM_FWD:
@@ -601,7 +642,11 @@ class Plan:
         self.c_fwd_eval = self._carray(self.fwd_eval)
 
     # ------------------------------------------------------------------ helpers
-    bn_count = None
+    @staticmethod
+    def _clone_op(op):
+        cp = L.YunetOp()
+        C.memmove(C.byref(cp), C.byref(op), C.sizeof(L.YunetOp))
+        return cp
 
     @staticmethod
     def _split64(v):
@@ -622,14 +667,9 @@ class Plan:
         return op
 
     def _carray(self, ops):
-        arr = (L.YunetOp * len(ops))()
-        for k, op in enumerate(ops):
-            C.memmove(C.byref(arr, k * C.sizeof(L.YunetOp)), C.byref(op), C.sizeof(L.YunetOp))
-        return arr
+        return (L.YunetOp * len(ops))(*ops)          # copies every record
 
     def _bn_struct(self, name, count):
-        if self.bn_count is None:
-            self.bn_count = {}
         self.bn_count[name] = count
         b = self.bn[name]
         return L.YunetBN(b['stats'].data_ptr(), b['bstats'].data_ptr(), b['gamma'], b['beta'],
@@ -637,8 +677,7 @@ class Plan:
 
     def _new_t(self, n, h, w, c, bn_name=None):
         buf = torch.empty(n, h, w, c, device=self.eng.device, dtype=self.act_dtype)
-        t = _T(buf, n, h, w, c, bn=bn_name)
-        return t
+        return _T(buf, n, h, w, c, bn=bn_name)
 
     def _grad_of(self, t):
         """(grad buffer, accumulate flag) for a consumer's backward; first writer overwrites."""
@@ -761,7 +800,7 @@ class Plan:
         # pool's consumer reads them through the ordinary BN+ReLU input transform of x's BatchNorm, and the
         # producer's backward expands the pooled gradient on load: no pooling kernels, no full-size dz.
         prod = self.producer.get(id(x))
-        if (sole_consumer and prod is not None and not os.environ.get('YUNET_NO_POOL_FUSION') and
+        if (sole_consumer and prod is not None and not self.sw['no_pool_fusion'] and
                 L.load().yunet_dp_pool_fusion_ok(x.n, x.h, x.w, prod[0], prod[1])):
             out = self._new_t(x.n, x.h // 2, x.w // 2, x.c, bn_name=x.bn)
             out.bn_count = x.bn_count
@@ -805,7 +844,7 @@ class Plan:
         self.fwd_a.append(op)
         # `a` is also max-pooled by a kernel of its own (built earlier in the forward = run later in the backward):
         # leave a's share of the gradient to that kernel (see _pool)
-        a.fuse_upadd = a.plain_pool and not os.environ.get('YUNET_NO_UPADD_POOL_FUSION')
+        a.fuse_upadd = a.plain_pool and not self.sw['no_upadd_pool_fusion']
 
         def bwd():
             if a.fuse_upadd:
@@ -871,8 +910,8 @@ class YuNetEngine:
         self.plans = collections.OrderedDict()      # (N, H, W, Gmax, precision) -> Plan, least recently used first
         self.plan = None
         self.always_bucket = False      # tests: run the two-segment backward + collectives at world size 1
-        self.use_lanes = False          # head chains of the coarser levels on executor side streams (Plan.__init__)
-        self.overlap_reduce = os.environ.get('YUNET_OVERLAP_REDUCE', '1') != '0'     # one GPU: see backward()
+        self.use_lanes = False          # head chains of the coarser levels on executor side streams (Plan._emit_neck_and_heads)
+        self.overlap_reduce = read_switch('overlap_reduce')     # one GPU: see backward()
         # comm_timing: events around the three collectives of a step (num_pos | bucket A on the side stream |
         # bucket B + logged scalars) and around the final wait for the side stream; comm_report() turns them
         # into milliseconds per step, split into EXPOSED (on the launch stream, nothing to hide behind) and
@@ -895,7 +934,7 @@ class YuNetEngine:
             # fast path: the data source already padded the GT (synthetic.GTList)
             cnt = gt_bboxes.counts
             own_b, own_k, own_c = plan.own_gt
-            if (not os.environ.get('YUNET_COPY_GT') and pb.device == own_b.device and cnt.device == own_b.device and
+            if (not read_switch('copy_gt') and pb.device == own_b.device and cnt.device == own_b.device and
                     pk.device == own_b.device and pb.dtype == torch.float32 and pk.dtype == torch.float32 and
                     cnt.dtype == torch.int32 and pb.is_contiguous() and pk.is_contiguous() and cnt.is_contiguous() and
                     tuple(pb.shape) == tuple(own_b.shape) and pk.numel() == own_k.numel() and cnt.numel() == n):
