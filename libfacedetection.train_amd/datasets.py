@@ -115,6 +115,11 @@ class RetinaFaceDataset:
             warnings.warn(f"RetinaFaceDataset: samples_per_gpu={_['samples_per_gpu']} reached the dataset unread -- this "
                           f'caller evaluates one image at a time; tools/widerface_batched.py and evaluation.'
                           f'single_gpu_test(samples_per_gpu=...) run the batched device test pipeline')
+        if _.get('group_by') is not None:          # tools/widerface_batched.py pops data.test.group_by the same way
+            import warnings
+            warnings.warn(f"RetinaFaceDataset: group_by={_['group_by']!r} reached the dataset unread -- this caller does "
+                          f'not group its batches; tools/widerface_batched.py and evaluation.single_gpu_test('
+                          f'group_by=...) do')
         self.ann_file, self.img_prefix, self.pipeline_cfg = ann_file, img_prefix, pipeline
         self.min_size, self.test_mode, self.gt_path = min_size, test_mode, gt_path
         self.NK = NK

@@ -473,38 +473,51 @@ def prepare_test_image(img_bgr, scale, device, resize='cv2'):
     return x, meta
 
 
-def _batched(samples_per_gpu, pipeline, cache):
+def _batched(samples_per_gpu, pipeline, cache, group_by=None):
     """True when single_gpu_test / multi_gpu_test are asked for the batched device path (test_pipeline.run_test);
     the defaults keep the per-image path."""
     if int(samples_per_gpu) < 1:
         raise ValueError(f'samples_per_gpu must be >= 1, got {samples_per_gpu}')
-    return int(samples_per_gpu) > 1 or pipeline is not None or cache is not None
+    if group_by is not None:
+        from .grouped_eval import check_group_by
+        check_group_by(group_by)
+    return int(samples_per_gpu) > 1 or pipeline is not None or cache is not None or group_by is not None
 
 
-def _run_batched(model, dataset, device, indices, scale, samples_per_gpu, pipeline, cache, log):
+def _run_batched(model, dataset, device, indices, scale, samples_per_gpu, pipeline, cache, log, group_by=None,
+                 max_batch_pixels='default'):
+    from . import grouped_eval
     from . import test_pipeline as TP
     pipe = pipeline if isinstance(pipeline, TP.DeviceTestPipeline) else TP.DeviceTestPipeline(pipeline, scale=scale)
     source = TP.source_for(dataset, cache, device)
-    return TP.run_test(model, dataset, device, indices, pipe, source, samples_per_gpu, log=log)
+    return grouped_eval.run_test(model, dataset, device, indices, pipe, source, samples_per_gpu, log=log, group_by=group_by,
+                       max_batch_pixels=max_batch_pixels)
 
 
 def single_gpu_test(model, dataset, device, scale=(640, 640), max_images=None, samples_per_gpu=1, pipeline=None,
-                    cache=None, log=None):
+                    cache=None, log=None, group_by=None, max_batch_pixels='default'):
     """mmdet/apis/test.py single_gpu_test for this path: eval-mode forward + get_bboxes(rescale=True) per image
     of a test-mode RetinaFaceDataset -> [[dets [n, 5]]] per image (boxes in original-image coordinates).
 
     samples_per_gpu > 1, pipeline (the config's test pipeline list, or a DeviceTestPipeline) or cache ('device':
     the decoded images stay in a device store kept on the dataset) select the batched device path
     (test_pipeline.run_test): consecutive images in batches of samples_per_gpu, the last batch short, results in
-    dataset order.  `scale` is the view when the pipeline names none."""
+    dataset order.  `scale` is the view when the pipeline names none.
+
+    group_by='canvas' selects that path too and batches the images by their padded shape instead
+    (grouped_eval.group_batches): every batch's canvas is each of its images' own pad_shape, so the detections are
+    those of samples_per_gpu=1 -- the per-image protocol, e.g. WIDER "in origin size" -- in fewer forwards.
+    max_batch_pixels caps the canvas pixels of a grouped batch (default samples_per_gpu * 1024 * 1024, None: no
+    cap).  The results stay in dataset order."""
     import torch
     was_training = model.training
     model.eval()
     out = []
     n = len(dataset) if max_images is None else min(len(dataset), max_images)
     with torch.no_grad():
-        if _batched(samples_per_gpu, pipeline, cache):
-            out = _run_batched(model, dataset, device, list(range(n)), scale, samples_per_gpu, pipeline, cache, log)
+        if _batched(samples_per_gpu, pipeline, cache, group_by):
+            out = _run_batched(model, dataset, device, list(range(n)), scale, samples_per_gpu, pipeline, cache, log,
+                               group_by, max_batch_pixels)
         else:
             for i in range(n):
                 img, meta = prepare_test_image(dataset.load_image(i), scale, device)
@@ -516,11 +529,12 @@ def single_gpu_test(model, dataset, device, scale=(640, 640), max_images=None, s
 
 
 def multi_gpu_test(model, dataset, device, scale=(640, 640), max_images=None, group=None, samples_per_gpu=1,
-                   pipeline=None, cache=None, log=None):
+                   pipeline=None, cache=None, log=None, group_by=None, max_batch_pixels='default'):
     """mmdet/apis/test.py multi_gpu_test for this path (what the reference's DistEvalHook runs): rank r takes the
     images r, r + world, r + 2 world, ...; the per-image results are gathered and put back in dataset order
     (collect_results).  Returns the full list on rank 0 and None on the other ranks.  samples_per_gpu / pipeline /
-    cache: as single_gpu_test, over the rank's own list."""
+    cache / group_by / max_batch_pixels: as single_gpu_test, over the rank's own list (the images are sharded
+    first and grouped inside the rank's shard)."""
     import torch
     import torch.distributed as dist
     rank, world = dist.get_rank(group), dist.get_world_size(group)
@@ -529,9 +543,9 @@ def multi_gpu_test(model, dataset, device, scale=(640, 640), max_images=None, gr
     n = len(dataset) if max_images is None else min(len(dataset), max_images)
     part = []
     with torch.no_grad():
-        if _batched(samples_per_gpu, pipeline, cache):
+        if _batched(samples_per_gpu, pipeline, cache, group_by):
             part = _run_batched(model, dataset, device, list(range(rank, n, world)), scale, samples_per_gpu, pipeline,
-                                cache, log)
+                                cache, log, group_by, max_batch_pixels)
         else:
             for i in range(rank, n, world):
                 img, meta = prepare_test_image(dataset.load_image(i), scale, device)

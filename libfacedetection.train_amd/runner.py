@@ -526,13 +526,19 @@ class EvalHook(Hook):
 
     def __init__(self, dataset, interval=1, by_epoch=True, metric='mAP', start=None, scale=(640, 640),
                  max_images=None, save_best=None, distributed=False, samples_per_gpu=1, pipeline=None, cache=None,
-                 score=None, **eval_kwargs):
+                 score=None, group_by=None, max_batch_pixels='default', **eval_kwargs):
         self.dataset, self.interval, self.by_epoch, self.metric = dataset, int(interval), by_epoch, metric
         self.start, self.scale, self.max_images, self.distributed = start, scale, max_images, distributed
         # the batched device test pipeline (evaluation.single_gpu_test): data.val_dataloader.samples_per_gpu, the
         # data.val.pipeline list (parsed once, here, so that an unsupported form raises before training starts) and
         # data.val.cache; the defaults keep the per-image path
         self.samples_per_gpu, self.cache = int(samples_per_gpu), cache
+        # data.val_dataloader.group_by ('canvas': batches of one padded shape, grouped_eval.group_batches) and
+        # max_batch_pixels, checked here for the same reason
+        from .grouped_eval import batch_pixel_cap, check_group_by
+        self.group_by = check_group_by(group_by)
+        batch_pixel_cap(self.samples_per_gpu, max_batch_pixels)
+        self.max_batch_pixels = max_batch_pixels
         if pipeline is not None:
             from .test_pipeline import DeviceTestPipeline
             pipeline = DeviceTestPipeline(pipeline, scale=scale)
@@ -570,6 +576,8 @@ class EvalHook(Hook):
             dev = torch.device('cuda', torch.cuda.current_device())
         sharded = self.distributed and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
         how = dict(samples_per_gpu=self.samples_per_gpu, pipeline=self.pipeline, cache=self.cache, log=runner.logger)
+        if self.group_by is not None:
+            how.update(group_by=self.group_by, max_batch_pixels=self.max_batch_pixels)
         if sharded:
             # BatchNorm running statistics are per rank (no SyncBN, broadcast_buffers=False): the reference's
             # DistEvalHook broadcasts rank 0's running_var / running_mean before multi_gpu_test
@@ -914,12 +922,15 @@ def train_detector(model, dataset, cfg, distributed=False, validate=False, times
         # mmdet/apis/train.py:206-222: data.val_dataloader.samples_per_gpu (default 1).  A value above 1, a
         # data.val.cache, or a val pipeline that spells its transforms out runs the batched device test pipeline,
         # built from that list; otherwise (the shipped configs) the per-image path, which reads img_scale only
-        val_spg = int((cfg.get('data').get('val_dataloader') or {}).get('samples_per_gpu', 1))
+        val_loader = cfg.get('data').get('val_dataloader') or {}
+        val_spg = int(val_loader.get('samples_per_gpu', 1))
+        grouped = {k: val_loader[k] for k in ('group_by', 'max_batch_pixels') if k in val_loader}
         val_cache = val_cfg.pop('cache', None)
         val_pipe = val_cfg.get('pipeline') or []
         spelled = any(t.get('type') == 'MultiScaleFlipAug' and t.get('transforms') for t in val_pipe)
-        batched = dict(samples_per_gpu=val_spg, cache=val_cache,
-                       pipeline=list(val_pipe) if (spelled or val_spg > 1 or val_cache is not None) else None)
+        batched = dict(samples_per_gpu=val_spg, cache=val_cache, **grouped,
+                       pipeline=list(val_pipe) if (spelled or val_spg > 1 or val_cache is not None
+                                                   or grouped.get('group_by') is not None) else None)
         if os.path.exists(val_cfg.get('ann_file', '')):
             runner.register_hook(EvalHook(build_dataset(val_cfg), scale=scale or (640, 640), distributed=distributed,
                                           **batched, **eval_cfg), 'LOW')

@@ -1,13 +1,16 @@
 #!/usr/bin/env python
 """tools/test_widerface.py through the batched device test pipeline (yunet_amd/test_pipeline.py): the same command line
-(CONFIG CHECKPOINT [--out DIR] [--save-preds] [--thr T] [--mode M] [--gt-path D] [--max-images N]) plus `--cache device`
-and `--score {host,device}`.
+(CONFIG CHECKPOINT [--out DIR] [--save-preds] [--thr T] [--mode M] [--gt-path D] [--max-images N]) plus `--cache device`,
+`--score {host,device}`, `--group canvas` and `--max-batch-pixels N|none`.
 
 `data.test.samples_per_gpu` is read as the reference's tool reads it (default 1) and `data.test.pipeline` is rewritten
 for --mode as the reference's tool does (img_scale of the MultiScaleFlipAug, the size of its Pad; an empty list is the
 pipeline evaluation.prepare_test_image hard-codes).  One kernel launch prepares a batch and the detections of a batch
 leave the device together; `--cache device` decodes into a device store first.  Origin size (--mode 2) has more batch
-geometries than the engine keeps plans and runs one image per batch, with the reason printed.  The prediction files and
+geometries than the engine keeps plans: with consecutive batches it runs one image per batch, with the reason printed;
+`--group canvas` (or `data.test.group_by = 'canvas'`) batches the images by their padded shape instead, which gives
+every image the tensor of the per-image protocol -- the same detections in fewer forwards (`--max-batch-pixels` caps
+the canvas pixels of such a batch, default samples_per_gpu * 1024 * 1024).  The prediction files and
 the `aps` file are those of tools/test_widerface.py (at one image per batch, text for text); use that tool for
 `--eval-only`.
 """
@@ -53,6 +56,13 @@ def own_parser():
                      help="'device': decode into a device store and feed the batches from it")
     own.add_argument('--score', default='host', choices=['host', 'device'],
                      help="where the WIDER APs are scored: numpy on the host, or the HIP scorer on the GPU (same APs)")
+    own.add_argument('--group', default=None, choices=['canvas'],
+                     help="'canvas': batch images of one padded shape together (also data.test.group_by); the per-image "
+                          'detections in fewer forwards')
+    own.add_argument('--max-batch-pixels', type=lambda v: 'none' if v.lower() == 'none' else int(v), default=None,
+                     metavar='N|none',
+                     help="canvas pixels a grouped batch may hold, 'none' for no cap (also data.test.max_batch_pixels; "
+                          'default samples_per_gpu * 1024 * 1024)')
     return own
 
 
@@ -84,11 +94,16 @@ def main():
     model.to(dev).eval()
     tcfg['test_mode'] = True
     spg = int(tcfg.pop('samples_per_gpu', 1))          # as the reference reads it (tools/test_widerface.py:101-104 there)
+    group_by = tcfg.pop('group_by', None)               # the command line wins over the config
+    cap = tcfg.pop('max_batch_pixels', 'default')
+    group_by = b.group if b.group is not None else group_by
+    cap = b.max_batch_pixels if b.max_batch_pixels is not None else cap
+    cap = None if cap == 'none' else cap
     ds = yunet_amd.build_dataset(tcfg)
     scale = tool.target_scale(a.mode)
     pipe = DeviceTestPipeline(mode_pipeline(tcfg.get('pipeline') or [], scale), scale=scale)
     dets = E.single_gpu_test(model, ds, dev, scale, a.max_images, samples_per_gpu=spg, pipeline=pipe, cache=b.cache,
-                             log=print)
+                             log=print, group_by=group_by, max_batch_pixels=cap)
     results = E.collect_wider_results(dets, ds, a.out if a.save_preds else None)
     aps = E.wider_evaluation(results, gt_path, 0.5, device=dev if b.score == 'device' else None)
     E.write_aps(a.out, aps)
