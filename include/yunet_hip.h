@@ -689,6 +689,29 @@ int yunet_score_wider_match(const double* pred, const long long* pred_off, const
 int yunet_score_map_tpfp(const float* dets, const long long* det_off, const float* gts, const long long* gt_off,
                          const int32_t* kept, const int32_t* order, int I, long long D, long long G, float iou_thr,
                          int32_t* code, int32_t* first, float* tp, float* fp, void* stream);
+/* The ranking and the curve of that protocol (evaluation.eval_map_single_class(rank='device')).  A score ranks by an
+ * order-preserving integer key of its fp32 bits: descending score, ties in row order -- np.argsort(-s, kind='stable')
+ * for finite scores (-0.0 and NaN are not supported: -0.0 ranks after +0.0, a NaN by its bit pattern).
+ * yunet_score_rank_images: order [D] int32 as yunet_score_map_tpfp takes it: per image (det_off), entry k is the local
+ *   row visited k-th.  One workgroup per image; up to YUNET_RANK_SEG_CAP rows the image's keys sit in LDS at once,
+ *   longer images pass through it in chunks of that size.  Entries of an image whose offsets are not sane stay -1.
+ * yunet_score_rank_global: rank [D] int32, the same order over all D rows (ties: image, then row), by a least-
+ *   significant-digit radix sort of (key, row) pairs in tiles of YUNET_RANK_RADIX_TILE; the result is the same on
+ *   every run.  scratch: yunet_score_rank_scratch_bytes(D) bytes, 8-byte aligned (0 for a D the calls refuse).
+ * yunet_score_map_curve: tp, fp [D] fp32 in row order (as yunet_score_map_tpfp writes them) and rank -> in ranked
+ *   order ctp, cfp [D] = the cumulative counts, summed as integers and converted to fp32; prec = ctp / max(ctp + cfp,
+ *   2^-23) in fp32, one rounding per operation; env[k] = max(prec[k ..]).  No atomics.  D >= YUNET_RANK_CURVE_MAX:
+ *   YUNET_EINVAL (below it fp32 cumulative sums are exact, so these are numpy's float32 results bit for bit).
+ *   scratch: as yunet_score_rank_global (the same buffer serves both calls, one after the other). */
+#define YUNET_RANK_SEG_CAP 1024       /* rows of an image ranked in LDS at once */
+#define YUNET_RANK_RADIX_TILE 4096    /* elements of a radix-sort / scan tile */
+#define YUNET_RANK_CURVE_MAX 16777216
+size_t yunet_score_rank_scratch_bytes(long long D);
+int yunet_score_rank_images(const float* dets, const long long* det_off, int I, long long D, int32_t* order,
+                            void* stream);
+int yunet_score_rank_global(const float* dets, long long D, int32_t* rank, void* scratch, void* stream);
+int yunet_score_map_curve(const float* tp, const float* fp, const int32_t* rank, long long D, float* ctp, float* cfp,
+                          float* prec, float* env, void* scratch, void* stream);
 
 /* Decoded-source store (pipelines.SourceStore).  One launch builds a batch's SourceBatch tables from the store's
  * per-image tables (M images: byte offset, (h, w), first GT row, GT count; boxes [*,4], kps [*,5,3]) and a device

@@ -19,6 +19,7 @@ EMA_MAX_SEGMENTS = 3                                        # YUNET_EMA_MAX_SEGM
 HIST_TOTAL, HIST_NOIMG, HIST_SPILLED, HIST_STATUS = 0, 1, 2, 3   # YUNET_HIST_* (yunet_box_size_hist totals[])
 HIST_SPILL, HIST_OVERFLOW, HIST_BAD_COUNT = 1, 2, 4             # its status bits
 SCORE_BLOCK, SCORE_GT_CHUNK, SCORE_MAX_THRESH = 256, 256, 1024   # YUNET_SCORE_* (csrc/score.hip)
+RANK_SEG_CAP, RANK_RADIX_TILE, RANK_CURVE_MAX = 1024, 4096, 1 << 24   # YUNET_RANK_* (csrc/score.hip: ranking and curve)
 NORM_BLOCK, NORM_TILE, NORM_MAX_BLOCKS, NORM_SCRATCH_BYTES = 256, 4096, 256, 8 + 8 * 256   # YUNET_NORM_* (csrc/optim.hip)
 NORM_INF, NORM_L1, NORM_L2 = 0, 1, 2
 OPT_ROW, OPT_MAX_GROUPS = 4, 255                                  # YUNET_OPT_* (the group table of csrc/optim.hip)
@@ -174,6 +175,10 @@ _SIGNATURES = {
                                 [C.c_void_p] * 4),
     'yunet_score_map_tpfp': (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_longlong, C.c_longlong, C.c_float] +
                              [C.c_void_p] * 5),
+    'yunet_score_rank_scratch_bytes': (C.c_size_t, [C.c_longlong]),
+    'yunet_score_rank_images': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
+    'yunet_score_rank_global': (C.c_int, [C.c_void_p, C.c_longlong] + [C.c_void_p] * 3),
+    'yunet_score_map_curve': (C.c_int, [C.c_void_p] * 3 + [C.c_longlong] + [C.c_void_p] * 6),
     'yunet_aug_gather': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int] +
                          [C.c_void_p] * 6),
     'yunet_aug_window_plan': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -20,6 +20,24 @@
 // mAP, two launches: map_match_kernel (fp32 IoU against kept + ignored boxes, a thread owns a visiting position,
 // atomicMin(first[g], position)) and map_tpfp_kernel (tp where the position is the ground truth's first).
 //
+// mAP, the ranking and the curve (eval_map_single_class(rank='device')).  Scores are compared through rank_key: an
+// order-preserving 32-bit integer of the fp32 score, inverted, so that ascending keys are descending scores; ties keep
+// the row order (np.argsort(-s, kind='stable')).
+//   rank_images_kernel    : the `order` table map_match_kernel visits, one workgroup per image.  A row's position is
+//                           the number of rows of its image that come before it, counted against the image's keys in
+//                           LDS: all of them at once up to YUNET_RANK_SEG_CAP rows, in chunks of that size beyond.
+//   radix_*_kernel        : the ranking of the whole set, a least-significant-digit radix sort of (key, index) pairs in
+//                           four 8-bit passes.  Per pass: the digit histogram of every tile of YUNET_RANK_RADIX_TILE
+//                           elements, one exclusive scan of the [digit][tile] table (one workgroup, a thread owns a
+//                           digit), and the scatter: a tile is walked in rows of 256 elements in order; within a row
+//                           the elements of a wave that share a digit find each other with eight ballots, the waves'
+//                           counts pass through LDS, and thread d keeps digit d's next free slot.  Every step is a
+//                           count, so the result is the same on every run.
+//   curve_*_kernel        : tp / fp gathered in ranked order, summed as integers (tile sums, one scan of them, the
+//                           scan inside the tiles), converted to fp32; precision = ctp / max(ctp + cfp, eps), one
+//                           rounding per operation; the tiles' maxima, their suffix maximum, and the reverse running
+//                           maximum of the precision (the envelope).  No atomics on any result.
+//
 // Every offset read from a device table is checked against the totals the host passes before it addresses anything.
 #include <limits.h>
 
@@ -381,6 +399,268 @@ __global__ __launch_bounds__(NT) void map_tpfp_kernel(const long long* __restric
     }
 }
 
+// ---------------------------------------------------------------------------------- mAP: ranking and curve
+constexpr int SEG = YUNET_RANK_SEG_CAP;
+constexpr int RT = YUNET_RANK_RADIX_TILE;
+constexpr int ROWS = RT / NT;                      // rows of 256 elements in a tile = elements a thread owns in a scan
+static_assert(SEG % NT == 0 && RT % NT == 0 && NT == 256, "a thread per digit, whole rows per tile");
+
+// ascending key = descending score (finite scores; -0.0 would rank after +0.0, a NaN by its bit pattern)
+__device__ __forceinline__ uint32_t rank_key(float s) {
+    const uint32_t b = (uint32_t)__float_as_int(s);
+    return (b >> 31) ? b : (~b & 0x7fffffffu);
+}
+
+// rows of the chunk skey[0 .. cnt) (rows c0 .. c0 + cnt of the image) that come before row r with key `mine`
+__device__ __forceinline__ int rows_before(const uint32_t* skey, int cnt, long long c0, uint32_t mine, long long r) {
+    int pos = 0;
+    for (int j = 0; j < cnt; ++j) {
+        const uint32_t k = skey[j];
+        pos += (k < mine) | ((k == mine) & (c0 + j < r));
+    }
+    return pos;
+}
+
+__global__ __launch_bounds__(NT) void rank_images_kernel(const float* __restrict__ det,
+                                                         const long long* __restrict__ doff, int I, long long D,
+                                                         int32_t* __restrict__ order) {
+    __shared__ uint32_t skey[SEG];
+    const int tid = threadIdx.x;
+    for (int i = blockIdx.x; i < I; i += gridDim.x) {
+        long long d0, n;
+        if (!span(doff, i, D, d0, n) || n == 0) continue;          // (uniform over the workgroup)
+        if (n <= SEG) {                                             // the whole image in LDS
+            __syncthreads();
+            for (int j = tid; j < n; j += NT) skey[j] = rank_key(det[(d0 + j) * 5 + 4]);
+            __syncthreads();
+            for (int r = tid; r < n; r += NT) order[d0 + rows_before(skey, (int)n, 0, skey[r], r)] = r;
+        } else {                                                    // a thread owns a row, the image passes in chunks
+            for (long long base = 0; base < n; base += NT) {
+                const long long r = base + tid;
+                const bool active = r < n;
+                const uint32_t mine = active ? rank_key(det[(d0 + r) * 5 + 4]) : 0u;
+                long long pos = 0;
+                for (long long c0 = 0; c0 < n; c0 += SEG) {
+                    const int cnt = (int)(n - c0 < SEG ? n - c0 : SEG);
+                    __syncthreads();
+                    for (int j = tid; j < cnt; j += NT) skey[j] = rank_key(det[(d0 + c0 + j) * 5 + 4]);
+                    __syncthreads();
+                    if (active) pos += rows_before(skey, cnt, c0, mine, r);
+                }
+                if (active && pos < n) order[d0 + pos] = (int32_t)r;
+            }
+        }
+    }
+}
+
+// key and index of element e on the way into a pass: the first pass reads the score column itself
+template <bool FIRST>
+__device__ __forceinline__ uint32_t radix_key(const float* __restrict__ det, const uint32_t* __restrict__ kin,
+                                              long long e) {
+    return FIRST ? rank_key(det[e * 5 + 4]) : kin[e];
+}
+
+template <bool FIRST>
+__global__ __launch_bounds__(NT) void radix_hist_kernel(const float* __restrict__ det,
+                                                        const uint32_t* __restrict__ kin, long long D, int shift,
+                                                        int nblk, uint32_t* __restrict__ hist) {
+    __shared__ unsigned h[NT];
+    const int tid = threadIdx.x;
+    h[tid] = 0;
+    __syncthreads();
+    const long long base = (long long)blockIdx.x * RT;
+    for (int m = 0; m < ROWS; ++m) {
+        const long long e = base + m * NT + tid;
+        if (e < D) atomicAdd(&h[(radix_key<FIRST>(det, kin, e) >> shift) & 255u], 1u);      // integer counts: exact
+    }
+    __syncthreads();
+    hist[(long long)tid * nblk + blockIdx.x] = h[tid];
+}
+
+// hist [256][nblk] -> its exclusive scan in (digit, tile) order, in place.  One workgroup; thread d owns digit d's row.
+__global__ __launch_bounds__(NT) void radix_scan_kernel(uint32_t* __restrict__ hist, int nblk) {
+    __shared__ unsigned buf[2 * NT];
+    const int tid = threadIdx.x;
+    uint32_t* row = hist + (long long)tid * nblk;
+    unsigned sum = 0;
+    for (int b = 0; b < nblk; ++b) sum += row[b];
+    unsigned run = block_scan(sum, buf, [](unsigned a, unsigned b) { return a + b; }) - sum;
+    for (int b = 0; b < nblk; ++b) {
+        const unsigned v = row[b];
+        row[b] = run;
+        run += v;
+    }
+}
+
+template <bool FIRST, bool LAST>
+__global__ __launch_bounds__(NT) void radix_scatter_kernel(const float* __restrict__ det,
+                                                           const uint32_t* __restrict__ kin,
+                                                           const int32_t* __restrict__ iin, long long D, int shift,
+                                                           int nblk, const uint32_t* __restrict__ hist,
+                                                           uint32_t* __restrict__ kout, int32_t* __restrict__ iout) {
+    __shared__ unsigned run[NT];                    // digit d's next free slot of the output
+    __shared__ unsigned wcnt[NT / 64][NT];          // this row: elements of wave w with digit d
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    run[tid] = hist[(long long)tid * nblk + blockIdx.x];
+#pragma unroll
+    for (int v = 0; v < NT / 64; ++v) wcnt[v][tid] = 0;
+    __syncthreads();
+    const long long base = (long long)blockIdx.x * RT;
+    for (int m = 0; m < ROWS; ++m) {
+        const long long e = base + m * NT + tid;
+        const bool active = e < D;
+        uint32_t k = 0;
+        int32_t ix = 0;
+        if (active) {
+            k = radix_key<FIRST>(det, kin, e);
+            ix = FIRST ? (int32_t)e : iin[e];
+        }
+        const unsigned d = (k >> shift) & 255u;
+        unsigned long long same = __ballot(active);                 // the wave's active lanes with this lane's digit
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const bool bit = (d >> b) & 1u;
+            const unsigned long long bal = __ballot(bit);
+            same &= bit ? bal : ~bal;
+        }
+        const unsigned below = (unsigned)__popcll(same & ((1ull << lane) - 1ull));
+        if (active) wcnt[w][d] = (unsigned)__popcll(same);           // (every lane of the group writes the same count)
+        __syncthreads();
+        if (active) {
+            unsigned long long off = (unsigned long long)run[d] + below;
+            for (int v = 0; v < w; ++v) off += wcnt[v][d];
+            if (off < (unsigned long long)D) {
+                iout[off] = ix;
+                if (!LAST) kout[off] = k;
+            }
+        }
+        __syncthreads();
+        unsigned add = 0;
+#pragma unroll
+        for (int v = 0; v < NT / 64; ++v) {
+            add += wcnt[v][tid];
+            wcnt[v][tid] = 0;
+        }
+        run[tid] += add;
+        __syncthreads();
+    }
+}
+
+// (tp, fp) flags of ranked position e as one word: tp in the low half, fp in the high half (each sum is < 2^24)
+__device__ __forceinline__ unsigned long long curve_flags(const float* __restrict__ tp, const float* __restrict__ fp,
+                                                          const int32_t* __restrict__ rank, long long e, long long D) {
+    if (e >= D) return 0ull;
+    const long long row = rank[e];
+    if (row < 0 || row >= D) return 0ull;
+    return (tp[row] != 0.0f ? 1ull : 0ull) | (fp[row] != 0.0f ? 1ull << 32 : 0ull);
+}
+
+__global__ __launch_bounds__(NT) void curve_sum_kernel(const float* __restrict__ tp, const float* __restrict__ fp,
+                                                       const int32_t* __restrict__ rank, long long D,
+                                                       unsigned long long* __restrict__ tsum) {
+    __shared__ unsigned long long buf[2 * NT];
+    const long long first = (long long)blockIdx.x * RT + (long long)threadIdx.x * ROWS;
+    unsigned long long s = 0;
+#pragma unroll
+    for (int m = 0; m < ROWS; ++m) s += curve_flags(tp, fp, rank, first + m, D);
+    block_scan(s, buf, [](unsigned long long a, unsigned long long b) { return a + b; });
+    if (threadIdx.x == 0) tsum[blockIdx.x] = buf[NT - 1];
+}
+
+// v [n] -> its exclusive scan (forward) or its exclusive suffix scan (reverse), in place; one workgroup, a thread owns
+// a contiguous piece
+template <class T, bool REVERSE, class Op>
+__device__ __forceinline__ void table_scan(T* __restrict__ v, int n, T identity, T* buf, Op op) {
+    const int per = (n + NT - 1) / NT;
+    const int piece = REVERSE ? NT - 1 - (int)threadIdx.x : (int)threadIdx.x;      // scanned in thread order
+    const int lo = piece * per < n ? piece * per : n, hi = lo + per < n ? lo + per : n;
+    T sum = identity;
+    for (int j = lo; j < hi; ++j) sum = op(sum, v[j]);
+    block_scan(sum, buf, op);
+    T run = threadIdx.x > 0 ? buf[threadIdx.x - 1] : identity;
+    if (REVERSE) {
+        for (int j = hi - 1; j >= lo; --j) {
+            const T x = v[j];
+            v[j] = run;
+            run = op(run, x);
+        }
+    } else {
+        for (int j = lo; j < hi; ++j) {
+            const T x = v[j];
+            v[j] = run;
+            run = op(run, x);
+        }
+    }
+}
+
+__global__ __launch_bounds__(NT) void curve_scan_kernel(unsigned long long* __restrict__ tsum, int nblk) {
+    __shared__ unsigned long long buf[2 * NT];
+    table_scan<unsigned long long, false>(tsum, nblk, 0ull, buf,
+                                          [](unsigned long long a, unsigned long long b) { return a + b; });
+}
+
+__global__ __launch_bounds__(NT) void curve_sufmax_kernel(float* __restrict__ tmax, int nblk) {
+    __shared__ float buf[2 * NT];
+    table_scan<float, true>(tmax, nblk, 0.0f, buf, [](float a, float b) { return a > b ? a : b; });
+}
+
+__global__ __launch_bounds__(NT) void curve_prec_kernel(const float* __restrict__ tp, const float* __restrict__ fp,
+                                                        const int32_t* __restrict__ rank, long long D,
+                                                        const unsigned long long* __restrict__ tsum, float eps,
+                                                        float* __restrict__ ctp, float* __restrict__ cfp,
+                                                        float* __restrict__ prec, float* __restrict__ tmax) {
+    __shared__ unsigned long long buf[2 * NT];
+    __shared__ float fbuf[2 * NT];
+    const int tid = threadIdx.x;
+    const long long first = (long long)blockIdx.x * RT + (long long)tid * ROWS;
+    unsigned long long inc[ROWS], s = 0;
+#pragma unroll
+    for (int m = 0; m < ROWS; ++m) {
+        s += curve_flags(tp, fp, rank, first + m, D);
+        inc[m] = s;
+    }
+    block_scan(s, buf, [](unsigned long long a, unsigned long long b) { return a + b; });
+    const unsigned long long before = tsum[blockIdx.x] + (tid > 0 ? buf[tid - 1] : 0ull);
+    float best = 0.0f;                                              // (a precision is never negative)
+#pragma unroll
+    for (int m = 0; m < ROWS; ++m) {
+        if (first + m < D) {
+            const unsigned long long c = before + inc[m];
+            const float t = (float)(unsigned)(c & 0xffffffffull), f = (float)(unsigned)(c >> 32);     // exact: < 2^24
+            const float den = t + f;
+            const float p = t / (den > eps ? den : eps);
+            ctp[first + m] = t;
+            cfp[first + m] = f;
+            prec[first + m] = p;
+            best = p > best ? p : best;
+        }
+    }
+    block_scan(best, fbuf, [](float a, float b) { return a > b ? a : b; });
+    if (tid == 0) tmax[blockIdx.x] = fbuf[NT - 1];
+}
+
+// env[e] = max(prec[e ..]): thread t owns piece NT - 1 - t of the tile, so that the scan in thread order runs backwards
+__global__ __launch_bounds__(NT) void curve_env_kernel(const float* __restrict__ prec, long long D,
+                                                       const float* __restrict__ tmax, float* __restrict__ env) {
+    __shared__ float fbuf[2 * NT];
+    const int tid = threadIdx.x;
+    const long long first = (long long)blockIdx.x * RT + (long long)(NT - 1 - tid) * ROWS;
+    float p[ROWS], best = 0.0f;
+#pragma unroll
+    for (int m = 0; m < ROWS; ++m) {
+        p[m] = first + m < D ? prec[first + m] : 0.0f;
+        best = p[m] > best ? p[m] : best;
+    }
+    block_scan(best, fbuf, [](float a, float b) { return a > b ? a : b; });
+    float run = tmax[blockIdx.x];                                   // (after curve_sufmax_kernel: the later tiles)
+    if (tid > 0) run = fbuf[tid - 1] > run ? fbuf[tid - 1] : run;
+#pragma unroll
+    for (int m = ROWS - 1; m >= 0; --m) {
+        run = p[m] > run ? p[m] : run;
+        if (first + m < D) env[first + m] = run;
+    }
+}
+
 int grid_for(long long work) {
     long long b = (work + NT - 1) / NT;
     return (int)(b < 1 ? 1 : b > 1024 ? 1024 : b);
@@ -441,5 +721,69 @@ extern "C" int yunet_score_map_tpfp(const float* dets, const long long* det_off,
                            iou_thr, code, first);
     }
     hipLaunchKernelGGL(map_tpfp_kernel, dim3(grid), dim3(NT), 0, s, det_off, gt_off, order, I, D, G, code, first, tp, fp);
+    return hip_status();
+}
+
+// ---- the ranking and the curve of the mAP protocol
+static long long rank_tiles(long long D) { return (D + RT - 1) / RT; }
+
+extern "C" size_t yunet_score_rank_scratch_bytes(long long D) {
+    if (D < 0 || D > INT_MAX) return 0;
+    return (size_t)(4 * (3 * D + 256 * rank_tiles(D)) + 8);
+}
+
+extern "C" int yunet_score_rank_images(const float* dets, const long long* det_off, int I, long long D, int32_t* order,
+                                       void* stream) {
+    if (I < 0 || D < 0 || D > INT_MAX) return YUNET_EINVAL;
+    if (I == 0 || D == 0) return 0;
+    if (!dets || !det_off || !order) return YUNET_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(order, 0xff, sizeof(int32_t) * D, s) != hipSuccess) return hip_status();      // -1: no row
+    hipLaunchKernelGGL(rank_images_kernel, dim3(I < 8192 ? I : 8192), dim3(NT), 0, s, dets, det_off, I, D, order);
+    return hip_status();
+}
+
+extern "C" int yunet_score_rank_global(const float* dets, long long D, int32_t* rank, void* scratch, void* stream) {
+    if (D < 0 || D > INT_MAX) return YUNET_EINVAL;
+    if (D == 0) return 0;
+    if (!dets || !rank || !scratch || ((uintptr_t)scratch & 7)) return YUNET_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int nblk = (int)rank_tiles(D);
+    uint32_t* ka = (uint32_t*)scratch;
+    uint32_t* kb = ka + D;
+    int32_t* ia = (int32_t*)(kb + D);
+    uint32_t* hist = (uint32_t*)(ia + D);
+    const dim3 g(nblk), b(NT);
+    // (key, index): scores -> (ka, ia) -> (kb, rank) -> (ka, ia) -> rank
+    hipLaunchKernelGGL(radix_hist_kernel<true>, g, b, 0, s, dets, nullptr, D, 0, nblk, hist);
+    hipLaunchKernelGGL(radix_scan_kernel, dim3(1), b, 0, s, hist, nblk);
+    hipLaunchKernelGGL((radix_scatter_kernel<true, false>), g, b, 0, s, dets, nullptr, nullptr, D, 0, nblk, hist, ka, ia);
+    hipLaunchKernelGGL(radix_hist_kernel<false>, g, b, 0, s, dets, ka, D, 8, nblk, hist);
+    hipLaunchKernelGGL(radix_scan_kernel, dim3(1), b, 0, s, hist, nblk);
+    hipLaunchKernelGGL((radix_scatter_kernel<false, false>), g, b, 0, s, dets, ka, ia, D, 8, nblk, hist, kb, rank);
+    hipLaunchKernelGGL(radix_hist_kernel<false>, g, b, 0, s, dets, kb, D, 16, nblk, hist);
+    hipLaunchKernelGGL(radix_scan_kernel, dim3(1), b, 0, s, hist, nblk);
+    hipLaunchKernelGGL((radix_scatter_kernel<false, false>), g, b, 0, s, dets, kb, rank, D, 16, nblk, hist, ka, ia);
+    hipLaunchKernelGGL(radix_hist_kernel<false>, g, b, 0, s, dets, ka, D, 24, nblk, hist);
+    hipLaunchKernelGGL(radix_scan_kernel, dim3(1), b, 0, s, hist, nblk);
+    hipLaunchKernelGGL((radix_scatter_kernel<false, true>), g, b, 0, s, dets, ka, ia, D, 24, nblk, hist, nullptr, rank);
+    return hip_status();
+}
+
+extern "C" int yunet_score_map_curve(const float* tp, const float* fp, const int32_t* rank, long long D, float* ctp,
+                                     float* cfp, float* prec, float* env, void* scratch, void* stream) {
+    if (D < 0 || D >= YUNET_RANK_CURVE_MAX) return YUNET_EINVAL;    // fp32 holds every count below 2^24 exactly
+    if (D == 0) return 0;
+    if (!tp || !fp || !rank || !ctp || !cfp || !prec || !env || !scratch || ((uintptr_t)scratch & 7)) return YUNET_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int nblk = (int)rank_tiles(D);
+    unsigned long long* tsum = (unsigned long long*)scratch;
+    float* tmax = (float*)(tsum + nblk);
+    const dim3 g(nblk), b(NT);
+    hipLaunchKernelGGL(curve_sum_kernel, g, b, 0, s, tp, fp, rank, D, tsum);
+    hipLaunchKernelGGL(curve_scan_kernel, dim3(1), b, 0, s, tsum, nblk);
+    hipLaunchKernelGGL(curve_prec_kernel, g, b, 0, s, tp, fp, rank, D, tsum, 1.1920928955078125e-07f, ctp, cfp, prec, tmax);
+    hipLaunchKernelGGL(curve_sufmax_kernel, dim3(1), b, 0, s, tmax, nblk);
+    hipLaunchKernelGGL(curve_env_kernel, g, b, 0, s, prec, D, tmax, env);
     return hip_status();
 }

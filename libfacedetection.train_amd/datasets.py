@@ -141,10 +141,11 @@ class RetinaFaceDataset:
     def load_image(self, idx):
         return imread_bgr(os.path.join(self.img_prefix, self.data_infos[idx]['filename']))
 
-    def evaluate(self, results, metric='mAP', logger=None, iou_thr=0.5, device=None, **_):
+    def evaluate(self, results, metric='mAP', logger=None, iou_thr=0.5, device=None, rank=None, **_):
         """CustomDataset.evaluate (mmdet/datasets/custom.py:310-367) for the metric the shipped configs ask
         for (`evaluation = dict(interval=..., metric='mAP')`): AP of the face class at each IoU threshold.
-        device: a CUDA device scores tp / fp there (evaluation.eval_map_single_class); None: on the host."""
+        device: a CUDA device scores tp / fp there (evaluation.eval_map_single_class); None: on the host.
+        rank='device' (with a device) also ranks the detections and builds the precision curve there."""
         from collections import OrderedDict
         from .evaluation import eval_map_single_class
         if not isinstance(metric, str):
@@ -154,9 +155,10 @@ class RetinaFaceDataset:
             raise KeyError(f'metric {metric} is not supported')
         anns = [self.get_ann_info(i) for i in range(len(results))]
         thrs = [iou_thr] if isinstance(iou_thr, float) else list(iou_thr)
+        how = {} if rank is None else dict(rank=rank)
         res, aps = OrderedDict(), []
         for t in thrs:
-            ap, _ = eval_map_single_class(results, anns, t, device=device)
+            ap, _ = eval_map_single_class(results, anns, t, device=device, **how)
             aps.append(ap)
             res[f'AP{int(t * 100):02d}'] = round(ap, 3)
         res['mAP'] = sum(aps) / len(aps)

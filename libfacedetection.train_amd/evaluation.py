@@ -21,7 +21,8 @@ wider_{face,easy,medium,hard}_val.mat.
 Both protocols have an integer stage (matching, first hits, prefix sums, counting) and a short floating-point
 tail (precision / recall / area).  The integer stage is `wider_pr_counts` / `tpfp_default`; the default runs it on the
 host in numpy, `device=<a CUDA device>` runs it in csrc/score.hip (kernels.score_wider / kernels.score_map_tpfp) on
-the packed set and reads the counters back -- the same integers, so the same APs.  The tail stays on the host.
+the packed set and reads the counters back -- the same integers, so the same APs.  The tail stays on the host; for the
+mAP, `rank='device'` also ranks the detections and builds the precision curve there (curve_device).
 """
 import os
 
@@ -411,17 +412,75 @@ def tpfp_device(dets, gts, igns, iou_thr, device):
     return both[0], both[1]
 
 
-def eval_map_single_class(det_results, annotations, iou_thr=0.5, device=None):
+def check_rank(rank, on_device):
+    """The `rank` option of eval_map_single_class / RetinaFaceDataset.evaluate / EvalHook: None, or 'device' together
+    with a device scorer."""
+    if rank not in (None, 'device'):
+        raise ValueError(f"rank={rank!r}; None (the host ranks the detections) or 'device'")
+    if rank == 'device' and not on_device:
+        raise ValueError("rank='device' ranks the detections in csrc/score.hip: it needs the device scorer "
+                         "(device=<a CUDA device>, EvalHook: score='device')")
+    return rank
+
+
+def curve_device(dets, gts, igns, iou_thr, device):
+    """The whole per-detection part of eval_map_single_class in csrc/score.hip, on one upload of the packed set: the
+    visiting order of every image (kernels.score_rank_images), tp / fp (kernels.score_map_tpfp), the ranking of all
+    detections (kernels.score_rank_global) and the curve (kernels.score_map_curve) -> float32 [4, sum n] in ranked
+    order, read back in one copy: cumulative tp, cumulative fp, precision, and the reverse running maximum of the
+    precision (the envelope average_precision_area walks).  Both orders are descending score with ties in row order,
+    np.argsort(-s, kind='stable'); scores are finite (no NaN, no -0.0)."""
+    import torch
+    from . import kernels as K
+    dev = _score_device(device)
+    off = lambda n: np.concatenate([[0], np.cumsum(np.asarray(n, dtype=np.int64))]).astype(np.int64)
+    alld = np.concatenate(dets) if dets else np.zeros((0, 5), np.float32)
+    if alld.shape[0] == 0:
+        return np.zeros((4, 0), np.float32)
+    if alld.shape[0] >= K.RANK_CURVE_MAX:
+        raise ValueError(f"rank='device' takes fewer than {K.RANK_CURVE_MAX} detections (fp32 counts stay exact), "
+                         f'got {alld.shape[0]}')
+    allg = np.concatenate([np.vstack([g, k]) for g, k in zip(gts, igns)])
+    kept = np.asarray([g.shape[0] for g in gts], dtype=np.int32)
+    with torch.cuda.device(dev):
+        d = _upload(dev, [off([x.shape[0] for x in dets]), off([g.shape[0] + k.shape[0] for g, k in zip(gts, igns)]),
+                          alld, allg, kept])
+        order = K.score_rank_images(d[2], d[0])
+        tp, fp = K.score_map_tpfp(d[2], d[0], d[3], d[1], d[4], order, float(np.float32(iou_thr)))
+        return K.score_map_curve(tp, fp, K.score_rank_global(d[2])).cpu().numpy()
+
+
+def area_from_envelope(recalls, envelope):
+    """average_precision_area given the envelope (max(precisions[k:]) per k) instead of the precisions: the same
+    array of terms, summed by the same numpy call."""
+    mrec = np.hstack((np.zeros(1, recalls.dtype), recalls, np.ones(1, recalls.dtype)))
+    mpre = np.hstack((np.zeros(1, recalls.dtype), envelope, np.zeros(1, recalls.dtype)))
+    ind = np.where(mrec[1:] != mrec[:-1])[0]
+    return np.float32(np.sum((mrec[ind + 1] - mrec[ind]) * mpre[ind + 1]))
+
+
+def eval_map_single_class(det_results, annotations, iou_thr=0.5, device=None, rank=None):
     """eval_map (mean_ap.py:522-686) for one class.  det_results: per image [[n, 5] array] (the per-class
     list of a detector's simple_test) or the [n, 5] array itself; annotations: per image dict(bboxes, labels,
     bboxes_ignore, labels_ignore) as RetinaFaceDataset.get_ann_info returns.  -> (mAP, dict(num_gts, num_dets,
     recall, precision, ap)).  device: a CUDA device takes tp / fp from the device scorer (tpfp_device) instead of
-    tpfp_default; the ranking, the cumulative sums and the area stay on the host."""
+    tpfp_default; the ranking, the cumulative sums and the area stay on the host.  rank='device' (with a device) moves
+    those too (curve_device): the host forms the recalls and sums the area's terms, vectorised, and nothing else.  Its
+    tie rule is the stable one -- descending score, ties in concatenation order -- where the host path's default
+    np.argsort is not stable beyond small arrays: on tied scores the two may order, and so score, differently."""
     assert len(det_results) == len(annotations)
+    check_rank(rank, device is not None)
     dets = [np.asarray(d[0] if isinstance(d, (list, tuple)) else d, dtype=np.float32).reshape(-1, 5) for d in det_results]
     gtl = [np.asarray(ann['bboxes'], dtype=np.float32).reshape(-1, 4) for ann in annotations]
     ignl = [np.asarray(ann.get('bboxes_ignore', np.zeros((0, 4))), dtype=np.float32).reshape(-1, 4) for ann in annotations]
     num_gts = sum(g.shape[0] for g in gtl)
+    eps = np.finfo(np.float32).eps
+    if rank == 'device':
+        tp, _, precisions, envelope = curve_device(dets, gtl, ignl, iou_thr, device)
+        recalls = tp / np.maximum(np.array([num_gts]), eps)
+        ap = area_from_envelope(recalls, envelope)
+        res = dict(num_gts=num_gts, num_dets=int(tp.shape[0]), recall=recalls, precision=precisions, ap=ap)
+        return (float(ap) if num_gts > 0 else 0.0), res
     if device is not None:
         tps, fps = [[v] for v in tpfp_device(dets, gtl, ignl, iou_thr, device)]
     else:
@@ -434,7 +493,6 @@ def eval_map_single_class(det_results, annotations, iou_thr=0.5, device=None):
     order = np.argsort(-alld[:, -1])
     tp = np.cumsum(np.hstack(tps)[order]) if alld.shape[0] else np.zeros(0, dtype=np.float32)
     fp = np.cumsum(np.hstack(fps)[order]) if alld.shape[0] else np.zeros(0, dtype=np.float32)
-    eps = np.finfo(np.float32).eps
     recalls = tp / np.maximum(np.array([num_gts]), eps)      # float64, like the reference's int array / float32 eps
     precisions = tp / np.maximum(tp + fp, eps)
     ap = average_precision_area(recalls, precisions)

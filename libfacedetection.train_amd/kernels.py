@@ -407,6 +407,54 @@ def score_map_tpfp(dets, det_off, gts, gt_off, kept, order, iou_thr):
     return tp, fp
 
 
+# csrc/score.hip, ranking: rows of an image ranked in LDS at once, elements of a radix-sort / scan tile, and the first
+# D the curve refuses
+RANK_SEG_CAP, RANK_RADIX_TILE, RANK_CURVE_MAX = L.RANK_SEG_CAP, L.RANK_RADIX_TILE, L.RANK_CURVE_MAX
+
+
+def _rank_scratch(D, dev):
+    return torch.empty(int(L.load().yunet_score_rank_scratch_bytes(D)), device=dev, dtype=torch.uint8)
+
+
+def score_rank_images(dets, det_off):
+    """yunet_score_rank_images: dets [D,5] fp32, det_off int64 [I+1] -> order int32 [D] as score_map_tpfp takes it (per
+    image: the row visited k-th; descending score, ties by ascending row = np.argsort(-s, kind='stable'))."""
+    n_img, D = det_off.numel() - 1, dets.shape[0]
+    _chk_table(dets.view(-1, 5), torch.float32, D, 'dets')
+    _chk_offsets(det_off, n_img, D, 'det_off')
+    order = torch.empty(D, device=dets.device, dtype=torch.int32)
+    L.check(L.load().yunet_score_rank_images(_p(dets), _p(det_off), n_img, D, _p(order), _stream()),
+            'yunet_score_rank_images')
+    return order
+
+
+def score_rank_global(dets):
+    """yunet_score_rank_global: dets [D,5] fp32 -> rank int32 [D], the stable descending order of all scores (ties in row
+    order = np.argsort(-s, kind='stable'))."""
+    D = dets.shape[0]
+    _chk_table(dets.view(-1, 5), torch.float32, D, 'dets')
+    assert D < 2 ** 31, 'dets: at most 2^31 - 1 rows'
+    rank = torch.empty(D, device=dets.device, dtype=torch.int32)
+    scratch = _rank_scratch(D, dets.device)
+    L.check(L.load().yunet_score_rank_global(_p(dets), D, _p(rank), _p(scratch), _stream()), 'yunet_score_rank_global')
+    return rank
+
+
+def score_map_curve(tp, fp, rank):
+    """yunet_score_map_curve: tp, fp fp32 [D] in row order and rank int32 [D] -> fp32 [4, D] in ranked order: cumulative
+    tp, cumulative fp, precision = ctp / max(ctp + cfp, eps) and its reverse running maximum.  D < RANK_CURVE_MAX."""
+    D = rank.shape[0]
+    _chk_table(tp, torch.float32, D, 'tp')
+    _chk_table(fp, torch.float32, D, 'fp')
+    _chk_table(rank, torch.int32, D, 'rank')
+    assert D < RANK_CURVE_MAX, f'the curve takes fewer than {RANK_CURVE_MAX} rows (exact fp32 counts)'
+    out = torch.empty(4, D, device=rank.device, dtype=torch.float32)
+    scratch = _rank_scratch(D, rank.device)
+    L.check(L.load().yunet_score_map_curve(_p(tp), _p(fp), _p(rank), D, _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]),
+                                           _p(scratch), _stream()), 'yunet_score_map_curve')
+    return out
+
+
 def box_loss_code(box_loss, mode=None):
     """YUNET_BOX_* of a loss class name of mmdet/models/losses/iou_loss.py (+ IoULoss's `mode`)."""
     if box_loss == 'IoULoss':

@@ -522,11 +522,12 @@ class EvalHook(Hook):
     mode='val').  The shipped configs set interval=1001 (> max_epochs): the hook is registered, as in the reference,
     and never fires there.  Distributed (DistEvalHook): the images are sharded over the ranks and the results gathered
     on rank 0 (evaluation.multi_gpu_test), as the reference does -- no rank idles behind a barrier.
-    `evaluation = dict(..., score='device')` scores the gathered detections on rank 0's GPU instead of in numpy."""
+    `evaluation = dict(..., score='device')` scores the gathered detections on rank 0's GPU instead of in numpy;
+    with `rank='device'` beside it the GPU also ranks them and builds the precision curve (evaluation.curve_device)."""
 
     def __init__(self, dataset, interval=1, by_epoch=True, metric='mAP', start=None, scale=(640, 640),
                  max_images=None, save_best=None, distributed=False, samples_per_gpu=1, pipeline=None, cache=None,
-                 score=None, group_by=None, max_batch_pixels='default', **eval_kwargs):
+                 score=None, group_by=None, max_batch_pixels='default', rank=None, **eval_kwargs):
         self.dataset, self.interval, self.by_epoch, self.metric = dataset, int(interval), by_epoch, metric
         self.start, self.scale, self.max_images, self.distributed = start, scale, max_images, distributed
         # the batched device test pipeline (evaluation.single_gpu_test): data.val_dataloader.samples_per_gpu, the
@@ -547,6 +548,8 @@ class EvalHook(Hook):
         if score not in (None, 'host', 'device'):
             raise ValueError(f"EvalHook: score={score!r}; 'host' or 'device'")
         self.score = score
+        from .evaluation import check_rank
+        self.rank = check_rank(rank, score == 'device')
         self.eval_kwargs = {k: v for k, v in eval_kwargs.items() if k in ('iou_thr',)}
         dropped = sorted(k for k in eval_kwargs if k not in self.eval_kwargs)
         if save_best is not None:
@@ -589,6 +592,8 @@ class EvalHook(Hook):
             dets = single_gpu_test(target, self.dataset, dev, self.scale, self.max_images, **how) if runner.rank == 0 else None
         if dets is not None:
             where = dict(device=dev) if self.score == 'device' else {}
+            if self.rank is not None:
+                where['rank'] = self.rank
             res = self.dataset.evaluate(dets, metric=self.metric, **where, **self.eval_kwargs)
             done = runner.iter if self.by_epoch else runner.iter + 1          # iterations completed so far
             entry = dict(mode='val', epoch=runner.epoch + 1, iter=done, **{k: float(v) for k, v in res.items()})
