@@ -48,7 +48,12 @@ typedef struct YunetBN {
                             * that end a kernel spread over `slots` times as many cache lines (at the 10 x 10
                             * and 20 x 20 levels ~250 workgroups x 128 atomics on eight lines cost 4-5 us of a
                             * 14-30 us launch)                  */
-    int32_t reserved_;
+    int32_t det_rows;      /* 0: as above.  R > 0 (the deterministic mode, fp32 storage only): both sum blocks are
+                            * [1 + R][2*C] and `slots` is 1 -- row 0 holds the sums every reader takes, workgroup b of a
+                            * kernel that PRODUCES sums adds its partial sums, accumulated inside the workgroup in a
+                            * fixed order, to row 1 + b with plain loads and stores (no atomics; a launch whose grid
+                            * exceeds R is refused), and yunet_bn_fold adds rows 1 .. R into row 0 in a fixed order
+                            * before the first reader runs.  Rows are zeroed before the step like the blocks above. */
 } YunetBN;
 
 /* Input transform of a fused unit (how it reads its input tensor). */
@@ -133,6 +138,22 @@ int yunet_stem_bwd_rz(const float* img, const float* w, const float* b, const fl
 
 int yunet_dp_fwd(const YunetDP* d, void* stream);
 int yunet_dp_bwd(const YunetDP* d, void* stream);
+
+/* ---- deterministic mode (YunetBN.det_rows > 0) ------------------------------------------------------------------
+ * The kernels that produce BatchNorm sums have a second form whose sums do not depend on the order in which waves
+ * and workgroups happen to run: yunet_dp_fwd (out_bn.det_rows), yunet_dp_bwd (in_bn.det_rows), yunet_pool_bwd(_add),
+ * yunet_upadd_bwd (bn->det_rows) select it from the descriptor, per launch: a launch that produces sums then runs on
+ * the tile kernels (no wave-streaming kernels, no split-bf16 backward); a launch that produces none -- a unit without an
+ * output BN in forward, a unit with an identity input transform in backward -- dispatches as without det_rows.  The
+ * stem has the entry below.  Same inputs, same library and
+ * same device model give the same bytes.  YUNET_EINVAL with bf16 activation storage. */
+/* yunet_stem_fwd with stats = a [1 + det_rows][2*cmid] block (det_rows >= 768, the kernel's grid). */
+int yunet_stem_fwd_det(const float* img, const float* w, const float* b, float* z, double* stats, int det_rows,
+                       int N, int H, int W, int cmid, void* stream);
+/* block[0][j] = sum of block[1 .. rows][j], j < 2*C, in a fixed order: slice s (0 .. 15) adds rows 1 + s, 1 + s + 16,
+ * ... in ascending order starting from 0.0, then the sixteen slice sums are added in ascending s starting from 0.0.
+ * In an op list: YUNET_OP_BN_FOLD with p[0] = block, i[0] = rows, i[1] = C. */
+int yunet_bn_fold(double* block, int rows, int C, void* stream);
 /* rows of wgrad_partials (= persistent grid) yunet_dp_bwd / yunet_stem_bwd use for a shape */
 int yunet_dp_bwd_blocks(int N, int H, int W, int cin, int cout);
 /* 1 if yunet_dp_fwd / yunet_dp_bwd accept YunetDP.pool_out / pool_idx for this shape (the unpacked
@@ -360,7 +381,8 @@ enum {
     YUNET_OP_ASSIGN, YUNET_OP_LOSS_NORM, YUNET_OP_LOSS, YUNET_OP_LOSS_FINALIZE,
     YUNET_OP_SGD, YUNET_OP_MEMSET, YUNET_OP_BN_BATCH, YUNET_OP_REDUCE_BATCH,
     YUNET_OP_FORK, YUNET_OP_JOIN,
-    YUNET_OP_ADD      /* ABI 9: yunet_add(p[0], p[1], p[2], n = i[1] << 32 | i[0]) */
+    YUNET_OP_ADD,     /* ABI 9: yunet_add(p[0], p[1], p[2], n = i[1] << 32 | i[0]) */
+    YUNET_OP_BN_FOLD  /* yunet_bn_fold(p[0], i[0], i[1]); YUNET_OP_STEM_FWD with i[4] = det_rows > 0 is yunet_stem_fwd_det */
 };
 /* Lanes (ABI 4).  The head chains of the pyramid levels (share conv -> fused head, and their backward) are
  * mutually independent: mmdet/models/dense_heads/yunet_head.py:175-247 walks them in a Python loop, and on the

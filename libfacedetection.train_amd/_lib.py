@@ -28,7 +28,7 @@ F32, BF16 = 0, 1
 BOX_EIOU, BOX_DIOU, BOX_IOU_LINEAR, BOX_IOU_SQUARE, BOX_IOU_LOG, BOX_GIOU, BOX_CIOU = 0, 1, 2, 3, 4, 5, 6
 (OP_STEM_FWD, OP_STEM_BWD, OP_DP_FWD, OP_DP_BWD, OP_POOL_FWD, OP_POOL_BWD, OP_UPADD_FWD,
  OP_UPADD_BWD, OP_BN_RUNNING, OP_BN_PARAM_GRAD, OP_REDUCE_PARTIALS, OP_ASSIGN, OP_LOSS_NORM,
- OP_LOSS, OP_LOSS_FINALIZE, OP_SGD, OP_MEMSET, OP_BN_BATCH, OP_REDUCE_BATCH, OP_FORK, OP_JOIN, OP_ADD) = range(1, 23)
+ OP_LOSS, OP_LOSS_FINALIZE, OP_SGD, OP_MEMSET, OP_BN_BATCH, OP_REDUCE_BATCH, OP_FORK, OP_JOIN, OP_ADD, OP_BN_FOLD) = range(1, 24)
 OP_LANE, MAX_LANES = 10, 2          # YunetOp.i[OP_LANE]: side stream of the op (0 = the caller's stream)
 OP_GROUP, DP_GROUP_MAX = 9, 3       # YunetOp.i[OP_GROUP] = g: this DP_FWD op and the g - 1 after it are independent (ABI 10)
 
@@ -36,7 +36,7 @@ OP_GROUP, DP_GROUP_MAX = 9, 3       # YunetOp.i[OP_GROUP] = g: this DP_FWD op an
 class YunetBN(C.Structure):
     _fields_ = [('stats', C.c_void_p), ('bstats', C.c_void_p), ('gamma', C.c_void_p),
                 ('beta', C.c_void_p), ('count', C.c_int32), ('eps', C.c_float),
-                ('slots', C.c_int32), ('reserved_', C.c_int32)]
+                ('slots', C.c_int32), ('det_rows', C.c_int32)]
 
 
 class YunetDP(C.Structure):
@@ -129,6 +129,8 @@ _SIGNATURES = {
     'yunet_conv_blocks': (C.c_int, []),
     'yunet_loss_blocks': (C.c_int, [C.c_int, C.c_int]),
     'yunet_stem_fwd': (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
+    'yunet_stem_fwd_det': (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
+    'yunet_bn_fold': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     'yunet_stem_bwd': (C.c_int, [C.c_void_p] * 3 + [C.POINTER(YunetBN), C.c_void_p] +
                        [C.c_int] * 5 + [C.c_void_p]),
     'yunet_stem_bwd_rz': (C.c_int, [C.c_void_p] * 4 + [C.POINTER(YunetBN), C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),

@@ -257,6 +257,12 @@ extern "C" int yunet_exec(const YunetOp* ops, int n_ops, void* main_stream) {
         }
         switch (o.opcode) {
             case YUNET_OP_STEM_FWD:
+                if (o.i[4] > 0) {        // deterministic BatchNorm sums: p[4] is a [1 + i[4]][32] block (fp32 storage only)
+                    rc = o.i[11] == YUNET_BF16 ? YUNET_EINVAL
+                                               : yunet_stem_fwd_det((const float*)o.p[0], (const float*)o.p[1], (const float*)o.p[2], (float*)o.p[3],
+                                                                    (double*)o.p[4], o.i[4], o.i[0], o.i[1], o.i[2], o.i[3], stream);
+                    break;
+                }
                 rc = (o.i[11] == YUNET_BF16 ? yunet_stem_fwd_bf16 : yunet_stem_fwd)((const float*)o.p[0], (const float*)o.p[1], (const float*)o.p[2],
                                     (float*)o.p[3], (double*)o.p[4], o.i[0], o.i[1], o.i[2], o.i[3],
                                     stream);
@@ -367,6 +373,9 @@ extern "C" int yunet_exec(const YunetOp* ops, int n_ops, void* main_stream) {
                 rc = yunet_add((const float*)o.p[0], (const float*)o.p[1], (float*)o.p[2], n, stream);
                 break;
             }
+            case YUNET_OP_BN_FOLD:
+                rc = yunet_bn_fold((double*)o.p[0], o.i[0], o.i[1], stream);
+                break;
             case YUNET_OP_BN_BATCH:
                 rc = yunet_bn_batch((const int32_t*)o.p[0], o.i[0], (const double*)o.p[1], (float*)o.p[2],
                                     (float*)o.p[3], o.f[0], (float*)o.p[4], o.i[1], stream);

@@ -386,6 +386,16 @@ __device__ __forceinline__ void atomic_add_f64(double* p, double v) {
     __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Deterministic mode (YunetBN::det_rows = R > 0, include/yunet_hip.h): the sum blocks are [1 + R][2C]; workgroup b of a
+// kernel that produces sums owns row 1 + b and adds to it with a plain load and store.  The launches that feed one block
+// (the consumers of one tensor, in backward) run one after the other on one stream, so a row is the sum of their
+// contributions in launch order.  A launcher refuses a grid above R (bn_det_fits); yunet_bn_fold adds the rows into row 0.
+__device__ __forceinline__ void bn_det_add(const double* base, int C, int i, double v) {
+    double* p = const_cast<double*>(base) + (size_t)(1 + blockIdx.x) * 2 * C + i;
+    *p += v;
+}
+static inline bool bn_det_fits(const YunetBN& bn, int grid) { return bn.det_rows >= grid && bn.slots <= 1; }
+
 static inline int hip_status() { return -(int)hipGetLastError(); }
 
 // conv_fwd64.hip: the plain fp32 64 -> 64 forward unit (no packing, no fused pooling)
@@ -400,5 +410,7 @@ int ACT_SUFFIX(launch_dp_fwd16s)(const YunetDP* d, hipStream_t stream);
 // conv_stem.hip: the fp32 stem on the matrix cores (forward; weight gradient with z recomputed from the image)
 int ACT_SUFFIX(launch_stem_fwd_mma)(const float* img, const float* w, const float* b, float* z, double* stats, int N, int H, int W,
                                     hipStream_t stream);
+int launch_stem_fwd_mma_det(const float* img, const float* w, const float* b, float* z, double* stats, int det_rows, int N, int H,
+                            int W, hipStream_t stream);      // fp32 storage only: stats = a [1 + det_rows][32] block
 int launch_stem_bwd_mma(const float* img, const float* w, const float* b, const float* dy, const YunetBN* bn, float* partials,
                         int blocks, int N, int H, int W, hipStream_t stream);

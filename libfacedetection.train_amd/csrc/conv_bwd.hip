@@ -81,7 +81,11 @@ struct BwdGeom {
 // FULL: the map is an exact multiple of the tile (H % TH == 0, W % TW == 0: the 160 x 160 and 80 x 80 levels), so
 // every interior tile pixel is a real pixel and the per-element validity tests -- hundreds of integer
 // instructions per tile -- compile away.  The launch picks the instance.
-template <int CIN, int COUT, int TH, int TW, bool PACKED, int GEMM = 0, bool POOLDY = false, bool FULL = false>
+// DET (YunetBN::det_rows of the producer's BatchNorm, include/yunet_hip.h): the producer's BN-backward sums take a fixed
+// order -- per tile every wave leaves its partial in a row of its own (in the dz tile, dead by then), thread c adds the
+// eight rows in wave order into s_bst, and the workgroup's sums go to its own row of the block (common.h: bn_det_add).
+// fp32 storage only.
+template <int CIN, int COUT, int TH, int TW, bool PACKED, int GEMM = 0, bool POOLDY = false, bool FULL = false, bool DET = false>
 __global__ __launch_bounds__(BWD_THREADS) void dp_bwd_kernel(const YunetDP d, const PackGeom pk) {
     using G = BwdGeom<CIN, COUT, TH, TW, GEMM>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -746,7 +750,13 @@ __global__ __launch_bounds__(BWD_THREADS) void dp_bwd_kernel(const YunetDP d, co
                     }
                 t0 += __shfl_xor(t0, 16, 64); t1 += __shfl_xor(t1, 16, 64);
                 t0 += __shfl_xor(t0, 32, 64); t1 += __shfl_xor(t1, 32, 64);
-                if (g == 0) {
+                if constexpr (DET) {
+                    // s_dz was last read by the depthwise phase (two barriers back) and is rewritten by the next tile's stage
+                    // (after the barrier that ends this tile): [BWD_WAVES][2 CIN] doubles of it carry the waves' partials
+                    static_assert((size_t)BWD_WAVES * 2 * CIN * 8 <= (size_t)G::HP * G::LSO * 4, "wave rows fit in the dz tile");
+                    double* wrow = reinterpret_cast<double*>(s_dz) + wid * 2 * CIN;
+                    if (g == 0) { wrow[c] = (double)t0; wrow[CIN + c] = (double)t1; }
+                } else if (g == 0) {
                     __hip_atomic_fetch_add(s_bst + c, (double)t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     __hip_atomic_fetch_add(s_bst + CIN + c, (double)t1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
@@ -761,6 +771,15 @@ __global__ __launch_bounds__(BWD_THREADS) void dp_bwd_kernel(const YunetDP d, co
                         s_a[((wid * G::MPW + mi) * 16 + 4 * g + r) * G::LSI + nt * 16 + l15] = da[mi][nt][r];
         }
         __syncthreads();
+        if constexpr (DET) {
+            if (bn_in && tid < 2 * CIN) {
+                const double* wrow = reinterpret_cast<const double*>(s_dz) + tid;
+                double v = s_bst[tid];
+#pragma unroll
+                for (int wv = 0; wv < BWD_WAVES; ++wv) v += wrow[wv * 2 * CIN];
+                s_bst[tid] = v;
+            }
+        }
 
         // ---- dx store (coalesced) + BN-backward sums of the producer ------------------------------
         if (d.dx && !(abl & 16)) {
@@ -856,10 +875,12 @@ __global__ __launch_bounds__(BWD_THREADS) void dp_bwd_kernel(const YunetDP d, co
     __syncthreads();
     reduce_pass(1, 5);
     // (c) BN-backward sums of the producer: one global fp64 atomic per channel
+    if constexpr (DET) {
+        if (bn_in && d.dx && d.in_bn.bstats && tid < 2 * CIN) bn_det_add(d.in_bn.bstats, CIN, tid, s_bst[tid]);
+    } else
     if (bn_in && d.dx && d.in_bn.bstats && tid < 2 * CIN) atomic_add_f64(bn_slot(d.in_bn.bstats, d.in_bn.slots, CIN) + tid, s_bst[tid]);
 }
-
-template <int CIN, int COUT, int TH, int TW, bool PACKED = false, int GEMM = 0, bool POOLDY = false, bool FULL = false>
+template <int CIN, int COUT, int TH, int TW, bool PACKED = false, int GEMM = 0, bool POOLDY = false, bool FULL = false, bool DET = false>
 int launch_dp_bwd(const YunetDP* d, hipStream_t stream) {
     using G = BwdGeom<CIN, COUT, TH, TW, GEMM>;
     if constexpr (FULL) {
@@ -868,8 +889,10 @@ int launch_dp_bwd(const YunetDP* d, hipStream_t stream) {
     static PerDevice attr_set;      // per device (common.h)
     PackGeom pk;
     const int grid = dp_bwd_launch_setup<TH, TW, PACKED>(
-        d, attr_set, reinterpret_cast<const void*>(dp_bwd_kernel<CIN, COUT, TH, TW, PACKED, GEMM, POOLDY, FULL>), G::SMEM, pk);
+        d, attr_set, reinterpret_cast<const void*>(dp_bwd_kernel<CIN, COUT, TH, TW, PACKED, GEMM, POOLDY, FULL, DET>), G::SMEM, pk);
     if (grid < 0) return grid;
+    static_assert(!DET || YUNET_ACT_DTYPE == YUNET_F32, "deterministic sums: fp32 storage only");
+    if (DET && !bn_det_fits(d->in_bn, grid)) return YUNET_EINVAL;
     if (grid < d->wgrad_blocks) {
         // yunet_dp_bwd_blocks() sized the partial buffer for another kernel's grid (the 64 -> 64 units on 8 x 8
         // tiles, while this launch is their exact-fp32 A/B variant on 8 x 16 tiles): the reduction sums every row,
@@ -879,7 +902,7 @@ int launch_dp_bwd(const YunetDP* d, hipStream_t stream) {
                            stream) != hipSuccess)
             return hip_status();
     }
-    hipLaunchKernelGGL((dp_bwd_kernel<CIN, COUT, TH, TW, PACKED, GEMM, POOLDY, FULL>), dim3(grid), dim3(BWD_THREADS), G::SMEM,
+    hipLaunchKernelGGL((dp_bwd_kernel<CIN, COUT, TH, TW, PACKED, GEMM, POOLDY, FULL, DET>), dim3(grid), dim3(BWD_THREADS), G::SMEM,
                        stream, *d, pk);
     return hip_status();
 }
@@ -893,6 +916,33 @@ extern "C" int ACT_SUFFIX(yunet_dp_bwd)(const YunetDP* d, void* stream) {
         d->wgrad_blocks != yunet_dp_bwd_blocks(d->N, d->H, d->W, d->cin, d->cout))
         return YUNET_EINVAL;   // the partial buffer must have exactly the rows the grid writes
     if (d->in_transform != YUNET_T_IDENTITY && d->in_transform != YUNET_T_BNRELU) return YUNET_EINVAL;
+    if (d->in_transform == YUNET_T_BNRELU && d->dx && d->in_bn.bstats && d->in_bn.det_rows) {
+        // deterministic BatchNorm sums (include/yunet_hip.h): the tile kernel in its DET form, exact-fp32 GEMMs, for every
+        // unit -- the same tiles, packed canvas and pooled dy as below; not dp_bwd64, dp_bwd16s or the split-bf16 GEMMs
+#ifndef YUNET_ACT_BF16
+        if (d->pool_idx) {
+            if (!yunet_dp_pool_fusion_ok(d->N, d->H, d->W, d->cin, d->cout) || !d->out_has_bn) return YUNET_EINVAL;
+            if (d->cin == 16) return launch_dp_bwd<16, 16, 16, 32, false, 0, true, false, true>(d, s);
+            if (d->cin == 32) return launch_dp_bwd<32, 64, 8, 16, false, 0, true, false, true>(d, s);
+            return launch_dp_bwd<64, 64, 8, 16, false, 0, true, false, true>(d, s);
+        }
+        if (dp_bwd_big_tile(d->H, d->W, d->cin, d->cout)) return launch_dp_bwd<16, 16, 16, 32, false, 0, false, false, true>(d, s);
+        if (dp_use_pack_bwd(d->N, d->H, d->W, d->cin, d->cout))
+            return d->cout == 64 ? launch_dp_bwd<64, 64, 8, 16, true, 0, false, false, true>(d, s)
+                                 : launch_dp_bwd<64, 16, 8, 16, true, 0, false, false, true>(d, s);
+#define DP_CASE(ci, co) \
+    if (d->cin == ci && d->cout == co) return launch_dp_bwd<ci, co, 8, 16, false, 0, false, false, true>(d, s);
+        DP_CASE(16, 16)
+        DP_CASE(16, 32)
+        DP_CASE(16, 64)
+        DP_CASE(32, 32)
+        DP_CASE(32, 64)
+        DP_CASE(64, 64)
+        DP_CASE(64, 16)
+#undef DP_CASE
+#endif
+        return YUNET_EINVAL;
+    }
     // the 16 -> 16 unit on the 160 x 160 / 80 x 80 levels: wave-streaming kernel that recomputes z from x instead of
     // reading it (conv_bwd16.hip); same grid and partial rows as the tile kernel it replaces
     if (d->cin == 16 && d->cout == 16 && dp_bwd_big_tile(d->H, d->W, 16, 16) && d->out_has_bn && d->dx && !d->accumulate_dx &&

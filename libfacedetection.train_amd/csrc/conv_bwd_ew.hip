@@ -155,6 +155,8 @@ __global__ __launch_bounds__(256) void stem_bwd_kernel(const float* __restrict__
 // upsample-add of the neck sends to a pyramid tap (dsum, identity branch).  Both shares pass the same ReLU mask and
 // feed the same BatchNorm-backward sums, so dx = mask (extra + route(dy_out)) is written once here instead of
 // upadd_bwd writing mask extra and this kernel re-reading z and read-modify-writing dx (engine.py: _upadd / _pool).
+// (DET: the deterministic form of the sums' flush, common.h: bn_det_add; fp32 storage only)
+template <bool DET = false>
 __global__ __launch_bounds__(256) void pool_bwd_kernel(const act_t* __restrict__ z, YunetBN bn,
                                                        const float* __restrict__ dyo,
                                                        const float* __restrict__ extra,
@@ -239,10 +241,12 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const act_t* __restrict__
         const int q = c >> 2, kk = (c & 3) + 4 * which;
         double v = 0.0;
         for (int p = 0; p < 256 / C4; ++p) v += red[(p * C4 + q) * 8 + kk];
-        atomic_add_f64(bn_slot(bn.bstats, bn.slots, C) + which * C + c, v);
+        if constexpr (DET) bn_det_add(bn.bstats, C, which * C + c, v);
+        else atomic_add_f64(bn_slot(bn.bstats, bn.slots, C) + which * C + c, v);
     }
 }
 
+template <bool DET = false>
 __global__ __launch_bounds__(256) void upadd_bwd_kernel(const act_t* __restrict__ za, YunetBN bna,
                                                         const act_t* __restrict__ zb, YunetBN bnb,
                                                         const float* __restrict__ dout,
@@ -330,7 +334,8 @@ __global__ __launch_bounds__(256) void upadd_bwd_kernel(const act_t* __restrict_
         const int q = c >> 2, kk = (c & 3) + 4 * which;                              \
         double v = 0.0;                                                              \
         for (int p = 0; p < 256 / C4; ++p) v += red[(p * C4 + q) * 8 + kk];          \
-        atomic_add_f64(bn_slot(DST, SLOTS, C) + which * C + c, v);                   \
+        if constexpr (DET) bn_det_add(DST, C, which * C + c, v);                     \
+        else atomic_add_f64(bn_slot(DST, SLOTS, C) + which * C + c, v);              \
     }
     UPADD_FLUSH(bsa, (dxa ? bna.bstats : nullptr), bna.slots)
     UPADD_FLUSH(bsb, bnb.bstats, bnb.slots)
@@ -343,6 +348,7 @@ __global__ __launch_bounds__(256) void upadd_bwd_kernel(const act_t* __restrict_
 // and separated a thread's four fine loads by them (3.3 TB/s); here the four loads + the coarse z are issued together
 // and the mask is a select (adding the +0.0 of a masked-out element leaves every sum unchanged: same values, same
 // order of additions as the general kernel).
+template <bool DET = false>
 __global__ __launch_bounds__(256) void upadd_bwd_coarse_kernel(const act_t* __restrict__ zb, YunetBN bnb,
                                                                const float* __restrict__ dout, float* __restrict__ dxb,
                                                                int acc_b, int N, int H, int W, int C) {
@@ -396,7 +402,8 @@ __global__ __launch_bounds__(256) void upadd_bwd_coarse_kernel(const act_t* __re
         const int q = c >> 2, kk = (c & 3) + 4 * which;
         double v = 0.0;
         for (int p = 0; p < 256 / C4; ++p) v += red[(p * C4 + q) * 8 + kk];
-        atomic_add_f64(bn_slot(bnb.bstats, bnb.slots, C) + which * C + c, v);
+        if constexpr (DET) bn_det_add(bnb.bstats, C, which * C + c, v);
+        else atomic_add_f64(bn_slot(bnb.bstats, bnb.slots, C) + which * C + c, v);
     }
 }
 
@@ -419,7 +426,17 @@ extern "C" int ACT_SUFFIX(yunet_pool_bwd_add)(const float* z, const YunetBN* bn,
                                               float* dx, int accumulate, int N, int H, int W, int C, void* stream) {
     if ((H & 1) || (W & 1) || (C & 3) || (256 % (C / 4)) || C > 64) return YUNET_EINVAL;
     const long long total = (long long)N * (H / 2) * (W / 2) * (C / 4);
-    hipLaunchKernelGGL(pool_bwd_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream,
+    if (bn->det_rows && bn->bstats) {          // deterministic sums (include/yunet_hip.h): fp32 storage only
+#ifndef YUNET_ACT_BF16
+        if (!bn_det_fits(*bn, ew_grid(total))) return YUNET_EINVAL;
+        hipLaunchKernelGGL(pool_bwd_kernel<true>, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream,
+                           reinterpret_cast<const act_t*>(z), *bn, dy_out, extra, dx, accumulate, N, H, W, C);
+        return hip_status();
+#else
+        return YUNET_EINVAL;
+#endif
+    }
+    hipLaunchKernelGGL(pool_bwd_kernel<false>, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const act_t*>(z), *bn, dy_out, extra, dx, accumulate, N, H, W, C);
     return hip_status();
 }
@@ -435,12 +452,28 @@ extern "C" int ACT_SUFFIX(yunet_upadd_bwd)(const float* za, const YunetBN* bna, 
                                            void* stream) {
     if ((H & 1) || (W & 1) || (C & 3) || (256 % (C / 4)) || C > 64) return YUNET_EINVAL;
     const long long total = (long long)N * (H / 2) * (W / 2) * (C / 4);
+    if ((bnb->det_rows && bnb->bstats) || (dxa && bna->det_rows && bna->bstats)) {      // deterministic sums: both blocks or neither
+#ifndef YUNET_ACT_BF16
+        if (!bnb->bstats || !bn_det_fits(*bnb, ew_grid(total)) || (dxa && (!bna->bstats || !bn_det_fits(*bna, ew_grid(total)))))
+            return YUNET_EINVAL;
+        if (!dxa)
+            hipLaunchKernelGGL(upadd_bwd_coarse_kernel<true>, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream,
+                               reinterpret_cast<const act_t*>(zb), *bnb, dout, dxb, accumulate_b, N, H, W, C);
+        else
+            hipLaunchKernelGGL(upadd_bwd_kernel<true>, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream,
+                               reinterpret_cast<const act_t*>(za), *bna, reinterpret_cast<const act_t*>(zb), *bnb, dout, dxa,
+                               accumulate_a, dxb, accumulate_b, N, H, W, C);
+        return hip_status();
+#else
+        return YUNET_EINVAL;
+#endif
+    }
     if (!dxa && yunet_options().upadd_coarse) {        // the coarse gradient alone: dedicated kernel (round 5)
-        hipLaunchKernelGGL(upadd_bwd_coarse_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL(upadd_bwd_coarse_kernel<false>, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream,
                            reinterpret_cast<const act_t*>(zb), *bnb, dout, dxb, accumulate_b, N, H, W, C);
         return hip_status();
     }
-    hipLaunchKernelGGL(upadd_bwd_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(upadd_bwd_kernel<false>, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const act_t*>(za), *bna, reinterpret_cast<const act_t*>(zb), *bnb, dout, dxa,
                        accumulate_a, dxb, accumulate_b, N, H, W, C);
     return hip_status();

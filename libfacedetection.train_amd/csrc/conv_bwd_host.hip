@@ -87,7 +87,43 @@ __global__ __launch_bounds__(1024) void reduce_partials_batch_kernel(const Yunet
     }
 }
 
+// Deterministic mode (YunetBN::det_rows): block[0][j] = sum of rows 1 .. rows of a [1 + rows][width] fp64 block.  16 columns
+// x 16 row slices per workgroup (128-byte row segments); slice s adds rows 1 + s, 1 + s + 16, ... in ascending order, thread
+// (s = 0, column) adds the sixteen slice sums in ascending s: the order include/yunet_hip.h documents, whatever the grid.
+__global__ __launch_bounds__(256) void bn_fold_kernel(double* __restrict__ block, int rows, int width) {
+    __shared__ double s[16][16];
+    const int cl = threadIdx.x & 15, sl = threadIdx.x >> 4;
+    const int col = blockIdx.x * 16 + cl;
+    double v = 0.0;
+    if (col < width) {
+        const double* p = block + (size_t)width + col;
+        int r = sl;
+        for (; r + 16 * 7 < rows; r += 16 * 8) {          // eight loads in flight, added in row order
+            double x[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) x[u] = p[(size_t)(r + 16 * u) * width];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v += x[u];
+        }
+        for (; r < rows; r += 16) v += p[(size_t)r * width];
+    }
+    s[sl][cl] = v;
+    __syncthreads();
+    if (sl == 0 && col < width) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) t += s[k][cl];
+        block[col] = t;
+    }
+}
+
 }  // namespace
+
+extern "C" int yunet_bn_fold(double* block, int rows, int C, void* stream) {
+    if (!block || rows < 1 || C < 1 || C > 4096) return YUNET_EINVAL;
+    hipLaunchKernelGGL(bn_fold_kernel, dim3((2 * C + 15) / 16), dim3(256), 0, (hipStream_t)stream, block, rows, 2 * C);
+    return hip_status();
+}
 
 extern "C" int yunet_dp_bwd_blocks(int N, int H, int W, int cin, int cout) {
     const bool two_per_cu = cin == 64 && cout == 64 && bwd64_nw(N, H, W) == 4;      // dp_bwd64 on 8 x 8 tiles

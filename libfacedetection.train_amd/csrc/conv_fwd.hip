@@ -208,7 +208,9 @@ struct DpGeom {
 // transform is the raw maximum / minimum: the depthwise phase writes, next to z, the raw winner of every 2x2
 // window [N,H/2,W/2,COUT] and its window position 2*dy + dx (one byte per element).  The consumer reads the
 // pooled tensor with the ordinary BN+ReLU input transform -- no pooling kernel, no second pass over z.
-template <int CIN, int COUT, int TH, int TW, bool PACKED, bool POOL = false>
+// DET (YunetBN::det_rows, include/yunet_hip.h): the workgroup's sums -- already added up in a fixed order -- go to its own
+// row of the block instead of a replica atomic (common.h: bn_det_add).  fp32 storage only.
+template <int CIN, int COUT, int TH, int TW, bool PACKED, bool POOL = false, bool DET = false>
 __global__ __launch_bounds__(256) void dp_fwd_kernel(const YunetDP d, const PackGeom pk) {
     static_assert(!(POOL && PACKED) && (!POOL || (TH % 2 == 0 && TW % 2 == 0)), "fused pooling: unpacked, even tiles");
     using G = DpGeom<CIN, COUT, TH, TW>;
@@ -610,17 +612,17 @@ __global__ __launch_bounds__(256) void dp_fwd_kernel(const YunetDP d, const Pack
             const int q = c >> 2, k = (c & 3) + 4 * which;
             double v = 0.0;
             for (int p = 0; p < G::PG; ++p) v += red[(p * G::C4O + q) * 8 + k];
-            atomic_add_f64(bn_slot(d.out_bn.stats, d.out_bn.slots, COUT) + which * COUT + c, v);
+            if constexpr (DET) bn_det_add(d.out_bn.stats, COUT, which * COUT + c, v);
+            else atomic_add_f64(bn_slot(d.out_bn.stats, d.out_bn.slots, COUT) + which * COUT + c, v);
         }
     }
 }
-
-template <int CIN, int COUT, int TH, int TW, bool PACKED = false, bool POOL = false>
+template <int CIN, int COUT, int TH, int TW, bool PACKED = false, bool POOL = false, bool DET = false>
 int launch_dp_fwd(const YunetDP* d, hipStream_t stream) {
     using G = DpGeom<CIN, COUT, TH, TW>;
     static PerDevice per_cu;        // resident workgroups per CU, per device (common.h)
     const int blocks_per_cu = per_device(per_cu, [] {
-        const void* fn = reinterpret_cast<const void*>(dp_fwd_kernel<CIN, COUT, TH, TW, PACKED, POOL>);
+        const void* fn = reinterpret_cast<const void*>(dp_fwd_kernel<CIN, COUT, TH, TW, PACKED, POOL, DET>);
         if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::SMEM) != hipSuccess) return -1;
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, G::SMEM) != hipSuccess || nb < 1)
@@ -639,7 +641,9 @@ int launch_dp_fwd(const YunetDP* d, hipStream_t stream) {
                              : d->N * ((d->W + TW - 1) / TW) * ((d->H + TH - 1) / TH);
     const int resident = yunet_cu_count() * blocks_per_cu;
     const int grid = tiles < resident ? tiles : resident;
-    hipLaunchKernelGGL((dp_fwd_kernel<CIN, COUT, TH, TW, PACKED, POOL>), dim3(grid), dim3(256), G::SMEM, stream, *d, pk);
+    static_assert(!DET || YUNET_ACT_DTYPE == YUNET_F32, "deterministic sums: fp32 storage only");
+    if (DET && !bn_det_fits(d->out_bn, grid)) return YUNET_EINVAL;
+    hipLaunchKernelGGL((dp_fwd_kernel<CIN, COUT, TH, TW, PACKED, POOL, DET>), dim3(grid), dim3(256), G::SMEM, stream, *d, pk);
     return hip_status();
 }
 
@@ -746,11 +750,46 @@ extern "C" int ACT_SUFFIX(yunet_stem_fwd)(const float* img, const float* w, cons
     return hip_status();
 }
 
+#ifndef YUNET_ACT_BF16
+extern "C" int yunet_stem_fwd_det(const float* img, const float* w, const float* b, float* z, double* stats, int det_rows,
+                                  int N, int H, int W, int cmid, void* stream) {
+    if (cmid != 16 || (H & 1) || (W & 1) || !stats) return YUNET_EINVAL;
+    return launch_stem_fwd_mma_det(img, w, b, z, stats, det_rows, N, H, W, (hipStream_t)stream);
+}
+#endif
+
 extern "C" int ACT_SUFFIX(yunet_dp_fwd)(const YunetDP* d, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (d->x_dtype != YUNET_ACT_DTYPE) return YUNET_EINVAL;
     if (d->z_dtype != YUNET_ACT_DTYPE && !(d->cout == 16 && d->z_dtype == YUNET_F32)) return YUNET_EINVAL;
     if (d->in_transform != YUNET_T_IDENTITY && d->in_transform != YUNET_T_BNRELU) return YUNET_EINVAL;
+    if (d->out_has_bn && d->out_bn.det_rows) {
+        // deterministic BatchNorm sums (include/yunet_hip.h): the tile kernel in its DET form for every unit -- the same
+        // choice of tile, packed canvas and fused pooling as below, none of the wave-streaming kernels
+#ifndef YUNET_ACT_BF16
+        if (d->z_dtype != YUNET_ACT_DTYPE || !d->out_bn.stats) return YUNET_EINVAL;
+        if (d->pool_out) {
+            if (!yunet_dp_pool_fusion_ok(d->N, d->H, d->W, d->cin, d->cout) || !d->out_bn.gamma || !d->pool_idx ||
+                (reinterpret_cast<uintptr_t>(d->pool_idx) & 3))
+                return YUNET_EINVAL;
+            if (d->cin == 16) return launch_dp_fwd<16, 16, 16, 32, false, true, true>(d, s);
+            if (d->cin == 32) return launch_dp_fwd<32, 64, 8, 16, false, true, true>(d, s);
+            return launch_dp_fwd<64, 64, 8, 16, false, true, true>(d, s);
+        }
+        if (d->cin == 16 && d->cout == 16 && d->W >= 64 && d->H >= 32) return launch_dp_fwd<16, 16, 16, 32, false, false, true>(d, s);
+        if (dp_use_pack(d->N, d->H, d->W, d->cin, d->cout) && d->cout == 64) return launch_dp_fwd<64, 64, 8, 16, true, false, true>(d, s);
+#define DP_CASE(ci, co) \
+    if (d->cin == ci && d->cout == co) return launch_dp_fwd<ci, co, 8, 16, false, false, true>(d, s);
+        DP_CASE(16, 16)
+        DP_CASE(16, 32)
+        DP_CASE(16, 64)
+        DP_CASE(32, 32)
+        DP_CASE(32, 64)
+        DP_CASE(64, 64)
+#undef DP_CASE
+#endif
+        return YUNET_EINVAL;
+    }
     // units with 16 input channels: wave-streaming kernels (conv_fwd16.hip)
     if (d->cin == 16 && (d->cout == 16 || (d->cout == 64 && !d->pool_out)) && d->z_dtype == YUNET_ACT_DTYPE && !d->prof && yunet_options().fwd16s &&
         (!d->pool_out || (yunet_dp_pool_fusion_ok(d->N, d->H, d->W, 16, 16) && d->out_bn.gamma && d->pool_idx &&
@@ -798,7 +837,8 @@ extern "C" int ACT_SUFFIX(yunet_dp_fwd_group)(const YunetDP* const* units, int n
     bool one_grid = n >= 2 && yunet_options().fwd_group != 0;
     for (int i = 0; i < n && one_grid; ++i) {
         const YunetDP* d = units[i];
-        one_grid = d && d->x_dtype == YUNET_ACT_DTYPE && d->z_dtype == YUNET_ACT_DTYPE && d->cin == 64 && d->cout == 64 &&
+        one_grid = d && !(d->out_has_bn && d->out_bn.det_rows) &&
+                   d->x_dtype == YUNET_ACT_DTYPE && d->z_dtype == YUNET_ACT_DTYPE && d->cin == 64 && d->cout == 64 &&
                    !d->pool_out && !d->prof && yunet_options().fwd64s != 0 &&
                    (d->in_transform == YUNET_T_IDENTITY || d->in_transform == YUNET_T_BNRELU) &&
                    !(dp_use_pack(d->N, d->H, d->W, d->cin, d->cout) && yunet_options().fwd64s < 2);

@@ -31,15 +31,18 @@ constexpr int WROW = C * 27 + C;
 static_assert(WAVES * WROW <= WAVES * WAVE_F, "flush area");
 }  // namespace stm
 
-template <bool BWD>
+// DET (forward only; YunetBN::det_rows, include/yunet_hip.h): every wave keeps its own fp64 row of band sums, the rows
+// are added in wave order and the workgroup's sums go to its own row of `stats` (common.h: bn_det_add) -- no atomics.
+template <bool BWD, bool DET = false>
 __global__ __launch_bounds__(stm::NTHR) void stem_mma_kernel(const float* __restrict__ img, const float* __restrict__ w,
                                                              const float* __restrict__ b, float* __restrict__ z,
                                                              double* __restrict__ stats, const float* __restrict__ dy,
                                                              const YunetBN bn, float* __restrict__ partials, const int N,
                                                              const int H, const int W, const int R) {
     using namespace stm;
+    static_assert(!(BWD && DET), "the weight gradient has no sums to order");
     __shared__ __attribute__((aligned(16))) float sm[WAVES * WAVE_F];
-    __shared__ double s_stat[2 * C];
+    __shared__ double s_stat[(DET ? WAVES : 1) * 2 * C];
     __shared__ __attribute__((aligned(16))) float s_k[4][C];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -48,7 +51,7 @@ __global__ __launch_bounds__(stm::NTHR) void stem_mma_kernel(const float* __rest
     float* ring = sm + wid * WAVE_F;
     float* slot = ring + RING_F;
 
-    if (tid < 2 * C) s_stat[tid] = 0.0;
+    if (tid < (DET ? WAVES : 1) * 2 * C) s_stat[tid] = 0.0;
     if (BWD && tid < C) {
         const BNFold f = bn_fold(bn_bwd_coef(bn, C, tid));       // dz = A dy + B z + D (common.h)
         s_k[0][tid] = f.a; s_k[1][tid] = f.b; s_k[2][tid] = f.dh; s_k[3][tid] = f.dl;
@@ -225,13 +228,22 @@ __global__ __launch_bounds__(stm::NTHR) void stem_mma_kernel(const float* __rest
                 float v = ts[i];
 #pragma unroll
                 for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m, 64);
-                if (l15 == 0)
+                if constexpr (DET) {
+                    if (l15 == 0) s_stat[wid * 2 * C + (i < 4 ? 0 : C) + 4 * g + (i & 3)] += (double)v;      // the wave's own row, task after task
+                } else if (l15 == 0)
                     __hip_atomic_fetch_add(&s_stat[(i < 4 ? 0 : C) + 4 * g + (i & 3)], (double)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         }
     }
     __syncthreads();
-    if constexpr (!BWD) {
+    if constexpr (DET) {
+        if (tid < 2 * C) {
+            double v = 0.0;
+#pragma unroll
+            for (int wv = 0; wv < WAVES; ++wv) v += s_stat[wv * 2 * C + tid];
+            bn_det_add(stats, C, tid, v);
+        }
+    } else if constexpr (!BWD) {
         if (tid < 2 * C) atomic_add_f64(&stats[tid], s_stat[tid]);
     } else {
         // ---- one partial row per workgroup: [co][27 taps] | [co] bias gradient -----------------------------------------
@@ -287,6 +299,16 @@ int ACT_SUFFIX(launch_stem_fwd_mma)(const float* img, const float* w, const floa
     return hip_status();
 }
 #ifndef YUNET_ACT_BF16
+// the same forward with order-fixed BN sums into the [1 + det_rows][2 C] block `stats` (YunetBN::det_rows)
+int launch_stem_fwd_mma_det(const float* img, const float* w, const float* b, float* z, double* stats, int det_rows, int N, int H,
+                            int W, hipStream_t stream) {
+    const int grid = 768;
+    if ((long long)3 * H * W * 4 >= (1ll << 31) || det_rows < grid) return YUNET_EINVAL;
+    const int R = stem_rows(N, H / 2, W / 2, grid * stm::WAVES);
+    hipLaunchKernelGGL((stem_mma_kernel<false, true>), dim3(grid), dim3(stm::NTHR), 0, stream, img, w, b, z, stats, (const float*)nullptr,
+                       YunetBN{}, (float*)nullptr, N, H, W, R);
+    return hip_status();
+}
 int launch_stem_bwd_mma(const float* img, const float* w, const float* b, const float* dy, const YunetBN* bn, float* partials,
                         int blocks, int N, int H, int W, hipStream_t stream) {
     if ((long long)3 * H * W * 4 >= (1ll << 31)) return YUNET_EINVAL;

@@ -32,6 +32,10 @@ BN_MOMENTUM = 0.1
 # lines and that tail was 4-5 us of a 14-35 us launch.  Eight replicas remove it (tools/ubench/bwd_ab.cpp,
 # DESIGN.md section 7); the readers add the replicas up.
 BN_SLOTS = max(1, int(os.environ.get('YUNET_BN_SLOTS', '8')))
+# Deterministic mode (YuNetEngine.deterministic): every layer's sum blocks are [1 + DET_ROWS, 2c] -- row 0 is
+# what readers take (slots = 1), rows 1.. are one per workgroup of the kernels that produce sums (YunetBN::det_rows).  1024 = the
+# largest persistent grid of those kernels (CONV_BLOCKS; the launchers refuse a larger grid).
+DET_ROWS = 1024
 MAX_PLANS = max(2, int(os.environ.get('YUNET_MAX_PLANS', '16')))     # plans kept per engine (see get_plan)
 LOG_HEAD = 8          # floats in front of the flat gradient: cls, bbox, obj, kps, total, 3 spare
 
@@ -293,6 +297,13 @@ class Plan:
     def __init__(self, eng, n, h, w, gmax):
         self.eng, self.n, self.h, self.w, self.gmax = eng, n, h, w, gmax
         self.sw = {name: read_switch(name) for name in PLAN_SWITCHES}      # the environment as it is NOW
+        # deterministic mode: order-fixed BatchNorm sums (per-workgroup rows + fold ops), no lanes, no grouped launches
+        self.det = bool(getattr(eng, 'deterministic', False))
+        if self.det and eng.precision == 'bf16':
+            raise NotImplementedError("deterministic=True with precision='bf16': the order-fixed BatchNorm sums exist for the "
+                                      'fp32 storage build only')
+        self.bn_rows = 1 + DET_ROWS if self.det else BN_SLOTS      # rows of a layer's sum block
+        self.bn_slots = 1 if self.det else BN_SLOTS                # ... of which readers add up this many (YunetBN::slots)
         # activation storage of this plan: fp32, or bf16 ("bf16 fwd / fp32 grads", BASELINE configs[2]):
         # every tensor a forward kernel writes except the head output; gradients stay fp32
         self.act_dtype = torch.bfloat16 if eng.precision == 'bf16' else torch.float32
@@ -329,13 +340,13 @@ class Plan:
         so = 0
         for name, c in zip(lay.bn_names, self.eng.params.bn_channels):
             yield name, c, so, lay.entries[name + '.weight'][0], lay.entries[name + '.bias'][0], self.bn_count.get(name)
-            so += 2 * c * BN_SLOTS
+            so += 2 * c * self.bn_rows
 
     def _bn_table(self, backward, pick=None):
         """Device table of the bn_batch kernel over the forward | backward sum blocks of the layers with pick(g_off)."""
         base = self.stats.numel() // 2 if backward else 0
         bn_offset = self.eng.params.bn_offset
-        rows = [[base + so, c, cnt, bn_offset[name], g_off, b_off, BN_SLOTS]
+        rows = [[base + so, c, cnt, bn_offset[name], g_off, b_off, self.bn_slots]
                 for name, c, so, g_off, b_off, cnt in self._bn_layers() if pick is None or pick(g_off)]
         return torch.tensor(rows, dtype=torch.int32).to(self.eng.device)
 
@@ -352,13 +363,13 @@ class Plan:
         BN statistic buffers: one fp64 block, zeroed by a single memset per step
         (every layer's sums are BN_SLOTS replicas [BN_SLOTS, 2c]: YunetBN::slots)"""
         fp = self.eng.params
-        tot_c = sum(fp.bn_channels) * BN_SLOTS
+        tot_c = sum(fp.bn_channels) * self.bn_rows
         self.stats = torch.zeros(4 * tot_c, device=self.eng.device, dtype=torch.float64)
         self.bn = {}
         for name, c, o, g_off, b_off, _ in self._bn_layers():
-            c2 = 2 * c * BN_SLOTS
-            self.bn[name] = dict(c=c, stats=self.stats[o:o + c2].view(BN_SLOTS, 2 * c),
-                                 bstats=self.stats[2 * tot_c + o:2 * tot_c + o + c2].view(BN_SLOTS, 2 * c),
+            c2 = 2 * c * self.bn_rows
+            self.bn[name] = dict(c=c, stats=self.stats[o:o + c2].view(self.bn_rows, 2 * c),
+                                 bstats=self.stats[2 * tot_c + o:2 * tot_c + o + c2].view(self.bn_rows, 2 * c),
                                  gamma=fp.data.data_ptr() + 4 * g_off, beta=fp.data.data_ptr() + 4 * b_off,
                                  dgamma=fp.grad.data_ptr() + 4 * g_off, dbeta=fp.grad.data_ptr() + 4 * b_off)
         self.ops_memset_stats = self._op(L.OP_MEMSET, p=[self.stats.data_ptr()], i=self._split64(self.stats.numel() * 8))
@@ -414,7 +425,7 @@ class Plan:
         # 149 KB of LDS admits one workgroup per CU, so concurrent launches queue instead of sharing CUs.
         feats = list(taps)
         level_of = {i: l for l, i in enumerate(arch['neck_out_idx'])}
-        self.lanes_ok = (self.sw['lanes'] or bool(getattr(self.eng, 'use_lanes', False))) and not self.towers
+        self.lanes_ok = (self.sw['lanes'] or bool(getattr(self.eng, 'use_lanes', False))) and not self.towers and not self.det
         self.lanes_used = 0
         # Round 5: the head chains wait until the whole top-down pathway is built, and the share convs of the levels --
         # mutually independent plain 64 -> 64 units -- are emitted next to each other as ONE group
@@ -422,7 +433,7 @@ class Plan:
         # levels a launch of their own is a prologue, one or two bands per wave and a drain (27 / 13 us for 13 + 3 MB).
         # Needs no lanes (one stream); the tower head (stacked_convs > 0) keeps the per-level order.
         grouped = (not self.lanes_ok and not self.towers and not self.sw['no_head_group']
-                   and arch['shared_stacked_convs'] >= 1)
+                   and arch['shared_stacked_convs'] >= 1 and not self.det)      # (det: a fold op follows every producer)
 
         def heads(idxs):
             self._emit_heads([(level_of[i], feats[i]) for i in idxs if i in level_of], grouped)
@@ -631,13 +642,14 @@ class Plan:
         self.eval_scratch = torch.zeros(64, device=self.eng.device, dtype=torch.float64)
         self.fwd_eval = [self._bn_batch_op(self.bn_table_f, 2)]
         for op in self.fwd_a[1:]:
-            if op.opcode in (L.OP_ASSIGN, L.OP_LOSS_NORM):
-                continue          # test time: no SimOTA on stale GT, gt_inds / norm stay untouched
+            if op.opcode in (L.OP_ASSIGN, L.OP_LOSS_NORM, L.OP_BN_FOLD):
+                continue          # test time: no SimOTA on stale GT, gt_inds / norm stay untouched; row 0 of the sums is op 0's
             cp = self._clone_op(op)
             if cp.opcode == L.OP_DP_FWD:
                 cp.dp.out_has_bn = 0
             elif cp.opcode == L.OP_STEM_FWD:
                 cp.p[4] = self.eval_scratch.data_ptr()
+                cp.i[4] = 0                    # (deterministic plans: the scratch is one plain block)
             self.fwd_eval.append(cp)
         self.c_fwd_eval = self._carray(self.fwd_eval)
 
@@ -673,7 +685,13 @@ class Plan:
         self.bn_count[name] = count
         b = self.bn[name]
         return L.YunetBN(b['stats'].data_ptr(), b['bstats'].data_ptr(), b['gamma'], b['beta'],
-                         count, BN_EPS, BN_SLOTS)
+                         count, BN_EPS, self.bn_slots, DET_ROWS if self.det else 0)
+
+    def _fold_op(self, name, backward):
+        """Deterministic mode: rows 1.. of layer `name`'s forward | backward sum block -> row 0 (yunet_bn_fold).  Forward: right
+        after the layer's producer; backward: in front of the producer's backward, the first reader of the sums its consumers left."""
+        b = self.bn[name]
+        return self._op(L.OP_BN_FOLD, p=[b['bstats' if backward else 'stats'].data_ptr()], i=[DET_ROWS, b['c']])
 
     def _new_t(self, n, h, w, c, bn_name=None):
         buf = torch.empty(n, h, w, c, device=self.eng.device, dtype=self.act_dtype)
@@ -697,9 +715,11 @@ class Plan:
         cnt = z0.n * z0.h * z0.w
         self._bn_struct('backbone.model0.bn1', cnt)
         op = self._op(L.OP_STEM_FWD, p=[None, wp, bp, z0.buf.data_ptr(), bn['stats'].data_ptr()],
-                      i=[self.n, self.h, self.w, 16])
+                      i=[self.n, self.h, self.w, 16] + ([DET_ROWS] if self.det else []))
         self.fwd_a.append(op)
         self.img_ptr_ops.append(('fwd_a', len(self.fwd_a) - 1))
+        if self.det:
+            self.fwd_a.append(self._fold_op('backbone.model0.bn1', False))
         blocks = K.stem_grid(self.n, self.h, self.w)
         width = 16 * 27 + 16
         part = torch.empty(blocks, width, device=self.eng.device, dtype=torch.float32)
@@ -708,6 +728,8 @@ class Plan:
 
         def bwd():
             assert z0.grad is not None
+            if self.det:
+                self.bwd.append(self._fold_op('backbone.model0.bn1', True))
             op = self._op(L.OP_STEM_BWD, p=[None, z0.buf.data_ptr(), z0.grad.data_ptr(),
                                             part.data_ptr(), wp, bp],      # wp, bp: fp32 storage recomputes z from the image
                           i=[self.n, self.h, self.w, 16, blocks])
@@ -760,6 +782,8 @@ class Plan:
         op = self._op(L.OP_DP_FWD)
         op.dp = d
         self.fwd_a.append(op)
+        if self.det and bn_name:
+            self.fwd_a.append(self._fold_op(bn_name, False))
         if zt is not None:
             self.fwd_op_of[id(zt)] = op          # _pool() may attach the fused pooling outputs
         blocks = K.dp_grid(x.n, x.h, x.w, u['cin'], u['cout'])
@@ -788,6 +812,8 @@ class Plan:
             d2.dx = gx.data_ptr()
             d2.accumulate_dx = acc
             d2.wgrad_partials, d2.wgrad_blocks = part.data_ptr(), blocks
+            if self.det and bn_name:
+                self.bwd.append(self._fold_op(bn_name, True))
             op = self._op(L.OP_DP_BWD)
             op.dp = d2
             self.bwd.append(op)
@@ -907,7 +933,7 @@ class YuNetEngine:
         self.params = FlatParams(self.layout, self.device)
         self.world_size = world_size
         self.process_group = process_group
-        self.plans = collections.OrderedDict()      # (N, H, W, Gmax, precision) -> Plan, least recently used first
+        self.plans = collections.OrderedDict()      # (N, H, W, Gmax, precision[, 'det']) -> Plan, least recently used first
         self.plan = None
         self.always_bucket = False      # tests: run the two-segment backward + collectives at world size 1
         self.use_lanes = False          # head chains of the coarser levels on executor side streams (Plan._emit_neck_and_heads)
@@ -919,6 +945,9 @@ class YuNetEngine:
         self.comm_timing = False
         self._comm_events = []
         self.precision = 'fp32'         # 'fp32' | 'bf16' (activation storage + forward matrix instruction)
+        # deterministic: same inputs, same state, same build, same device model -> the same bytes (losses, gradients, BN
+        # buffers), one process at world size 1; fp32 storage only.  Plans are keyed by it (set_deterministic, get_plan).
+        self.deterministic = False
         self.lib = L.load()
         self._host_idx = {}
         # one-shot all-reduce over peer-mapped inboxes (oneshot.py / csrc/collective.hip) instead of the process
@@ -970,13 +999,23 @@ class YuNetEngine:
     def set_precision(self, precision):
         if precision not in ('fp32', 'bf16'):
             raise ValueError(f"precision {precision!r}: 'fp32' or 'bf16'")
+        if precision == 'bf16' and self.deterministic:
+            raise NotImplementedError("precision='bf16' with deterministic=True: the order-fixed BatchNorm sums exist for the "
+                                      'fp32 storage build only')
         self.precision = precision
+
+    def set_deterministic(self, flag=True):
+        """Order-fixed BatchNorm sums for the plans built from now on (README: what is and is not covered)."""
+        if flag and self.precision == 'bf16':
+            raise NotImplementedError("deterministic=True with precision='bf16': the order-fixed BatchNorm sums exist for the "
+                                      'fp32 storage build only')
+        self.deterministic = bool(flag)
 
     def get_plan(self, n, h, w, max_gt):
         gmax = 64
         while gmax < max_gt:
             gmax *= 2
-        key = (n, h, w, gmax, self.precision)
+        key = (n, h, w, gmax, self.precision) + (('det',) if self.deterministic else ())
         plan = self.plans.get(key)
         if plan is None:
             if h % 32 or w % 32:

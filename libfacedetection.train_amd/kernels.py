@@ -44,17 +44,20 @@ def _chk_f32(*ts):
 class BN:
     """Python-side YunetBN: keeps the tensors alive while the descriptor is in use."""
 
-    def __init__(self, stats, gamma, beta, count, eps=1e-5, bstats=None, slots=1):
+    def __init__(self, stats, gamma, beta, count, eps=1e-5, bstats=None, slots=1, det_rows=0):
         # slots > 1: stats / bstats are [slots, 2C] replica blocks (YunetBN::slots); the sums are their column sums
-        assert stats.dtype == torch.float64 and stats.numel() == slots * 2 * gamma.numel()
-        assert bstats is None or bstats.numel() == slots * 2 * gamma.numel()
+        # det_rows = R > 0 (deterministic sums, YunetBN::det_rows): [1 + R, 2C] blocks, row 0 = the sums after bn_fold
+        rows = 1 + det_rows if det_rows else slots
+        assert not det_rows or slots == 1
+        assert stats.dtype == torch.float64 and stats.numel() == rows * 2 * gamma.numel()
+        assert bstats is None or bstats.numel() == rows * 2 * gamma.numel()
         self.stats, self.gamma, self.beta, self.bstats = stats, gamma, beta, bstats
-        self.count, self.eps, self.slots = int(count), float(eps), int(slots)
+        self.count, self.eps, self.slots, self.det_rows = int(count), float(eps), int(slots), int(det_rows)
 
     def c(self):
         return L.YunetBN(self.stats.data_ptr(), self.bstats.data_ptr() if self.bstats is not None
                          else None, self.gamma.data_ptr(), self.beta.data_ptr(), self.count,
-                         self.eps, self.slots)
+                         self.eps, self.slots, self.det_rows)
 
 
 _NULL_BN = L.YunetBN(None, None, None, None, 1, 1e-5)
@@ -85,6 +88,24 @@ def stem_fwd(img, w, b, stats, dtype=torch.float32):
     fn = getattr(L.load(), 'yunet_stem_fwd' + _act(z)[1])
     L.check(fn(_p(img), _p(w), _p(b), _p(z), _p(stats), n, h, ww, 16, _stream()), 'yunet_stem_fwd')
     return z
+
+
+def stem_fwd_det(img, w, b, block):
+    """stem_fwd (fp32 storage) with order-fixed BN sums: block fp64 [1 + R, 32], workgroup g adds to row 1 + g."""
+    _chk_f32(img, w, b)
+    n, _, h, ww = img.shape
+    assert block.dtype == torch.float64 and block.dim() == 2 and block.shape[1] == 32 and block.is_contiguous()
+    z = torch.empty(n, h // 2, ww // 2, 16, device=img.device, dtype=torch.float32)
+    L.check(L.load().yunet_stem_fwd_det(_p(img), _p(w), _p(b), _p(z), _p(block), block.shape[0] - 1, n, h, ww, 16, _stream()),
+            'yunet_stem_fwd_det')
+    return z
+
+
+def bn_fold(block):
+    """block fp64 [1 + R, 2C]: row 0 = rows 1 .. R added in the fixed order of yunet_bn_fold."""
+    assert block.dtype == torch.float64 and block.dim() == 2 and block.shape[1] % 2 == 0 and block.is_contiguous()
+    L.check(L.load().yunet_bn_fold(_p(block), block.shape[0] - 1, block.shape[1] // 2, _stream()), 'yunet_bn_fold')
+    return block[0]
 
 
 def stem_bwd(img, z, dy, bn, w=None, b=None):
@@ -180,11 +201,12 @@ def dp_fwd(x, w_pw, b_pw, w_dw, b_dw, in_bn=None, out_bn=None, z=None, z_img_str
 
 
 def dp_bwd(x, w_pw, b_pw, w_dw, b_dw, z, dy, in_bn=None, out_bn=None, dy_scale=None,
-           dx=None, accumulate_dx=False, z_img_stride=None, need_dx=True, pool_idx=None):
+           dx=None, accumulate_dx=False, z_img_stride=None, need_dx=True, pool_idx=None, partials=None):
     """ConvDPUnit backward.  x, z: saved activations (fp32 or bf16); dy, dx fp32.
     Returns (dx, d_w_pw, d_b_pw, d_w_dw, d_b_dw).
     pool_idx (the idx of dp_fwd(..., pool=True)): dy is the POOLED gradient [N,H/2,W/2,cout] -- the dx
-    the pool's consumer wrote -- and reaches the recorded window positions while the tile is staged."""
+    the pool's consumer wrote -- and reaches the recorded window positions while the tile is staged.
+    partials: a [dp_grid(...), dp_row_width(...)] fp32 buffer for the per-workgroup weight-gradient rows (default: a fresh one)."""
     _chk_f32(w_pw, b_pw, w_dw, b_dw, dy)
     _chk_act(x)
     n, h, w, cin = x.shape
@@ -202,7 +224,8 @@ def dp_bwd(x, w_pw, b_pw, w_dw, b_dw, z, dy, in_bn=None, out_bn=None, dy_scale=N
         d.pool_idx = pool_idx.data_ptr()
     blocks = dp_grid(n, h, w, cin, cout)
     width = dp_row_width(cin, cout)
-    part = torch.empty(blocks, width, device=x.device, dtype=torch.float32)
+    part = torch.empty(blocks, width, device=x.device, dtype=torch.float32) if partials is None else partials
+    assert tuple(part.shape) == (blocks, width) and part.dtype == torch.float32 and part.is_contiguous()
     d.wgrad_partials, d.wgrad_blocks = part.data_ptr(), blocks
     if z.dtype != x.dtype:
         d.z_dtype = d.x_dtype          # heads: z (the fp32 flat) is never read in backward

@@ -888,11 +888,42 @@ def auto_scale_lr(cfg, distributed, log=print):
     return cfg.optimizer['lr']
 
 
+_DETERMINISTIC = False       # set_random_seed(seed, deterministic=True): read by train_detector
+
+
+def set_random_seed(seed, deterministic=False):
+    """mmdet/apis/train.py:196-214: seed python's, numpy's and torch's generators.  `deterministic` -- cuDNN's
+    deterministic mode in the reference -- selects the bit-reproducible training step of the fused engine
+    (YuNet.set_deterministic) for every model train_detector builds afterwards.  As in the reference, where False leaves
+    the cuDNN flags alone, a later set_random_seed(seed) does not switch the mode off; cfg.deterministic = True is the
+    per-run spelling."""
+    import random
+    import numpy as np
+    global _DETERMINISTIC
+    random.seed(seed)
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    if torch.cuda.is_available():
+        torch.cuda.manual_seed_all(seed)
+    if deterministic:
+        _DETERMINISTIC = True
+
+
+def wants_deterministic(cfg):
+    """cfg.deterministic = True, or set_random_seed(seed, deterministic=True) earlier in this process."""
+    return bool(cfg.get('deterministic', False)) or _DETERMINISTIC
+
+
 def train_detector(model, dataset, cfg, distributed=False, validate=False, timestamp=None,
                    meta=None, max_iters=None, device='cuda', log=print):
     """mmdet/apis/train.py:117-246 surface: DDP wrap, optimizer, EpochBasedRunner, fp16 / optimizer /
     lr / checkpoint / logger hooks from the config, auto-resume / resume / load_from, run.
     Returns the logged history (one dict of python floats per logging interval)."""
+    if wants_deterministic(cfg):
+        if cfg.get('fp16', None) is not None:
+            raise NotImplementedError('deterministic training with cfg.fp16 (bf16 activation storage): the deterministic mode '
+                                      'covers the fp32 storage build only')
+        model.set_deterministic(True)
     model = model.to(device)
     model.train()
     if distributed:

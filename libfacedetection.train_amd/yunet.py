@@ -274,10 +274,24 @@ class YuNet(nn.Module):
         reference's analogue is fp16 training, mmdet/apis/train.py:181-185 -> Fp16OptimizerHook)."""
         if precision not in ('fp32', 'bf16'):
             raise ValueError(f"precision {precision!r}: 'fp32' or 'bf16'")
+        if precision == 'bf16' and getattr(self, '_deterministic', False):
+            raise NotImplementedError("precision='bf16' with deterministic=True: the deterministic mode covers the fp32 "
+                                      'storage build only')
         self._precision = precision
         self.fp16_enabled = precision != 'fp32'
         if self.engine is not None:
             self.engine.set_precision(precision)
+
+    def set_deterministic(self, flag=True):
+        """Bit-reproducible training step (engine.YuNetEngine.deterministic): same inputs, same state, same build and same
+        device model give the same losses, gradients, parameters and BatchNorm buffers, byte for byte -- one process,
+        world size 1, fp32 storage.  Plans built before the call keep their mode; the next step builds its own."""
+        if flag and getattr(self, '_precision', 'fp32') == 'bf16':
+            raise NotImplementedError("deterministic=True with precision='bf16': the deterministic mode covers the fp32 "
+                                      'storage build only')
+        self._deterministic = bool(flag)
+        if self.engine is not None:
+            self.engine.set_deterministic(flag)
 
     def set_data_parallel(self, world_size, group=None):
         """Called by YuNetDistributedDataParallel: one process per GPU, RCCL collectives."""
@@ -307,6 +321,7 @@ class YuNet(nn.Module):
         sd = {k: v.detach().clone() for k, v in self.state_dict().items()}
         eng = YuNetEngine(self.arch(), device, self._world, self._group)
         eng.set_precision(getattr(self, '_precision', 'fp32'))
+        eng.set_deterministic(getattr(self, '_deterministic', False))
         eng.params.load_state_dict(sd)
         fp = eng.params
         for name, p in self.named_parameters():

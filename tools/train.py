@@ -41,7 +41,8 @@ def parse_args(argv=None):
     p.add_argument('--seed', type=int, default=None, help='random seed')
     p.add_argument('--diff-seed', action='store_true', help='different seeds for different ranks')
     p.add_argument('--deterministic', action='store_true',
-                   help='accepted for compatibility: the HIP kernels of the step do not depend on a cuDNN mode')
+                   help='bit-reproducible training step: the same seed, state, build and device model give the same bytes '
+                        '(losses, gradients, parameters, BN buffers); one process, fp32 storage; about 1.3x the step time')
     p.add_argument('--options', nargs='+', action=DictAction, help='(deprecated) use --cfg-options')
     p.add_argument('--cfg-options', nargs='+', action=DictAction,
                    help='override settings of the config: key=value pairs, key="[a,b]" or key=a,b for lists, '
@@ -83,6 +84,8 @@ def prepare_config(args):
     if args.resume_from is not None:
         cfg['resume_from'] = args.resume_from
     cfg['auto_resume'] = args.auto_resume
+    if args.deterministic:
+        cfg['deterministic'] = True                 # the config key of the mode: the dumped config records it
     if args.gpus is not None:
         cfg['gpu_ids'] = [0]
         warnings.warn('`--gpus` is deprecated because we only support single GPU mode in non-distributed '
@@ -138,7 +141,10 @@ def main(argv=None):
     timestamp = time.strftime('%Y%m%d_%H%M%S', time.localtime())
     seed = args.seed if args.seed is not None else 0
     seed = seed + rank if args.diff_seed else seed
-    torch.manual_seed(seed)
+    if args.deterministic:
+        R.set_random_seed(seed, deterministic=True)      # (mmdet/apis/train.py: set_random_seed(seed, deterministic=...))
+    else:
+        torch.manual_seed(seed)
     cfg['seed'] = seed
     model = yunet_amd.build_detector(cfg.model)
     model.init_weights()
