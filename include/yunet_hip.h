@@ -104,7 +104,14 @@ typedef struct YunetDP {
      *             max_pool2d(relu(bn(z))) exactly, and its backward yields the BN-backward sums unchanged.
      *   backward: pool_idx != NULL: dy is the POOLED gradient [N,H/2,W/2,cout] the consumer wrote as its dx
      *             (ReLU mask applied); it reaches the recorded window position while the tile is staged -- no
-     *             full-size gradient of z exists. */
+     *             full-size gradient of z exists.
+     *   z == NULL: where nobody reads the full-size output -- the pool its only consumer, and a backward that
+     *             recomputes z (yunet_dp_bwd_reads_z() == 0) -- yunet_dp_fwd accepts a NULL z for the 16 -> 16 unit
+     *             with pool_out set that runs on the wave-streaming kernel (option "fwd16s", not deterministic, no
+     *             prof): the kernel then skips the z path and writes pool_out, pool_idx and the BN sums only, the same
+     *             bytes as with a z.  yunet_dp_bwd accepts a NULL z exactly where yunet_dp_bwd_reads_z() is 0.  Every
+     *             other unit, kernel and entry (yunet_dp_fwd_group included) returns YUNET_EINVAL for a NULL z and
+     *             launches nothing. */
     float* pool_out;
     uint8_t* pool_idx;
 } YunetDP;
@@ -159,6 +166,10 @@ int yunet_dp_bwd_blocks(int N, int H, int W, int cin, int cout);
 /* 1 if yunet_dp_fwd / yunet_dp_bwd accept YunetDP.pool_out / pool_idx for this shape (the unpacked
  * 16->16 units on maps >= 32x64, the 32->64 units and the unpacked 64->64 units; H, W even) */
 int yunet_dp_pool_fusion_ok(int N, int H, int W, int cin, int cout);
+/* 0 if the kernel yunet_dp_bwd selects for this (backward) descriptor does not read YunetDP.z, under the options the
+ * process runs with now: today the wave-streaming 16 -> 16 backward (option "bwd16s"; a big-tile map, out_has_bn, a plain
+ * dx, no deterministic sums, no prof), which recomputes z from x.  1 for every other unit.  Host only. */
+int yunet_dp_bwd_reads_z(const YunetDP* d);
 int yunet_stem_bwd_blocks(int N, int H, int W);
 
 /* F.max_pool2d(relu(bn(z)), 2)  (yunet_backbone.py:39-40).  out [N,H/2,W/2,C]. */

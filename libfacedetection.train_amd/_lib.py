@@ -142,6 +142,7 @@ _SIGNATURES = {
     'yunet_pool_fwd': (C.c_int, [C.c_void_p, C.POINTER(YunetBN), C.c_void_p] + [C.c_int] * 4 +
                        [C.c_void_p]),
     'yunet_dp_pool_fusion_ok': (C.c_int, [C.c_int] * 5),
+    'yunet_dp_bwd_reads_z': (C.c_int, [C.POINTER(YunetDP)]),
     'yunet_pool_bwd': (C.c_int, [C.c_void_p, C.POINTER(YunetBN), C.c_void_p, C.c_void_p] +
                        [C.c_int] * 5 + [C.c_void_p]),
     'yunet_pool_bwd_add': (C.c_int, [C.c_void_p, C.POINTER(YunetBN), C.c_void_p, C.c_void_p, C.c_void_p] +

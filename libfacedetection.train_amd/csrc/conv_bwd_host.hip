@@ -142,6 +142,9 @@ extern "C" int yunet_dp_pool_fusion_ok(int N, int H, int W, int cin, int cout) {
     if (cin == 32 && cout == 64) return 1;       // YuNet_s: the unit in front of its 80x80 -> 40x40 pool
     return 0;
 }
+extern "C" int yunet_dp_bwd_reads_z(const YunetDP* d) {
+    return d && dp_bwd_streams16(d) ? 0 : 1;
+}
 extern "C" int yunet_stem_bwd_blocks(int N, int H, int W) {
     const long long tiles = (long long)N * ((W / 2 + SB_TW - 1) / SB_TW) * ((H / 2 + SB_TH - 1) / SB_TH);
     return (int)(tiles < STEM_BWD_MAX_BLOCKS ? tiles : STEM_BWD_MAX_BLOCKS);

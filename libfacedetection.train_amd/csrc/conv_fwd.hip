@@ -763,7 +763,15 @@ extern "C" int ACT_SUFFIX(yunet_dp_fwd)(const YunetDP* d, void* stream) {
     if (d->x_dtype != YUNET_ACT_DTYPE) return YUNET_EINVAL;
     if (d->z_dtype != YUNET_ACT_DTYPE && !(d->cout == 16 && d->z_dtype == YUNET_F32)) return YUNET_EINVAL;
     if (d->in_transform != YUNET_T_IDENTITY && d->in_transform != YUNET_T_BNRELU) return YUNET_EINVAL;
-    if (d->out_has_bn && d->out_bn.det_rows) {
+    const bool det = d->out_has_bn && d->out_bn.det_rows;
+    // units with 16 input channels: wave-streaming kernels (conv_fwd16.hip)
+    const bool fwd16s = !det && d->cin == 16 && (d->cout == 16 || (d->cout == 64 && !d->pool_out)) && d->z_dtype == YUNET_ACT_DTYPE &&
+                        !d->prof && yunet_options().fwd16s &&
+                        (!d->pool_out || (yunet_dp_pool_fusion_ok(d->N, d->H, d->W, 16, 16) && d->out_bn.gamma && d->pool_idx &&
+                                          !(reinterpret_cast<uintptr_t>(d->pool_idx) & 3)));
+    // a null z (include/yunet_hip.h): the pooled 16 -> 16 unit on that kernel alone; every other kernel stores through it
+    if (!d->z && !(fwd16s && d->pool_out)) return YUNET_EINVAL;
+    if (det) {
         // deterministic BatchNorm sums (include/yunet_hip.h): the tile kernel in its DET form for every unit -- the same
         // choice of tile, packed canvas and fused pooling as below, none of the wave-streaming kernels
 #ifndef YUNET_ACT_BF16
@@ -790,11 +798,7 @@ extern "C" int ACT_SUFFIX(yunet_dp_fwd)(const YunetDP* d, void* stream) {
 #endif
         return YUNET_EINVAL;
     }
-    // units with 16 input channels: wave-streaming kernels (conv_fwd16.hip)
-    if (d->cin == 16 && (d->cout == 16 || (d->cout == 64 && !d->pool_out)) && d->z_dtype == YUNET_ACT_DTYPE && !d->prof && yunet_options().fwd16s &&
-        (!d->pool_out || (yunet_dp_pool_fusion_ok(d->N, d->H, d->W, 16, 16) && d->out_bn.gamma && d->pool_idx &&
-                          !(reinterpret_cast<uintptr_t>(d->pool_idx) & 3))))
-        return ACT_SUFFIX(launch_dp_fwd16s)(d, s);
+    if (fwd16s) return ACT_SUFFIX(launch_dp_fwd16s)(d, s);
     if (d->pool_out) {
         // also write the raw max_pool2d winners + their window positions (fused pooling)
         if (!yunet_dp_pool_fusion_ok(d->N, d->H, d->W, d->cin, d->cout) || !d->out_bn.gamma || !d->pool_idx ||   // (out_has_bn may be 0: eval())
@@ -839,7 +843,7 @@ extern "C" int ACT_SUFFIX(yunet_dp_fwd_group)(const YunetDP* const* units, int n
         const YunetDP* d = units[i];
         one_grid = d && !(d->out_has_bn && d->out_bn.det_rows) &&
                    d->x_dtype == YUNET_ACT_DTYPE && d->z_dtype == YUNET_ACT_DTYPE && d->cin == 64 && d->cout == 64 &&
-                   !d->pool_out && !d->prof && yunet_options().fwd64s != 0 &&
+                   d->z && !d->pool_out && !d->prof && yunet_options().fwd64s != 0 &&
                    (d->in_transform == YUNET_T_IDENTITY || d->in_transform == YUNET_T_BNRELU) &&
                    !(dp_use_pack(d->N, d->H, d->W, d->cin, d->cout) && yunet_options().fwd64s < 2);
     }

@@ -30,15 +30,17 @@ struct G {
 };
 }  // namespace f16s
 
-template <int COUT, bool POOL>
-__global__ __launch_bounds__(f16s::NTHR) __attribute__((amdgpu_waves_per_eu(3, 3)))      // <= 168 registers: three workgroups per CU
-void dp_fwd16s_kernel(const YunetDP d, const int R) {
+// The kernel's body.  ZOUT = false (POOL only; a null YunetDP.z, see dp_fwd16s_kernel): the full-size z is not produced --
+// no slot Z, no 16-byte z stores; the BN sums, the winners and their positions are the same values from the same operations.
+template <int COUT, bool POOL, bool ZOUT>
+__device__ __forceinline__ void dp_fwd16s_body(const YunetDP d, const int R) {
     using namespace f16s;
     using GG = G<COUT>;
     constexpr int PXW = GG::PXW, NT = GG::NT, MT = GG::MT, PST = GG::PST, SLOT = GG::SLOT, WAVE_F = GG::WAVE_F;
     constexpr int NSEG = PXW * COUT / 64;                   // pixels per lane in layout C: 8 (16 channels) | 16 (64 channels)
     constexpr int HALO = POOL ? 2 : 1, OUTW = PXW - 2 * HALO;
     static_assert(!POOL || COUT == 16, "fused pooling: the 16 -> 16 unit");
+    static_assert(ZOUT || POOL, "only the pooled unit has a consumer that does without the full-size z");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* sm = reinterpret_cast<float*>(smem);
     float* s_w2 = sm + WAVES * WAVE_F;                      // [9][COUT]
@@ -105,7 +107,8 @@ void dp_fwd16s_kernel(const YunetDP d, const int R) {
         const int y0 = band * R, y1 = (y0 + R < H) ? y0 + R : H;
         const int xs = strip * OUTW - HALO;                   // image column of the strip's pixel 0
         const auto r_x = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<act_t*>(const_cast<float*>(d.x)) + (size_t)n * d.x_img_stride, 0, xbytes, 0x00020000);
-        const auto r_z = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<act_t*>(d.z) + (size_t)n * d.z_img_stride, 0, zbytes, 0x00020000);
+        // (ZOUT = false: a null base with zero bytes; never used)
+        const auto r_z = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<act_t*>(d.z) + (ZOUT ? (size_t)n * d.z_img_stride : (size_t)0), 0, ZOUT ? zbytes : 0u, 0x00020000);
         const auto r_po = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<act_t*>(d.pool_out) + (POOL ? (size_t)n * poel : (size_t)0), 0, POOL ? pobytes : 0u, 0x00020000);
         const auto r_pi = __builtin_amdgcn_make_buffer_rsrc(d.pool_idx + (POOL ? (size_t)n * poel : (size_t)0), 0, POOL ? poel : 0u, 0x00020000);
         // layout C: bit k = pixel NSEG sg + k is an output pixel of this strip
@@ -184,7 +187,7 @@ void dp_fwd16s_kernel(const YunetDP d, const int R) {
                     const float v = ((omask >> k) & 1u) ? zdone[k] : 0.0f;
                     ts0 += v;
                     ts1 = fmaf(v, v, ts1);
-                    zq[k * PST] = zdone[k];
+                    if constexpr (ZOUT) zq[k * PST] = zdone[k];
                 }
                 if constexpr (POOL) {
                     if ((q & 1) == 0) {
@@ -207,17 +210,21 @@ void dp_fwd16s_kernel(const YunetDP d, const int R) {
                         }
                     }
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                if (ZOUT || (q & 1)) {                        // (without z: only the row that closes a window pair has LDS traffic)
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                }
+                if constexpr (ZOUT) {
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const int j = 16 * nt + l15;
-                    const bool mine = (unsigned)colP(nt) < (unsigned)W && j >= HALO && j < PXW - HALO;
+                    for (int nt = 0; nt < NT; ++nt) {
+                        const int j = 16 * nt + l15;
+                        const bool mine = (unsigned)colP(nt) < (unsigned)W && j >= HALO && j < PXW - HALO;
 #pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) {
-                        const float4 v = *reinterpret_cast<const float4*>(slot_z + j * PST + 16 * mt + 4 * g);
-                        act_bufst4(r_z, mine ? (unsigned)((q * W + colP(nt)) * COUT + 16 * mt + 4 * g) * ACT_B : zbytes, v);
+                        for (int mt = 0; mt < MT; ++mt) {
+                            const float4 v = *reinterpret_cast<const float4*>(slot_z + j * PST + 16 * mt + 4 * g);
+                            act_bufst4(r_z, mine ? (unsigned)((q * W + colP(nt)) * COUT + 16 * mt + 4 * g) * ACT_B : zbytes, v);
+                        }
                     }
                 }
                 if constexpr (POOL) {
@@ -255,6 +262,21 @@ void dp_fwd16s_kernel(const YunetDP d, const int R) {
     }
 }
 
+// One kernel per (COUT, POOL): the name profiles and bench.py key on.  The pooled unit whose full-size output nobody reads
+// (include/yunet_hip.h: a null YunetDP.z) takes the body without the z path -- a kernel argument, so the branch is scalar
+// and taken once per wave.
+template <int COUT, bool POOL>
+__global__ __launch_bounds__(f16s::NTHR) __attribute__((amdgpu_waves_per_eu(3, 3)))      // <= 168 registers: three workgroups per CU
+void dp_fwd16s_kernel(const YunetDP d, const int R) {
+    if constexpr (POOL) {
+        if (d.z == nullptr) {
+            dp_fwd16s_body<COUT, POOL, false>(d, R);
+            return;
+        }
+    }
+    dp_fwd16s_body<COUT, POOL, true>(d, R);
+}
+
 // rows per band: minimise (tasks per wave, rounded up) x (rows of a task incl. the two halo rows + set-up)
 int fwd16s_rows(int N, int H, int W, int outw, int waves, bool even) {
     const long long strips = (W + outw - 1) / outw;
@@ -283,6 +305,7 @@ int launch_fwd16s(const YunetDP* d, hipStream_t stream) {
     if (blocks_per_cu < 1) return YUNET_EINVAL;
     if ((long long)d->H * d->W * COUT * 4 >= (1ll << 31)) return YUNET_EINVAL;      // 32-bit byte offsets per image
     if (d->x_dtype != YUNET_ACT_DTYPE || d->z_dtype != YUNET_ACT_DTYPE) return YUNET_EINVAL;
+    if (!d->z && !(POOL && d->pool_out)) return YUNET_EINVAL;      // only the pooled unit does without its full-size output
     constexpr int HALO = POOL ? 2 : 1, OUTW = GG::PXW - 2 * HALO;
     int grid = yunet_cu_count() * blocks_per_cu;
     const int R = fwd16s_rows(d->N, d->H, d->W, OUTW, grid * f16s::WAVES, POOL);

@@ -481,7 +481,7 @@ int ACT_SUFFIX(launch_dp_fwd64s_group)(const YunetDP* const* ds, int n, hipStrea
         if (i < n) {
             m.d[i] = *ds[i];
             const int g = fwd64s_geometry(ds[i], blocks_per_cu, false, &m.R[i]);
-            if (g < 1) return YUNET_EINVAL;
+            if (g < 1 || !ds[i]->z) return YUNET_EINVAL;
             at += g;
         } else {
             m.d[i] = *ds[0];          // (no workgroup maps to it)
@@ -494,6 +494,6 @@ int ACT_SUFFIX(launch_dp_fwd64s_group)(const YunetDP* const* ds, int n, hipStrea
 }
 
 int ACT_SUFFIX(launch_dp_fwd64s)(const YunetDP* d, hipStream_t stream) {
-    if (d->x_dtype != YUNET_ACT_DTYPE || d->z_dtype != YUNET_ACT_DTYPE) return YUNET_EINVAL;
+    if (d->x_dtype != YUNET_ACT_DTYPE || d->z_dtype != YUNET_ACT_DTYPE || !d->z) return YUNET_EINVAL;
     return d->pool_out ? launch_fwd64s<true>(d, stream) : launch_fwd64s<false>(d, stream);
 }

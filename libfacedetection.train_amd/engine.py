@@ -46,13 +46,16 @@ LOG_HEAD = 8          # floats in front of the flat gradient: cls, bbox, obj, kp
 #   no_head_group         plan build    share convs of the levels as launches of their own, not as one OP_GROUP
 #   no_pool_fusion        plan build    max_pool2d as kernels of its own, not inside the producing ConvDPUnit
 #   no_upadd_pool_fusion  plan build    a tap's gradient written by the merge backward AND the pool backward
+#   keep_pool_z           plan build    the full-size output of a fused-pool unit allocated and written though nobody reads it
 #   overlap_reduce        engine init   one GPU: reduction of segment A on the side stream (YuNetEngine.backward)
 #   copy_gt               every step    padded GT copied into the plan's buffers instead of read in place (stage_gt)
-PLAN_SWITCHES = ('lanes', 'no_head_group', 'no_pool_fusion', 'no_upadd_pool_fusion')
+PLAN_SWITCHES = ('lanes', 'no_head_group', 'no_pool_fusion', 'no_upadd_pool_fusion', 'keep_pool_z')
 
 
 def read_switch(name):
     v = os.environ.get('YUNET_' + name.upper())
+    if name == 'keep_pool_z':
+        return bool(v) and v != '0'          # (A/B runs spell both sides: =1 | =0)
     return v != '0' if name == 'overlap_reduce' else bool(v)
 
 
@@ -325,6 +328,7 @@ class Plan:
         self._alloc_loss_buffers()
         self._emit_loss_step()
         kernels_bwd, marks = self._emit_backward()
+        self._elide_pool_z()
         self.c_fwd_a = self._carray(self.fwd_a)
         self.c_fwd_b = self._carray(self.fwd_b)
         self.c_bwd = self._carray(self.bwd)
@@ -578,6 +582,41 @@ class Plan:
         self.bwd.append(self._bn_batch_op(self.bn_table_b, 1))
         return kernels_bwd, marks
 
+    def _elide_pool_z(self):
+        """Needs the forward and backward op records (before they are copied into the c_* arrays); leaves `elided_z`.
+        A unit with fused pooling writes the window winners, which is all its consumer reads (_pool: the pool is the tensor's
+        sole consumer).  Where the unit's backward recomputes z as well (yunet_dp_bwd_reads_z on the descriptor the backward
+        op carries: dp_bwd16s, under the options of this process), nothing in a training step reads the full-size output:
+        the tensor is dropped (`buf` = None) and both records carry a null z, which the forward kernel takes as `do not
+        produce it` (include/yunet_hip.h).  The other readers of activations work on predictions and statistics only (hooks.py:
+        the flat head output and the GT; deterministic mode's fold ops: the sum blocks); functional.py allocates its own z.
+        forward_eval leaves every intermediate readable (tests walk Plan.tensors after it): eval_ops() allocates the tensor
+        when an eval forward first runs on this plan.  YUNET_KEEP_POOL_Z=1: nothing is dropped."""
+        self.elided_z = []          # (tensor, its OP_DP_FWD record)
+        if self.sw['keep_pool_z']:
+            return
+        bwd_of = {op.dp.pool_idx: op for op in self.bwd if op.opcode == L.OP_DP_BWD and op.dp.pool_idx}
+        for _, zt in self.tensors.values():
+            if zt.pooled_into is None or zt.grad is not None:
+                continue
+            fop, bop = self.fwd_op_of[id(zt)], bwd_of.get(zt.pooled_into[1].data_ptr())
+            if bop is None or fop.dp.z != zt.buf.data_ptr() or bop.dp.z != fop.dp.z:
+                continue
+            if L.load().yunet_dp_bwd_reads_z(C.byref(bop.dp)):
+                continue
+            fop.dp.z = bop.dp.z = None
+            zt.buf = None
+            self.elided_z.append((zt, fop))
+
+    def eval_ops(self):
+        """c_fwd_eval, every tensor of Plan.tensors behind it: a full-size output the training lists do without
+        (_elide_pool_z) is allocated on the first call and written by the eval forward as before."""
+        for zt, idx in self._eval_z:
+            if zt.buf is None:
+                zt.buf = torch.empty(zt.n, zt.h, zt.w, zt.c, device=self.eng.device, dtype=self.act_dtype)
+                self.fwd_eval[idx].dp.z = self.c_fwd_eval[idx].dp.z = zt.buf.data_ptr()
+        return self.c_fwd_eval
+
     def _build_deferred(self):
         """`c_fwd_b_loss` / `c_fwd_b_rest` from fwd_b, and the GT binding state (`own_gt`, `_gt_bound`).
         N > 1: the same two phases with the num_pos normaliser DEFERRED -- the loss kernel leaves the cls / bbox /
@@ -641,6 +680,7 @@ class Plan:
         do not accumulate: ConvDPUnits get out_has_bn = 0, the stem sums into a scratch block)"""
         self.eval_scratch = torch.zeros(64, device=self.eng.device, dtype=torch.float64)
         self.fwd_eval = [self._bn_batch_op(self.bn_table_f, 2)]
+        self._eval_z = []           # (elided tensor, index of its unit in fwd_eval): eval_ops()
         for op in self.fwd_a[1:]:
             if op.opcode in (L.OP_ASSIGN, L.OP_LOSS_NORM, L.OP_BN_FOLD):
                 continue          # test time: no SimOTA on stale GT, gt_inds / norm stay untouched; row 0 of the sums is op 0's
@@ -650,6 +690,7 @@ class Plan:
             elif cp.opcode == L.OP_STEM_FWD:
                 cp.p[4] = self.eval_scratch.data_ptr()
                 cp.i[4] = 0                    # (deterministic plans: the scratch is one plain block)
+            self._eval_z += [(zt, len(self.fwd_eval)) for zt, fop in self.elided_z if fop is op]
             self.fwd_eval.append(cp)
         self.c_fwd_eval = self._carray(self.fwd_eval)
 
@@ -1256,7 +1297,7 @@ class YuNetEngine:
         self.plan = plan
         self._img = img
         plan.set_img(img)
-        self._exec(plan.c_fwd_eval, 'yunet_exec(fwd_eval)')
+        self._exec(plan.eval_ops(), 'yunet_exec(fwd_eval)')
         return plan.flat
 
     @torch.no_grad()

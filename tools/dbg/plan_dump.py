@@ -1,6 +1,12 @@
 """Serialise the op lists of engine plans, built without a GPU, in a form two commits can be diffed on.
 
     python tools/dbg/plan_dump.py OUT.txt        # run at both commits, then `cmp` the two files
+    python tools/dbg/plan_dump.py OUT.txt --elide   # the plans as a training process builds them by default
+
+The plans are built with YUNET_KEEP_POOL_Z=1: every full-size output allocated, the form the recorded digest
+(tests/golden/plan_dump_default.sha256) describes.  By default a plan drops the output of a fused-pool unit whose backward
+recomputes it (Plan._elide_pool_z); --elide dumps that form, which differs from the other in those units' `dp.z` alone
+(tests/test_pool_z_elision_plan.py).
 
 A plan is a set of `YunetOp` arrays full of raw pointers; their values change from run to run, what must not change
 is WHERE they point.  Every pointer is therefore written as (name of the plan / parameter buffer that contains it,
@@ -110,9 +116,10 @@ def dump_plan(eng, plan, w):
     return n_ops
 
 
-def main(path):
+def main(path, elide=False):
     for s in SWITCHES:
         os.environ.pop(s, None)
+    os.environ['YUNET_KEEP_POOL_Z'] = '0' if elide else '1'
     n_cfg = n_ops = 0
     with open(path, 'w') as f:
         def w(line):
@@ -140,4 +147,4 @@ def main(path):
 
 
 if __name__ == '__main__':
-    main(sys.argv[1])
+    main(sys.argv[1], elide='--elide' in sys.argv[2:])
