@@ -53,8 +53,13 @@ typedef struct YunetBN {
                             * kernel that PRODUCES sums adds its partial sums, accumulated inside the workgroup in a
                             * fixed order, to row 1 + b with plain loads and stores (no atomics; a launch whose grid
                             * exceeds R is refused), and yunet_bn_fold adds rows 1 .. R into row 0 in a fixed order
-                            * before the first reader runs.  Rows are zeroed before the step like the blocks above. */
+                            * before the first reader runs.  Rows are zeroed before the step like the blocks above.
+                            * R | YUNET_DET_FAST: the same blocks and rows, produced by the order-fixed forms of the
+                            * kernels the default mode uses (below: the deterministic mode). */
 } YunetBN;
+/* Flag in YunetBN.det_rows, above the row count (every reader masks it off): the fast deterministic level. */
+#define YUNET_DET_FAST (1 << 30)
+#define YUNET_DET_ROWS(det_rows) ((det_rows) & (YUNET_DET_FAST - 1))
 
 /* Input transform of a fused unit (how it reads its input tensor). */
 enum { YUNET_T_IDENTITY = 0, YUNET_T_BNRELU = 1 };
@@ -107,7 +112,7 @@ typedef struct YunetDP {
      *             full-size gradient of z exists.
      *   z == NULL: where nobody reads the full-size output -- the pool its only consumer, and a backward that
      *             recomputes z (yunet_dp_bwd_reads_z() == 0) -- yunet_dp_fwd accepts a NULL z for the 16 -> 16 unit
-     *             with pool_out set that runs on the wave-streaming kernel (option "fwd16s", not deterministic, no
+     *             with pool_out set that runs on the wave-streaming kernel (option "fwd16s", not deterministic -- or at its fast level --, no
      *             prof): the kernel then skips the z path and writes pool_out, pool_idx and the BN sums only, the same
      *             bytes as with a z.  yunet_dp_bwd accepts a NULL z exactly where yunet_dp_bwd_reads_z() is 0.  Every
      *             other unit, kernel and entry (yunet_dp_fwd_group included) returns YUNET_EINVAL for a NULL z and
@@ -153,7 +158,15 @@ int yunet_dp_bwd(const YunetDP* d, void* stream);
  * the tile kernels (no wave-streaming kernels, no split-bf16 backward); a launch that produces none -- a unit without an
  * output BN in forward, a unit with an identity input transform in backward -- dispatches as without det_rows.  The
  * stem has the entry below.  Same inputs, same library and
- * same device model give the same bytes.  YUNET_EINVAL with bf16 activation storage. */
+ * same device model give the same bytes.  YUNET_EINVAL with bf16 activation storage.
+ * The fast level (det_rows = R | YUNET_DET_FAST; same blocks, rows and fold): yunet_dp_fwd and yunet_dp_bwd take the
+ * dispatch of the default mode -- the same predicates, tiles, grids and options -- and a launch that produces sums runs
+ * the DET instance of the kernel chosen there: the wave-streaming kernels (16 -> 16, 16 -> 64, 64 -> 64 forward, 16 -> 16
+ * backward; each wave adds its bands into an fp64 row of its own in LDS, the rows are added in wave order), the
+ * split-bf16 64 -> 64 and 32 -> 64 backward, the whole-tile instances.  The arithmetic of everything but the sums is that
+ * of the default mode, bit for bit; the bytes differ from the plain level's (other kernels).  A NULL z and
+ * yunet_dp_bwd_reads_z() == 0 hold for the pooled 16 -> 16 unit as in the default mode; yunet_dp_fwd_group launches such
+ * units one by one.  The element-wise kernels, the stem entry and yunet_bn_fold ignore the flag. */
 /* yunet_stem_fwd with stats = a [1 + det_rows][2*cmid] block (det_rows >= 768, the kernel's grid). */
 int yunet_stem_fwd_det(const float* img, const float* w, const float* b, float* z, double* stats, int det_rows,
                        int N, int H, int W, int cmid, void* stream);

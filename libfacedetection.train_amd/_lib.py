@@ -25,6 +25,7 @@ NORM_INF, NORM_L1, NORM_L2 = 0, 1, 2
 OPT_ROW, OPT_MAX_GROUPS = 4, 255                                  # YUNET_OPT_* (the group table of csrc/optim.hip)
 T_IDENTITY, T_BNRELU = 0, 1
 F32, BF16 = 0, 1
+DET_FAST = 1 << 30         # YUNET_DET_FAST: flag in YunetBN.det_rows, above the row count
 BOX_EIOU, BOX_DIOU, BOX_IOU_LINEAR, BOX_IOU_SQUARE, BOX_IOU_LOG, BOX_GIOU, BOX_CIOU = 0, 1, 2, 3, 4, 5, 6
 (OP_STEM_FWD, OP_STEM_BWD, OP_DP_FWD, OP_DP_BWD, OP_POOL_FWD, OP_POOL_BWD, OP_UPADD_FWD,
  OP_UPADD_BWD, OP_BN_RUNNING, OP_BN_PARAM_GRAD, OP_REDUCE_PARTIALS, OP_ASSIGN, OP_LOSS_NORM,

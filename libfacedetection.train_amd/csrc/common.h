@@ -394,7 +394,10 @@ __device__ __forceinline__ void bn_det_add(const double* base, int C, int i, dou
     double* p = const_cast<double*>(base) + (size_t)(1 + blockIdx.x) * 2 * C + i;
     *p += v;
 }
-static inline bool bn_det_fits(const YunetBN& bn, int grid) { return bn.det_rows >= grid && bn.slots <= 1; }
+static inline bool bn_det_fits(const YunetBN& bn, int grid) { return YUNET_DET_ROWS(bn.det_rows) >= grid && bn.slots <= 1; }
+// YUNET_DET_FAST above the row count: the launch takes the default mode's dispatch and lands on the DET instance of the
+// kernel chosen there (dp_fwd16s, dp_fwd64s, dp_bwd16s, dp_bwd64, the split-bf16 / FULL tile instances)
+static inline bool bn_det_fast(const YunetBN& bn) { return YUNET_DET_ROWS(bn.det_rows) && (bn.det_rows & YUNET_DET_FAST); }
 
 static inline int hip_status() { return -(int)hipGetLastError(); }
 

@@ -909,6 +909,71 @@ int launch_dp_bwd(const YunetDP* d, hipStream_t stream) {
 
 }  // namespace
 
+namespace {
+// The dispatch of the default mode.  DET = true (the fast deterministic level, YUNET_DET_FAST in the producer's det_rows; fp32
+// storage): the same predicates, tiles and grids, every tile kernel in its DET instance; launch_dp_bwd16s and launch_dp_bwd64
+// pick theirs from the descriptor.
+template <bool DET>
+int dp_bwd_dispatch(const YunetDP* d, hipStream_t s) {
+    // the 16 -> 16 unit on the 160 x 160 / 80 x 80 levels: wave-streaming kernel that recomputes z from x instead of
+    // reading it (conv_bwd16.hip); same grid and partial rows as the tile kernel it replaces
+    if (dp_bwd_streams16(d)) return ACT_SUFFIX(launch_dp_bwd16s)(d, s);
+    if (d->pool_idx) {
+        // dy is the pooled gradient + argmax bytes (max_pool2d backward while staging)
+        if (!yunet_dp_pool_fusion_ok(d->N, d->H, d->W, d->cin, d->cout) || !d->out_has_bn) return YUNET_EINVAL;
+        const bool full816 = d->H % 8 == 0 && d->W % 16 == 0, full1632 = d->H % 16 == 0 && d->W % 32 == 0;
+        if (d->cin == 16) return full1632 ? launch_dp_bwd<16, 16, 16, 32, false, 0, true, true, DET>(d, s)
+                                          : launch_dp_bwd<16, 16, 16, 32, false, 0, true, false, DET>(d, s);
+        // 32 -> 64 (YuNet_s, in front of its 80 x 80 -> 40 x 40 pool): on the exact-fp32 matrix instruction this unit is
+        // MATRIX-bound (12.3 kFLOP per pixel at 157 TFLOP/s: 0.87 ms per 512-image launch = 0.16 of the HBM peak, the
+        // slowest kernel of the YuNet_s step); round 5 puts it on the split-bf16 path of the 64 -> 64 units (GEMM = 1)
+        if (d->cin == 32 && yunet_options().bwd_fp32mma == 0 && yunet_options().bwd32_split)
+            return full816 ? launch_dp_bwd<32, 64, 8, 16, false, 1, true, true, DET>(d, s)
+                           : launch_dp_bwd<32, 64, 8, 16, false, 1, true, false, DET>(d, s);
+        if (d->cin == 32) return full816 ? launch_dp_bwd<32, 64, 8, 16, false, 0, true, true, DET>(d, s)
+                                         : launch_dp_bwd<32, 64, 8, 16, false, 0, true, false, DET>(d, s);
+        // (option bwd_fp32mma: the exact-fp32 matrix instruction for this instance too -- before round 5 the pooled-dy
+        // 64 -> 64 unit stayed on the split-bf16 kernel even with the option set)
+        if (yunet_options().bwd_fp32mma != 0) return launch_dp_bwd<64, 64, 8, 16, false, 0, true, false, DET>(d, s);
+        return ACT_SUFFIX(launch_dp_bwd64)(d, bwd64_nw(d->N, d->H, d->W), s);
+    }
+#define DP_CASE(ci, co) \
+    if (d->cin == ci && d->cout == co) return launch_dp_bwd<ci, co, 8, 16, false, 0, false, false, DET>(d, s);
+    if (dp_bwd_big_tile(d->H, d->W, d->cin, d->cout))    // 160x160 / 80x80 levels: bigger tile
+        return (d->H % 16 == 0 && d->W % 32 == 0) ? launch_dp_bwd<16, 16, 16, 32, false, 0, false, true, DET>(d, s)
+                                                  : launch_dp_bwd<16, 16, 16, 32, false, 0, false, false, DET>(d, s);
+    // 64 -> 64 units: split-bf16 GEMMs (gradients only); the option bwd_fp32mma keeps the exact-fp32
+    // matrix instruction (bench.py's exact_fp32_bwd line, tools/kbench.py)
+    const bool f32mma = yunet_options().bwd_fp32mma != 0;
+    if (dp_use_pack_bwd(d->N, d->H, d->W, d->cin, d->cout)) {           // 20x20 / 10x10 levels: packed canvas
+        if (d->cout == 64) {
+            if (f32mma) return launch_dp_bwd<64, 64, 8, 16, true, 0, false, false, DET>(d, s);
+            return ACT_SUFFIX(launch_dp_bwd64)(d, bwd64_nw(d->N, d->H, d->W), s);
+        }
+        return launch_dp_bwd<64, 16, 8, 16, true, 0, false, false, DET>(d, s);
+    }
+    if (d->cin == 64 && d->cout == 64 && !f32mma)
+        return ACT_SUFFIX(launch_dp_bwd64)(d, bwd64_nw(d->N, d->H, d->W), s);
+    if (d->cin == 32 && d->cout == 64 && !f32mma && yunet_options().bwd32_split)      // (plain 32 -> 64: split-bf16 as above)
+        return (d->H % 8 == 0 && d->W % 16 == 0) ? launch_dp_bwd<32, 64, 8, 16, false, 1, false, true, DET>(d, s)
+                                                 : launch_dp_bwd<32, 64, 8, 16, false, 1, false, false, DET>(d, s);
+    if (d->H % 8 == 0 && d->W % 16 == 0) {       // whole-tile maps of the 16-channel stages (80 x 80 in the shipped nets)
+        if (d->cin == 16 && d->cout == 64) return launch_dp_bwd<16, 64, 8, 16, false, 0, false, true, DET>(d, s);
+        if (d->cin == 16 && d->cout == 32) return launch_dp_bwd<16, 32, 8, 16, false, 0, false, true, DET>(d, s);
+        if (d->cin == 32 && d->cout == 32) return launch_dp_bwd<32, 32, 8, 16, false, 0, false, true, DET>(d, s);
+    }
+    DP_CASE(16, 16)
+    DP_CASE(16, 32)
+    DP_CASE(16, 64)
+    DP_CASE(32, 32)
+    DP_CASE(32, 64)
+    DP_CASE(64, 64)
+    DP_CASE(64, 16)
+#undef DP_CASE
+    return YUNET_EINVAL;
+}
+}  // namespace
+
 extern "C" int ACT_SUFFIX(yunet_dp_bwd)(const YunetDP* d, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (d->x_dtype != YUNET_ACT_DTYPE) return YUNET_EINVAL;
@@ -917,6 +982,9 @@ extern "C" int ACT_SUFFIX(yunet_dp_bwd)(const YunetDP* d, void* stream) {
         return YUNET_EINVAL;   // the partial buffer must have exactly the rows the grid writes
     if (d->in_transform != YUNET_T_IDENTITY && d->in_transform != YUNET_T_BNRELU) return YUNET_EINVAL;
     if (!d->z && !dp_bwd_streams16(d)) return YUNET_EINVAL;      // a null z: only where the kernel recomputes it (bwd_grid.h)
+#ifndef YUNET_ACT_BF16
+    if (dp_bwd_det_fast(d)) return dp_bwd_dispatch<true>(d, s);
+#endif
     if (dp_bwd_det(d)) {
         // deterministic BatchNorm sums (include/yunet_hip.h): the tile kernel in its DET form, exact-fp32 GEMMs, for every
         // unit -- the same tiles, packed canvas and pooled dy as below; not dp_bwd64, dp_bwd16s or the split-bf16 GEMMs
@@ -944,60 +1012,5 @@ extern "C" int ACT_SUFFIX(yunet_dp_bwd)(const YunetDP* d, void* stream) {
 #endif
         return YUNET_EINVAL;
     }
-    // the 16 -> 16 unit on the 160 x 160 / 80 x 80 levels: wave-streaming kernel that recomputes z from x instead of
-    // reading it (conv_bwd16.hip); same grid and partial rows as the tile kernel it replaces
-    if (dp_bwd_streams16(d)) return ACT_SUFFIX(launch_dp_bwd16s)(d, s);
-    if (d->pool_idx) {
-        // dy is the pooled gradient + argmax bytes (max_pool2d backward while staging)
-        if (!yunet_dp_pool_fusion_ok(d->N, d->H, d->W, d->cin, d->cout) || !d->out_has_bn) return YUNET_EINVAL;
-        const bool full816 = d->H % 8 == 0 && d->W % 16 == 0, full1632 = d->H % 16 == 0 && d->W % 32 == 0;
-        if (d->cin == 16) return full1632 ? launch_dp_bwd<16, 16, 16, 32, false, 0, true, true>(d, s)
-                                          : launch_dp_bwd<16, 16, 16, 32, false, 0, true>(d, s);
-        // 32 -> 64 (YuNet_s, in front of its 80 x 80 -> 40 x 40 pool): on the exact-fp32 matrix instruction this unit is
-        // MATRIX-bound (12.3 kFLOP per pixel at 157 TFLOP/s: 0.87 ms per 512-image launch = 0.16 of the HBM peak, the
-        // slowest kernel of the YuNet_s step); round 5 puts it on the split-bf16 path of the 64 -> 64 units (GEMM = 1)
-        if (d->cin == 32 && yunet_options().bwd_fp32mma == 0 && yunet_options().bwd32_split)
-            return full816 ? launch_dp_bwd<32, 64, 8, 16, false, 1, true, true>(d, s)
-                           : launch_dp_bwd<32, 64, 8, 16, false, 1, true>(d, s);
-        if (d->cin == 32) return full816 ? launch_dp_bwd<32, 64, 8, 16, false, 0, true, true>(d, s)
-                                         : launch_dp_bwd<32, 64, 8, 16, false, 0, true>(d, s);
-        // (option bwd_fp32mma: the exact-fp32 matrix instruction for this instance too -- before round 5 the pooled-dy
-        // 64 -> 64 unit stayed on the split-bf16 kernel even with the option set)
-        if (yunet_options().bwd_fp32mma != 0) return launch_dp_bwd<64, 64, 8, 16, false, 0, true>(d, s);
-        return ACT_SUFFIX(launch_dp_bwd64)(d, bwd64_nw(d->N, d->H, d->W), s);
-    }
-#define DP_CASE(ci, co) \
-    if (d->cin == ci && d->cout == co) return launch_dp_bwd<ci, co, 8, 16>(d, s);
-    if (dp_bwd_big_tile(d->H, d->W, d->cin, d->cout))    // 160x160 / 80x80 levels: bigger tile
-        return (d->H % 16 == 0 && d->W % 32 == 0) ? launch_dp_bwd<16, 16, 16, 32, false, 0, false, true>(d, s)
-                                                  : launch_dp_bwd<16, 16, 16, 32>(d, s);
-    // 64 -> 64 units: split-bf16 GEMMs (gradients only); the option bwd_fp32mma keeps the exact-fp32
-    // matrix instruction (bench.py's exact_fp32_bwd line, tools/kbench.py)
-    const bool f32mma = yunet_options().bwd_fp32mma != 0;
-    if (dp_use_pack_bwd(d->N, d->H, d->W, d->cin, d->cout)) {           // 20x20 / 10x10 levels: packed canvas
-        if (d->cout == 64) {
-            if (f32mma) return launch_dp_bwd<64, 64, 8, 16, true>(d, s);
-            return ACT_SUFFIX(launch_dp_bwd64)(d, bwd64_nw(d->N, d->H, d->W), s);
-        }
-        return launch_dp_bwd<64, 16, 8, 16, true>(d, s);
-    }
-    if (d->cin == 64 && d->cout == 64 && !f32mma)
-        return ACT_SUFFIX(launch_dp_bwd64)(d, bwd64_nw(d->N, d->H, d->W), s);
-    if (d->cin == 32 && d->cout == 64 && !f32mma && yunet_options().bwd32_split)      // (plain 32 -> 64: split-bf16 as above)
-        return (d->H % 8 == 0 && d->W % 16 == 0) ? launch_dp_bwd<32, 64, 8, 16, false, 1, false, true>(d, s)
-                                                 : launch_dp_bwd<32, 64, 8, 16, false, 1>(d, s);
-    if (d->H % 8 == 0 && d->W % 16 == 0) {       // whole-tile maps of the 16-channel stages (80 x 80 in the shipped nets)
-        if (d->cin == 16 && d->cout == 64) return launch_dp_bwd<16, 64, 8, 16, false, 0, false, true>(d, s);
-        if (d->cin == 16 && d->cout == 32) return launch_dp_bwd<16, 32, 8, 16, false, 0, false, true>(d, s);
-        if (d->cin == 32 && d->cout == 32) return launch_dp_bwd<32, 32, 8, 16, false, 0, false, true>(d, s);
-    }
-    DP_CASE(16, 16)
-    DP_CASE(16, 32)
-    DP_CASE(16, 64)
-    DP_CASE(32, 32)
-    DP_CASE(32, 64)
-    DP_CASE(64, 64)
-    DP_CASE(64, 16)
-#undef DP_CASE
-    return YUNET_EINVAL;
+    return dp_bwd_dispatch<false>(d, s);
 }

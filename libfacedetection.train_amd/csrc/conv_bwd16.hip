@@ -28,6 +28,7 @@
 // byte per element when the unit feeds max_pool2d: YunetDP.pool_idx) and dx -- z is not read.
 #include "common.h"
 #include "dp_bwd_parts.h"
+#include "bwd_grid.h"
 
 namespace {
 namespace b16s {
@@ -44,8 +45,9 @@ constexpr int OFF_B2 = OFF_W2 + 9 * C;
 constexpr int OFF_B1 = OFF_B2 + C;
 constexpr int OFF_FOLD = OFF_B1 + C;               // [4][C]  A | B | Dh | Dl of the unit's own BN
 constexpr int OFF_IN = OFF_FOLD + 4 * C;           // [5][C]  mean | scale | beta | invstd | mean_lo of the producer's BN
-constexpr int OFF_ST = OFF_IN + 5 * C;             // double [2][C]
+constexpr int OFF_ST = OFF_IN + 5 * C;             // double [2][C]; DET: double [WAVES][2][C], one row per wave
 constexpr int SMEM_F = OFF_ST + 4 * C;
+constexpr int SMEM_F_DET = OFF_ST + WAVES * 4 * C;
 static_assert(WROW <= WAVE_F, "flush area inside the wave's slots");
 static_assert((OFF_ST * 4) % 8 == 0, "fp64 alignment");
 }  // namespace b16s
@@ -54,7 +56,11 @@ __device__ __forceinline__ float lane_read(int src_lane, float v) {       // v o
     return __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane << 2, __float_as_int(v)));
 }
 
-template <bool POOLDY>
+// DET (YUNET_DET_FAST in the producer's YunetBN::det_rows): every wave keeps its own fp64 row of band sums -- the lane that
+// owns a channel adds band after band with plain LDS accesses, in the wave's static task order -- thread c adds the eight
+// rows in wave order after the closing barrier and the result goes to the workgroup's row of the [1 + R][2C] block
+// (common.h: bn_det_add).  No fp64 atomic of any scope; everything else is the same code.
+template <bool POOLDY, bool DET = false>
 __global__ __launch_bounds__(b16s::NTHR, 1) void dp_bwd16s_kernel(const YunetDP d, const int R) {
     using namespace b16s;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -86,7 +92,7 @@ __global__ __launch_bounds__(b16s::NTHR, 1) void dp_bwd16s_kernel(const YunetDP 
             s_in[tid] = 0.f; s_in[C + tid] = 1.f; s_in[2 * C + tid] = 0.f; s_in[3 * C + tid] = 1.f; s_in[4 * C + tid] = 0.f;
         }
     }
-    if (tid < 2 * C) s_st[tid] = 0.0;
+    if (tid < (DET ? WAVES : 1) * 2 * C) s_st[tid] = 0.0;
     // weight fragments: A operands of the p GEMM (W1[co = l15][ci = 4 g + s]) and of the da GEMM (W1[co = 4 g + s][ci = l15])
     float w1a[4], w1t[4];
 #pragma unroll
@@ -391,6 +397,13 @@ __global__ __launch_bounds__(b16s::NTHR, 1) void dp_bwd16s_kernel(const YunetDP 
                 float a = ts0[i], b = ts1[i];
 #pragma unroll
                 for (int m = 1; m < 16; m <<= 1) { a += __shfl_xor(a, m, 64); b += __shfl_xor(b, m, 64); }
+                if constexpr (DET) {
+                    if (l15 == 0) {
+                        double* wst = s_st + wid * 2 * C;
+                        wst[4 * g + i] += (double)a;
+                        wst[C + 4 * g + i] += (double)b;
+                    }
+                } else
                 if (l15 == 0) {
                     __hip_atomic_fetch_add(&s_st[4 * g + i], (double)a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     __hip_atomic_fetch_add(&s_st[C + 4 * g + i], (double)b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -429,6 +442,14 @@ __global__ __launch_bounds__(b16s::NTHR, 1) void dp_bwd16s_kernel(const YunetDP 
         for (int wv = 0; wv < WAVES; ++wv) v += sm[wv * WAVE_F + i];
         row[i] = v;
     }
+    if constexpr (DET) {
+        if (bn_in && d.in_bn.bstats && tid < 2 * C) {
+            double v = 0.0;
+#pragma unroll
+            for (int wv = 0; wv < WAVES; ++wv) v += s_st[wv * 2 * C + tid];
+            bn_det_add(d.in_bn.bstats, C, tid, v);
+        }
+    } else
     if (bn_in && d.in_bn.bstats && tid < 2 * C) atomic_add_f64(bn_slot(d.in_bn.bstats, d.in_bn.slots, C) + tid, s_st[tid]);
 }
 
@@ -447,19 +468,20 @@ int bwd16s_rows(int N, int H, int W, int waves) {
     return best;
 }
 
-template <bool POOLDY>
+template <bool POOLDY, bool DET = false>
 int launch_bwd16s(const YunetDP* d, hipStream_t stream) {
-    constexpr size_t smem = (size_t)b16s::SMEM_F * 4;
+    constexpr size_t smem = (size_t)(DET ? b16s::SMEM_F_DET : b16s::SMEM_F) * 4;
     static PerDevice attr_set;      // per device (common.h)
     if (per_device(attr_set, [] {
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(dp_bwd16s_kernel<POOLDY>),
+            return hipFuncSetAttribute(reinterpret_cast<const void*>(dp_bwd16s_kernel<POOLDY, DET>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) == hipSuccess ? 1 : -1;
         }) < 0)
         return YUNET_EINVAL;
     if ((long long)d->H * d->W * 16 * 4 >= (1ll << 31)) return YUNET_EINVAL;      // 32-bit byte offsets per image
     const int grid = d->wgrad_blocks;                                             // every workgroup writes its partial row
+    if (DET && !bn_det_fits(d->in_bn, grid)) return YUNET_EINVAL;
     const int R = bwd16s_rows(d->N, d->H, d->W, grid * b16s::WAVES);
-    hipLaunchKernelGGL(dp_bwd16s_kernel<POOLDY>, dim3(grid), dim3(b16s::NTHR), smem, stream, *d, R);
+    hipLaunchKernelGGL((dp_bwd16s_kernel<POOLDY, DET>), dim3(grid), dim3(b16s::NTHR), smem, stream, *d, R);
     return hip_status();
 }
 
@@ -471,5 +493,12 @@ int launch_bwd16s(const YunetDP* d, hipStream_t stream) {
 // the BatchNorm sums were taken from (the tile kernel reads the rounded one).
 int ACT_SUFFIX(launch_dp_bwd16s)(const YunetDP* d, hipStream_t stream) {
     if (d->x_dtype != YUNET_ACT_DTYPE) return YUNET_EINVAL;
+#ifndef YUNET_ACT_BF16
+    // the producer's BN-backward sums into order-fixed rows (bwd_grid.h: dp_bwd_det): the DET instances, fast level only
+    if (dp_bwd_det(d)) {
+        if (!dp_bwd_det_fast(d)) return YUNET_EINVAL;
+        return d->pool_idx ? launch_bwd16s<true, true>(d, stream) : launch_bwd16s<false, true>(d, stream);
+    }
+#endif
     return d->pool_idx ? launch_bwd16s<true>(d, stream) : launch_bwd16s<false>(d, stream);
 }

@@ -2,6 +2,7 @@
 // launch_dp_bwd64 (common.h).
 #include "common.h"
 #include "dp_bwd_parts.h"
+#include "bwd_grid.h"
 
 #include <type_traits>
 
@@ -104,7 +105,9 @@ __device__ __forceinline__ f32x4 mfma3r(const u32x4 ah, const u32x4 al, const u3
 }
 }  // namespace bwd64
 
-template <int NW, bool PACKED, bool POOLDY>
+// DET (YUNET_DET_FAST in the producer's YunetBN::det_rows): the workgroup's sums -- already added up in a fixed order -- go to
+// its own row of the [1 + R][2C] block (common.h: bn_det_add) instead of one fp64 atomic per channel; nothing else differs.
+template <int NW, bool PACKED, bool POOLDY, bool DET = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))     // 256 registers per lane: 8 waves per CU
 void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
     using namespace bwd64;
@@ -832,7 +835,8 @@ void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
     if (bn_in && d.dx && d.in_bn.bstats && tid < 2 * C) {
         double v = s_bst[tid];
         if constexpr (MH == 2) v += s_bst[2 * C + tid];
-        atomic_add_f64(bn_slot(d.in_bn.bstats, d.in_bn.slots, C) + tid, v);
+        if constexpr (DET) bn_det_add(d.in_bn.bstats, C, tid, v);
+        else atomic_add_f64(bn_slot(d.in_bn.bstats, d.in_bn.slots, C) + tid, v);
     }
     __syncthreads();
     my[0] = gw2[6]; my[1] = gw2[7]; my[2] = gw2[8]; my[3] = gb1; my[4] = gb2;
@@ -840,16 +844,25 @@ void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
     reduce_pass(1, 5);
 }
 
-template <int NW, bool PACKED, bool POOLDY>
+template <int NW, bool PACKED, bool POOLDY, bool DET = false>
 int launch_dp_bwd64(const YunetDP* d, hipStream_t stream) {
     using G = bwd64::Geo<NW>;
     static PerDevice attr_set;      // per device (common.h)
     PackGeom pk;
     const int grid = dp_bwd_launch_setup<G::TH, G::TW, PACKED>(
-        d, attr_set, reinterpret_cast<const void*>(dp_bwd64_kernel<NW, PACKED, POOLDY>), G::SMEM, pk);
+        d, attr_set, reinterpret_cast<const void*>(dp_bwd64_kernel<NW, PACKED, POOLDY, DET>), G::SMEM, pk);
     if (grid < 0) return grid;
-    hipLaunchKernelGGL((dp_bwd64_kernel<NW, PACKED, POOLDY>), dim3(grid), dim3(G::NT), G::SMEM, stream, *d, pk);
+    if (DET && !bn_det_fits(d->in_bn, grid)) return YUNET_EINVAL;
+    hipLaunchKernelGGL((dp_bwd64_kernel<NW, PACKED, POOLDY, DET>), dim3(grid), dim3(G::NT), G::SMEM, stream, *d, pk);
     return hip_status();
+}
+// the six instances the dispatcher reaches, in the form DET
+template <bool DET>
+int launch_dp_bwd64_form(const YunetDP* d, int nw, hipStream_t stream) {
+    if (d->pool_idx) return nw == 4 ? launch_dp_bwd64<4, false, true, DET>(d, stream) : launch_dp_bwd64<8, false, true, DET>(d, stream);
+    if (dp_use_pack_bwd(d->N, d->H, d->W, d->cin, d->cout))
+        return nw == 4 ? launch_dp_bwd64<4, true, false, DET>(d, stream) : launch_dp_bwd64<8, true, false, DET>(d, stream);
+    return nw == 4 ? launch_dp_bwd64<4, false, false, DET>(d, stream) : launch_dp_bwd64<8, false, false, DET>(d, stream);
 }
 
 }  // namespace
@@ -857,8 +870,9 @@ int launch_dp_bwd64(const YunetDP* d, hipStream_t stream) {
 // conv_bwd.hip's dispatcher: nw = bwd64_nw(N, H, W) (bwd_grid.h: the choice also fixes the rows of wgrad_partials);
 // pooled dy (YunetDP.pool_idx: unpacked levels only, yunet_dp_pool_fusion_ok), else the packed canvas on the small levels
 int ACT_SUFFIX(launch_dp_bwd64)(const YunetDP* d, int nw, hipStream_t stream) {
-    if (d->pool_idx) return nw == 4 ? launch_dp_bwd64<4, false, true>(d, stream) : launch_dp_bwd64<8, false, true>(d, stream);
-    if (dp_use_pack_bwd(d->N, d->H, d->W, d->cin, d->cout))
-        return nw == 4 ? launch_dp_bwd64<4, true, false>(d, stream) : launch_dp_bwd64<8, true, false>(d, stream);
-    return nw == 4 ? launch_dp_bwd64<4, false, false>(d, stream) : launch_dp_bwd64<8, false, false>(d, stream);
+#ifndef YUNET_ACT_BF16
+    // a launch that produces the producer's BN-backward sums into order-fixed rows (bwd_grid.h: dp_bwd_det)
+    if (dp_bwd_det(d)) return bn_det_fast(d->in_bn) ? launch_dp_bwd64_form<true>(d, nw, stream) : YUNET_EINVAL;
+#endif
+    return launch_dp_bwd64_form<false>(d, nw, stream);
 }

@@ -426,7 +426,7 @@ extern "C" int ACT_SUFFIX(yunet_pool_bwd_add)(const float* z, const YunetBN* bn,
                                               float* dx, int accumulate, int N, int H, int W, int C, void* stream) {
     if ((H & 1) || (W & 1) || (C & 3) || (256 % (C / 4)) || C > 64) return YUNET_EINVAL;
     const long long total = (long long)N * (H / 2) * (W / 2) * (C / 4);
-    if (bn->det_rows && bn->bstats) {          // deterministic sums (include/yunet_hip.h): fp32 storage only
+    if (YUNET_DET_ROWS(bn->det_rows) && bn->bstats) {          // deterministic sums (include/yunet_hip.h): fp32 storage only
 #ifndef YUNET_ACT_BF16
         if (!bn_det_fits(*bn, ew_grid(total))) return YUNET_EINVAL;
         hipLaunchKernelGGL(pool_bwd_kernel<true>, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream,
@@ -452,7 +452,7 @@ extern "C" int ACT_SUFFIX(yunet_upadd_bwd)(const float* za, const YunetBN* bna, 
                                            void* stream) {
     if ((H & 1) || (W & 1) || (C & 3) || (256 % (C / 4)) || C > 64) return YUNET_EINVAL;
     const long long total = (long long)N * (H / 2) * (W / 2) * (C / 4);
-    if ((bnb->det_rows && bnb->bstats) || (dxa && bna->det_rows && bna->bstats)) {      // deterministic sums: both blocks or neither
+    if ((YUNET_DET_ROWS(bnb->det_rows) && bnb->bstats) || (dxa && YUNET_DET_ROWS(bna->det_rows) && bna->bstats)) {      // deterministic sums: both blocks or neither
 #ifndef YUNET_ACT_BF16
         if (!bnb->bstats || !bn_det_fits(*bnb, ew_grid(total)) || (dxa && (!bna->bstats || !bn_det_fits(*bna, ew_grid(total)))))
             return YUNET_EINVAL;

@@ -763,9 +763,12 @@ extern "C" int ACT_SUFFIX(yunet_dp_fwd)(const YunetDP* d, void* stream) {
     if (d->x_dtype != YUNET_ACT_DTYPE) return YUNET_EINVAL;
     if (d->z_dtype != YUNET_ACT_DTYPE && !(d->cout == 16 && d->z_dtype == YUNET_F32)) return YUNET_EINVAL;
     if (d->in_transform != YUNET_T_IDENTITY && d->in_transform != YUNET_T_BNRELU) return YUNET_EINVAL;
-    const bool det = d->out_has_bn && d->out_bn.det_rows;
+    const bool det = d->out_has_bn && YUNET_DET_ROWS(d->out_bn.det_rows);
+    // the fast deterministic level (YUNET_DET_FAST, fp32 storage): the dispatch of the default mode; the launchers of the
+    // wave-streaming kernels pick their DET instances from the descriptor
+    const bool det_fast = det && bn_det_fast(d->out_bn) && YUNET_ACT_DTYPE == YUNET_F32;
     // units with 16 input channels: wave-streaming kernels (conv_fwd16.hip)
-    const bool fwd16s = !det && d->cin == 16 && (d->cout == 16 || (d->cout == 64 && !d->pool_out)) && d->z_dtype == YUNET_ACT_DTYPE &&
+    const bool fwd16s = (!det || det_fast) && d->cin == 16 && (d->cout == 16 || (d->cout == 64 && !d->pool_out)) && d->z_dtype == YUNET_ACT_DTYPE &&
                         !d->prof && yunet_options().fwd16s &&
                         (!d->pool_out || (yunet_dp_pool_fusion_ok(d->N, d->H, d->W, 16, 16) && d->out_bn.gamma && d->pool_idx &&
                                           !(reinterpret_cast<uintptr_t>(d->pool_idx) & 3)));
@@ -776,6 +779,17 @@ extern "C" int ACT_SUFFIX(yunet_dp_fwd)(const YunetDP* d, void* stream) {
         // choice of tile, packed canvas and fused pooling as below, none of the wave-streaming kernels
 #ifndef YUNET_ACT_BF16
         if (d->z_dtype != YUNET_ACT_DTYPE || !d->out_bn.stats) return YUNET_EINVAL;
+        if (det_fast) {
+            // the predicates of the default dispatch below, in its order; what they leave falls through to the tile kernels,
+            // whose DET instances are the ones of the plain deterministic level (same tiles, packed canvas and fused pooling)
+            if (fwd16s) return launch_dp_fwd16s(d, s);
+            const bool pool_ok = d->pool_out && yunet_dp_pool_fusion_ok(d->N, d->H, d->W, d->cin, d->cout) && d->out_bn.gamma &&
+                                 d->pool_idx && !(reinterpret_cast<uintptr_t>(d->pool_idx) & 3);
+            const bool packed_tile = dp_use_pack(d->N, d->H, d->W, d->cin, d->cout) && yunet_options().fwd64s < 2;
+            if (d->cin == 64 && d->cout == 64 && (unsigned long long)d->prof < 64ull && yunet_options().fwd64s &&
+                (d->pool_out ? pool_ok : !packed_tile))
+                return launch_dp_fwd64s(d, s);
+        }
         if (d->pool_out) {
             if (!yunet_dp_pool_fusion_ok(d->N, d->H, d->W, d->cin, d->cout) || !d->out_bn.gamma || !d->pool_idx ||
                 (reinterpret_cast<uintptr_t>(d->pool_idx) & 3))
@@ -841,7 +855,7 @@ extern "C" int ACT_SUFFIX(yunet_dp_fwd_group)(const YunetDP* const* units, int n
     bool one_grid = n >= 2 && yunet_options().fwd_group != 0;
     for (int i = 0; i < n && one_grid; ++i) {
         const YunetDP* d = units[i];
-        one_grid = d && !(d->out_has_bn && d->out_bn.det_rows) &&
+        one_grid = d && !(d->out_has_bn && YUNET_DET_ROWS(d->out_bn.det_rows)) &&
                    d->x_dtype == YUNET_ACT_DTYPE && d->z_dtype == YUNET_ACT_DTYPE && d->cin == 64 && d->cout == 64 &&
                    d->z && !d->pool_out && !d->prof && yunet_options().fwd64s != 0 &&
                    (d->in_transform == YUNET_T_IDENTITY || d->in_transform == YUNET_T_BNRELU) &&

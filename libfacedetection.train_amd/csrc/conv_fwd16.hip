@@ -32,7 +32,11 @@ struct G {
 
 // The kernel's body.  ZOUT = false (POOL only; a null YunetDP.z, see dp_fwd16s_kernel): the full-size z is not produced --
 // no slot Z, no 16-byte z stores; the BN sums, the winners and their positions are the same values from the same operations.
-template <int COUT, bool POOL, bool ZOUT>
+// DET (YUNET_DET_FAST in YunetBN::det_rows): every wave keeps its own fp64 row of sums -- the lane that owns a channel adds
+// band after band with plain LDS accesses, in the wave's static task order -- thread c adds the four rows in wave order after
+// the closing barrier and the result goes to the workgroup's row of the [1 + R][2 COUT] block (common.h: bn_det_add): no fp64
+// atomic of any scope; everything else is the same code.
+template <int COUT, bool POOL, bool ZOUT, bool DET = false>
 __device__ __forceinline__ void dp_fwd16s_body(const YunetDP d, const int R) {
     using namespace f16s;
     using GG = G<COUT>;
@@ -47,7 +51,7 @@ __device__ __forceinline__ void dp_fwd16s_body(const YunetDP d, const int R) {
     float* s_b2 = s_w2 + 9 * COUT;
     float* s_b1 = s_b2 + COUT;
     float* s_in = s_b1 + COUT;                              // [3][16] mean | scale | beta of the producer's BN
-    double* s_st = reinterpret_cast<double*>(s_in + 3 * CIN);   // [2][COUT] (the float offset up to here is even: 8-byte aligned)
+    double* s_st = reinterpret_cast<double*>(s_in + 3 * CIN);   // [2][COUT] (the float offset up to here is even: 8-byte aligned); DET: [WAVES][2][COUT]
     static_assert(((WAVES * WAVE_F + 11 * COUT + 3 * CIN) & 1) == 0, "fp64 alignment");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -66,7 +70,7 @@ __device__ __forceinline__ void dp_fwd16s_body(const YunetDP d, const int R) {
             s_in[tid] = 0.f; s_in[CIN + tid] = 1.f; s_in[2 * CIN + tid] = 0.f;
         }
     }
-    for (int i = tid; i < 2 * COUT; i += NTHR) s_st[i] = 0.0;
+    for (int i = tid; i < (DET ? WAVES : 1) * 2 * COUT; i += NTHR) s_st[i] = 0.0;
     // A operands of the pointwise product: W1[co = 16 mt + l15][ci = 4 g + s]
     float w1a[MT][4];
 #pragma unroll
@@ -250,6 +254,13 @@ __device__ __forceinline__ void dp_fwd16s_body(const YunetDP d, const int R) {
                 a += __shfl_xor(a, 16, 64); b += __shfl_xor(b, 16, 64);
                 a += __shfl_xor(a, 32, 64); b += __shfl_xor(b, 32, 64);
             }
+            if constexpr (DET) {
+                if (sg == 0) {
+                    double* wst = s_st + wid * 2 * COUT;
+                    wst[cc] += (double)a;
+                    wst[COUT + cc] += (double)b;
+                }
+            } else
             if (sg == 0) {
                 __hip_atomic_fetch_add(&s_st[cc], (double)a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 __hip_atomic_fetch_add(&s_st[COUT + cc], (double)b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -258,6 +269,15 @@ __device__ __forceinline__ void dp_fwd16s_body(const YunetDP d, const int R) {
     }
     if (d.out_has_bn) {
         __syncthreads();
+        if constexpr (DET) {
+            static_assert(2 * COUT <= NTHR, "one thread per sum");
+            if (tid < 2 * COUT) {          // (not a loop: bn_det_add is a load and a store)
+                double v = 0.0;
+#pragma unroll
+                for (int wv = 0; wv < WAVES; ++wv) v += s_st[wv * 2 * COUT + tid];
+                bn_det_add(d.out_bn.stats, COUT, tid, v);
+            }
+        } else
         for (int i = tid; i < 2 * COUT; i += NTHR) atomic_add_f64(bn_slot(d.out_bn.stats, d.out_bn.slots, COUT) + i, s_st[i]);
     }
 }
@@ -265,16 +285,16 @@ __device__ __forceinline__ void dp_fwd16s_body(const YunetDP d, const int R) {
 // One kernel per (COUT, POOL): the name profiles and bench.py key on.  The pooled unit whose full-size output nobody reads
 // (include/yunet_hip.h: a null YunetDP.z) takes the body without the z path -- a kernel argument, so the branch is scalar
 // and taken once per wave.
-template <int COUT, bool POOL>
+template <int COUT, bool POOL, bool DET = false>
 __global__ __launch_bounds__(f16s::NTHR) __attribute__((amdgpu_waves_per_eu(3, 3)))      // <= 168 registers: three workgroups per CU
 void dp_fwd16s_kernel(const YunetDP d, const int R) {
     if constexpr (POOL) {
         if (d.z == nullptr) {
-            dp_fwd16s_body<COUT, POOL, false>(d, R);
+            dp_fwd16s_body<COUT, POOL, false, DET>(d, R);
             return;
         }
     }
-    dp_fwd16s_body<COUT, POOL, true>(d, R);
+    dp_fwd16s_body<COUT, POOL, true, DET>(d, R);
 }
 
 // rows per band: minimise (tasks per wave, rounded up) x (rows of a task incl. the two halo rows + set-up)
@@ -290,13 +310,14 @@ int fwd16s_rows(int N, int H, int W, int outw, int waves, bool even) {
     return best;
 }
 
-template <int COUT, bool POOL>
+template <int COUT, bool POOL, bool DET = false>
 int launch_fwd16s(const YunetDP* d, hipStream_t stream) {
     using GG = f16s::G<COUT>;
-    constexpr size_t smem = ((size_t)f16s::WAVES * GG::WAVE_F + 11 * COUT + 3 * 16) * 4 + 2 * COUT * 8;
+    // (DET: one fp64 row of sums per wave -- 23.4 KB for 16 output channels, 41.9 KB for 64: still three workgroups per CU)
+    constexpr size_t smem = ((size_t)f16s::WAVES * GG::WAVE_F + 11 * COUT + 3 * 16) * 4 + (DET ? f16s::WAVES : 1) * 2 * COUT * 8;
     static PerDevice per_cu;        // resident workgroups per CU, per device (common.h)
     const int blocks_per_cu = per_device(per_cu, [] {
-        const void* fn = reinterpret_cast<const void*>(dp_fwd16s_kernel<COUT, POOL>);
+        const void* fn = reinterpret_cast<const void*>(dp_fwd16s_kernel<COUT, POOL, DET>);
         if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, f16s::NTHR, smem) != hipSuccess || nb < 1) nb = 1;
@@ -312,7 +333,8 @@ int launch_fwd16s(const YunetDP* d, hipStream_t stream) {
     const long long tasks = (long long)d->N * ((d->W + OUTW - 1) / OUTW) * ((d->H + R - 1) / R);
     const long long need = (tasks + f16s::WAVES - 1) / f16s::WAVES;
     if (need < grid) grid = (int)need;
-    hipLaunchKernelGGL((dp_fwd16s_kernel<COUT, POOL>), dim3(grid), dim3(f16s::NTHR), smem, stream, *d, R);
+    if (DET && (!d->out_bn.stats || !bn_det_fits(d->out_bn, grid))) return YUNET_EINVAL;
+    hipLaunchKernelGGL((dp_fwd16s_kernel<COUT, POOL, DET>), dim3(grid), dim3(f16s::NTHR), smem, stream, *d, R);
     return hip_status();
 }
 
@@ -321,6 +343,14 @@ int launch_fwd16s(const YunetDP* d, hipStream_t stream) {
 // conv_fwd.hip's dispatcher: units with 16 input channels and 16 or 64 output channels (fused pooling: 16 -> 16); compiled
 // once per activation storage type (fp32 | -DYUNET_ACT_BF16: x, z and the pooled winners as bf16, same arithmetic)
 int ACT_SUFFIX(launch_dp_fwd16s)(const YunetDP* d, hipStream_t stream) {
+#ifndef YUNET_ACT_BF16
+    // BatchNorm sums into order-fixed rows (YunetBN::det_rows): the DET instances, fast level only
+    if (d->out_has_bn && YUNET_DET_ROWS(d->out_bn.det_rows)) {
+        if (!bn_det_fast(d->out_bn)) return YUNET_EINVAL;
+        if (d->cout == 16) return d->pool_out ? launch_fwd16s<16, true, true>(d, stream) : launch_fwd16s<16, false, true>(d, stream);
+        return launch_fwd16s<64, false, true>(d, stream);
+    }
+#endif
     if (d->cout == 16) return d->pool_out ? launch_fwd16s<16, true>(d, stream) : launch_fwd16s<16, false>(d, stream);
     return launch_fwd16s<64, false>(d, stream);
 }

@@ -40,6 +40,7 @@ constexpr int SPX = PX + 2;                                  // slot pixels: the
 constexpr size_t W1_BYTES = (size_t)3 * C * C * 2;          // bf16 planes h | m | l, [co][ci], 16-byte chunks XOR-swizzled
 constexpr size_t SLOT_FLOATS = (size_t)SPX * LS;
 constexpr size_t SMEM = W1_BYTES + (WAVES * SLOT_FLOATS + 9 * C + C + C + C + 2 * C) * 4 + 2 * C * 8;
+constexpr size_t SMEM_DET = SMEM + (WAVES - 1) * 2 * C * 8;  // DET: one fp64 row of sums per wave (51 840 bytes: still three per CU)
 }  // namespace f64s
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -52,7 +53,11 @@ __device__ __forceinline__ float med3(float a, float b, float c) { return __buil
 // even row of a pair waits in registers for the odd one (16 more registers: this instance runs two waves per SIMD).
 // `first` / `nblk`: this workgroup's number inside the grid of ITS unit and the size of that grid (a launch may carry
 // the grids of several independent units one after the other: dp_fwd64s_group_kernel below)
-template <bool POOL>
+// DET (YUNET_DET_FAST in YunetBN::det_rows): every wave keeps its own fp64 row -- the lane that owns a channel adds band after
+// band with plain LDS accesses, in the wave's static task order -- thread c adds the four rows in wave order after the
+// closing barrier and the result goes to the workgroup's row of the [1 + R][2C] block (common.h: bn_det_add): no fp64
+// atomic of any scope; everything else is the same code.
+template <bool POOL, bool DET = false>
 __device__ __forceinline__ void dp_fwd64s_body(const YunetDP& d, const int R, const int first, const int nblk) {
     using namespace f64s;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -63,7 +68,7 @@ __device__ __forceinline__ void dp_fwd64s_body(const YunetDP& d, const int R, co
     float* s_sc = s_b2 + C;                                           // a = med3(x * sc + sh, floor, cap)
     float* s_sh = s_sc + C;
     float* s_b1 = s_sh + C;                                           // [2][C]: zeros | pointwise bias
-    double* s_st = reinterpret_cast<double*>(s_b1 + 2 * C);           // [2 C] sum | sum of squares
+    double* s_st = reinterpret_cast<double*>(s_b1 + 2 * C);           // [2 C] sum | sum of squares; DET: [WAVES][2 C]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, g = lane >> 4;
@@ -97,7 +102,13 @@ __device__ __forceinline__ void dp_fwd64s_body(const YunetDP& d, const int R, co
         }
         s_sc[tid] = sc; s_sh[tid] = sh;
     }
-    if (tid < 2 * C) s_st[tid] = 0.0;
+    if (tid < 2 * C) {
+        s_st[tid] = 0.0;
+        if constexpr (DET) {
+#pragma unroll
+            for (int wv = 1; wv < WAVES; ++wv) s_st[wv * 2 * C + tid] = 0.0;
+        }
+    }
     for (int i = tid; i < WAVES * 2 * LS; i += NTHR) s_p[(i / (2 * LS)) * SLOT_FLOATS + PX * LS + i % (2 * LS)] = 0.0f;
     __syncthreads();
 
@@ -371,6 +382,16 @@ __device__ __forceinline__ void dp_fwd64s_body(const YunetDP& d, const int R, co
                 v += __shfl_xor(v, 32, 64);
                 ts[i] = v;
             }
+            if constexpr (DET) {
+                if (cgrp == 0) {
+                    double* wst = s_st + wid * 2 * C;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        wst[cq * 4 + i] += (double)ts[i];
+                        wst[C + cq * 4 + i] += (double)ts[4 + i];
+                    }
+                }
+            } else
             if (cgrp == 0) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -382,13 +403,21 @@ __device__ __forceinline__ void dp_fwd64s_body(const YunetDP& d, const int R, co
     }
     if (d.out_has_bn) {
         __syncthreads();
+        if constexpr (DET) {
+            if (tid < 2 * C) {
+                double v = 0.0;
+#pragma unroll
+                for (int wv = 0; wv < WAVES; ++wv) v += s_st[wv * 2 * C + tid];
+                bn_det_add(d.out_bn.stats, C, tid, v);
+            }
+        } else
         if (tid < 2 * C) atomic_add_f64(bn_slot(d.out_bn.stats, d.out_bn.slots, C) + tid, s_st[tid]);
     }
 }
 
-template <bool POOL>
+template <bool POOL, bool DET = false>
 __global__ __launch_bounds__(f64s::NTHR, POOL ? 2 : 3) void dp_fwd64s_kernel(const YunetDP d, const int R) {
-    dp_fwd64s_body<POOL>(d, R, first_tile(), (int)gridDim.x);
+    dp_fwd64s_body<POOL, DET>(d, R, first_tile(), (int)gridDim.x);
 }
 
 // Several mutually independent plain units in ONE grid (the share convs of the three pyramid levels: yunet_head.py:175-247
@@ -444,21 +473,23 @@ static int fwd64s_geometry(const YunetDP* d, int blocks_per_cu, bool pool, int* 
     return grid;
 }
 
-template <bool POOL>
+template <bool POOL, bool DET = false>
 static int launch_fwd64s(const YunetDP* d, hipStream_t stream) {
+    constexpr size_t smem = DET ? f64s::SMEM_DET : f64s::SMEM;
     static PerDevice per_cu;        // resident workgroups per CU, per device (common.h)
     const int blocks_per_cu = per_device(per_cu, [] {
-        const void* fn = reinterpret_cast<const void*>(dp_fwd64s_kernel<POOL>);
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f64s::SMEM) != hipSuccess) return -1;
+        const void* fn = reinterpret_cast<const void*>(dp_fwd64s_kernel<POOL, DET>);
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, f64s::NTHR, f64s::SMEM) != hipSuccess || nb < 1) nb = 1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, f64s::NTHR, smem) != hipSuccess || nb < 1) nb = 1;
         return nb > 3 ? 3 : nb;
     });
     if (blocks_per_cu < 1) return YUNET_EINVAL;
     int R = 0;
     const int grid = fwd64s_geometry(d, blocks_per_cu, POOL, &R);
     if (grid < 1) return YUNET_EINVAL;
-    hipLaunchKernelGGL(dp_fwd64s_kernel<POOL>, dim3(grid), dim3(f64s::NTHR), f64s::SMEM, stream, *d, R);
+    if (DET && (!d->out_bn.stats || !bn_det_fits(d->out_bn, grid))) return YUNET_EINVAL;
+    hipLaunchKernelGGL((dp_fwd64s_kernel<POOL, DET>), dim3(grid), dim3(f64s::NTHR), smem, stream, *d, R);
     return hip_status();
 }
 
@@ -495,5 +526,12 @@ int ACT_SUFFIX(launch_dp_fwd64s_group)(const YunetDP* const* ds, int n, hipStrea
 
 int ACT_SUFFIX(launch_dp_fwd64s)(const YunetDP* d, hipStream_t stream) {
     if (d->x_dtype != YUNET_ACT_DTYPE || d->z_dtype != YUNET_ACT_DTYPE || !d->z) return YUNET_EINVAL;
+#ifndef YUNET_ACT_BF16
+    // BatchNorm sums into order-fixed rows (YunetBN::det_rows): the DET instances, fast level only
+    if (d->out_has_bn && YUNET_DET_ROWS(d->out_bn.det_rows)) {
+        if (!bn_det_fast(d->out_bn)) return YUNET_EINVAL;
+        return d->pool_out ? launch_fwd64s<true, true>(d, stream) : launch_fwd64s<false, true>(d, stream);
+    }
+#endif
     return d->pool_out ? launch_fwd64s<true>(d, stream) : launch_fwd64s<false>(d, stream);
 }

@@ -36,6 +36,16 @@ BN_SLOTS = max(1, int(os.environ.get('YUNET_BN_SLOTS', '8')))
 # what readers take (slots = 1), rows 1.. are one per workgroup of the kernels that produce sums (YunetBN::det_rows).  1024 = the
 # largest persistent grid of those kernels (CONV_BLOCKS; the launchers refuse a larger grid).
 DET_ROWS = 1024
+
+
+def det_level(flag):
+    """The deterministic option as it is stored: False | True | 'fast' ('fast': the order-fixed forms of the kernels the default
+    mode uses, YUNET_DET_FAST; True: the exact-fp32 tile kernel set).  Any other string is an error."""
+    if isinstance(flag, str):
+        if flag != 'fast':
+            raise ValueError(f"deterministic {flag!r}: False, True or 'fast'")
+        return 'fast'
+    return bool(flag)
 MAX_PLANS = max(2, int(os.environ.get('YUNET_MAX_PLANS', '16')))     # plans kept per engine (see get_plan)
 LOG_HEAD = 8          # floats in front of the flat gradient: cls, bbox, obj, kps, total, 3 spare
 
@@ -301,10 +311,14 @@ class Plan:
         self.eng, self.n, self.h, self.w, self.gmax = eng, n, h, w, gmax
         self.sw = {name: read_switch(name) for name in PLAN_SWITCHES}      # the environment as it is NOW
         # deterministic mode: order-fixed BatchNorm sums (per-workgroup rows + fold ops), no lanes, no grouped launches
-        self.det = bool(getattr(eng, 'deterministic', False))
+        level = det_level(getattr(eng, 'deterministic', False))
+        self.det = bool(level)
         if self.det and eng.precision == 'bf16':
-            raise NotImplementedError("deterministic=True with precision='bf16': the order-fixed BatchNorm sums exist for the "
+            raise NotImplementedError(f"deterministic={level!r} with precision='bf16': the order-fixed BatchNorm sums exist for the "
                                       'fp32 storage build only')
+        # YunetBN::det_rows of every descriptor; 'fast' sets YUNET_DET_FAST above the row count: the same blocks, memset and
+        # fold ops, the dispatch of the default mode on its kernels' DET instances
+        self.det_rows = (DET_ROWS | (L.DET_FAST if level == 'fast' else 0)) if self.det else 0
         self.bn_rows = 1 + DET_ROWS if self.det else BN_SLOTS      # rows of a layer's sum block
         self.bn_slots = 1 if self.det else BN_SLOTS                # ... of which readers add up this many (YunetBN::slots)
         # activation storage of this plan: fp32, or bf16 ("bf16 fwd / fp32 grads", BASELINE configs[2]):
@@ -726,7 +740,7 @@ class Plan:
         self.bn_count[name] = count
         b = self.bn[name]
         return L.YunetBN(b['stats'].data_ptr(), b['bstats'].data_ptr(), b['gamma'], b['beta'],
-                         count, BN_EPS, self.bn_slots, DET_ROWS if self.det else 0)
+                         count, BN_EPS, self.bn_slots, self.det_rows)
 
     def _fold_op(self, name, backward):
         """Deterministic mode: rows 1.. of layer `name`'s forward | backward sum block -> row 0 (yunet_bn_fold).  Forward: right
@@ -974,7 +988,7 @@ class YuNetEngine:
         self.params = FlatParams(self.layout, self.device)
         self.world_size = world_size
         self.process_group = process_group
-        self.plans = collections.OrderedDict()      # (N, H, W, Gmax, precision[, 'det']) -> Plan, least recently used first
+        self.plans = collections.OrderedDict()      # (N, H, W, Gmax, precision[, 'det' | 'det-fast']) -> Plan, least recently used first
         self.plan = None
         self.always_bucket = False      # tests: run the two-segment backward + collectives at world size 1
         self.use_lanes = False          # head chains of the coarser levels on executor side streams (Plan._emit_neck_and_heads)
@@ -1041,22 +1055,25 @@ class YuNetEngine:
         if precision not in ('fp32', 'bf16'):
             raise ValueError(f"precision {precision!r}: 'fp32' or 'bf16'")
         if precision == 'bf16' and self.deterministic:
-            raise NotImplementedError("precision='bf16' with deterministic=True: the order-fixed BatchNorm sums exist for the "
+            raise NotImplementedError(f"precision='bf16' with deterministic={self.deterministic!r}: the order-fixed BatchNorm sums exist for the "
                                       'fp32 storage build only')
         self.precision = precision
 
     def set_deterministic(self, flag=True):
-        """Order-fixed BatchNorm sums for the plans built from now on (README: what is and is not covered)."""
+        """Order-fixed BatchNorm sums for the plans built from now on (README: what is and is not covered).  False | True |
+        'fast': True runs every launch that produces sums on the exact-fp32 tile kernels, 'fast' on the order-fixed forms
+        of the kernels the default mode uses -- the same contract, different bytes."""
+        flag = det_level(flag)
         if flag and self.precision == 'bf16':
-            raise NotImplementedError("deterministic=True with precision='bf16': the order-fixed BatchNorm sums exist for the "
+            raise NotImplementedError(f"deterministic={flag!r} with precision='bf16': the order-fixed BatchNorm sums exist for the "
                                       'fp32 storage build only')
-        self.deterministic = bool(flag)
+        self.deterministic = flag
 
     def get_plan(self, n, h, w, max_gt):
         gmax = 64
         while gmax < max_gt:
             gmax *= 2
-        key = (n, h, w, gmax, self.precision) + (('det',) if self.deterministic else ())
+        key = (n, h, w, gmax, self.precision) + (('det-fast' if self.deterministic == 'fast' else 'det',) if self.deterministic else ())
         plan = self.plans.get(key)
         if plan is None:
             if h % 32 or w % 32:

@@ -47,7 +47,8 @@ class BN:
     def __init__(self, stats, gamma, beta, count, eps=1e-5, bstats=None, slots=1, det_rows=0):
         # slots > 1: stats / bstats are [slots, 2C] replica blocks (YunetBN::slots); the sums are their column sums
         # det_rows = R > 0 (deterministic sums, YunetBN::det_rows): [1 + R, 2C] blocks, row 0 = the sums after bn_fold
-        rows = 1 + det_rows if det_rows else slots
+        # (det_rows may carry L.DET_FAST above the row count: the fast deterministic level, same blocks)
+        rows = 1 + (det_rows & (L.DET_FAST - 1)) if det_rows else slots
         assert not det_rows or slots == 1
         assert stats.dtype == torch.float64 and stats.numel() == rows * 2 * gamma.numel()
         assert bstats is None or bstats.numel() == rows * 2 * gamma.numel()

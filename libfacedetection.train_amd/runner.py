@@ -13,6 +13,7 @@ import warnings
 import torch
 
 from . import synthetic
+from .engine import det_level
 from .optim import build_optimizer
 from .parallel import build_ddp, get_dist_info
 
@@ -888,7 +889,7 @@ def auto_scale_lr(cfg, distributed, log=print):
     return cfg.optimizer['lr']
 
 
-_DETERMINISTIC = False       # set_random_seed(seed, deterministic=True): read by train_detector
+_DETERMINISTIC = False       # set_random_seed(seed, deterministic=True | 'fast'): read by train_detector
 
 
 def set_random_seed(seed, deterministic=False):
@@ -896,22 +897,24 @@ def set_random_seed(seed, deterministic=False):
     deterministic mode in the reference -- selects the bit-reproducible training step of the fused engine
     (YuNet.set_deterministic) for every model train_detector builds afterwards.  As in the reference, where False leaves
     the cuDNN flags alone, a later set_random_seed(seed) does not switch the mode off; cfg.deterministic = True is the
-    per-run spelling."""
+    per-run spelling.  'fast' selects the fast deterministic level (YuNet.set_deterministic('fast'))."""
     import random
     import numpy as np
     global _DETERMINISTIC
+    deterministic = det_level(deterministic)
     random.seed(seed)
     np.random.seed(seed)
     torch.manual_seed(seed)
     if torch.cuda.is_available():
         torch.cuda.manual_seed_all(seed)
     if deterministic:
-        _DETERMINISTIC = True
+        _DETERMINISTIC = deterministic
 
 
 def wants_deterministic(cfg):
-    """cfg.deterministic = True, or set_random_seed(seed, deterministic=True) earlier in this process."""
-    return bool(cfg.get('deterministic', False)) or _DETERMINISTIC
+    """cfg.deterministic = True | 'fast', or set_random_seed(seed, deterministic=...) earlier in this process: the level
+    (False | True | 'fast'); the config's own spelling wins."""
+    return det_level(cfg.get('deterministic', False)) or _DETERMINISTIC
 
 
 def train_detector(model, dataset, cfg, distributed=False, validate=False, timestamp=None,
@@ -923,7 +926,7 @@ def train_detector(model, dataset, cfg, distributed=False, validate=False, times
         if cfg.get('fp16', None) is not None:
             raise NotImplementedError('deterministic training with cfg.fp16 (bf16 activation storage): the deterministic mode '
                                       'covers the fp32 storage build only')
-        model.set_deterministic(True)
+        model.set_deterministic(wants_deterministic(cfg))
     model = model.to(device)
     model.train()
     if distributed:

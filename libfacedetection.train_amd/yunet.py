@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from .builder import DETECTORS, build_backbone, build_head, build_neck
-from .engine import YuNetEngine
+from .engine import YuNetEngine, det_level
 
 
 class _LogRecord:
@@ -275,7 +275,7 @@ class YuNet(nn.Module):
         if precision not in ('fp32', 'bf16'):
             raise ValueError(f"precision {precision!r}: 'fp32' or 'bf16'")
         if precision == 'bf16' and getattr(self, '_deterministic', False):
-            raise NotImplementedError("precision='bf16' with deterministic=True: the deterministic mode covers the fp32 "
+            raise NotImplementedError(f"precision='bf16' with deterministic={self._deterministic!r}: the deterministic mode covers the fp32 "
                                       'storage build only')
         self._precision = precision
         self.fp16_enabled = precision != 'fp32'
@@ -285,11 +285,14 @@ class YuNet(nn.Module):
     def set_deterministic(self, flag=True):
         """Bit-reproducible training step (engine.YuNetEngine.deterministic): same inputs, same state, same build and same
         device model give the same losses, gradients, parameters and BatchNorm buffers, byte for byte -- one process,
-        world size 1, fp32 storage.  Plans built before the call keep their mode; the next step builds its own."""
+        world size 1, fp32 storage.  Plans built before the call keep their mode; the next step builds its own.
+        False | True | 'fast': 'fast' keeps the kernels of the default mode (their order-fixed forms) instead of the
+        exact-fp32 tile kernels -- the same contract at a lower cost, other bytes than True."""
+        flag = det_level(flag)
         if flag and getattr(self, '_precision', 'fp32') == 'bf16':
-            raise NotImplementedError("deterministic=True with precision='bf16': the deterministic mode covers the fp32 "
+            raise NotImplementedError(f"deterministic={flag!r} with precision='bf16': the deterministic mode covers the fp32 "
                                       'storage build only')
-        self._deterministic = bool(flag)
+        self._deterministic = flag
         if self.engine is not None:
             self.engine.set_deterministic(flag)
 

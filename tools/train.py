@@ -2,7 +2,7 @@
 """Train YuNet on MI355X -- the command line of the reference's tools/train.py (tools/train.py:24-104):
 
     CONFIG [--work-dir DIR] [--resume-from CKPT] [--auto-resume] [--no-validate]
-           [--gpu-id N | --gpus N | --gpu-ids N ...] [--seed S] [--diff-seed] [--deterministic]
+           [--gpu-id N | --gpus N | --gpu-ids N ...] [--seed S] [--diff-seed] [--deterministic | --deterministic-fast]
            [--cfg-options K=V ... | --options K=V ...] [--launcher {none,pytorch,slurm,mpi}] [--local_rank R]
            [--auto-scale-lr]
 
@@ -43,6 +43,9 @@ def parse_args(argv=None):
     p.add_argument('--deterministic', action='store_true',
                    help='bit-reproducible training step: the same seed, state, build and device model give the same bytes '
                         '(losses, gradients, parameters, BN buffers); one process, fp32 storage; about 1.3x the step time')
+    p.add_argument('--deterministic-fast', action='store_true',
+                   help="the same contract on the order-fixed forms of the default mode's kernels (cfg.deterministic = 'fast'): "
+                        'other bytes than --deterministic, a lower cost; wins over --deterministic when both are given')
     p.add_argument('--options', nargs='+', action=DictAction, help='(deprecated) use --cfg-options')
     p.add_argument('--cfg-options', nargs='+', action=DictAction,
                    help='override settings of the config: key=value pairs, key="[a,b]" or key=a,b for lists, '
@@ -86,6 +89,8 @@ def prepare_config(args):
     cfg['auto_resume'] = args.auto_resume
     if args.deterministic:
         cfg['deterministic'] = True                 # the config key of the mode: the dumped config records it
+    if args.deterministic_fast:
+        cfg['deterministic'] = 'fast'
     if args.gpus is not None:
         cfg['gpu_ids'] = [0]
         warnings.warn('`--gpus` is deprecated because we only support single GPU mode in non-distributed '
@@ -141,8 +146,9 @@ def main(argv=None):
     timestamp = time.strftime('%Y%m%d_%H%M%S', time.localtime())
     seed = args.seed if args.seed is not None else 0
     seed = seed + rank if args.diff_seed else seed
-    if args.deterministic:
-        R.set_random_seed(seed, deterministic=True)      # (mmdet/apis/train.py: set_random_seed(seed, deterministic=...))
+    if args.deterministic or args.deterministic_fast:
+        # (mmdet/apis/train.py: set_random_seed(seed, deterministic=...))
+        R.set_random_seed(seed, deterministic='fast' if args.deterministic_fast else True)
     else:
         torch.manual_seed(seed)
     cfg['seed'] = seed
