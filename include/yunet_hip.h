@@ -372,6 +372,10 @@ int yunet_sgd_step_ex(float* params, const float* grads, float* momentum_buf, in
 enum { YUNET_NORM_INF = 0, YUNET_NORM_L1 = 1, YUNET_NORM_L2 = 2 };
 #define YUNET_OPT_ROW 4               /* doubles per group: lr, weight_decay, momentum (SGD) | beta1 (Adam), beta2 */
 #define YUNET_OPT_MAX_GROUPS 255
+#define YUNET_OPT_FROZEN 255          /* byte of the group map that means NO UPDATE (group ids end at 254): the grouped kernels
+                                       * leave such an element's parameter and state (momentum | exp_avg, exp_avg_sq) untouched
+                                       * and read neither its gradient nor a table row -- parameters with requires_grad = False
+                                       * and elements no group covers (optim.py) */
 
 /* torch.nn.utils.clip_grad_norm_ without its host side: out[0] = || grads * grad_scale ||_p  (norm_type YUNET_NORM_*),
  * out[1] = min(1, max_norm / (out[0] + 1e-6)), both written by the one launch, nothing read back.  The sum runs in fp64 in
@@ -381,8 +385,8 @@ enum { YUNET_NORM_INF = 0, YUNET_NORM_L1 = 1, YUNET_NORM_L2 = 2 };
 int yunet_grad_norm(const float* grads, int64_t n, float grad_scale, int norm_type, float max_norm, void* scratch,
                     float* out, void* stream);
 /* yunet_sgd_step_ex with lr / weight_decay / momentum per parameter group: element i belongs to group group_of_elem[i]
- * (< n_groups <= YUNET_OPT_MAX_GROUPS) and reads row group_of_elem[i] of `table` ([n_groups, YUNET_OPT_ROW] doubles in
- * device memory, rounded to fp32 the way torch rounds its python scalars).  The gradient is multiplied by
+ * (< n_groups <= YUNET_OPT_MAX_GROUPS; YUNET_OPT_FROZEN: the element is skipped) and reads row group_of_elem[i] of `table`
+ * ([n_groups, YUNET_OPT_ROW] doubles in device memory, rounded to fp32 the way torch rounds its python scalars).  The gradient is multiplied by
  * grad_scale * clip_coef[0]; clip_coef is out + 1 of yunet_grad_norm, or NULL for no clipping.  A group with momentum 0
  * leaves its part of momentum_buf alone.  One group and clip_coef = NULL give the bits of yunet_sgd_step_ex. */
 int yunet_sgd_step_grouped(float* params, const float* grads, float* momentum_buf, int64_t n,

@@ -23,6 +23,7 @@ RANK_SEG_CAP, RANK_RADIX_TILE, RANK_CURVE_MAX = 1024, 4096, 1 << 24   # YUNET_RA
 NORM_BLOCK, NORM_TILE, NORM_MAX_BLOCKS, NORM_SCRATCH_BYTES = 256, 4096, 256, 8 + 8 * 256   # YUNET_NORM_* (csrc/optim.hip)
 NORM_INF, NORM_L1, NORM_L2 = 0, 1, 2
 OPT_ROW, OPT_MAX_GROUPS = 4, 255                                  # YUNET_OPT_* (the group table of csrc/optim.hip)
+OPT_FROZEN = 255                                                  # YUNET_OPT_FROZEN: the group-map byte that means no update
 T_IDENTITY, T_BNRELU = 0, 1
 F32, BF16 = 0, 1
 DET_FAST = 1 << 30         # YUNET_DET_FAST: flag in YunetBN.det_rows, above the row count

@@ -6,6 +6,7 @@
 // from python floats: 1 - 0.999f is 6e-5 away from 1 - 0.999, far more than the update's fp32 rounding.  Every block turns
 // the rows into the fp32 constants torch hands its kernels once (thread t = group t: one load per thread, no loop) and
 // keeps them in LDS; the elements are one per thread like sgd_kernel, so a group boundary may fall anywhere.
+// The byte YUNET_OPT_FROZEN is no group: such an element is left alone -- parameter and state keep their bytes.
 #include "common.h"
 
 namespace {
@@ -15,6 +16,7 @@ constexpr int VPT = YUNET_NORM_TILE / (4 * NT);           // float4 per thread a
 static_assert(VPT * 4 * NT == YUNET_NORM_TILE, "tile = whole float4 per thread");
 static_assert(YUNET_NORM_MAX_BLOCKS <= NT, "the last block folds one partial per thread");
 static_assert(YUNET_OPT_MAX_GROUPS <= NT, "one thread per group row");
+static_assert(YUNET_OPT_FROZEN >= YUNET_OPT_MAX_GROUPS && YUNET_OPT_FROZEN <= 255, "the frozen byte is no group id");
 
 struct NormScratch {
     unsigned int arrived;                                 // ticket counter: zero between launches
@@ -134,7 +136,7 @@ __global__ __launch_bounds__(NT) void sgd_grouped_kernel(float* __restrict__ p, 
     }
     __syncthreads();
     const long long i = (long long)blockIdx.x * NT + threadIdx.x;
-    if (i >= n) return;
+    if (i >= n || gid[i] == YUNET_OPT_FROZEN) return;      // frozen: no load of p / g / buf, no store
     const float4 r = row[group_of(gid, i, ngroups)];
     const float lr = r.x, wd = r.y, momentum = r.z;
     const float gscale = clip_scale(gscale_in, coef);
@@ -189,7 +191,7 @@ __global__ __launch_bounds__(NT) void adam_grouped_kernel(float* __restrict__ p,
     }
     __syncthreads();
     const long long i = (long long)blockIdx.x * NT + threadIdx.x;
-    if (i >= n) return;
+    if (i >= n || gid[i] == YUNET_OPT_FROZEN) return;      // frozen: parameter and both moments keep their bytes
     const AdamRow r = row[group_of(gid, i, ngroups)];
     const float gscale = clip_scale(gscale_in, coef);
     float w = p[i];

@@ -287,6 +287,7 @@ class _T:
         self.plain_pool = False     # a pool_bwd op of its own will write this tensor's gradient (_pool, unfused form)
         self.fuse_upadd = False     # ... and applies the TFPN merge's share of it too (_upadd: `upadd_share` = that gradient)
         self.upadd_share = None
+        self.needs_grad = True      # a trainable parameter in its producer or upstream of it (Plan._trainable: frozen prefix)
 
 
 class _BNRef:
@@ -301,6 +302,7 @@ class _BNRef:
 
 
 _NULL_BN = L.YunetBN(None, None, None, None, 1, BN_EPS)
+_NONE = frozenset()
 
 
 class Plan:
@@ -310,6 +312,10 @@ class Plan:
     def __init__(self, eng, n, h, w, gmax):
         self.eng, self.n, self.h, self.w, self.gmax = eng, n, h, w, gmax
         self.sw = {name: read_switch(name) for name in PLAN_SWITCHES}      # the environment as it is NOW
+        # freeze signature (YuNetEngine.set_frozen): BatchNorm layers on their running statistics, and
+        # state_dict keys of the parameters without gradient.  Both empty: every list below is the one it always was.
+        self.frozen_bn, self.frozen_params = getattr(eng, 'frozen', (_NONE, _NONE))
+        self.zero_bstats = None     # the frozen layers' readers take their backward sums from here: never written
         # deterministic mode: order-fixed BatchNorm sums (per-workgroup rows + fold ops), no lanes, no grouped launches
         level = det_level(getattr(eng, 'deterministic', False))
         self.det = bool(level)
@@ -360,13 +366,15 @@ class Plan:
             yield name, c, so, lay.entries[name + '.weight'][0], lay.entries[name + '.bias'][0], self.bn_count.get(name)
             so += 2 * c * self.bn_rows
 
-    def _bn_table(self, backward, pick=None):
-        """Device table of the bn_batch kernel over the forward | backward sum blocks of the layers with pick(g_off)."""
+    def _bn_table(self, backward, pick=None, names=None):
+        """Device table of the bn_batch kernel over the forward | backward sum blocks of the layers with pick(g_off)
+        and names(name).  No such layer: None (the launch refuses an empty table; the caller emits no op)."""
         base = self.stats.numel() // 2 if backward else 0
         bn_offset = self.eng.params.bn_offset
         rows = [[base + so, c, cnt, bn_offset[name], g_off, b_off, self.bn_slots]
-                for name, c, so, g_off, b_off, cnt in self._bn_layers() if pick is None or pick(g_off)]
-        return torch.tensor(rows, dtype=torch.int32).to(self.eng.device)
+                for name, c, so, g_off, b_off, cnt in self._bn_layers()
+                if (pick is None or pick(g_off)) and (names is None or names(name))]
+        return torch.tensor(rows, dtype=torch.int32).to(self.eng.device) if rows else None
 
     def _bn_batch_op(self, table, mode, momentum=0.0):
         """One launch over the layers of `table`: mode 0 updates the running statistics, 1 writes d(gamma) / d(beta)
@@ -392,6 +400,62 @@ class Plan:
                                  dgamma=fp.grad.data_ptr() + 4 * g_off, dbeta=fp.grad.data_ptr() + 4 * b_off)
         self.ops_memset_stats = self._op(L.OP_MEMSET, p=[self.stats.data_ptr()], i=self._split64(self.stats.numel() * 8))
         self.fwd_a.append(self.ops_memset_stats)
+        if self.frozen_bn:
+            unknown = self.frozen_bn - set(self.bn)
+            if unknown:
+                raise KeyError(f'frozen BatchNorm layers {sorted(unknown)}: not layers of this model')
+            # the frozen layers' forward sums come from their running statistics, right after the memset (row 0 of a
+            # deterministic block): the table needs every layer's count, so _emit_loss_step puts the op at this index
+            self._fill_idx = len(self.fwd_a)
+            self.fwd_a.append(None)
+            self.zero_bstats = torch.zeros(self.bn_slots * 2 * max(fp.bn_channels), device=self.eng.device, dtype=torch.float64)
+
+    # ------------------------------------------------------------------ freeze signature
+    def _unit_keys(self, name):
+        """state_dict keys of the conv tensors of kernel unit `name`: the entries inside its weight-gradient row."""
+        lay = self.eng.layout
+        lo = lay.units[name]['off']
+        hi = lo + (16 * 27 + 16 if name == 'stem' else lay.unit_width(name))
+        return [k for k, (off, _) in lay.entries.items() if lo <= off < hi]
+
+    def _conv_trainable(self, name):
+        """A reduce job for the unit: any of its conv tensors takes a gradient."""
+        return not self.frozen_params or any(k not in self.frozen_params for k in self._unit_keys(name))
+
+    def _bn_trainable(self, bn_name):
+        """gamma or beta of the layer takes a gradient (a frozen layer's may: its sums are still d(gamma), d(beta))."""
+        return bn_name + '.weight' not in self.frozen_params or bn_name + '.bias' not in self.frozen_params
+
+    def _trainable(self, name, bn_name):
+        return self._conv_trainable(name) or (bn_name is not None and self._bn_trainable(bn_name))
+
+    def _frozen_ranges(self):
+        """[(offset, elements)] of the flat gradient that belong to parameters without gradient, merged where they touch."""
+        lay = self.eng.layout
+        unknown = self.frozen_params - set(lay.entries)
+        if unknown:
+            raise KeyError(f'frozen parameters {sorted(unknown)}: not parameters of this model')
+        out = []
+        for off, shape in sorted(lay.entries[k] for k in self.frozen_params):
+            n = int(math.prod(shape))
+            if out and out[-1][0] + out[-1][1] == off:
+                out[-1] = (out[-1][0], out[-1][1] + n)
+            else:
+                out.append((off, n))
+        return out
+
+    def _zero_frozen_ops(self, lo=0, hi=None):
+        """OP_MEMSETs over the frozen ranges inside [lo, hi) of the flat gradient: they follow the reduction and the mode-1
+        BatchNorm launch, which write whole rows (a partly frozen unit) -- and a range nobody writes may hold what a plan of
+        another signature left there."""
+        hi = self.eng.layout.numel if hi is None else hi
+        gbase = self.eng.params.grad.data_ptr()
+        ops = []
+        for off, n in self._frozen_ranges():
+            a, b = max(off, lo), min(off + n, hi)
+            if a < b:
+                ops.append(self._op(L.OP_MEMSET, p=[gbase + 4 * a], i=self._split64(4 * (b - a))))
+        return ops
 
     def _alloc_head_outputs(self):
         """Loss-step geometry (`sizes`, `P`, `levels`, `level_base`) and the [N,P,16] buffers the heads write and
@@ -564,8 +628,28 @@ class Plan:
         # BN running statistics (nn.BatchNorm2d momentum 0.1) and, in backward, d(gamma)/d(beta)
         # of ALL BatchNorm layers: one launch each, driven by a small device table
         self.bn_table_f = self._bn_table(backward=False)
-        self.bn_table_b = self._bn_table(backward=True)
-        self.fwd_b.append(self._bn_batch_op(self.bn_table_f, 0, BN_MOMENTUM))
+        if not self.frozen_bn and not self.frozen_params:
+            self.bn_table_run = self.bn_table_f
+            self.bn_table_b = self._bn_table(backward=True)
+            self.nbt_step = 1
+        else:
+            # a frozen layer keeps running_mean / running_var (the unbiased-variance factor alone would change the
+            # latter) and num_batches_tracked; a layer whose gamma and beta are both frozen has no row in the mode-1 table
+            self.bn_table_run = self._bn_table(backward=False, names=lambda nm: nm not in self.frozen_bn)
+            self.bn_table_b = self._bn_table(backward=True, names=self._bn_trainable)
+            # what a step adds to num_batches_tracked: 1 | a 0 / 1 vector | None when every layer is frozen
+            if not self.frozen_bn:
+                self.nbt_step = 1
+            elif len(self.frozen_bn) == len(self.bn):
+                self.nbt_step = None
+            else:
+                self.nbt_step = torch.tensor([int(nm not in self.frozen_bn) for nm in self.eng.layout.bn_names],
+                                             dtype=torch.int64).to(self.eng.device)
+        if self.frozen_bn:
+            self.bn_table_frozen = self._bn_table(backward=False, names=lambda nm: nm in self.frozen_bn)
+            self.op_fill_frozen = self.fwd_a[self._fill_idx] = self._bn_batch_op(self.bn_table_frozen, 2)
+        if self.bn_table_run is not None:
+            self.fwd_b.append(self._bn_batch_op(self.bn_table_run, 0, BN_MOMENTUM))
 
     def _emit_backward(self):
         """bwd_nodes -> `bwd`, `reduce_jobs`, `reduce_table`.  Returns (the kernel ops alone, marks) for _split_backward;
@@ -586,15 +670,26 @@ class Plan:
             self._lane = lane
             node()
             self._lane = 0
-            marks.append((len(self.bwd), len(self.reduce_jobs)))
+            marks.append((len(self.bwd), len(self.reduce_jobs)))          # (a dropped node -- frozen prefix -- repeats the mark)
         if self.lanes_used & ~joined:
             self.bwd.append(self._op(L.OP_JOIN, i=[self.lanes_used & ~joined]))
         kernels_bwd = list(self.bwd)
         # all weight-gradient partial reductions in ONE launch (table lives on the device)
         self.reduce_table, chunk = K.reduce_job_table(self.reduce_jobs, self.eng.device)
-        self.bwd.append(self._op(L.OP_REDUCE_BATCH, p=[self.reduce_table.data_ptr()], i=[len(self.reduce_jobs), chunk]))
-        self.bwd.append(self._bn_batch_op(self.bn_table_b, 1))
+        self.bwd += self._tail_ops(self.reduce_table, len(self.reduce_jobs), chunk, self.bn_table_b)
         return kernels_bwd, marks
+
+    def _tail_ops(self, tab, n_jobs, chunk, bn_table, lo=0, hi=None):
+        """What closes a backward list: the reduction of its units' partials, d(gamma) / d(beta) of its layers, zeros over
+        the frozen ranges of its part [lo, hi) of the flat gradient.  An empty table has no launch."""
+        ops = []
+        if n_jobs:
+            ops.append(self._op(L.OP_REDUCE_BATCH, p=[tab.data_ptr()], i=[n_jobs, chunk]))
+        if bn_table is not None:
+            ops.append(self._bn_batch_op(bn_table, 1))
+        if self.frozen_params:
+            ops += self._zero_frozen_ops(lo, hi)
+        return ops
 
     def _elide_pool_z(self):
         """Needs the forward and backward op records (before they are copied into the c_* arrays); leaves `elided_z`.
@@ -609,6 +704,8 @@ class Plan:
         self.elided_z = []          # (tensor, its OP_DP_FWD record)
         if self.sw['keep_pool_z']:
             return
+        # (a unit of a frozen prefix has no backward op: `bop` is None below and its z stays -- the forward entry takes a
+        # null z only together with a backward descriptor that says so)
         bwd_of = {op.dp.pool_idx: op for op in self.bwd if op.opcode == L.OP_DP_BWD and op.dp.pool_idx}
         for _, zt in self.tensors.values():
             if zt.pooled_into is None or zt.grad is not None:
@@ -671,14 +768,13 @@ class Plan:
         ops_a = max(m[0] for m in marks if m[1] <= n_a)
         tab_a, chunk_a = K.reduce_job_table(self.reduce_jobs[:n_a], dev)
         tab_b, chunk_b = K.reduce_job_table(self.reduce_jobs[n_a:], dev)
-        self.bn_table_ba = self._bn_table(backward=True, pick=lambda g_off: g_off >= split_off)
-        self.bn_table_bb = self._bn_table(backward=True, pick=lambda g_off: g_off < split_off)
+        names = self._bn_trainable if self.frozen_params else None
+        self.bn_table_ba = self._bn_table(backward=True, pick=lambda g_off: g_off >= split_off, names=names)
+        self.bn_table_bb = self._bn_table(backward=True, pick=lambda g_off: g_off < split_off, names=names)
         self.keep += [tab_a, tab_b]
-
-        def tail_ops(tab, nj, ch, bnt):
-            return [self._op(L.OP_REDUCE_BATCH, p=[tab.data_ptr()], i=[nj, ch]), self._bn_batch_op(bnt, 1)]
-        self.bwd_a = kernels_bwd[:ops_a] + tail_ops(tab_a, n_a, chunk_a, self.bn_table_ba)
-        self.bwd_b = kernels_bwd[ops_a:] + tail_ops(tab_b, len(self.reduce_jobs) - n_a, chunk_b, self.bn_table_bb)
+        self.bwd_a = kernels_bwd[:ops_a] + self._tail_ops(tab_a, n_a, chunk_a, self.bn_table_ba, lo=split_off)
+        self.bwd_b = kernels_bwd[ops_a:] + self._tail_ops(tab_b, len(self.reduce_jobs) - n_a, chunk_b, self.bn_table_bb,
+                                                          hi=split_off)
         self.c_bwd_a = self._carray(self.bwd_a)
         self.c_bwd_b = self._carray(self.bwd_b)
         # one GPU: segment A's kernels alone + its reduction as a list of its own, which then runs on the side
@@ -695,6 +791,9 @@ class Plan:
         self.eval_scratch = torch.zeros(64, device=self.eng.device, dtype=torch.float64)
         self.fwd_eval = [self._bn_batch_op(self.bn_table_f, 2)]
         self._eval_z = []           # (elided tensor, index of its unit in fwd_eval): eval_ops()
+        # A plan with frozen layers has their mode-2 fill at fwd_a[1]; it is cloned like any other op, so eval() on such a
+        # plan fills those layers twice with the same values (one 64-thread block per layer).  Kept on purpose: every op
+        # stays at the index it has in fwd_a, which is what set_img relies on.
         for op in self.fwd_a[1:]:
             if op.opcode in (L.OP_ASSIGN, L.OP_LOSS_NORM, L.OP_BN_FOLD):
                 continue          # test time: no SimOTA on stale GT, gt_inds / norm stay untouched; row 0 of the sums is op 0's
@@ -748,6 +847,20 @@ class Plan:
         b = self.bn[name]
         return self._op(L.OP_BN_FOLD, p=[b['bstats' if backward else 'stats'].data_ptr()], i=[DET_ROWS, b['c']])
 
+    def _reader_bn(self, bn, name):
+        """The descriptor the READER of layer `name`'s backward sums takes (the producer's backward: its out_bn, the
+        stem's bn[0]).  Frozen layer: the sums it subtracts are zero -- the shared zero block -- which turns the kernels' BN
+        backward into dz = scale * dy; the consumers keep accumulating into the layer's own block (d(gamma), d(beta))."""
+        if name in self.frozen_bn:
+            bn.bstats = self.zero_bstats.data_ptr()
+        return bn
+
+    def _bwd_fold(self, name):
+        """Deterministic plans: whether a backward fold op precedes the reader of layer `name`.  A frozen layer's reader
+        takes the zero block, so the fold serves the mode-1 launch alone (row 0 = d(beta) | d(gamma)): none when both are
+        frozen too."""
+        return self.det and (name not in self.frozen_bn or self._bn_trainable(name))
+
     def _new_t(self, n, h, w, c, bn_name=None):
         buf = torch.empty(n, h, w, c, device=self.eng.device, dtype=self.act_dtype)
         return _T(buf, n, h, w, c, bn=bn_name)
@@ -769,12 +882,21 @@ class Plan:
         bn = self.bn['backbone.model0.bn1']
         cnt = z0.n * z0.h * z0.w
         self._bn_struct('backbone.model0.bn1', cnt)
-        op = self._op(L.OP_STEM_FWD, p=[None, wp, bp, z0.buf.data_ptr(), bn['stats'].data_ptr()],
-                      i=[self.n, self.h, self.w, 16] + ([DET_ROWS] if self.det else []))
+        frozen = 'backbone.model0.bn1' in self.frozen_bn
+        if frozen:
+            # the stem kernel always sums: into a scratch block nobody reads (one plain block, as in _build_eval)
+            self.stem_scratch = torch.zeros(64, device=self.eng.device, dtype=torch.float64)
+            op = self._op(L.OP_STEM_FWD, p=[None, wp, bp, z0.buf.data_ptr(), self.stem_scratch.data_ptr()],
+                          i=[self.n, self.h, self.w, 16])
+        else:
+            op = self._op(L.OP_STEM_FWD, p=[None, wp, bp, z0.buf.data_ptr(), bn['stats'].data_ptr()],
+                          i=[self.n, self.h, self.w, 16] + ([DET_ROWS] if self.det else []))
         self.fwd_a.append(op)
         self.img_ptr_ops.append(('fwd_a', len(self.fwd_a) - 1))
-        if self.det:
+        if self.det and not frozen:
             self.fwd_a.append(self._fold_op('backbone.model0.bn1', False))
+        z0.needs_grad = self._trainable('stem', 'backbone.model0.bn1')
+        has_job = self._conv_trainable('stem')
         blocks = K.stem_grid(self.n, self.h, self.w)
         width = 16 * 27 + 16
         part = torch.empty(blocks, width, device=self.eng.device, dtype=torch.float32)
@@ -782,16 +904,19 @@ class Plan:
         gptr = fp.grad.data_ptr() + 4 * u['off']
 
         def bwd():
+            if not z0.needs_grad:
+                return                                                    # frozen prefix: nothing here takes a gradient
             assert z0.grad is not None
-            if self.det:
+            if self._bwd_fold('backbone.model0.bn1'):
                 self.bwd.append(self._fold_op('backbone.model0.bn1', True))
             op = self._op(L.OP_STEM_BWD, p=[None, z0.buf.data_ptr(), z0.grad.data_ptr(),
                                             part.data_ptr(), wp, bp],      # wp, bp: fp32 storage recomputes z from the image
                           i=[self.n, self.h, self.w, 16, blocks])
-            op.bn[0] = self._bn_struct('backbone.model0.bn1', cnt)
+            op.bn[0] = self._reader_bn(self._bn_struct('backbone.model0.bn1', cnt), 'backbone.model0.bn1')
             self.bwd.append(op)
             self.img_ptr_ops.append(('bwd', len(self.bwd) - 1))
-            self.reduce_jobs.append((part.data_ptr(), gptr, blocks, width, 0))
+            if has_job:
+                self.reduce_jobs.append((part.data_ptr(), gptr, blocks, width, 0))
         self.bwd_nodes.append((self._lane, bwd, self._join_before))
 
     def _dp_desc(self, x, name, z, z_img_stride=None):
@@ -836,9 +961,16 @@ class Plan:
         d, u, bn_name = self._dp_desc(x, name, zptr, z_img_stride)
         op = self._op(L.OP_DP_FWD)
         op.dp = d
+        frozen = bn_name in self.frozen_bn
+        if frozen:
+            op.dp.out_has_bn = 0          # the producer does not accumulate: the sums are the running statistics' (as in eval)
         self.fwd_a.append(op)
-        if self.det and bn_name:
+        if self.det and bn_name and not frozen:
             self.fwd_a.append(self._fold_op(bn_name, False))
+        needs_grad = x.needs_grad or self._trainable(name, bn_name)
+        if zt is not None:
+            zt.needs_grad = needs_grad
+        has_job = self._conv_trainable(name)
         if zt is not None:
             self.fwd_op_of[id(zt)] = op          # _pool() may attach the fused pooling outputs
         blocks = K.dp_grid(x.n, x.h, x.w, u['cin'], u['cout'])
@@ -848,7 +980,11 @@ class Plan:
         gptr = self.eng.params.grad.data_ptr() + 4 * u['off']
 
         def bwd():
+            if not needs_grad:
+                return                    # frozen prefix: no trainable parameter here or upstream
             d2, _, _ = self._dp_desc(x, name, zptr, z_img_stride)
+            if bn_name:
+                d2.out_bn = self._reader_bn(d2.out_bn, bn_name)
             if zt is not None and zt.pooled_into is not None:
                 # fused max_pool2d backward: dy = the pooled gradient its consumer wrote + argmax bytes
                 out, idx = zt.pooled_into
@@ -867,12 +1003,13 @@ class Plan:
             d2.dx = gx.data_ptr()
             d2.accumulate_dx = acc
             d2.wgrad_partials, d2.wgrad_blocks = part.data_ptr(), blocks
-            if self.det and bn_name:
+            if bn_name and self._bwd_fold(bn_name):
                 self.bwd.append(self._fold_op(bn_name, True))
             op = self._op(L.OP_DP_BWD)
             op.dp = d2
             self.bwd.append(op)
-            self.reduce_jobs.append((part.data_ptr(), gptr, blocks, width, 0))
+            if has_job:                   # (all four tensors frozen: the partials of a unit kept for dx go nowhere)
+                self.reduce_jobs.append((part.data_ptr(), gptr, blocks, width, 0))
         self.bwd_nodes.append((self._lane, bwd, self._join_before))
 
     def _pool(self, x, sole_consumer=False):
@@ -885,6 +1022,7 @@ class Plan:
                 L.load().yunet_dp_pool_fusion_ok(x.n, x.h, x.w, prod[0], prod[1])):
             out = self._new_t(x.n, x.h // 2, x.w // 2, x.c, bn_name=x.bn)
             out.bn_count = x.bn_count
+            out.needs_grad = x.needs_grad
             idx = torch.empty(x.n, x.h // 2, x.w // 2, x.c, device=self.eng.device, dtype=torch.uint8)
             self.keep.append(idx)
             fop = self.fwd_op_of[id(x)]
@@ -898,8 +1036,11 @@ class Plan:
         op.bn[0] = self._bn_struct(x.bn, cnt)
         self.fwd_a.append(op)
         x.plain_pool = True
+        out.needs_grad = x.needs_grad
 
         def bwd():
+            if not x.needs_grad:
+                return                    # frozen prefix (a merge share left to this op is dropped with it)
             # a pyramid tap: its other consumer is the identity branch of the TFPN merge, whose backward ran earlier (the
             # merge comes later in the forward) and left its share of the gradient to this op -- same ReLU mask, same
             # BatchNorm sums, so the tap's gradient is written ONCE instead of written, re-read and re-written
@@ -926,8 +1067,11 @@ class Plan:
         # `a` is also max-pooled by a kernel of its own (built earlier in the forward = run later in the backward):
         # leave a's share of the gradient to that kernel (see _pool)
         a.fuse_upadd = a.plain_pool and not self.sw['no_upadd_pool_fusion']
+        out.needs_grad = a.needs_grad or b.needs_grad
 
         def bwd():
+            if not out.needs_grad:
+                return
             if a.fuse_upadd:
                 a.upadd_share = out.grad
                 ga_ptr, acc_a = None, 0
@@ -988,7 +1132,7 @@ class YuNetEngine:
         self.params = FlatParams(self.layout, self.device)
         self.world_size = world_size
         self.process_group = process_group
-        self.plans = collections.OrderedDict()      # (N, H, W, Gmax, precision[, 'det' | 'det-fast']) -> Plan, least recently used first
+        self.plans = collections.OrderedDict()      # (N, H, W, Gmax, precision[, 'det' | 'det-fast'][, ('frozen', ..)]) -> Plan, least recently used first
         self.plan = None
         self.always_bucket = False      # tests: run the two-segment backward + collectives at world size 1
         self.use_lanes = False          # head chains of the coarser levels on executor side streams (Plan._emit_neck_and_heads)
@@ -1003,6 +1147,9 @@ class YuNetEngine:
         # deterministic: same inputs, same state, same build, same device model -> the same bytes (losses, gradients, BN
         # buffers), one process at world size 1; fp32 storage only.  Plans are keyed by it (set_deterministic, get_plan).
         self.deterministic = False
+        # freeze signature (set_frozen): (BatchNorm layers on their running statistics, parameters without gradient)
+        self.frozen = (_NONE, _NONE)
+        self._frozen_key = ()
         self.lib = L.load()
         self._host_idx = {}
         # one-shot all-reduce over peer-mapped inboxes (oneshot.py / csrc/collective.hip) instead of the process
@@ -1069,11 +1216,23 @@ class YuNetEngine:
                                       'fp32 storage build only')
         self.deterministic = flag
 
+    def set_frozen(self, bn_names=(), param_keys=()):
+        """The freeze signature of the plans used from now on: `bn_names` -- BatchNorm layers (state_dict prefixes) that
+        normalise with their running statistics and leave them, and num_batches_tracked, untouched; `param_keys` --
+        state_dict keys of parameters that take no gradient (their range of the flat gradient is exactly zero).  YuNet reads
+        both from its modules' own flags at every step (bn.training, p.requires_grad).  Plans are keyed by it."""
+        if not bn_names and not param_keys:
+            self.frozen, self._frozen_key = (_NONE, _NONE), ()
+        else:                # (no cache of the last signature: YuNet._sync_frozen calls only when it changed)
+            self.frozen = (frozenset(bn_names), frozenset(param_keys))
+            self._frozen_key = (('frozen', tuple(sorted(self.frozen[0])), tuple(sorted(self.frozen[1]))),)
+
     def get_plan(self, n, h, w, max_gt):
         gmax = 64
         while gmax < max_gt:
             gmax *= 2
         key = (n, h, w, gmax, self.precision) + (('det-fast' if self.deterministic == 'fast' else 'det',) if self.deterministic else ())
+        key += self._frozen_key          # () with nothing frozen: the key it always was
         plan = self.plans.get(key)
         if plan is None:
             if h % 32 or w % 32:
@@ -1135,7 +1294,8 @@ class YuNetEngine:
             self._exec(plan.c_fwd_b_rest, 'yunet_exec(fwd_b: finalize)')
         else:
             self._exec(plan.c_fwd_b, 'yunet_exec(fwd_b)')
-        self.params.num_batches_tracked += 1
+        if plan.nbt_step is not None:                # 1 | frozen layers: a 0 / 1 vector, or None when every layer is frozen
+            self.params.num_batches_tracked += plan.nbt_step
         return plan.losses
 
     def scale_buffer(self):

@@ -175,7 +175,7 @@ def conv_dp_unit(m, x):
     n, _, h, w = x.shape
     if m.withBNRelu:
         bn = m.bn
-        training = m.training or bn.running_mean is None
+        training = bn.training or bn.running_mean is None      # the BatchNorm's own flag: a frozen layer under train()
         y, stats = _DPUnitFn.apply(x, m.conv1.weight, m.conv1.bias, m.conv2.weight, m.conv2.bias, bn.weight, bn.bias,
                                    bn.running_mean, bn.running_var, bn.eps, training)
         if training and bn.track_running_stats and bn.running_mean is not None:
@@ -202,8 +202,8 @@ def stem(m, x):
     bn = m.bn1
     n, _, h, w = x.shape
     y, stats = _StemFn.apply(x, m.conv1.weight, m.conv1.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                             bn.eps, m.training)
-    if m.training and bn.track_running_stats:
+                             bn.eps, bn.training)
+    if bn.training and bn.track_running_stats:
         _track(bn, stats, n * (h // 2) * (w // 2))
     return y
 

@@ -11,8 +11,11 @@ The shipped configs (configs/yunet_n.py:1: SGD, lr 0.01, momentum 0.9, weight_de
 paramwise_cfg, no grad_clip) are one group without clipping and launch the plain yunet_sgd_step_ex kernel, as before.
 
 Not supported, and refused with the reason: Adam's amsgrad / maximize / foreach / capturable / fused flags,
-paramwise_cfg.dcn_offset_lr_mult (no DCN layers here), clipping norms other than 1, 2 and inf, and parameters frozen with
-requires_grad=False (freeze a part with custom_keys lr_mult=0 instead).
+paramwise_cfg.dcn_offset_lr_mult (no DCN layers here) and clipping norms other than 1, 2 and inf.
+
+Frozen parameters (requires_grad=False when the group map is built) and every element that no group covers carry the byte
+L.OPT_FROZEN in the map: the grouped kernels leave their parameter and state bytes untouched.  One such byte sends the
+update through the grouped launch; with none, the paths are the ones above.
 """
 import warnings
 
@@ -55,15 +58,12 @@ class _FusedOptimizer:
             g = dict(self.defaults, **g)
             g.setdefault('initial_lr', g['lr'])
             self.param_groups.append(g)
-        frozen = [p for g in self.param_groups for p in g['params'] if not p.requires_grad]
-        if frozen:
-            raise NotImplementedError('parameters with requires_grad=False are not supported by the fused optimizers: '
-                                      'freeze a part with paramwise_cfg custom_keys lr_mult=0')
         self._state = {k: None for k in self.STATE}
         self._steps = 0
         self._pending = None       # torch-format per-parameter state waiting for the engine's flat layout
         self._lr_dev, self._lr_val = None, None
         self._map, self._table, self._table_val = None, None, None
+        self._map_sig, self._covered = None, None
         self._norm_scratch, self._norm_out = None, None
         self.grad_scale = 1.0      # multiplies the gradient inside the kernels (loss-scale removal)
         self.grad_clip = None      # dict(max_norm=, norm_type=2): set by OptimizerHook; clipping runs on the device
@@ -103,19 +103,39 @@ class _FusedOptimizer:
         """The device image of the groups: the byte map (built once per layout) and the table (uploaded when a value in
         it changed)."""
         n = eng.params.data.numel()
-        if self._map is None or self._map.numel() != n or self._map.device != eng.device:
-            host = torch.zeros(n, dtype=torch.uint8)
-            for gi, g in enumerate(self.param_groups):
-                for p in g['params']:
-                    off = self._offset(eng, p)
-                    host[off:off + p.numel()] = gi
-            self._map = host.to(eng.device)
+        sig = self._frozen_ids()
+        if self._map is None or self._map.numel() != n or self._map.device != eng.device or sig != self._map_sig:
+            self._map = self._host_map(eng).to(eng.device)
+            self._map_sig = sig
             self._table = torch.zeros(len(self.param_groups), L.OPT_ROW, device=eng.device, dtype=torch.float64)
             self._table_val = None
         rows = [self._row(g) for g in self.param_groups]
         if rows != self._table_val:
             self._table.copy_(torch.tensor(rows, dtype=torch.float64))
             self._table_val = rows
+
+    def _frozen_ids(self):
+        """id() of the parameters that take no update, as a frozenset; the map is rebuilt when it changes (a stage frozen
+        or thawed between two steps).  A bound YuNet says which parameters its last step gave no gradient
+        (YuNet.frozen_parameters: the flags as forward_train read them, so gradient and update agree, and the ~90 flags --
+        20 us -- are read once per step, not twice); any other model: requires_grad is read here."""
+        named = getattr(self.model, 'frozen_parameters', None)
+        named = named() if named is not None else None
+        if named is not None:
+            return frozenset(id(p) for _, p in named)
+        return frozenset(id(p) for g in self.param_groups for p in g['params'] if not p.requires_grad)
+
+    def _host_map(self, eng):
+        """The byte map on the host: a trainable parameter's elements carry its group, everything else -- parameters with
+        requires_grad=False and elements of the flat buffer that no group covers -- L.OPT_FROZEN."""
+        host = torch.full((eng.params.data.numel(),), L.OPT_FROZEN, dtype=torch.uint8)
+        frozen = self._frozen_ids()
+        for gi, g in enumerate(self.param_groups):
+            for p in g['params']:
+                if id(p) not in frozen:
+                    off = self._offset(eng, p)
+                    host[off:off + p.numel()] = gi
+        return host
 
     def _clip_coef(self, eng):
         """Launch the norm kernel when clipping is on; returns the device float the update multiplies the gradient by."""
@@ -146,8 +166,17 @@ class _FusedOptimizer:
         K.norm_type_code(cfg.get('norm_type', 2))           # refuse other norms here, with the reason
         self.grad_clip = dict(max_norm=float(cfg['max_norm']), norm_type=cfg.get('norm_type', 2))
 
-    def _grouped(self):
-        return len(self.param_groups) > 1 or self.grad_clip is not None
+    def _grouped(self, eng=None):
+        """Several groups, clipping, or an element without update (a frozen parameter, or one no group covers)."""
+        if len(self.param_groups) > 1 or self.grad_clip is not None:
+            return True
+        if eng is None:
+            return False
+        if self._frozen_ids():
+            return True
+        if self._covered is None:
+            self._covered = sum(p.numel() for p in self.param_groups[0]['params'])
+        return self._covered != eng.params.data.numel()
 
     def zero_grad(self, set_to_none=False):
         """Gradients are overwritten (not accumulated) by the fused backward; nothing to do."""
@@ -267,7 +296,7 @@ class FusedSGD(_FusedOptimizer):
     def _update(self, eng):
         g = self.param_groups[0]
         first = self._steps == 0
-        if not self._grouped():
+        if not self._grouped(eng):
             # the default path: one group, no clipping -- the plain kernel, lr in its own device word
             if self._lr_val != g['lr']:
                 self._lr_dev.fill_(float(g['lr']))

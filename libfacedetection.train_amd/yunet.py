@@ -330,6 +330,11 @@ class YuNet(nn.Module):
         for name, p in self.named_parameters():
             p.data = fp.view(name)
             p.grad = fp.view(name, of=fp.grad)
+        # what the freeze signature is read from at every step (_sync_frozen): the modules' own flags
+        self._params = list(self.named_parameters())
+        self._bn_mods = [(bn_name, self.get_submodule(bn_name)) for bn_name in fp.layout.bn_names]
+        self._frozen_sig = ((), ())
+        self._sentinel = self._params[0]
         for i, bn_name in enumerate(fp.layout.bn_names):
             mod = self.get_submodule(bn_name)
             o, c = fp.bn_offset[bn_name], fp.bn_channels[i]
@@ -410,6 +415,32 @@ class YuNet(nn.Module):
             self.bind_engine(device)
         return self.engine
 
+    def _sync_frozen(self, eng):
+        """Fine-tuning: the engine honours the modules' own flags.  A BatchNorm2d with training == False under
+        model.train() is frozen (running statistics in, nothing written back); a parameter with requires_grad == False
+        takes no gradient (.grad None) and no update.  Read at every step -- two short walks, nothing else while the
+        signature stays what it was -- and handed to the engine, whose plans are keyed by it."""
+        sig = (tuple(n for n, m in self._bn_mods if not m.training),
+               tuple(n for n, p in self._params if not p.requires_grad))
+        if sig == self._frozen_sig:
+            return
+        self._frozen_sig = sig
+        eng.set_frozen(*sig)
+        frozen = set(sig[1])
+        for name, p in self._params:
+            p.grad = None if name in frozen else eng.params.view(name, of=eng.params.grad)
+        self._sentinel = next(((n, p) for n, p in self._params if n not in frozen), self._params[0])
+
+    def frozen_parameters(self):
+        """[(name, parameter)] of the parameters the last forward_train found with requires_grad == False: the ones whose
+        range of the flat gradient that step left at zero.  The fused optimizers give exactly these no update.  None before
+        an engine is bound (nothing was read yet)."""
+        sig = getattr(self, '_frozen_sig', None)
+        if sig is None:
+            return None
+        frozen = set(sig[1])
+        return [(n, p) for n, p in self._params if n in frozen] if frozen else []
+
     def _after_backward(self):
         eng = self.engine
         rec = self._log_pending
@@ -417,11 +448,11 @@ class YuNet(nn.Module):
             # the world-averaged logged scalars arrived in the head of the gradient buffer
             self._log_pending = None
             self._log_copy(rec, eng.params.log_head)
-        w = self.backbone.model0.conv1.weight
-        if w.grad is None or w.grad.data_ptr() != eng.params.view(
-                'backbone.model0.conv1.weight', of=eng.params.grad).data_ptr():
+        name, w = self._sentinel                        # the first parameter that takes a gradient
+        if w.requires_grad and (w.grad is None or w.grad.data_ptr() != eng.params.view(name, of=eng.params.grad).data_ptr()):
+            frozen = self._frozen_sig[1]
             for name, p in self.named_parameters():     # zero_grad(set_to_none=True) happened
-                p.grad = eng.params.view(name, of=eng.params.grad)
+                p.grad = None if name in frozen else eng.params.view(name, of=eng.params.grad)
 
     # ------------------------------------------------------------------ training path
     def forward_train(self, img, img_metas, gt_bboxes, gt_labels, gt_keypointss=None,
@@ -435,6 +466,7 @@ class YuNet(nn.Module):
         if not self.training:
             raise RuntimeError('forward_train requires model.train() (batch-statistics BatchNorm)')
         eng = self._ensure_engine(img.device)
+        self._sync_frozen(eng)
         ev = getattr(self, '_log_last_event', None)
         if ev is not None:
             # the previous step's logged scalars are copied to the host on a side stream from buffers
