@@ -398,6 +398,14 @@ int yunet_sgd_step_grouped(float* params, const float* grads, float* momentum_bu
 int yunet_adam_step_grouped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
                             const uint8_t* group_of_elem, const double* table, int n_groups, float eps, int decoupled,
                             int step, float grad_scale, const float* clip_coef, void* stream);
+/* Gradient accumulation over the flat gradient (the parameter range only, never the logged scalars in front of it):
+ *   YUNET_ACCUM_SAVE   acc[i] = grads[i]              in front of a backward that is to ADD to what grads holds
+ *   YUNET_ACCUM_ADD    grads[i] = acc[i] + grads[i]   behind it: one fp32 add per element (NaN / Inf propagate, -0 + -0 = -0)
+ * Element-wise, 16-byte accesses where grads and acc reach a 16-byte boundary after the same number of elements (scalar
+ * head and tail; everything scalar otherwise); both pointers 4-byte aligned, any n >= 0 (n = 0: nothing is launched).  No
+ * atomics: the same input gives the same bits.  One launch on `stream`. */
+enum { YUNET_ACCUM_SAVE = 0, YUNET_ACCUM_ADD = 1 };
+int yunet_grad_accum(float* acc, float* grads, int64_t n, int mode, void* stream);
 
 /* ---- op-list executor ---------------------------------------------------------------- */
 /* A training step is a fixed sequence of the calls above; the host builds it once as an

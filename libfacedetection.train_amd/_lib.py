@@ -22,6 +22,7 @@ SCORE_BLOCK, SCORE_GT_CHUNK, SCORE_MAX_THRESH = 256, 256, 1024   # YUNET_SCORE_*
 RANK_SEG_CAP, RANK_RADIX_TILE, RANK_CURVE_MAX = 1024, 4096, 1 << 24   # YUNET_RANK_* (csrc/score.hip: ranking and curve)
 NORM_BLOCK, NORM_TILE, NORM_MAX_BLOCKS, NORM_SCRATCH_BYTES = 256, 4096, 256, 8 + 8 * 256   # YUNET_NORM_* (csrc/optim.hip)
 NORM_INF, NORM_L1, NORM_L2 = 0, 1, 2
+ACCUM_SAVE, ACCUM_ADD = 0, 1                      # YUNET_ACCUM_* (yunet_grad_accum)
 OPT_ROW, OPT_MAX_GROUPS = 4, 255                                  # YUNET_OPT_* (the group table of csrc/optim.hip)
 OPT_FROZEN = 255                                                  # YUNET_OPT_FROZEN: the group-map byte that means no update
 T_IDENTITY, T_BNRELU = 0, 1
@@ -216,6 +217,7 @@ _SIGNATURES = {
                                          C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
     'yunet_adam_step_grouped': (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int,
                                           C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    'yunet_grad_accum': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     'yunet_sgd_step': (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_float, C.c_float,
                                                     C.c_float, C.c_int, C.c_void_p]),
     'yunet_exec': (C.c_int, [C.POINTER(YunetOp), C.c_int, C.c_void_p]),

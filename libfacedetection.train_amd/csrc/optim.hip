@@ -7,6 +7,9 @@
 // the rows into the fp32 constants torch hands its kernels once (thread t = group t: one load per thread, no loop) and
 // keeps them in LDS; the elements are one per thread like sgd_kernel, so a group boundary may fall anywhere.
 // The byte YUNET_OPT_FROZEN is no group: such an element is left alone -- parameter and state keep their bytes.
+//
+// Gradient accumulation (yunet_grad_accum): SAVE copies the flat gradient aside in front of a backward, ADD puts the saved
+// total back on top of what the backward wrote -- one fp32 add per element, no multiply near it, no atomics.
 #include "common.h"
 
 namespace {
@@ -207,6 +210,42 @@ __global__ __launch_bounds__(NT) void adam_grouped_kernel(float* __restrict__ p,
     p[i] = w - r.step_size * (m / denom);                  // param.addcdiv_(exp_avg, denom, value=-step_size)
 }
 
+// One unit per thread, no loop: a float4 of the 16-byte aligned body [head, head + 4 * nvec), and -- the first three threads
+// at most -- one element of the scalar head [0, head) and one of the scalar tail [head + 4 * nvec, n).  The host picks
+// `head` so that grad + head is 16-byte aligned and takes nvec = 0 (everything scalar, one element per thread) when
+// acc + head is not.  ADD is one fp32 add per element (v_pk_add_f32 over the pairs of a float4, v_add_f32 in the scalar
+// parts) with no multiply to contract with: NaN / Inf propagate, -0 + -0 stays -0.
+template <int MODE>
+__global__ __launch_bounds__(NT) void grad_accum_kernel(float* __restrict__ acc, float* __restrict__ g, long long n,
+                                                        int head, long long nvec, int scalar) {
+    const long long t = (long long)blockIdx.x * NT + threadIdx.x;
+    if (t < nvec) {
+        float4* gp = reinterpret_cast<float4*>(g + head) + t;
+        float4* ap = reinterpret_cast<float4*>(acc + head) + t;
+        if (MODE == YUNET_ACCUM_SAVE) {
+            *ap = *gp;
+        } else {
+            const float4 a = *ap, b = *gp;
+            *gp = make_float4(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y), __fadd_rn(a.z, b.z), __fadd_rn(a.w, b.w));
+        }
+    }
+    if (scalar) {                                         // no 16-byte body: element t
+        if (t < n) {
+            if (MODE == YUNET_ACCUM_SAVE) acc[t] = g[t];
+            else g[t] = __fadd_rn(acc[t], g[t]);
+        }
+        return;
+    }
+    const long long tail0 = head + 4 * nvec;
+    long long e = -1;
+    if (t < head) e = t;                                  // head and tail are at most 3 elements each: threads 0..2 take
+    else if (t >= 4 && t - 4 < n - tail0) e = tail0 + (t - 4);      // the head, threads 4..6 the tail (the same wave)
+    if (e >= 0) {
+        if (MODE == YUNET_ACCUM_SAVE) acc[e] = g[e];
+        else g[e] = __fadd_rn(acc[e], g[e]);
+    }
+}
+
 template <int MODE>
 void launch_norm(bool vec, unsigned blocks, hipStream_t s, const float* g, long long n, float gscale, float max_norm,
                  NormScratch* scratch, float* out) {
@@ -264,5 +303,28 @@ extern "C" int yunet_adam_step_grouped(float* params, const float* grads, float*
     hipLaunchKernelGGL(adam_grouped_kernel, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, params, grads, exp_avg,
                        exp_avg_sq, (long long)n, group_of_elem, table, n_groups, eps, decoupled ? 1 : 0, step,
                        grad_scale, clip_coef);
+    return hip_status();
+}
+
+extern "C" int yunet_grad_accum(float* acc, float* grads, int64_t n, int mode, void* stream) {
+    if (n < 0 || (mode != YUNET_ACCUM_SAVE && mode != YUNET_ACCUM_ADD)) return YUNET_EINVAL;
+    if (n == 0) return 0;
+    if (!acc || !grads || (reinterpret_cast<uintptr_t>(acc) & 3) || (reinterpret_cast<uintptr_t>(grads) & 3)) return YUNET_EINVAL;
+    // elements in front of the first 16-byte boundary of grads; acc must reach a boundary with the same count
+    long long head = (long long)((16 - (reinterpret_cast<uintptr_t>(grads) & 15)) & 15) / 4;
+    if (head > n) head = n;
+    const bool vec = ((reinterpret_cast<uintptr_t>(acc) + 4 * (uintptr_t)head) & 15) == 0;
+    const long long nvec = vec ? (n - head) / 4 : 0;
+    long long threads = vec ? nvec : n;
+    if (threads < 8) threads = 8;                          // threads 0..2 and 4..6 carry the head and the tail
+    const long long blocks = (threads + NT - 1) / NT;
+    if (blocks > 0x7fffffffll) return YUNET_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (mode == YUNET_ACCUM_SAVE)
+        hipLaunchKernelGGL((grad_accum_kernel<YUNET_ACCUM_SAVE>), dim3((unsigned)blocks), dim3(NT), 0, s, acc, grads,
+                           (long long)n, (int)head, nvec, vec ? 0 : 1);
+    else
+        hipLaunchKernelGGL((grad_accum_kernel<YUNET_ACCUM_ADD>), dim3((unsigned)blocks), dim3(NT), 0, s, acc, grads,
+                           (long long)n, (int)head, nvec, vec ? 0 : 1);
     return hip_status();
 }

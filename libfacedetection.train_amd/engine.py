@@ -1150,6 +1150,11 @@ class YuNetEngine:
         # freeze signature (set_frozen): (BatchNorm layers on their running statistics, parameters without gradient)
         self.frozen = (_NONE, _NONE)
         self._frozen_key = ()
+        # gradient accumulation (set_grad_accumulation): off -- backward() overwrites the flat gradient
+        self.grad_accumulation = False
+        self._acc = None                # fp32 [layout.numel]: the total saved in front of a backward; allocated on first use
+        self._grad_fresh = True         # the flat gradient holds no total to keep (new buffer | zero_grad() since the last backward)
+        self.accum_launches = {'save': 0, 'add': 0}      # yunet_grad_accum launches of this engine, per mode
         self.lib = L.load()
         self._host_idx = {}
         # one-shot all-reduce over peer-mapped inboxes (oneshot.py / csrc/collective.hip) instead of the process
@@ -1215,6 +1220,36 @@ class YuNetEngine:
             raise NotImplementedError(f"deterministic={flag!r} with precision='bf16': the order-fixed BatchNorm sums exist for the "
                                       'fp32 storage build only')
         self.deterministic = flag
+
+    def set_grad_accumulation(self, flag=True):
+        """On: backward() ADDS this call's gradient to what params.grad held before the call (torch's .grad semantics)
+        instead of overwriting it -- unless the buffer is known to hold no total (mark_grad_zeroed(), backward(fresh=True)),
+        in which case the backward is the one it always was.  Off (default): no buffer, no launch, the same op lists."""
+        self.grad_accumulation = bool(flag)
+
+    def mark_grad_zeroed(self):
+        """An optimizer's zero_grad(): the next backward has no total to keep and launches nothing extra."""
+        self._grad_fresh = True
+
+    def _accum_save(self, fresh):
+        """In front of the first backward op: acc <- params.grad on the launch stream when this backward accumulates.
+        Returns whether it does (then _accum_add() closes the backward).  The total is read from the gradient itself, so
+        in-place edits between two backwards (p.grad.zero_(), grad.mul_) are honoured."""
+        keep = self.grad_accumulation and not fresh and not self._grad_fresh
+        self._grad_fresh = False
+        if not keep:
+            return False
+        if self._acc is None:
+            self._acc = torch.empty(self.layout.numel, device=self.device, dtype=torch.float32)
+        K.grad_accum(self._acc, self.params.grad, 'save')
+        self.accum_launches['save'] += 1
+        return True
+
+    def _accum_add(self):
+        """After the whole backward (every stream joined, every bucket reduced): params.grad <- acc + params.grad.  The
+        LOG_HEAD floats in front of the gradient are not part of the range."""
+        K.grad_accum(self._acc, self.params.grad, 'add')
+        self.accum_launches['add'] += 1
 
     def set_frozen(self, bn_names=(), param_keys=()):
         """The freeze signature of the plans used from now on: `bn_names` -- BatchNorm layers (state_dict prefixes) that
@@ -1305,9 +1340,12 @@ class YuNetEngine:
         plan = self.plan
         return plan.dy_up if plan.deferred else plan.dy_scale
 
-    def backward(self, grad_scales=None):
-        """d(sum_i s_i * loss_i)/d(params) -> params.grad (overwritten)."""
+    def backward(self, grad_scales=None, fresh=False):
+        """d(sum_i s_i * loss_i)/d(params) -> params.grad: overwritten, or -- with set_grad_accumulation(True) and a total
+        to keep -- added to what params.grad held before the call (SAVE in front of the first backward op, ADD behind the
+        last one).  `fresh`: the caller knows the buffer holds no total (the parameters' .grad were None)."""
         plan = self.plan
+        keep = self._accum_save(fresh)
         if grad_scales is not None:
             s = [float(v) for v in grad_scales]
             vec = [s[0]] + [s[1]] * 4 + [s[2]] + [s[3]] * 10
@@ -1329,10 +1367,14 @@ class YuNetEngine:
                 self._exec(plan.c_tail_a, 'yunet_exec(bwd_a reduction)')
             self._exec(plan.c_bwd_b, 'yunet_exec(bwd_b)')
             main.wait_stream(side)
+            if keep:
+                self._accum_add()
             return
         if (self.world_size <= 1 and not self.always_bucket) or plan.split_off is None:
             self._exec(plan.c_bwd, 'yunet_exec(bwd)')
             self.allreduce_grads()
+            if keep:
+                self._accum_add()
             return
         # two segments: bucket A (tail of the flat buffer) is all-reduced on the side stream
         # while the kernels of segment B run; bucket B carries the logged scalars in its head
@@ -1351,6 +1393,8 @@ class YuNetEngine:
         ew = self._comm_mark(main, ('bucket_b', eb))
         main.wait_stream(side)
         self._comm_mark(main, ('wait_a', ew))
+        if keep:
+            self._accum_add()        # both buckets are reduced: every micro-step keeps its own all-reduce
 
     def _comm_mark(self, stream, close=None):
         """comm_timing: record an event on `stream`; with close = (name, start event) file the pair."""

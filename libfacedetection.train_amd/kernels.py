@@ -627,6 +627,20 @@ def adam_step_grouped(params, grads, exp_avg, exp_avg_sq, group_of, table, step,
             'yunet_adam_step_grouped')
 
 
+ACCUM_MODES = {'save': L.ACCUM_SAVE, 'add': L.ACCUM_ADD}
+
+
+def grad_accum(acc, grads, mode):
+    """mode 'save': acc <- grads; 'add': grads <- acc + grads (one fp32 add per element), one launch on the current stream
+    (yunet_grad_accum).  Contiguous fp32 runs of the same length, 4-byte aligned is enough; length 0 launches nothing."""
+    if mode not in ACCUM_MODES:
+        raise ValueError(f"grad_accum: mode {mode!r} is not 'save' or 'add'")
+    _chk_f32(acc, grads)
+    if acc.numel() != grads.numel():
+        raise ValueError('grad_accum: acc and grads differ in size')
+    L.check(L.load().yunet_grad_accum(_p(acc), _p(grads), grads.numel(), ACCUM_MODES[mode], _stream()), 'yunet_grad_accum')
+
+
 def ema_coefficients(momentum):
     """(keep, m) of the EMA hooks: 1 - momentum in double, as the reference's python does, then both as fp32 -- what
     torch's  ema.mul_(1 - momentum).add_(src, alpha=momentum)  hands its fp32 kernels."""

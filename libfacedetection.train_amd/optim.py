@@ -179,7 +179,11 @@ class _FusedOptimizer:
         return self._covered != eng.params.data.numel()
 
     def zero_grad(self, set_to_none=False):
-        """Gradients are overwritten (not accumulated) by the fused backward; nothing to do."""
+        """No launch: the fused backward overwrites the flat gradient.  The engine is told that the buffer holds no total
+        to keep, so with gradient accumulation on (YuNet.set_grad_accumulation) the next backward overwrites as well."""
+        eng = getattr(self.model, 'engine', None)
+        if eng is not None:
+            eng.mark_grad_zeroed()
         return None
 
     @torch.no_grad()

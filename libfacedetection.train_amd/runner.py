@@ -464,9 +464,14 @@ class Fp16OptimizerHook(OptimizerHook):
         target.set_precision('bf16')
 
     def after_train_iter(self, runner):
-        opt = runner.optimizer
-        opt.zero_grad()
+        runner.optimizer.zero_grad()
         (runner.outputs['loss'] * self.scale).backward()
+        self._unscale_and_step(runner)
+
+    def _unscale_and_step(self, runner):
+        """What follows the scaled backward: finite check, scale removal, [clip], step, dynamic-scale bookkeeping.
+        Returns whether the update was applied."""
+        opt = runner.optimizer
         target = runner.model.module if hasattr(runner.model, 'module') else runner.model
         grad = target.engine.params.grad
         # mmcv's GradScaler-based hook skips a step with non-finite gradients for static scales too
@@ -475,7 +480,7 @@ class Fp16OptimizerHook(OptimizerHook):
             if self.dynamic:
                 self.scale = max(self.scale / 2.0, 1.0)
                 self._good = 0
-            return                                             # skip the step, like LossScaler
+            return False                                       # skip the step, like LossScaler
         fused_clip = self._fused_clip(runner)
         if hasattr(opt, 'grad_scale') and (self.grad_clip is None or fused_clip):
             # fused optimizers: folded into the update kernel, and into the norm kernel, which therefore measures the
@@ -497,6 +502,113 @@ class Fp16OptimizerHook(OptimizerHook):
             self._good += 1
             if self._good % self.growth_interval == 0:
                 self.scale *= 2.0
+        return True
+
+
+def _unwrap(model):
+    return model.module if hasattr(model, 'module') else model
+
+
+class GradientCumulativeOptimizerHook(OptimizerHook):
+    """optimizer_config = dict(type='GradientCumulativeOptimizerHook', cumulative_iters=k [, grad_clip=...]) (mmcv >= 1.3.9):
+    k iterations of (loss / loss_factor).backward() onto the same gradient, then [clip] -> step -> zero_grad.  There is no
+    zero_grad in front of each backward: before_run switches gradient accumulation on in the model
+    (YuNet.set_grad_accumulation), so the fused backward adds to .grad; the backward right after a zero_grad overwrites and
+    costs nothing extra.
+
+    Schedule, fixed at the first after_train_iter: start_iter = runner.iter, residual = max_iters - start_iter,
+    divisible_iters = residual // k * k, remainder_iters = residual - divisible_iters.  loss_factor is k while
+    runner.iter < start_iter + divisible_iters and remainder_iters afterwards; an update happens at every_n_iters(runner, k)
+    and at the last iteration of the run.
+    Deviation from mmcv, on purpose: mmcv compares the absolute runner.iter with divisible_iters, which counts from the
+    starting iteration -- after a resume its last `start_iter` full windows would already be divided by remainder_iters
+    (by zero when the residual is a multiple of k).  Here the comparison is relative to start_iter; a run that starts at
+    iteration 0 is mmcv's exactly.  The update boundaries stay on the absolute iteration count, as in mmcv: a resumed
+    iteration that is no multiple of k makes the first window shorter (its gradient is still divided by k), which is what
+    the warning says.
+
+    With a fused optimizer clipping is the norm kernel and the update kernel on the accumulated gradient; `grad_norm` joins
+    log_vars on the iterations that update.  BatchNorm statistics are those of each micro-batch: k micro-batches are not
+    one large batch unless every BatchNorm layer is frozen (the second warning).  At world size > 1 every micro-step keeps
+    its gradient all-reduce, like mmcv's hook under MMDistributedDataParallel."""
+
+    def __init__(self, cumulative_iters=1, grad_clip=None):
+        if not isinstance(cumulative_iters, int) or isinstance(cumulative_iters, bool) or cumulative_iters <= 0:
+            raise TypeError(f'cumulative_iters only accepts positive int, but got {type(cumulative_iters)} instead.')
+        super().__init__(grad_clip)
+        self.cumulative_iters = cumulative_iters
+        self.start_iter = self.divisible_iters = self.remainder_iters = 0
+        self.initialized = False
+
+    def before_run(self, runner):
+        super().before_run(runner)
+        target = _unwrap(runner.model)
+        if hasattr(target, 'set_grad_accumulation'):
+            target.set_grad_accumulation(True)
+
+    @staticmethod
+    def has_batch_norm(module):
+        """A BatchNorm layer that normalises with batch statistics (a layer in eval() is the same under micro-batching)."""
+        return any(isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.training for m in module.modules())
+
+    def _warn(self, runner, msg):
+        warn = getattr(runner.logger, 'warning', None)
+        (warn if warn is not None else runner.logger)(msg)
+
+    def _init(self, runner):
+        k = self.cumulative_iters
+        if runner.iter % k != 0:
+            self._warn(runner, 'Resume iter number is not divisible by cumulative_iters in GradientCumulativeOptimizerHook, '
+                               'which means the gradient of some iters is lost and the result may be influenced slightly.')
+        if k > 1 and self.has_batch_norm(runner.model):
+            self._warn(runner, 'GradientCumulativeOptimizerHook may slightly decrease performance if the model has '
+                               'BatchNorm layers.')
+        self.start_iter = runner.iter
+        residual = runner.max_iters - runner.iter
+        self.divisible_iters = residual // k * k
+        self.remainder_iters = residual - self.divisible_iters
+        self.initialized = True
+
+    def loss_factor(self, runner):
+        if not self.initialized:
+            self._init(runner)
+        return self.cumulative_iters if runner.iter < self.start_iter + self.divisible_iters else self.remainder_iters
+
+    def is_boundary(self, runner):
+        return self.every_n_iters(runner, self.cumulative_iters) or runner.iter + 1 == runner.max_iters
+
+    def after_train_iter(self, runner):
+        (runner.outputs['loss'] / self.loss_factor(runner)).backward()
+        if not self.is_boundary(runner):
+            return
+        if self.grad_clip is not None and not self._fused_clip(runner):
+            params = [p for p in runner.model.parameters() if p.requires_grad and p.grad is not None]
+            norm = torch.nn.utils.clip_grad_norm_(params, **self.grad_clip)
+            if runner.outputs.get('log_vars') is not None:
+                runner.outputs['log_vars']['grad_norm'] = norm
+        runner.optimizer.step()
+        if self._fused_clip(runner):
+            self._log_grad_norm(runner)
+        runner.optimizer.zero_grad()
+
+
+class GradientCumulativeFp16OptimizerHook(GradientCumulativeOptimizerHook, Fp16OptimizerHook):
+    """GradientCumulativeOptimizerHook under cfg.fp16 (bf16 activation storage with loss scaling, Fp16OptimizerHook):
+    (loss * scale / loss_factor).backward() every iteration; the finite check, the scale's removal, clipping and the update
+    run on the accumulated gradient at the boundary only.  A non-finite total skips the update and halves a dynamic scale;
+    the gradient is zeroed either way, so the next window starts fresh.  The scale changes at boundaries only: every
+    micro-batch of a window carries the same one."""
+
+    def __init__(self, cumulative_iters=1, loss_scale=512., grad_clip=None, distributed=True):
+        GradientCumulativeOptimizerHook.__init__(self, cumulative_iters, grad_clip)
+        Fp16OptimizerHook.__init__(self, grad_clip, loss_scale, distributed)
+
+    def after_train_iter(self, runner):          # (before_run: both bases' -- accumulation on, grad_clip, bf16 storage)
+        (runner.outputs['loss'] * self.scale / self.loss_factor(runner)).backward()
+        if not self.is_boundary(runner):
+            return
+        self._unscale_and_step(runner)
+        runner.optimizer.zero_grad()
 
 
 class CheckpointHook(Hook):
@@ -700,14 +812,16 @@ class TensorboardLoggerHook(LoggerHook):
 
 HOOKS = dict(TextLoggerHook=TextLoggerHook, YuNetTextLoggerHook=YuNetTextLoggerHook,
              TensorboardLoggerHook=TensorboardLoggerHook, CheckpointHook=CheckpointHook, OptimizerHook=OptimizerHook,
-             Fp16OptimizerHook=Fp16OptimizerHook)
+             Fp16OptimizerHook=Fp16OptimizerHook, GradientCumulativeOptimizerHook=GradientCumulativeOptimizerHook,
+             GradientCumulativeFp16OptimizerHook=GradientCumulativeFp16OptimizerHook)
 
 
 class EpochBasedRunner:
     """The slice of mmcv.runner.EpochBasedRunner the reference's train_detector drives
     (mmdet/apis/train.py:169-246): register_training_hooks / register_hook / resume /
     load_checkpoint / run, and per iteration  before_train_iter hooks -> model.train_step ->
-    after_train_iter hooks (OptimizerHook: zero_grad, backward, step)."""
+    after_train_iter hooks (OptimizerHook: zero_grad, backward, step; GradientCumulativeOptimizerHook: backward, and
+    step + zero_grad every k iterations)."""
 
     def __init__(self, model, optimizer=None, work_dir=None, logger=print, meta=None, max_epochs=None,
                  max_iters=None):
@@ -917,13 +1031,31 @@ def wants_deterministic(cfg):
     return det_level(cfg.get('deterministic', False)) or _DETERMINISTIC
 
 
+CUMULATIVE_HOOKS = ('GradientCumulativeOptimizerHook', 'GradientCumulativeFp16OptimizerHook')
+
+
+def optimizer_hook_config(cfg, distributed=False):
+    """What train_detector hands register_training_hooks as optimizer_config: with cfg.fp16 the fp16 hook itself
+    (mmdet/apis/train.py:181-185) -- GradientCumulativeFp16OptimizerHook when optimizer_config.type names a cumulative hook,
+    Fp16OptimizerHook otherwise -- and without it the config dict, whose `type` the runner looks up in HOOKS."""
+    fp16_cfg = cfg.get('fp16', None)
+    opt_cfg = dict(cfg.get('optimizer_config') or {})
+    if fp16_cfg is None:
+        return opt_cfg
+    if opt_cfg.get('type') in CUMULATIVE_HOOKS:
+        opt_cfg.pop('type')
+        return GradientCumulativeFp16OptimizerHook(**opt_cfg, **fp16_cfg, distributed=distributed)
+    return Fp16OptimizerHook(**opt_cfg, **fp16_cfg, distributed=distributed)
+
+
 def train_detector(model, dataset, cfg, distributed=False, validate=False, timestamp=None,
                    meta=None, max_iters=None, device='cuda', log=print):
     """mmdet/apis/train.py:117-246 surface: DDP wrap, optimizer, EpochBasedRunner, fp16 / optimizer /
     lr / checkpoint / logger hooks from the config, auto-resume / resume / load_from, run.
     Returns the logged history (one dict of python floats per logging interval)."""
     if wants_deterministic(cfg):
-        if cfg.get('fp16', None) is not None:
+        if cfg.get('fp16', None) is not None or \
+                dict(cfg.get('optimizer_config') or {}).get('type') == 'GradientCumulativeFp16OptimizerHook':
             raise NotImplementedError('deterministic training with cfg.fp16 (bf16 activation storage): the deterministic mode '
                                       'covers the fp32 storage build only')
         model.set_deterministic(wants_deterministic(cfg))
@@ -936,12 +1068,7 @@ def train_detector(model, dataset, cfg, distributed=False, validate=False, times
     optimizer = build_optimizer(model, cfg.optimizer)
     runner = EpochBasedRunner(model, optimizer, cfg.get('work_dir'), log, meta,
                               max_epochs=cfg.runner['max_epochs'], max_iters=max_iters)
-    fp16_cfg = cfg.get('fp16', None)
-    opt_cfg = dict(cfg.get('optimizer_config') or {})
-    if fp16_cfg is not None:
-        optimizer_config = Fp16OptimizerHook(**opt_cfg, **fp16_cfg, distributed=distributed)
-    else:
-        optimizer_config = opt_cfg
+    optimizer_config = optimizer_hook_config(cfg, distributed)
     log_config = cfg.get('log_config')
     if max_iters is not None and max_iters <= 64 and log_config is not None:
         log_config = dict(log_config, interval=1)          # short smoke runs: log every iteration

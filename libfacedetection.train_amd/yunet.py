@@ -129,7 +129,9 @@ class _EngineStep(torch.autograd.Function):
             z = eng.scale_buffer().new_zeros(())
             gs = [(g if g is not None else z) + (gt if gt is not None else z) for g in (g0, g1, g2, g3)]
             eng.scale_buffer().copy_(torch.stack([gs[0]] + [gs[1]] * 4 + [gs[2]] + [gs[3]] * 10))
-        eng.backward()                      # kernels + (world > 1) the bucketed gradient all-reduce
+        # kernels + (world > 1) the bucketed gradient all-reduce; .grad None (a first backward, zero_grad(set_to_none=True)):
+        # nothing to accumulate onto (engine.set_grad_accumulation)
+        eng.backward(fresh=model._sentinel[1].grad is None)
         model._after_backward()
         return None, None, None
 
@@ -296,6 +298,16 @@ class YuNet(nn.Module):
         if self.engine is not None:
             self.engine.set_deterministic(flag)
 
+    def set_grad_accumulation(self, flag=True):
+        """Gradient accumulation (engine.YuNetEngine.set_grad_accumulation): with it on, backward() adds to the parameters'
+        .grad as PyTorch does, so k calls of (loss / k).backward() without a zero_grad() in between leave the gradient of the
+        k micro-batches together -- of any geometry; the flat gradient is shared by all plans.  A backward that follows
+        optimizer.zero_grad(), or finds .grad None, costs nothing extra.  Off (default): .grad is overwritten.
+        BatchNorm statistics stay those of each micro-batch (README)."""
+        self._grad_accum = bool(flag)
+        if self.engine is not None:
+            self.engine.set_grad_accumulation(flag)
+
     def set_data_parallel(self, world_size, group=None):
         """Called by YuNetDistributedDataParallel: one process per GPU, RCCL collectives."""
         self._world, self._group = world_size, group
@@ -325,6 +337,7 @@ class YuNet(nn.Module):
         eng = YuNetEngine(self.arch(), device, self._world, self._group)
         eng.set_precision(getattr(self, '_precision', 'fp32'))
         eng.set_deterministic(getattr(self, '_deterministic', False))
+        eng.set_grad_accumulation(getattr(self, '_grad_accum', False))
         eng.params.load_state_dict(sd)
         fp = eng.params
         for name, p in self.named_parameters():
