@@ -91,9 +91,19 @@ typedef struct YunetDP {
     YunetBN out_bn;            /* this unit's BN (stats written fwd, bstats read bwd) */
     /* backward only */
     const float* dy;           /* [N,H,W,cout] grad wrt BN output (or wrt z if no BN) */
-    const float* dy_scale;     /* [cout] per-channel factor on dy (device) or NULL    */
+    const float* dy_scale;     /* [cout] per-channel factor on dy (device) or NULL; read only when out_has_bn == 0 (the
+                                  fused heads): behind an output BN the kernels fold that BN's backward into dz and
+                                  ignore dy_scale */
     float* dx;                 /* [N,H,W,cin] grad wrt the BN output of the producer
-                                  (ReLU mask applied) or wrt x if IDENTITY; NULL skips */
+                                  (ReLU mask applied) or wrt x if IDENTITY; NULL skips: no input gradient is written AND
+                                  in_bn.bstats is left untouched (the producer's BN-backward sums are added only by a
+                                  launch that writes dx); the weight and bias gradients are those of the launch with a dx,
+                                  bit for bit.  x, dx and (with their own stride) z, dy may be strided: image i starts
+                                  i * x_img_stride / i * z_img_stride elements after the pointer; the elements between
+                                  the images are neither read nor written.  Every image must start on a 16-byte boundary
+                                  (the kernels use 128-bit accesses): that is the caller's responsibility, the entry
+                                  points do not check it (dense tensors and the [N,P,16] fp32 head output always do).
+                                  A pooled dy (pool_idx), pool_out and pool_idx are always dense. */
     float* wgrad_partials;     /* [nblocks, cout*cin + cout + cout*9 + cout] fp32     */
     int32_t wgrad_blocks;      /* number of partial rows (= launch grid)              */
     unsigned long long* prof;  /* optional [grid,8] per-workgroup phase cycle counters (or NULL) */

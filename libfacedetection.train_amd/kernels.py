@@ -158,16 +158,34 @@ def reduce_partials_batch(parts, outs, accumulate=None):
     return tab      # keep alive until the launch has run
 
 
+def _chk_strided(t, n, stride, dense, what):
+    """a flat buffer that holds n images of `dense` elements, `stride` elements apart, from its first element on"""
+    assert stride >= dense and t.numel() >= (n - 1) * stride + dense, \
+        f'{what}: {n} images of {dense} elements at stride {stride} do not fit {t.numel()} elements'
+    assert t.data_ptr() % 16 == 0 and (stride * t.element_size()) % 16 == 0, \
+        f'{what}: every image must start on a 16-byte boundary (the kernels use 128-bit accesses)'
+
+
 def _dp_desc(x, w_pw, b_pw, w_dw, b_dw, z, in_bn, out_bn, x_img_stride=None,
-             z_img_stride=None):
-    n, h, w, cin = x.shape
-    cout = w_pw.shape[0]
+             z_img_stride=None, shape=None):
+    """shape = (N, H, W): x and z are FLAT buffers (any tensor whose first element is image 0's first element), image i
+    at element i * x_img_stride / i * z_img_stride; None: N, H, W come from the dense 4-D x."""
+    cout, cin = w_pw.shape[0], w_pw.shape[1]
+    if shape is None:
+        n, h, w, xc = x.shape
+        assert xc == cin
+    else:
+        n, h, w = shape
     d = L.YunetDP()
     d.N, d.H, d.W, d.cin, d.cout = n, h, w, cin, cout
     d.in_transform = L.T_BNRELU if in_bn is not None else L.T_IDENTITY
     d.out_has_bn = 1 if out_bn is not None else 0
     d.x_img_stride = x_img_stride if x_img_stride is not None else h * w * cin
     d.z_img_stride = z_img_stride if z_img_stride is not None else h * w * cout
+    if shape is not None or x_img_stride is not None:
+        _chk_strided(x, n, d.x_img_stride, h * w * cin, 'x')
+    if z is not None and (shape is not None or z_img_stride is not None):
+        _chk_strided(z, n, d.z_img_stride, h * w * cout, 'z')
     d.x = x.data_ptr()
     d.in_bn = in_bn.c() if in_bn is not None else _NULL_BN
     d.out_bn = out_bn.c() if out_bn is not None else _NULL_BN
@@ -179,20 +197,24 @@ def _dp_desc(x, w_pw, b_pw, w_dw, b_dw, z, in_bn, out_bn, x_img_stride=None,
     return d
 
 
-def dp_fwd(x, w_pw, b_pw, w_dw, b_dw, in_bn=None, out_bn=None, z=None, z_img_stride=None, pool=False):
+def dp_fwd(x, w_pw, b_pw, w_dw, b_dw, in_bn=None, out_bn=None, z=None, z_img_stride=None, pool=False,
+           x_img_stride=None, shape=None):
     """ConvDPUnit forward.  x [N,H,W,Cin] raw producer output (in_bn given) or activations, fp32 or
     bf16 storage.  Returns raw z [N,H,W,Cout] in x's storage type (pass z to choose: the fused heads
     write fp32); accumulates out_bn.stats when out_bn is given.
     pool=True (fused max_pool2d of the BN+ReLU output): returns (z, pooled, idx) -- pooled [N,H/2,W/2,Cout]
     holds the RAW z of every window's winner (feed it to the consumer with in_bn = this unit's BN),
-    idx the uint8 window positions 2*dy + dx."""
+    idx the uint8 window positions 2*dy + dx.
+    shape = (N, H, W): x and z are flat buffers with x_img_stride / z_img_stride elements between images (YunetDP's
+    fields; default: dense); z defaults to a fresh flat buffer of N * z_img_stride elements.  pooled and idx stay dense."""
     _chk_f32(w_pw, b_pw, w_dw, b_dw)
     _chk_act(x, z)
-    n, h, w, _ = x.shape
+    n, h, w = x.shape[:3] if shape is None else shape
     cout = w_pw.shape[0]
     if z is None:
-        z = torch.empty(n, h, w, cout, device=x.device, dtype=x.dtype)
-    d = _dp_desc(x, w_pw, b_pw, w_dw, b_dw, z, in_bn, out_bn, z_img_stride=z_img_stride)
+        z = torch.empty(n, h, w, cout, device=x.device, dtype=x.dtype) if shape is None else \
+            torch.empty(n * (z_img_stride or h * w * cout), device=x.device, dtype=x.dtype)
+    d = _dp_desc(x, w_pw, b_pw, w_dw, b_dw, z, in_bn, out_bn, x_img_stride, z_img_stride, shape)
     if pool:
         pooled = torch.empty(n, h // 2, w // 2, cout, device=x.device, dtype=x.dtype)
         idx = torch.empty(n, h // 2, w // 2, cout, device=x.device, dtype=torch.uint8)
@@ -202,19 +224,31 @@ def dp_fwd(x, w_pw, b_pw, w_dw, b_dw, in_bn=None, out_bn=None, z=None, z_img_str
 
 
 def dp_bwd(x, w_pw, b_pw, w_dw, b_dw, z, dy, in_bn=None, out_bn=None, dy_scale=None,
-           dx=None, accumulate_dx=False, z_img_stride=None, need_dx=True, pool_idx=None, partials=None):
+           dx=None, accumulate_dx=False, z_img_stride=None, need_dx=True, pool_idx=None, partials=None,
+           x_img_stride=None, shape=None):
     """ConvDPUnit backward.  x, z: saved activations (fp32 or bf16); dy, dx fp32.
     Returns (dx, d_w_pw, d_b_pw, d_w_dw, d_b_dw).
     pool_idx (the idx of dp_fwd(..., pool=True)): dy is the POOLED gradient [N,H/2,W/2,cout] -- the dx
     the pool's consumer wrote -- and reaches the recorded window positions while the tile is staged.
-    partials: a [dp_grid(...), dp_row_width(...)] fp32 buffer for the per-workgroup weight-gradient rows (default: a fresh one)."""
+    partials: a [dp_grid(...), dp_row_width(...)] fp32 buffer for the per-workgroup weight-gradient rows (default: a fresh one).
+    need_dx=False: YunetDP.dx = NULL (no input gradient, and in_bn.bstats is left alone).
+    shape = (N, H, W): x, z, dy and dx are flat buffers -- x and dx with x_img_stride elements between images, z and dy
+    with z_img_stride (a pooled dy stays dense); dx defaults to a fresh flat buffer of N * x_img_stride elements."""
     _chk_f32(w_pw, b_pw, w_dw, b_dw, dy)
     _chk_act(x)
-    n, h, w, cin = x.shape
-    cout = w_pw.shape[0]
+    n, h, w = x.shape[:3] if shape is None else shape
+    cout, cin = w_pw.shape[0], w_pw.shape[1]
     if dx is None and need_dx:
-        dx = torch.empty(x.shape, device=x.device, dtype=torch.float32)
-    d = _dp_desc(x, w_pw, b_pw, w_dw, b_dw, z, in_bn, out_bn, z_img_stride=z_img_stride)
+        dx = torch.empty(x.shape, device=x.device, dtype=torch.float32) if shape is None else \
+            torch.empty(n * (x_img_stride or h * w * cin), device=x.device, dtype=torch.float32)
+    d = _dp_desc(x, w_pw, b_pw, w_dw, b_dw, z, in_bn, out_bn, x_img_stride, z_img_stride, shape)
+    strided = shape is not None or x_img_stride is not None or z_img_stride is not None
+    if dx is not None:
+        _chk_f32(dx)
+        if strided:
+            _chk_strided(dx, n, d.x_img_stride, h * w * cin, 'dx')
+    if strided and pool_idx is None:
+        _chk_strided(dy, n, d.z_img_stride, h * w * cout, 'dy')
     d.dy = dy.data_ptr()
     d.dy_scale = dy_scale.data_ptr() if dy_scale is not None else None
     d.dx = dx.data_ptr() if dx is not None else None

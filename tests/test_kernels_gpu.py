@@ -240,7 +240,7 @@ def test_dp_bwd_accumulate():
     dx1 = base.clone()
     k.dp_bwd(*args, dx=dx1, accumulate_dx=True)
     torch.cuda.synchronize()
-    assert torch.allclose(dx1, base + dx0, atol=1e-5, rtol=1e-5)
+    assert torch.equal(dx1, base + dx0)       # one fp32 add per element (every instance: tests/test_dp_descriptor_gpu.py)
 
 
 @pytest.mark.parametrize('n,h,w', [(2, 32, 32), (3, 64, 96), (1, 20, 36), (2, 320, 320), (5, 66, 150)])
