@@ -313,7 +313,9 @@ int yunet_loss_norm(const float* img_stats, int N, float inv_world, float* norm,
 /* box losses of mmdet/models/losses/iou_loss.py: EIoULoss :194-227 | DIoULoss :137-172 | IoULoss :14-50 (mode linear /
  * square / log; YuNet_Head's own default is mode 'square', yunet_head.py:59-64) | GIoULoss :103-120 | CIoULoss :230-293 */
 enum { YUNET_BOX_EIOU = 0, YUNET_BOX_DIOU = 1, YUNET_BOX_IOU_LINEAR = 2, YUNET_BOX_IOU_SQUARE = 3, YUNET_BOX_IOU_LOG = 4,
-       YUNET_BOX_GIOU = 5, YUNET_BOX_CIOU = 6 };
+       YUNET_BOX_GIOU = 5, YUNET_BOX_CIOU = 6,
+       YUNET_BOX_BOUNDED = 7   /* BoundedIoULoss, iou_loss.py:55-97: beta in smooth_point, eps in box_eps; runs in the second
+                                * instance of the loss kernel (yunet_loss_terms, or yunet_loss, which forwards this code) */ };
 typedef struct YunetLossCfg {
     int32_t box_loss;            /* YUNET_BOX_*  (losses/iou_loss.py:194-227 / 137-172) */
     float w_cls, w_box, w_obj, w_kps;   /* loss_weight of each term                    */
@@ -341,7 +343,31 @@ int yunet_loss(const float* flat, const int32_t* gt_inds, const float* max_overl
                float* dflat, float* partials, int blocks, void* stream);
 int yunet_loss_finalize(const float* partials, int blocks, float* losses, float* mirror,
                         void* stream);
-/* The same with the deferred normaliser of YunetLossCfg.defer_num_total: num_total (device, nullable) = the
+/* Which loss each term uses, beyond the default selection (additive; NOT a member of YunetOp, whose layout is pinned).
+ * All-zero = sigmoid BCE for cls and obj, smooth-L1 for kps: then yunet_loss_terms IS yunet_loss (same kernel, same bits).
+ *   VarifocalLoss  (losses/varifocal_loss.py:11-56)  cls: positives, t = max_overlaps; obj: every prior, t in {0, 1}.  The
+ *                  focal weight alpha |sigmoid(x) - t|^gamma of the t <= 0 side is differentiated (the reference does not
+ *                  detach it).  gamma >= 1 and alpha >= 0 (YUNET_EINVAL otherwise).
+ *   L1Loss (smooth_l1_loss.py:36-52) | MSELoss (mse_loss.py:9-12) | BalancedL1Loss (balanced_l1_loss.py:13-53; beta =
+ *                  YunetLossCfg.kps_beta): the targets, visibility weight and normaliser of the smooth-L1 term.
+ * In an op list: YUNET_OP_LOSS with i[4] = cls_loss, i[5] = obj_loss, i[6] = kps_loss, i[7] = cls_iou_weighted |
+ * obj_iou_weighted << 1, f[0..5] = cls_alpha, cls_gamma, obj_alpha, obj_gamma, kps_alpha, kps_gamma. */
+enum { YUNET_CLS_BCE = 0, YUNET_CLS_VARIFOCAL = 1 };
+enum { YUNET_KPS_SMOOTH_L1 = 0, YUNET_KPS_L1 = 1, YUNET_KPS_MSE = 2, YUNET_KPS_BALANCED_L1 = 3 };
+typedef struct YunetLossTerms {
+    int32_t cls_loss, obj_loss;  /* YUNET_CLS_*                                        */
+    int32_t kps_loss;            /* YUNET_KPS_*                                        */
+    int32_t cls_iou_weighted, obj_iou_weighted;   /* VarifocalLoss.iou_weighted         */
+    float cls_alpha, cls_gamma;  /* VarifocalLoss of loss_cls (0.75, 2.0)              */
+    float obj_alpha, obj_gamma;  /* VarifocalLoss of loss_obj                          */
+    float kps_alpha, kps_gamma;  /* BalancedL1Loss (0.5, 1.5)                          */
+} YunetLossTerms;
+/* yunet_loss with the terms chosen by `terms` (NULL = all-zero). */
+int yunet_loss_terms(const float* flat, const int32_t* gt_inds, const float* max_overlaps,
+                     const float* gt_boxes, const float* gt_kps, const YunetLevels* lv,
+                     const YunetLossCfg* cfg, const YunetLossTerms* terms, const float* norm, int N, int P, int Gmax,
+                     float* dflat, float* partials, int blocks, void* stream);
+/* yunet_loss_finalize with the deferred normaliser of YunetLossCfg.defer_num_total: num_total (device, nullable) = the
  * all-reduced mean num_pos; the first three losses are multiplied by 1 / max(num_total[0], 1) and dy_norm [16]
  * (nullable) receives the per-channel factor of d(loss)/d(flat) -- that value for cls | dx dy dw dh | obj, 1 for the
  * ten kps channels (normalised by the rank-local weight sum inside yunet_loss) -- which the fused head units take

@@ -28,7 +28,9 @@ OPT_FROZEN = 255                                                  # YUNET_OPT_FR
 T_IDENTITY, T_BNRELU = 0, 1
 F32, BF16 = 0, 1
 DET_FAST = 1 << 30         # YUNET_DET_FAST: flag in YunetBN.det_rows, above the row count
-BOX_EIOU, BOX_DIOU, BOX_IOU_LINEAR, BOX_IOU_SQUARE, BOX_IOU_LOG, BOX_GIOU, BOX_CIOU = 0, 1, 2, 3, 4, 5, 6
+BOX_EIOU, BOX_DIOU, BOX_IOU_LINEAR, BOX_IOU_SQUARE, BOX_IOU_LOG, BOX_GIOU, BOX_CIOU, BOX_BOUNDED = 0, 1, 2, 3, 4, 5, 6, 7
+CLS_BCE, CLS_VARIFOCAL = 0, 1                                     # YUNET_CLS_* (YunetLossTerms.cls_loss / obj_loss)
+KPS_SMOOTH_L1, KPS_L1, KPS_MSE, KPS_BALANCED_L1 = 0, 1, 2, 3      # YUNET_KPS_* (YunetLossTerms.kps_loss)
 (OP_STEM_FWD, OP_STEM_BWD, OP_DP_FWD, OP_DP_BWD, OP_POOL_FWD, OP_POOL_BWD, OP_UPADD_FWD,
  OP_UPADD_BWD, OP_BN_RUNNING, OP_BN_PARAM_GRAD, OP_REDUCE_PARTIALS, OP_ASSIGN, OP_LOSS_NORM,
  OP_LOSS, OP_LOSS_FINALIZE, OP_SGD, OP_MEMSET, OP_BN_BATCH, OP_REDUCE_BATCH, OP_FORK, OP_JOIN, OP_ADD, OP_BN_FOLD) = range(1, 24)
@@ -64,6 +66,23 @@ class YunetLossCfg(C.Structure):
     _fields_ = [('box_loss', C.c_int32), ('w_cls', C.c_float), ('w_box', C.c_float),
                 ('w_obj', C.c_float), ('w_kps', C.c_float), ('box_eps', C.c_float),
                 ('smooth_point', C.c_float), ('kps_beta', C.c_float), ('defer_num_total', C.c_int32)]
+
+
+class YunetLossTerms(C.Structure):
+    """Which loss each term uses (yunet_loss_terms); all-zero = the default selection.  Not a member of YunetOp: an op list
+    carries it in YUNET_OP_LOSS's i[4..7] and f[0..5] (op_slots)."""
+    _fields_ = [('cls_loss', C.c_int32), ('obj_loss', C.c_int32), ('kps_loss', C.c_int32),
+                ('cls_iou_weighted', C.c_int32), ('obj_iou_weighted', C.c_int32),
+                ('cls_alpha', C.c_float), ('cls_gamma', C.c_float), ('obj_alpha', C.c_float), ('obj_gamma', C.c_float),
+                ('kps_alpha', C.c_float), ('kps_gamma', C.c_float)]
+
+    def op_slots(self):
+        """-> (i[4..7], f[0..5]) of a YUNET_OP_LOSS op."""
+        return ([self.cls_loss, self.obj_loss, self.kps_loss, (self.cls_iou_weighted & 1) | (self.obj_iou_weighted & 1) << 1],
+                [self.cls_alpha, self.cls_gamma, self.obj_alpha, self.obj_gamma, self.kps_alpha, self.kps_gamma])
+
+    def is_default(self):
+        return self.cls_loss == CLS_BCE and self.obj_loss == CLS_BCE and self.kps_loss == KPS_SMOOTH_L1
 
 
 class YunetAssignCfg(C.Structure):
@@ -207,6 +226,9 @@ _SIGNATURES = {
     'yunet_loss': (C.c_int, [C.c_void_p] * 5 + [C.POINTER(YunetLevels), C.POINTER(YunetLossCfg),
                                                 C.c_void_p] + [C.c_int] * 3 +
                    [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'yunet_loss_terms': (C.c_int, [C.c_void_p] * 5 + [C.POINTER(YunetLevels), C.POINTER(YunetLossCfg),
+                                                      C.POINTER(YunetLossTerms), C.c_void_p] + [C.c_int] * 3 +
+                         [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     'yunet_loss_finalize': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'yunet_loss_finalize_ex': (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5),
     'yunet_sgd_step_ex': (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_float,

@@ -1145,107 +1145,78 @@ __device__ __forceinline__ float bce_logits(float x, float t) {
 
 #define LOSS_THREADS 256
 
+// ---- the loss terms beyond the default selection (YunetLossTerms): compiled into loss_terms_kernel only ---------------
+__device__ __forceinline__ D4 dabs(D4 a) {          // torch.abs: the gradient at 0 is 0
+    if (a.v > 0.0f) return a;
+    if (a.v < 0.0f) return mk(0.0f) - a;
+    return mk(fabsf(a.v));
+}
+__device__ __forceinline__ D4 dsmooth(D4 c, float beta) {   // where(c < beta, 0.5 c c / beta, c - 0.5 beta)
+    if (c.v < beta) return dscale(dscale(c * c, 0.5f), 1.0f / beta);
+    return dadd(c, -0.5f * beta);
+}
+// bounded_iou_loss, mmdet/models/losses/iou_loss.py:55-97, its four components summed (reduction 'sum' over [n, 4])
+__device__ D4 bounded_iou(D4 px1, D4 py1, D4 px2, D4 py2, float tx1, float ty1, float tx2, float ty2, float beta, float eps) {
+    const D4 pcx = dscale(px1 + px2, 0.5f), pcy = dscale(py1 + py2, 0.5f);
+    const D4 pw = px2 - px1, ph = py2 - py1;
+    const float tcx = (tx1 + tx2) * 0.5f, tcy = (ty1 + ty2) * 0.5f, tw = tx2 - tx1, th = ty2 - ty1;
+    const D4 ax = dscale(dabs(mk(tcx) - pcx), 2.0f), ay = dscale(dabs(mk(tcy) - pcy), 2.0f);
+    const D4 ldx = mk(1.0f) - dmax((mk(tw) - ax) / dadd(mk(tw) + ax, eps), mk(0.0f));
+    const D4 ldy = mk(1.0f) - dmax((mk(th) - ay) / dadd(mk(th) + ay, eps), mk(0.0f));
+    const D4 ldw = mk(1.0f) - dmin(mk(tw) / dadd(pw, eps), pw / mk(tw + eps));
+    const D4 ldh = mk(1.0f) - dmin(mk(th) / dadd(ph, eps), ph / mk(th + eps));
+    return ((dsmooth(ldx, beta) + dsmooth(ldy, beta)) + dsmooth(ldw, beta)) + dsmooth(ldh, beta);
+}
+
+// varifocal_loss, mmdet/models/losses/varifocal_loss.py:11-56, one element: the term and d term / d x.  The focal weight of
+// the t <= 0 side, alpha |sigma - t|^gamma, depends on the prediction and is not detached there: its derivative is the
+// second summand.  sigma and 1 - sigma both come from exp(-|x|), so neither cancels at a saturated logit, and the BCE keeps
+// its log1p form.
+__device__ __forceinline__ float varifocal(float x, float t, float alpha, float gamma, int iou_weighted, float* grad) {
+    const float e = expf(-fabsf(x));
+    const float r = 1.0f / (1.0f + e);
+    const float sg = x >= 0.0f ? r : e * r, sn = x >= 0.0f ? e * r : r;      // sigma, 1 - sigma
+    const float bce = ((1.0f - t) * x - fminf(x, 0.0f)) + log1pf(e);
+    const float df = sg - t;
+    if (t > 0.0f) {
+        const float fw = iou_weighted ? t : 1.0f;
+        *grad = fw * df;
+        return bce * fw;
+    }
+    const float a = fabsf(df);
+    float pw, pw1;                                    // a^gamma, a^(gamma - 1)
+    if (gamma == 2.0f) {
+        pw = a * a;
+        pw1 = a;
+    } else {
+        pw = powf(a, gamma);
+        pw1 = powf(a, gamma - 1.0f);
+    }
+    const float sgn = df > 0.0f ? 1.0f : (df < 0.0f ? -1.0f : 0.0f);
+    *grad = alpha * pw * df + bce * (alpha * gamma * pw1 * sgn) * (sg * sn);
+    return bce * (alpha * pw);
+}
+
+// The loss step proper, two instances of one body (loss_kernel_body.inc).
 __global__ __launch_bounds__(LOSS_THREADS) void loss_kernel(
     const float* __restrict__ flat, const int32_t* __restrict__ gt_inds,
     const float* __restrict__ max_overlaps, const float* __restrict__ gt_boxes,
     const float* __restrict__ gt_kps, Levels L, YunetLossCfg cfg, const float* __restrict__ norm,
     int N, int P, int Gmax, float* __restrict__ dflat, float* __restrict__ partials) {
-    // cfg.defer_num_total: norm[0] (the all-reduced positives, possibly still in flight on another stream) is NOT
-    // read: the cls / bbox / obj terms and their gradients leave this kernel un-normalised (x 1.0 is exact) and
-    // loss_finalize_kernel applies 1 / max(num_total, 1) to the losses and hands it to the head backward as dy_scale
-    const float num_total = cfg.defer_num_total ? 1.0f : fmaxf(norm[0], 1.0f);
-    const float inv_total = 1.0f / num_total;
-    const float kps_den = norm[1] + 1.1920928955078125e-07f;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    const long long total = (long long)N * P;
-    for (long long e = (long long)blockIdx.x * LOSS_THREADS + threadIdx.x; e < total;
-         e += (long long)gridDim.x * LOSS_THREADS) {
-        const int n = (int)(e / P), p = (int)(e - (long long)n * P);
-        const float4* src = reinterpret_cast<const float4*>(flat + e * 16);
-        float4 q0 = src[0], q1 = src[1], q2 = src[2], q3 = src[3];
-        float o[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) o[i] = 0.0f;
-        const int gi = gt_inds[e];
-        const float t_obj = gi > 0 ? 1.0f : 0.0f;
-        const float xo = q1.y;
-        acc[2] += bce_logits(xo, t_obj);
-        o[5] = cfg.w_obj * (sigmoidf_ref(xo) - t_obj) * inv_total;
-        if (gi > 0) {
-            const int g = gi - 1;
-            float px, py, s;
-            prior_of(L, p, px, py, s);
-            // cls: BCE with IoU soft target, positives only
-            const float t = max_overlaps[e];
-            acc[0] += bce_logits(q0.x, t);
-            o[0] = cfg.w_cls * (sigmoidf_ref(q0.x) - t) * inv_total;
-            // box: decode as duals w.r.t. (dx, dy, dw, dh)
-            D4 ddx = mk(q0.y), ddy = mk(q0.z), ddw = mk(q0.w), ddh = mk(q1.x);
-            ddx.d[0] = 1.f; ddy.d[1] = 1.f; ddw.d[2] = 1.f; ddh.d[3] = 1.f;
-            const D4 cx = dadd(dscale(ddx, s), px), cy = dadd(dscale(ddy, s), py);
-            D4 ew = mk(expf(ddw.v)), eh = mk(expf(ddh.v));
-            ew.d[2] = ew.v; eh.d[3] = eh.v;
-            const D4 bw = dscale(ew, s), bh = dscale(eh, s);
-            const D4 hx = dscale(bw, 0.5f), hy = dscale(bh, 0.5f);   // w/2 is exact
-            const D4 x1 = cx - hx, y1 = cy - hy, x2 = cx + hx, y2 = cy + hy;
-            const float* tb = gt_boxes + ((size_t)n * Gmax + g) * 4;
-            D4 lb;
-            switch (cfg.box_loss) {      // uniform over the launch
-                case YUNET_BOX_EIOU: lb = eiou(x1, y1, x2, y2, tb[0], tb[1], tb[2], tb[3], cfg.smooth_point, cfg.box_eps); break;
-                case YUNET_BOX_DIOU: lb = diou(x1, y1, x2, y2, tb[0], tb[1], tb[2], tb[3], cfg.box_eps); break;
-                case YUNET_BOX_GIOU: lb = giou(x1, y1, x2, y2, tb[0], tb[1], tb[2], tb[3], cfg.box_eps); break;
-                case YUNET_BOX_CIOU: lb = ciou(x1, y1, x2, y2, tb[0], tb[1], tb[2], tb[3], cfg.box_eps); break;
-                default: lb = iou_family(x1, y1, x2, y2, tb[0], tb[1], tb[2], tb[3], cfg.box_loss - YUNET_BOX_IOU_LINEAR, cfg.box_eps);
-            }
-            acc[1] += lb.v;
-            // (d * w) * 1/num_total, in this order: with the deferred normaliser the last factor is applied by the head
-            // backward (dy_scale) and the product must round the same way
-            const float kb = cfg.w_box;
-            o[1] = lb.d[0] * kb * inv_total; o[2] = lb.d[1] * kb * inv_total;
-            o[3] = lb.d[2] * kb * inv_total; o[4] = lb.d[3] * kb * inv_total;
-            // kps: smooth-L1 on (kps - prior_xy)/stride, weight = mean visibility
-            const float* kp = gt_kps + ((size_t)n * Gmax + g) * 15;
-            const float w = ((((kp[2] + kp[5]) + kp[8]) + kp[11]) + kp[14]) / 5.0f;
-            const float pr[10] = {q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
-            const float kk = cfg.w_kps / kps_den;
-            float lk = 0.0f;
-#pragma unroll
-            for (int j = 0; j < 10; ++j) {
-                const float tgt = (kp[(j >> 1) * 3 + (j & 1)] - ((j & 1) ? py : px)) / s;
-                const float d = pr[j] - tgt;
-                const float ad = fabsf(d);
-                const bool quad = ad < cfg.kps_beta;
-                lk += (quad ? 0.5f * ad * ad / cfg.kps_beta : ad - 0.5f * cfg.kps_beta) * w;
-                const float gsl = quad ? d / cfg.kps_beta : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
-                o[6 + j] = gsl * w * kk;
-            }
-            acc[3] += lk;
-        }
-        float4* dst = reinterpret_cast<float4*>(dflat + e * 16);
-        dst[0] = make_float4(o[0], o[1], o[2], o[3]);
-        dst[1] = make_float4(o[4], o[5], o[6], o[7]);
-        dst[2] = make_float4(o[8], o[9], o[10], o[11]);
-        dst[3] = make_float4(o[12], o[13], o[14], o[15]);
-    }
-    // deterministic block reduction -> one partial row per block
-    __shared__ float s_p[LOSS_THREADS / 64][4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        float v = acc[k];
-#pragma unroll
-        for (int o2 = 32; o2 >= 1; o2 >>= 1) v += __shfl_xor(v, o2, 64);
-        if ((threadIdx.x & 63) == 0) s_p[threadIdx.x >> 6][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        float v = 0.0f;
-        for (int w = 0; w < LOSS_THREADS / 64; ++w) v += s_p[w][threadIdx.x];
-        // loss_i = weight * sum / normaliser
-        const float wgt = threadIdx.x == 0 ? cfg.w_cls : threadIdx.x == 1 ? cfg.w_box
-                          : threadIdx.x == 2 ? cfg.w_obj : cfg.w_kps;
-        const float den = threadIdx.x == 3 ? kps_den : num_total;
-        partials[blockIdx.x * 4 + threadIdx.x] = wgt * v / den;
-    }
+    constexpr bool EXT = false;
+    constexpr YunetLossTerms tm{};
+    constexpr float bal_b = 0.0f;
+#include "loss_kernel_body.inc"
+}
+
+// bal_b: BalancedL1Loss's b = e^(gamma / alpha) - 1, formed once on the host (balanced_l1_loss.py:47)
+__global__ __launch_bounds__(LOSS_THREADS) void loss_terms_kernel(
+    const float* __restrict__ flat, const int32_t* __restrict__ gt_inds,
+    const float* __restrict__ max_overlaps, const float* __restrict__ gt_boxes,
+    const float* __restrict__ gt_kps, Levels L, YunetLossCfg cfg, YunetLossTerms tm, float bal_b,
+    const float* __restrict__ norm, int N, int P, int Gmax, float* __restrict__ dflat, float* __restrict__ partials) {
+    constexpr bool EXT = true;
+#include "loss_kernel_body.inc"
 }
 
 __global__ void loss_finalize_kernel(const float* __restrict__ partials, int blocks,
@@ -1371,11 +1342,47 @@ extern "C" int yunet_loss_norm(const float* img_stats, int N, float inv_world, f
     return -(int)hipGetLastError();
 }
 
+extern "C" int yunet_loss_terms(const float* flat, const int32_t* gt_inds, const float* max_overlaps,
+                                const float* gt_boxes, const float* gt_kps, const YunetLevels* lv,
+                                const YunetLossCfg* cfg, const YunetLossTerms* terms, const float* norm, int N, int P,
+                                int Gmax, float* dflat, float* partials, int blocks, void* stream) {
+    if (!lv || !cfg || blocks < 1) return YUNET_EINVAL;
+    const YunetLossTerms tm = terms ? *terms : YunetLossTerms{};
+    const bool dflt = tm.cls_loss == YUNET_CLS_BCE && tm.obj_loss == YUNET_CLS_BCE && tm.kps_loss == YUNET_KPS_SMOOTH_L1 &&
+                      cfg->box_loss != YUNET_BOX_BOUNDED;
+    if (dflt)       // the default selection is yunet_loss itself: the same kernel, the same bits
+        return yunet_loss(flat, gt_inds, max_overlaps, gt_boxes, gt_kps, lv, cfg, norm, N, P, Gmax, dflat, partials, blocks,
+                          stream);
+    if (cfg->box_loss < YUNET_BOX_EIOU || cfg->box_loss > YUNET_BOX_BOUNDED) return YUNET_EINVAL;
+    if ((tm.cls_loss != YUNET_CLS_BCE && tm.cls_loss != YUNET_CLS_VARIFOCAL) ||
+        (tm.obj_loss != YUNET_CLS_BCE && tm.obj_loss != YUNET_CLS_VARIFOCAL) || tm.kps_loss < YUNET_KPS_SMOOTH_L1 ||
+        tm.kps_loss > YUNET_KPS_BALANCED_L1)
+        return YUNET_EINVAL;
+    // varifocal: d/dx holds |sigma - t|^(gamma - 1), unbounded at sigma = t below gamma = 1
+    if (tm.cls_loss == YUNET_CLS_VARIFOCAL && !(tm.cls_gamma >= 1.0f && tm.cls_alpha >= 0.0f)) return YUNET_EINVAL;
+    if (tm.obj_loss == YUNET_CLS_VARIFOCAL && !(tm.obj_gamma >= 1.0f && tm.obj_alpha >= 0.0f)) return YUNET_EINVAL;
+    if (cfg->box_loss == YUNET_BOX_BOUNDED && !(cfg->smooth_point > 0.0f)) return YUNET_EINVAL;
+    float bal_b = 0.0f;
+    if (tm.kps_loss == YUNET_KPS_BALANCED_L1) {
+        if (!(tm.kps_alpha > 0.0f) || !(cfg->kps_beta > 0.0f)) return YUNET_EINVAL;
+        bal_b = (float)(exp((double)tm.kps_gamma / (double)tm.kps_alpha) - 1.0);
+        if (!(bal_b > 0.0f) || !(bal_b < 3.0e38f)) return YUNET_EINVAL;
+    }
+    Levels L = make_levels(lv);
+    if (L.base[YUNET_MAX_LEVELS] != P) return YUNET_EINVAL;
+    hipLaunchKernelGGL(loss_terms_kernel, dim3(blocks), dim3(LOSS_THREADS), 0, (hipStream_t)stream, flat, gt_inds,
+                       max_overlaps, gt_boxes, gt_kps, L, *cfg, tm, bal_b, norm, N, P, Gmax, dflat, partials);
+    return -(int)hipGetLastError();
+}
+
 extern "C" int yunet_loss(const float* flat, const int32_t* gt_inds, const float* max_overlaps,
                           const float* gt_boxes, const float* gt_kps, const YunetLevels* lv,
                           const YunetLossCfg* cfg, const float* norm, int N, int P, int Gmax,
                           float* dflat, float* partials, int blocks, void* stream) {
     if (!lv || !cfg || blocks < 1) return YUNET_EINVAL;
+    if (cfg->box_loss == YUNET_BOX_BOUNDED)       // no code of this entry before YunetLossTerms: the second instance has it
+        return yunet_loss_terms(flat, gt_inds, max_overlaps, gt_boxes, gt_kps, lv, cfg, nullptr, norm, N, P, Gmax, dflat,
+                                partials, blocks, stream);
     Levels L = make_levels(lv);
     if (L.base[YUNET_MAX_LEVELS] != P) return YUNET_EINVAL;
     hipLaunchKernelGGL(loss_kernel, dim3(blocks), dim3(LOSS_THREADS), 0, (hipStream_t)stream, flat,

@@ -622,6 +622,15 @@ class Plan:
         op.loss = K.make_loss_cfg(arch['loss_bbox'], arch['loss_cls_weight'], arch['loss_bbox_weight'], arch['loss_obj_weight'],
                                   arch['loss_kps_weight'], float(arch.get('loss_bbox_eps', 1e-6)),
                                   float(arch.get('loss_bbox_smooth_point', 0.1)), arch['kps_beta'], arch.get('loss_bbox_mode'))
+        # the other terms' selection (YunetLossTerms) rides in slots this op leaves free: i[4..7], f[0..5]; an arch without
+        # the keys, or with the default types, leaves them zero
+        terms = K.make_loss_terms(arch.get('loss_cls'), arch.get('loss_obj'), arch.get('loss_kps'))
+        if not terms.is_default():
+            ti, tf = terms.op_slots()
+            for k, v in enumerate(ti):
+                op.i[4 + k] = int(v)
+            for k, v in enumerate(tf):
+                op.f[k] = float(v)
         self.fwd_b.append(op)
         self.fwd_b.append(self._op(L.OP_LOSS_FINALIZE, p=[self.loss_partials.data_ptr(), self.losses.data_ptr(),
                                                          self.eng.params.log_head.data_ptr()], i=[self.loss_blocks]))

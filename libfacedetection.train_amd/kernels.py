@@ -520,19 +520,76 @@ def box_loss_code(box_loss, mode=None):
             return {'linear': L.BOX_IOU_LINEAR, 'square': L.BOX_IOU_SQUARE, 'log': L.BOX_IOU_LOG}[mode or 'log']
         except KeyError:
             raise ValueError(f"IoULoss mode {mode!r}: 'linear', 'square' or 'log'") from None
-    table = {'EIoULoss': L.BOX_EIOU, 'DIoULoss': L.BOX_DIOU, 'GIoULoss': L.BOX_GIOU, 'CIoULoss': L.BOX_CIOU}
+    table = {'EIoULoss': L.BOX_EIOU, 'DIoULoss': L.BOX_DIOU, 'GIoULoss': L.BOX_GIOU, 'CIoULoss': L.BOX_CIOU,
+             'BoundedIoULoss': L.BOX_BOUNDED}
     if box_loss not in table:
         raise NotImplementedError(f'loss_bbox type {box_loss!r}: the fused loss kernel implements IoULoss, GIoULoss, '
-                                  f'DIoULoss, CIoULoss and EIoULoss (BoundedIoULoss is a smooth-L1 on box deltas)')
+                                  f'DIoULoss, CIoULoss, EIoULoss and BoundedIoULoss')
     return table[box_loss]
 
 
+CLS_LOSSES = {'CrossEntropyLoss': L.CLS_BCE, 'VarifocalLoss': L.CLS_VARIFOCAL}
+KPS_LOSSES = {'SmoothL1Loss': L.KPS_SMOOTH_L1, 'L1Loss': L.KPS_L1, 'MSELoss': L.KPS_MSE, 'BalancedL1Loss': L.KPS_BALANCED_L1}
+
+
+def _term(name, spec, table):
+    """(type name, parameters) of one loss term: a type name or a dict(type=..., **parameters); None = the default."""
+    if spec is None:
+        return next(iter(table)), {}
+    spec = dict(type=spec) if isinstance(spec, str) else dict(spec)
+    kind = spec.pop('type')
+    if kind not in table:
+        raise NotImplementedError(f'{name} type {kind!r}: the fused loss kernel implements ' + ', '.join(table))
+    if not spec.pop('use_sigmoid', True):
+        raise NotImplementedError(f'{name}: use_sigmoid=False (the head predicts one sigmoid score per prior)')
+    return kind, spec
+
+
+def _varifocal(name, par):
+    alpha, gamma = float(par.get('alpha', 0.75)), float(par.get('gamma', 2.0))
+    if not alpha >= 0.0:
+        raise ValueError(f'{name}: VarifocalLoss alpha={alpha} must be >= 0')
+    if not gamma >= 1.0:
+        raise ValueError(f'{name}: VarifocalLoss gamma={gamma} must be >= 1 (the derivative of |sigmoid(x) - t|^gamma '
+                         'is unbounded at sigmoid(x) = t below 1)')
+    return alpha, gamma, int(bool(par.get('iou_weighted', True)))
+
+
+def make_loss_terms(loss_cls=None, loss_obj=None, loss_kps=None):
+    """YunetLossTerms of the three terms that have a choice beside loss_bbox.  Each is None (the default: CrossEntropyLoss /
+    CrossEntropyLoss / SmoothL1Loss), a type name, or dict(type=..., alpha=, gamma=, iou_weighted=) with the reference
+    constructors' defaults.  BalancedL1Loss / SmoothL1Loss take their beta from make_loss_cfg's kps_beta."""
+    t = L.YunetLossTerms()
+    for name, spec in (('loss_cls', loss_cls), ('loss_obj', loss_obj)):
+        kind, par = _term(name, spec, CLS_LOSSES)
+        setattr(t, name[5:] + '_loss', CLS_LOSSES[kind])
+        if kind == 'VarifocalLoss':
+            a, g, w = _varifocal(name, par)
+            setattr(t, name[5:] + '_alpha', a)
+            setattr(t, name[5:] + '_gamma', g)
+            setattr(t, name[5:] + '_iou_weighted', w)
+    kind, par = _term('loss_kps', loss_kps, KPS_LOSSES)
+    t.kps_loss = KPS_LOSSES[kind]
+    if kind == 'BalancedL1Loss':
+        t.kps_alpha, t.kps_gamma = float(par.get('alpha', 0.5)), float(par.get('gamma', 1.5))
+        if not t.kps_alpha > 0.0 or not t.kps_gamma > 0.0:
+            raise ValueError(f'loss_kps: BalancedL1Loss alpha={t.kps_alpha}, gamma={t.kps_gamma} must be > 0')
+    return t
+
+
 def make_loss_cfg(box_loss='EIoULoss', w_cls=1.0, w_box=5.0, w_obj=1.0, w_kps=0.1,
-                  box_eps=1e-6, smooth_point=0.1, kps_beta=1.0 / 9.0, box_mode=None):
+                  box_eps=1e-6, smooth_point=0.1, kps_beta=1.0 / 9.0, box_mode=None, terms=None):
+    """-> YunetLossCfg.  BoundedIoULoss: box_eps = its eps, smooth_point = its beta.  `terms` (a YunetLossTerms of
+    make_loss_terms) rides on the returned object as `.terms` for `loss()` / the engine; None = the default terms."""
     c = L.YunetLossCfg()
     c.box_loss = box_loss_code(box_loss, box_mode)
     c.w_cls, c.w_box, c.w_obj, c.w_kps = w_cls, w_box, w_obj, w_kps
     c.box_eps, c.smooth_point, c.kps_beta = box_eps, smooth_point, kps_beta
+    if c.box_loss == L.BOX_BOUNDED and not c.smooth_point > 0.0:
+        raise ValueError(f'loss_bbox: BoundedIoULoss beta={smooth_point} must be > 0')
+    if terms is not None and terms.kps_loss in (L.KPS_SMOOTH_L1, L.KPS_BALANCED_L1) and not c.kps_beta > 0.0:
+        raise ValueError(f'loss_kps: beta={kps_beta} must be > 0')
+    c.terms = terms
     return c
 
 
@@ -579,9 +636,10 @@ def loss(flat, gt_inds, ovl, gt_boxes, gt_kps, img_stats, sizes, strides, cfg, i
     part = torch.empty(blocks, 4, device=dev, dtype=torch.float32)
     dflat = torch.empty_like(flat)
     lv = make_levels(sizes, strides)
-    L.check(lib.yunet_loss(_p(flat), _p(gt_inds), _p(ovl), _p(gt_boxes), _p(gt_kps), C.byref(lv),
-                           C.byref(cfg), _p(norm), n, p, gmax, _p(dflat), _p(part), blocks,
-                           _stream()), 'yunet_loss')
+    terms = getattr(cfg, 'terms', None)               # None: the default terms, which yunet_loss_terms hands to yunet_loss
+    L.check(lib.yunet_loss_terms(_p(flat), _p(gt_inds), _p(ovl), _p(gt_boxes), _p(gt_kps), C.byref(lv),
+                                 C.byref(cfg), None if terms is None else C.byref(terms), _p(norm), n, p, gmax, _p(dflat),
+                                 _p(part), blocks, _stream()), 'yunet_loss_terms')
     losses = torch.empty(5, device=dev, dtype=torch.float32)      # cls, bbox, obj, kps, total
     L.check(lib.yunet_loss_finalize(_p(part), blocks, _p(losses), None, _stream()), 'yunet_loss_finalize')
     return losses[:4], dflat, norm

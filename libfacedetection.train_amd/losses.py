@@ -209,3 +209,132 @@ class SmoothL1Loss(_FusedLoss):
         d = (pred - target).abs()
         loss = torch.where(d < self.beta, 0.5 * d * d / self.beta, d - 0.5 * self.beta)
         return self.loss_weight * _reduce(loss, weight, reduction, avg_factor)
+
+
+# ---- the other losses the reference head accepts term by term (fused: csrc/loss_step.hip, loss_terms_kernel) -----------
+@LOSSES.register_module()
+class VarifocalLoss(_FusedLoss):
+    """varifocal_loss.py:11-134.  The target is an IoU-aware score: on loss_cls the positives' max_overlaps, on loss_obj
+    0 / 1, where it is a focal weighting alpha sigmoid(x)^gamma of the negatives."""
+
+    def __init__(self, use_sigmoid=True, alpha=0.75, gamma=2.0, iou_weighted=True, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        if use_sigmoid is not True:
+            raise NotImplementedError('Only sigmoid varifocal loss supported now.')
+        if not alpha >= 0.0:
+            raise ValueError(f'VarifocalLoss alpha={alpha} must be >= 0')
+        if not gamma >= 1.0:
+            raise ValueError(f'VarifocalLoss gamma={gamma} must be >= 1 (the derivative of |sigmoid(x) - t|^gamma is '
+                             'unbounded at sigmoid(x) = t below 1)')
+        self.use_sigmoid, self.alpha, self.gamma, self.iou_weighted = True, alpha, gamma, iou_weighted
+        self.reduction, self.loss_weight = reduction, loss_weight
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None, **kw):
+        reduction = _pick_reduction(self, reduction_override)
+        if pred.shape != target.shape:
+            raise ValueError('pred and target should be of the same size')
+        target = target.type_as(pred)
+        pos, neg = (target > 0.0).to(pred.dtype), (target <= 0.0).to(pred.dtype)
+        focal = (target * pos if self.iou_weighted else pos) + \
+            self.alpha * (pred.sigmoid() - target).abs().pow(self.gamma) * neg        # not detached, as in the reference
+        loss = F.binary_cross_entropy_with_logits(pred, target, reduction='none') * focal
+        return self.loss_weight * _reduce(loss, weight, reduction, avg_factor)
+
+
+class _Elementwise(_FusedLoss):
+    def elementwise(self, d):
+        raise NotImplementedError
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None, **kw):
+        reduction = _pick_reduction(self, reduction_override)
+        if self.empty_is_zero and target.numel() == 0:
+            return self.loss_weight * (pred.sum() * 0)
+        if pred.shape != target.shape:
+            raise ValueError('pred and target should be of the same size')
+        return self.loss_weight * _reduce(self.elementwise(pred - target), weight, reduction, avg_factor)
+
+
+@LOSSES.register_module()
+class L1Loss(_Elementwise):
+    """smooth_l1_loss.py:36-52, 107-146: |pred - target| (gradient 0 at 0)."""
+    empty_is_zero = True
+
+    def __init__(self, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        self.reduction, self.loss_weight = reduction, loss_weight
+
+    def elementwise(self, d):
+        return d.abs()
+
+
+@LOSSES.register_module()
+class MSELoss(_Elementwise):
+    """mse_loss.py:9-57: (pred - target)^2."""
+    empty_is_zero = False
+
+    def __init__(self, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        self.reduction, self.loss_weight = reduction, loss_weight
+
+    def elementwise(self, d):
+        return d * d
+
+
+@LOSSES.register_module()
+class BalancedL1Loss(_Elementwise):
+    """balanced_l1_loss.py:13-124 (Libra R-CNN): with b = e^(gamma / alpha) - 1,
+    |d| < beta ? alpha / b (b |d| + 1) log(b |d| / beta + 1) - alpha |d| : gamma |d| + gamma / b - alpha beta."""
+    empty_is_zero = True
+
+    def __init__(self, alpha=0.5, gamma=1.5, beta=1.0, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        if not beta > 0:
+            raise ValueError(f'BalancedL1Loss beta={beta} must be > 0')
+        self.alpha, self.gamma, self.beta = alpha, gamma, beta
+        self.reduction, self.loss_weight = reduction, loss_weight
+
+    def elementwise(self, d):
+        import math
+        diff = d.abs()
+        alpha, gamma, beta = self.alpha, self.gamma, self.beta
+        b = math.e ** (gamma / alpha) - 1
+        return torch.where(diff < beta, alpha / b * (b * diff + 1) * torch.log(b * diff / beta + 1) - alpha * diff,
+                           gamma * diff + gamma / b - alpha * beta)
+
+
+@LOSSES.register_module()
+class BoundedIoULoss(_IoUFamily):
+    """iou_loss.py:55-97, 376-409: the smooth-L1 (beta) of four bounded terms -- centre offsets against the target's size,
+    clamped at 0, and the smaller of the two width / height ratios.  Element-wise it is [n, 4]."""
+
+    def __init__(self, beta=0.2, eps=1e-3, reduction='mean', loss_weight=1.0):
+        super().__init__(eps, reduction, loss_weight)
+        self.beta = beta
+
+    @property
+    def smooth_point(self):        # where the fused step's configuration keeps the smooth-L1 threshold of a box loss
+        return self.beta
+
+    def elementwise(self, pred, target):
+        eps, beta = self.eps, self.beta
+        pcx, pcy = (pred[:, 0] + pred[:, 2]) * 0.5, (pred[:, 1] + pred[:, 3]) * 0.5
+        pw, ph = pred[:, 2] - pred[:, 0], pred[:, 3] - pred[:, 1]
+        with torch.no_grad():
+            tcx, tcy = (target[:, 0] + target[:, 2]) * 0.5, (target[:, 1] + target[:, 3]) * 0.5
+            tw, th = target[:, 2] - target[:, 0], target[:, 3] - target[:, 1]
+        dx, dy = tcx - pcx, tcy - pcy
+        ldx = 1 - torch.max((tw - 2 * dx.abs()) / (tw + 2 * dx.abs() + eps), torch.zeros_like(dx))
+        ldy = 1 - torch.max((th - 2 * dy.abs()) / (th + 2 * dy.abs() + eps), torch.zeros_like(dy))
+        ldw = 1 - torch.min(tw / (pw + eps), pw / (tw + eps))
+        ldh = 1 - torch.min(th / (ph + eps), ph / (th + eps))
+        comb = torch.stack([ldx, ldy, ldw, ldh], dim=-1).flatten(1)
+        return torch.where(comb < beta, 0.5 * comb * comb / beta, comb - 0.5 * beta)
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None, **kw):
+        """iou_loss.py:386-409: the weight multiplies the [n, 4] terms as given ([n, 1] or [n, 4]; no per-box averaging
+        as in the IoU forms)."""
+        if weight is not None and not torch.any(weight > 0):
+            w = weight.unsqueeze(1) if pred.dim() == weight.dim() + 1 else weight
+            return (pred * w).sum()
+        reduction = _pick_reduction(self, reduction_override)
+        return self.loss_weight * _reduce(self.elementwise(pred, target), weight, reduction, avg_factor)

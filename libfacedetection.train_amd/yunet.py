@@ -256,7 +256,11 @@ class YuNet(nn.Module):
     # ------------------------------------------------------------------ engine binding
     def arch(self):
         bb, hd = self.backbone, self.bbox_head
+        # (raises on a reduction, loss type or parameter the fused loss step does not implement)
+        # loss_cls / loss_obj / loss_kps: dict(type=, **parameters), present only beside the default terms
+        terms = hd.loss_term_specs() if hd.loss_cfg().terms is not None else {}
         return dict(
+            **terms,
             stage_channels=bb.stage_channels, downsample_idx=bb.downsample_idx, out_idx=bb.out_idx,
             neck_channels=self.neck.in_channels, neck_out_idx=self.neck.out_idx,
             feat_channels=hd.feat_channels, shared_stacked_convs=hd.shared_stack_convs,
@@ -265,8 +269,7 @@ class YuNet(nn.Module):
             loss_bbox_eps=hd.loss_bbox.eps, loss_bbox_smooth_point=getattr(hd.loss_bbox, 'smooth_point', 0.1),
             loss_bbox_mode=getattr(hd.loss_bbox, 'mode', None),
             loss_cls_weight=hd.loss_cls.loss_weight, loss_obj_weight=hd.loss_obj.loss_weight,
-            loss_kps_weight=hd.loss_kps.loss_weight, kps_beta=hd.loss_kps.beta,
-            center_radius=hd.assigner.center_radius if hd.assigner is not None else 2.5,
+            loss_kps_weight=hd.loss_kps.loss_weight, kps_beta=getattr(hd.loss_kps, 'beta', 1.0),            center_radius=hd.assigner.center_radius if hd.assigner is not None else 2.5,
             candidate_topk=getattr(hd.assigner, 'candidate_topk', 10), iou_weight=getattr(hd.assigner, 'iou_weight', 3.0),
             cls_weight=getattr(hd.assigner, 'cls_weight', 1.0))
 

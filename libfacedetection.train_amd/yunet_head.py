@@ -175,10 +175,26 @@ class YuNet_Head(nn.Module):
                                           f"reduction={want!r} (normalised by num_pos / the keypoint "
                                           'weight sum inside the kernel)')
         box = type(self.loss_bbox).__name__
+        specs = self.loss_term_specs()
+        default = [s['type'] for s in specs.values()] == ['CrossEntropyLoss', 'CrossEntropyLoss', 'SmoothL1Loss']
         return K.make_loss_cfg(box, self.loss_cls.loss_weight, self.loss_bbox.loss_weight,
                                self.loss_obj.loss_weight, self.loss_kps.loss_weight,
                                self.loss_bbox.eps, getattr(self.loss_bbox, 'smooth_point', 0.1),
-                               self.loss_kps.beta, getattr(self.loss_bbox, 'mode', None))
+                               getattr(self.loss_kps, 'beta', 1.0), getattr(self.loss_bbox, 'mode', None),
+                               terms=None if default else K.make_loss_terms(**specs))
+
+    def loss_term_specs(self):
+        """{'loss_cls', 'loss_obj', 'loss_kps': dict(type=, **parameters)} of the terms' modules, as kernels.make_loss_terms
+        and the engine's `arch` take them."""
+        out = {}
+        for name in ('loss_cls', 'loss_obj', 'loss_kps'):
+            m = getattr(self, name)
+            spec = dict(type=type(m).__name__)
+            for k in ('use_sigmoid', 'alpha', 'gamma', 'iou_weighted'):
+                if hasattr(m, k):
+                    spec[k] = getattr(m, k)
+            out[name] = spec
+        return out
 
     def loss(self, cls_scores, bbox_preds, objectnesses, kps_preds, gt_bboxes, gt_labels,
              gt_kpss, img_metas, gt_bboxes_ignore=None):
