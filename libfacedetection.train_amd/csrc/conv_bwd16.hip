@@ -74,6 +74,7 @@ __global__ __launch_bounds__(b16s::NTHR, 1) void dp_bwd16s_kernel(const YunetDP 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, g = lane >> 4;          // layout P: pixel (of a tile) | channel quad;  layout C: channel | pixel segment
+    const int gq = 4 * g;                              // layout P: first channel of the quad
     const int H = d.H, W = d.W;
     const bool bn_in = d.in_transform == YUNET_T_BNRELU;
 
@@ -101,22 +102,30 @@ __global__ __launch_bounds__(b16s::NTHR, 1) void dp_bwd16s_kernel(const YunetDP 
         w1t[s] = d.w_pw[(4 * g + s) * C + l15];
     }
     __syncthreads();
+    auto ld4 = [&](const float* p, float (&o)[4]) {
+        const float4 v = *reinterpret_cast<const float4*>(p);
+        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+    };
     // layout C constants of this lane's channel (c = l15): the nine taps, the depthwise bias, the folded BN backward
     float wt[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) wt[k] = s_w2[k * C + l15];
     const float b2c = s_b2[l15];
     const float fA = s_fold[l15], fB = s_fold[C + l15], fDh = s_fold[2 * C + l15], fDl = s_fold[3 * C + l15];
+    // layout P constants of this lane's channel quad: the producer's BN and the pointwise bias.  Built with packed fp32
+    // arithmetic the kernel needed 250 registers, read these 24 values from LDS in every row step and re-derived its lane
+    // indices per phase from opaque copies to stay there; unpacked (csrc/Makefile: UNPACKED) it needs 195, so the tables and
+    // the addresses stay in registers (209): 0.420 -> 0.346 ms per 160 x 160 launch (profiles/unpacked_fp32.json; this
+    // source built WITH packing takes all 256 registers and keeps two thirds of that gain)
+    float im[4], isc[4], ibt[4], iiv[4], ilo[4], b1q[4];
+    ld4(s_in + gq, im); ld4(s_in + C + gq, isc); ld4(s_in + 2 * C + gq, ibt);
+    ld4(s_in + 3 * C + gq, iiv); ld4(s_in + 4 * C + gq, ilo); ld4(s_b1 + gq, b1q);
 
     const float relu_floor = bn_in ? 0.0f : -__builtin_inff();
     float* slot_a = sm + wid * WAVE_F;             // p row (P write, C read), then the a row of the dW1 GEMM
     float* slot_d = slot_a + SLOT;                 // dp row (C write; P read for da, k-major read for dW1)
     float* ring_x = slot_d + SLOT;                 // [XRING][2][lane][4]
     float* pf_dy = ring_x + XRING * 2 * 256;       // dy row, layout P -> C
-    auto ld4 = [&](const float* p, float (&o)[4]) {
-        const float4 v = *reinterpret_cast<const float4*>(p);
-        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-    };
 
     // persistent accumulators.  Layout C: depthwise weight gradient of channel l15 (9 taps), db1, db2 over the lane's
     // pixels; layout P: dW1[ci = 4 g + i][co = l15] (matrix result)
@@ -148,8 +157,8 @@ __global__ __launch_bounds__(b16s::NTHR, 1) void dp_bwd16s_kernel(const YunetDP 
             POOLDY ? pooledbytes : gbytes, 0x00020000);
         const auto r_id = __builtin_amdgcn_make_buffer_rsrc(d.pool_idx + (POOLDY ? (size_t)n * (pooledbytes / 4u) : (size_t)0), 0,
                                                             POOLDY ? pooledbytes / 4u : 0u, 0x00020000);
-        // layout P geometry, re-derived where it is used: pixel 16 t + l15 is image column xs + 16 t + l15
-        auto colP = [&](int t) { return xs + 16 * t + opaque(l15); };
+        // layout P geometry: pixel 16 t + l15 is image column xs + 16 t + l15
+        auto colP = [&](int t) { return xs + 16 * t + l15; };
         auto colvP = [&](int t) { return (unsigned)colP(t) < (unsigned)W; };
         auto ownP = [&](int t) {
             const int j = 16 * t + l15;
@@ -196,9 +205,6 @@ __global__ __launch_bounds__(b16s::NTHR, 1) void dp_bwd16s_kernel(const YunetDP 
             const bool xin = (unsigned)X < (unsigned)H;
             // ---- [P] x(X) -> ring; a = T(x); p(X) = W1 a + b1 -> slot A -----------------------------------------------
             {
-                const int gq = opaque(4 * g);      // (a fresh copy per phase: the table reads stay inside the loop, live only here)
-                float im[4], isc[4], ibt[4], b1q[4];
-                ld4(s_in + gq, im); ld4(s_in + C + gq, isc); ld4(s_in + 2 * C + gq, ibt); ld4(s_b1 + gq, b1q);
                 float* rx = ring_x + ring * 512;
                 const float4 xr[2] = {act_unpack(lx[0]), act_unpack(lx[1])};
                 issue_x(X + 1);            // (the row past the band's last one is fetched and never used)
@@ -223,14 +229,13 @@ __global__ __launch_bounds__(b16s::NTHR, 1) void dp_bwd16s_kernel(const YunetDP 
             // ---- [C] p(X) of channel l15, pixels 8 g .. 8 g + 7 (+ the two neighbours outside the segment) --------------
             float pLe, pRe;
             {
-                const int cq = opaque(l15), sq = opaque(g);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) { p0[k] = p1[k]; p1[k] = p2[k]; }
-                const float* pc = slot_a + (8 * sq) * PST + cq;
+                const float* pc = slot_a + (8 * g) * PST + l15;
 #pragma unroll
                 for (int k = 0; k < 8; ++k) p2[k] = pc[k * PST];
-                pLe = slot_a[(sq > 0 ? 8 * sq - 1 : 0) * PST + cq];
-                pRe = slot_a[(sq < 3 ? 8 * sq + 8 : PXW - 1) * PST + cq];
+                pLe = slot_a[(g > 0 ? 8 * g - 1 : 0) * PST + l15];
+                pRe = slot_a[(g < 3 ? 8 * g + 8 : PXW - 1) * PST + l15];
             }
             // z in accumulate form: p(X) is the bottom tap row of z(X - 1), the middle of z(X), the top of z(X + 1)
 #pragma unroll
@@ -254,7 +259,6 @@ __global__ __launch_bounds__(b16s::NTHR, 1) void dp_bwd16s_kernel(const YunetDP 
             const bool qin = (unsigned)q < (unsigned)H;
             float dz[8];
             {
-                const int cq = opaque(l15), sq = opaque(g), gq = opaque(4 * g);
                 // layout P -> C through the dy slot [px][PST].  Pooled dy (max_pool2d backward): the gradient reaches the
                 // window maximum only -- decided here, where a lane holds the four position bytes of its channel quad
 #pragma unroll
@@ -271,7 +275,7 @@ __global__ __launch_bounds__(b16s::NTHR, 1) void dp_bwd16s_kernel(const YunetDP 
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                const float* dyp = pf_dy + (8 * sq) * PST + cq;
+                const float* dyp = pf_dy + (8 * g) * PST + l15;
                 float dyv[8];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) dyv[k] = dyp[k * PST];
@@ -309,8 +313,7 @@ __global__ __launch_bounds__(b16s::NTHR, 1) void dp_bwd16s_kernel(const YunetDP 
             // ---- row r = X - 2: [C] dp -> slot D; [P] da = W1^T dp, ReLU mask + producer's BN-backward sums, dx; dW1 += a^T dp
             const int r = X - 2;
             {
-                const int cq = opaque(l15), sq = opaque(g);
-                float* dq = slot_d + (8 * sq) * PST + cq;
+                float* dq = slot_d + (8 * g) * PST + l15;
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     const float v = ((omask >> k) & 1u) ? dpdone[k] : 0.0f;
@@ -324,8 +327,7 @@ __global__ __launch_bounds__(b16s::NTHR, 1) void dp_bwd16s_kernel(const YunetDP 
             {
                 const float* rx = ring_x + ring * 512;                  // x(X - 2)
 #pragma unroll
-                for (int t = 0; t < 2; ++t) {          // one tile at a time (fenced: its temporaries die before the next)
-                    const int gq = opaque(4 * g);
+                for (int t = 0; t < 2; ++t) {
                     const int j = 16 * t + l15;
                     float xr[4], dp[4], xc[4], tt[4];
                     ld4(rx + t * 256 + lane * 4, xr);
@@ -333,30 +335,22 @@ __global__ __launch_bounds__(b16s::NTHR, 1) void dp_bwd16s_kernel(const YunetDP 
                     f32x4 da = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int s = 0; s < 4; ++s) da = mfma16(w1t[s], dp[s], da);
-                    {
-                        float im[4], isc[4], ibt[4];
-                        ld4(s_in + gq, im); ld4(s_in + C + gq, isc); ld4(s_in + 2 * C + gq, ibt);
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            xc[i] = xr[i] - im[i];
-                            tt[i] = fmaf(xc[i], isc[i], ibt[i]);
-                        }
+                    for (int i = 0; i < 4; ++i) {
+                        xc[i] = xr[i] - im[i];
+                        tt[i] = fmaf(xc[i], isc[i], ibt[i]);
                     }
                     // the a row of the dW1 GEMM replaces the p row in slot A (read in full at the top of the step)
                     *reinterpret_cast<float4*>(slot_a + j * PST + gq) =
                         make_float4(fmaxf(tt[0], relu_floor), fmaxf(tt[1], relu_floor), fmaxf(tt[2], relu_floor), fmaxf(tt[3], relu_floor));
                     float4 o;
                     float* op = &o.x;
-                    {
-                        float iiv[4], ilo[4];
-                        ld4(s_in + 3 * C + gq, iiv); ld4(s_in + 4 * C + gq, ilo);
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const float v = (!bn_in || tt[i] > 0.0f) ? da[i] : 0.0f;
-                            ts0[i] += v;
-                            ts1[i] = fmaf(v, (xc[i] - ilo[i]) * iiv[i], ts1[i]);      // v * xhat (the mean as hi + lo: bn_center)
-                            op[i] = v;
-                        }
+                    for (int i = 0; i < 4; ++i) {
+                        const float v = (!bn_in || tt[i] > 0.0f) ? da[i] : 0.0f;
+                        ts0[i] += v;
+                        ts1[i] = fmaf(v, (xc[i] - ilo[i]) * iiv[i], ts1[i]);      // v * xhat (the mean as hi + lo: bn_center)
+                        op[i] = v;
                     }
                     __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&o), r_dx,
                                                            ownP(t) ? (unsigned)((r * W + colP(t)) * C + gq) * 4u : gbytes, 0, DX_AUX);
@@ -372,7 +366,8 @@ __global__ __launch_bounds__(b16s::NTHR, 1) void dp_bwd16s_kernel(const YunetDP 
                     gw1 = mfma16(slot_a[at], slot_d[at], gw1);
                     gwb = mfma16(slot_a[at + 4 * PST], slot_d[at + 4 * PST], gwb);
                 }
-                gw1 += gwb;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) gw1[i] += gwb[i];          // (per element: a vector-typed add becomes two v_pk_add_f32)
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // slot A is free for the next p row
             __builtin_amdgcn_wave_barrier();

@@ -25,6 +25,8 @@ def assembly(path, tmp):
     flags = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-w']
     if os.path.basename(path) in ('loss_step.hip', 'augment.hip', 'detect.hip'):
         flags.append('-ffp-contract=off')
+    if os.path.basename(path) in ('conv_bwd16.hip',):          # csrc/Makefile: UNPACKED
+        flags.append('-fno-slp-vectorize')
     subprocess.run([HIPCC] + flags + ['-S', '--cuda-device-only', '-o', out, path], check=True, capture_output=True)
     return out
 
