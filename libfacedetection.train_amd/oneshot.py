@@ -6,9 +6,10 @@ the exposed gradient bucket (~50 KB) and the overlapped one (~250 KB).  xGMI is 
 stores its message straight into every peer's inbox and sums the world's slots in rank order -- one kernel per rank,
 identical bits on every rank, no ring.  `torch.distributed` is used only to exchange the 64-byte IPC handles.
 
-Opt-in (`YUNET_ONESHOT_AR=1`, `engine.enable_oneshot()`): it has been executed with two processes sharing ONE GPU
-(tests/test_oneshot_gpu.py) -- the only multi-process configuration this build environment has -- and `verify()`
-checks it against the process group's own all-gather before the engine relies on it.
+Opt-in (`YUNET_ONESHOT_AR=1`, `engine.enable_oneshot()`): it has been executed with two and with three processes
+sharing ONE GPU (tests/test_oneshot_gpu.py; tests/test_oneshot_pieces_gpu.py: every piece count, bit-exact against
+the rank-order sum) -- the only multi-process configuration this build environment has -- and `verify()` checks it
+against the process group's own all-gather before the engine relies on it.
 """
 import ctypes as C
 
