@@ -193,6 +193,17 @@ int yunet_dp_pool_fusion_ok(int N, int H, int W, int cin, int cout);
  * process runs with now: today the wave-streaming 16 -> 16 backward (option "bwd16s"; a big-tile map, out_has_bn, a plain
  * dx, no deterministic sums, no prof), which recomputes z from x.  1 for every other unit.  Host only. */
 int yunet_dp_bwd_reads_z(const YunetDP* d);
+/* The kernel instance yunet_dp_fwd (backward = 0) or yunet_dp_bwd (backward != 0) selects for this descriptor, under the
+ * options the process runs with now, as the kernel's own name with every template argument and no blanks -- e.g.
+ * dp_fwd_kernel<64,64,8,16,true,false,false>, dp_fwd16s_kernel<16,true,false>, dp_bwd64_kernel<4,false,true,false> -- the
+ * name a profiler shows, the last argument (the deterministic form) included.  The storage build is the one d->x_dtype
+ * names.  0 and the NUL-terminated name in name[0 .. cap); YUNET_EINVAL, nothing written, for a descriptor the entry would
+ * refuse before it launches (a refusal that needs the grid or the device is the launch's own), a NULL d or name, or a cap
+ * the name does not fit.  Host only: no device is touched. */
+int yunet_dp_route(const YunetDP* d, int backward, char* name, int cap);
+/* 1 if yunet_dp_fwd_group (the build units[0]->x_dtype names) launches these n units as one grid under the options the
+ * process runs with now, 0 if it launches them one by one or refuses the call.  Host only. */
+int yunet_dp_fwd_group_one_grid(const YunetDP* const* units, int n);
 int yunet_stem_bwd_blocks(int N, int H, int W);
 
 /* F.max_pool2d(relu(bn(z)), 2)  (yunet_backbone.py:39-40).  out [N,H/2,W/2,C]. */

@@ -165,6 +165,8 @@ _SIGNATURES = {
                        [C.c_void_p]),
     'yunet_dp_pool_fusion_ok': (C.c_int, [C.c_int] * 5),
     'yunet_dp_bwd_reads_z': (C.c_int, [C.POINTER(YunetDP)]),
+    'yunet_dp_fwd_group_one_grid': (C.c_int, [C.POINTER(C.POINTER(YunetDP)), C.c_int]),
+    'yunet_dp_route': (C.c_int, [C.POINTER(YunetDP), C.c_int, C.c_char_p, C.c_int]),
     'yunet_pool_bwd': (C.c_int, [C.c_void_p, C.POINTER(YunetBN), C.c_void_p, C.c_void_p] +
                        [C.c_int] * 5 + [C.c_void_p]),
     'yunet_pool_bwd_add': (C.c_int, [C.c_void_p, C.POINTER(YunetBN), C.c_void_p, C.c_void_p, C.c_void_p] +

@@ -11,23 +11,6 @@
 static inline bool dp_bwd_big_tile(int H, int W, int cin, int cout) {
     return cin == 16 && cout == 16 && W >= 64 && H >= 32;
 }
-// The units whose backward runs on the wave-streaming dp_bwd16s (conv_bwd16.hip): the 16 -> 16 unit on a big-tile map, followed
-// by BatchNorm, with a plain (non-accumulating) dx, outside deterministic mode -- or at its fast level (YUNET_DET_FAST, fp32
-// storage), where the kernel runs in its DET form -- and the phase-clock debug mode, option bwd16s on.  That kernel
-// recomputes z from x and never reads YunetDP.z.  The one rule behind yunet_dp_bwd's dispatch (conv_bwd.hip) and the
-// yunet_dp_bwd_reads_z query (conv_bwd_host.hip).
-static inline bool dp_bwd_det(const YunetDP* d) {
-    return d->in_transform == YUNET_T_BNRELU && d->dx && d->in_bn.bstats && YUNET_DET_ROWS(d->in_bn.det_rows);
-}
-// ... and at the fast level: the default mode's dispatch, DET instances (fp32 storage only: the bf16 build refuses det_rows)
-static inline bool dp_bwd_det_fast(const YunetDP* d) {
-    return dp_bwd_det(d) && bn_det_fast(d->in_bn) && d->x_dtype == YUNET_F32;
-}
-static inline bool dp_bwd_streams16(const YunetDP* d) {
-    return (!dp_bwd_det(d) || dp_bwd_det_fast(d)) && d->cin == 16 && d->cout == 16 && dp_bwd_big_tile(d->H, d->W, 16, 16) &&
-           d->out_has_bn && d->dx && !d->accumulate_dx && !d->prof && yunet_options().bwd16s &&
-           (!d->pool_idx || (yunet_dp_pool_fusion_ok(d->N, d->H, d->W, 16, 16) && !(reinterpret_cast<uintptr_t>(d->pool_idx) & 3)));
-}
 // Waves per workgroup of dp_bwd64 (the 64 -> 64 units): 8 = one 512-thread workgroup per CU on 8 x 16 tiles,
 // 4 = two independent 256-thread workgroups per CU on 8 x 8 tiles.  Measured (tools/ubench/bwd_ab, N = 256):
 // 80 x 80 0.415 vs 0.429 ms, 40 x 40 0.139 vs 0.126 ms (a 40-wide map fills 8 x 8 tiles exactly, 17 % of every

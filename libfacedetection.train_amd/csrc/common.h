@@ -402,14 +402,15 @@ static inline bool bn_det_fast(const YunetBN& bn) { return YUNET_DET_ROWS(bn.det
 static inline int hip_status() { return -(int)hipGetLastError(); }
 
 // conv_fwd64.hip: the plain fp32 64 -> 64 forward unit (no packing, no fused pooling)
-int ACT_SUFFIX(launch_dp_fwd64s)(const YunetDP* d, hipStream_t stream);
+struct DpRoute;      // dp_route.h: the launchers below pick POOL / DET / nw from it
+int ACT_SUFFIX(launch_dp_fwd64s)(const YunetDP* d, const DpRoute& r, hipStream_t stream);
 int ACT_SUFFIX(launch_dp_fwd64s_group)(const YunetDP* const* ds, int n, hipStream_t stream);     // independent plain units, one grid
 // conv_bwd16.hip: backward of the fp32 16 -> 16 unit (plain or pooled dy), z recomputed from x
-int ACT_SUFFIX(launch_dp_bwd16s)(const YunetDP* d, hipStream_t stream);
+int ACT_SUFFIX(launch_dp_bwd16s)(const YunetDP* d, const DpRoute& r, hipStream_t stream);
 // conv_bwd64.hip: backward of the 64 -> 64 unit on nw = 4 | 8 waves per workgroup (plain, packed canvas or pooled dy)
-int ACT_SUFFIX(launch_dp_bwd64)(const YunetDP* d, int nw, hipStream_t stream);
+int ACT_SUFFIX(launch_dp_bwd64)(const YunetDP* d, const DpRoute& r, hipStream_t stream);
 // conv_fwd16.hip: forward of the fp32 16 -> 16 (plain | fused pooling) and 16 -> 64 units
-int ACT_SUFFIX(launch_dp_fwd16s)(const YunetDP* d, hipStream_t stream);
+int ACT_SUFFIX(launch_dp_fwd16s)(const YunetDP* d, const DpRoute& r, hipStream_t stream);
 // conv_stem.hip: the fp32 stem on the matrix cores (forward; weight gradient with z recomputed from the image)
 int ACT_SUFFIX(launch_stem_fwd_mma)(const float* img, const float* w, const float* b, float* z, double* stats, int N, int H, int W,
                                     hipStream_t stream);

@@ -14,7 +14,7 @@
 // dW1 += a^T * dp (MFMA, K = pixels, accumulators persistent across tiles);
 // da = dp * W1 (MFMA); dx = da * relu-mask, BN-backward sums of the producer.
 #include "common.h"
-#include "bwd_grid.h"
+#include "dp_route.h"
 #include "dp_bwd_parts.h"
 
 #include <type_traits>
@@ -909,108 +909,30 @@ int launch_dp_bwd(const YunetDP* d, hipStream_t stream) {
 
 }  // namespace
 
-namespace {
-// The dispatch of the default mode.  DET = true (the fast deterministic level, YUNET_DET_FAST in the producer's det_rows; fp32
-// storage): the same predicates, tiles and grids, every tile kernel in its DET instance; launch_dp_bwd16s and launch_dp_bwd64
-// pick theirs from the descriptor.
-template <bool DET>
-int dp_bwd_dispatch(const YunetDP* d, hipStream_t s) {
-    // the 16 -> 16 unit on the 160 x 160 / 80 x 80 levels: wave-streaming kernel that recomputes z from x instead of
-    // reading it (conv_bwd16.hip); same grid and partial rows as the tile kernel it replaces
-    if (dp_bwd_streams16(d)) return ACT_SUFFIX(launch_dp_bwd16s)(d, s);
-    if (d->pool_idx) {
-        // dy is the pooled gradient + argmax bytes (max_pool2d backward while staging)
-        if (!yunet_dp_pool_fusion_ok(d->N, d->H, d->W, d->cin, d->cout) || !d->out_has_bn) return YUNET_EINVAL;
-        const bool full816 = d->H % 8 == 0 && d->W % 16 == 0, full1632 = d->H % 16 == 0 && d->W % 32 == 0;
-        if (d->cin == 16) return full1632 ? launch_dp_bwd<16, 16, 16, 32, false, 0, true, true, DET>(d, s)
-                                          : launch_dp_bwd<16, 16, 16, 32, false, 0, true, false, DET>(d, s);
-        // 32 -> 64 (YuNet_s, in front of its 80 x 80 -> 40 x 40 pool): on the exact-fp32 matrix instruction this unit is
-        // MATRIX-bound (12.3 kFLOP per pixel at 157 TFLOP/s: 0.87 ms per 512-image launch = 0.16 of the HBM peak, the
-        // slowest kernel of the YuNet_s step); round 5 puts it on the split-bf16 path of the 64 -> 64 units (GEMM = 1)
-        if (d->cin == 32 && yunet_options().bwd_fp32mma == 0 && yunet_options().bwd32_split)
-            return full816 ? launch_dp_bwd<32, 64, 8, 16, false, 1, true, true, DET>(d, s)
-                           : launch_dp_bwd<32, 64, 8, 16, false, 1, true, false, DET>(d, s);
-        if (d->cin == 32) return full816 ? launch_dp_bwd<32, 64, 8, 16, false, 0, true, true, DET>(d, s)
-                                         : launch_dp_bwd<32, 64, 8, 16, false, 0, true, false, DET>(d, s);
-        // (option bwd_fp32mma: the exact-fp32 matrix instruction for this instance too -- before round 5 the pooled-dy
-        // 64 -> 64 unit stayed on the split-bf16 kernel even with the option set)
-        if (yunet_options().bwd_fp32mma != 0) return launch_dp_bwd<64, 64, 8, 16, false, 0, true, false, DET>(d, s);
-        return ACT_SUFFIX(launch_dp_bwd64)(d, bwd64_nw(d->N, d->H, d->W), s);
-    }
-#define DP_CASE(ci, co) \
-    if (d->cin == ci && d->cout == co) return launch_dp_bwd<ci, co, 8, 16, false, 0, false, false, DET>(d, s);
-    if (dp_bwd_big_tile(d->H, d->W, d->cin, d->cout))    // 160x160 / 80x80 levels: bigger tile
-        return (d->H % 16 == 0 && d->W % 32 == 0) ? launch_dp_bwd<16, 16, 16, 32, false, 0, false, true, DET>(d, s)
-                                                  : launch_dp_bwd<16, 16, 16, 32, false, 0, false, false, DET>(d, s);
-    // 64 -> 64 units: split-bf16 GEMMs (gradients only); the option bwd_fp32mma keeps the exact-fp32
-    // matrix instruction (bench.py's exact_fp32_bwd line, tools/kbench.py)
-    const bool f32mma = yunet_options().bwd_fp32mma != 0;
-    if (dp_use_pack_bwd(d->N, d->H, d->W, d->cin, d->cout)) {           // 20x20 / 10x10 levels: packed canvas
-        if (d->cout == 64) {
-            if (f32mma) return launch_dp_bwd<64, 64, 8, 16, true, 0, false, false, DET>(d, s);
-            return ACT_SUFFIX(launch_dp_bwd64)(d, bwd64_nw(d->N, d->H, d->W), s);
-        }
-        return launch_dp_bwd<64, 16, 8, 16, true, 0, false, false, DET>(d, s);
-    }
-    if (d->cin == 64 && d->cout == 64 && !f32mma)
-        return ACT_SUFFIX(launch_dp_bwd64)(d, bwd64_nw(d->N, d->H, d->W), s);
-    if (d->cin == 32 && d->cout == 64 && !f32mma && yunet_options().bwd32_split)      // (plain 32 -> 64: split-bf16 as above)
-        return (d->H % 8 == 0 && d->W % 16 == 0) ? launch_dp_bwd<32, 64, 8, 16, false, 1, false, true, DET>(d, s)
-                                                 : launch_dp_bwd<32, 64, 8, 16, false, 1, false, false, DET>(d, s);
-    if (d->H % 8 == 0 && d->W % 16 == 0) {       // whole-tile maps of the 16-channel stages (80 x 80 in the shipped nets)
-        if (d->cin == 16 && d->cout == 64) return launch_dp_bwd<16, 64, 8, 16, false, 0, false, true, DET>(d, s);
-        if (d->cin == 16 && d->cout == 32) return launch_dp_bwd<16, 32, 8, 16, false, 0, false, true, DET>(d, s);
-        if (d->cin == 32 && d->cout == 32) return launch_dp_bwd<32, 32, 8, 16, false, 0, false, true, DET>(d, s);
-    }
-    DP_CASE(16, 16)
-    DP_CASE(16, 32)
-    DP_CASE(16, 64)
-    DP_CASE(32, 32)
-    DP_CASE(32, 64)
-    DP_CASE(64, 64)
-    DP_CASE(64, 16)
-#undef DP_CASE
-    return YUNET_EINVAL;
-}
-}  // namespace
-
+// map a route (dp_route.h) to its instance; the DET forms exist with fp32 storage only
+#ifndef YUNET_ACT_BF16
+#define DP_BWD_LAUNCH(ci, co, th_, tw_, pk, g, pl, fl) \
+    (r.det ? launch_dp_bwd<ci, co, th_, tw_, pk, g, pl, fl, true>(d, s) : launch_dp_bwd<ci, co, th_, tw_, pk, g, pl, fl>(d, s))
+#else
+#define DP_BWD_LAUNCH(ci, co, th_, tw_, pk, g, pl, fl) launch_dp_bwd<ci, co, th_, tw_, pk, g, pl, fl>(d, s)
+#endif
+#define DP_FULL_0(...)
+#define DP_FULL_1(...) if (r.full) return DP_BWD_LAUNCH(__VA_ARGS__, true);
 extern "C" int ACT_SUFFIX(yunet_dp_bwd)(const YunetDP* d, void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    if (d->x_dtype != YUNET_ACT_DTYPE) return YUNET_EINVAL;
-    if (!d->wgrad_partials ||
-        d->wgrad_blocks != yunet_dp_bwd_blocks(d->N, d->H, d->W, d->cin, d->cout))
-        return YUNET_EINVAL;   // the partial buffer must have exactly the rows the grid writes
-    if (d->in_transform != YUNET_T_IDENTITY && d->in_transform != YUNET_T_BNRELU) return YUNET_EINVAL;
-    if (!d->z && !dp_bwd_streams16(d)) return YUNET_EINVAL;      // a null z: only where the kernel recomputes it (bwd_grid.h)
-#ifndef YUNET_ACT_BF16
-    if (dp_bwd_det_fast(d)) return dp_bwd_dispatch<true>(d, s);
-#endif
-    if (dp_bwd_det(d)) {
-        // deterministic BatchNorm sums (include/yunet_hip.h): the tile kernel in its DET form, exact-fp32 GEMMs, for every
-        // unit -- the same tiles, packed canvas and pooled dy as below; not dp_bwd64, dp_bwd16s or the split-bf16 GEMMs
-#ifndef YUNET_ACT_BF16
-        if (d->pool_idx) {
-            if (!yunet_dp_pool_fusion_ok(d->N, d->H, d->W, d->cin, d->cout) || !d->out_has_bn) return YUNET_EINVAL;
-            if (d->cin == 16) return launch_dp_bwd<16, 16, 16, 32, false, 0, true, false, true>(d, s);
-            if (d->cin == 32) return launch_dp_bwd<32, 64, 8, 16, false, 0, true, false, true>(d, s);
-            return launch_dp_bwd<64, 64, 8, 16, false, 0, true, false, true>(d, s);
-        }
-        if (dp_bwd_big_tile(d->H, d->W, d->cin, d->cout)) return launch_dp_bwd<16, 16, 16, 32, false, 0, false, false, true>(d, s);
-        if (dp_use_pack_bwd(d->N, d->H, d->W, d->cin, d->cout))
-            return d->cout == 64 ? launch_dp_bwd<64, 64, 8, 16, true, 0, false, false, true>(d, s)
-                                 : launch_dp_bwd<64, 16, 8, 16, true, 0, false, false, true>(d, s);
-#define DP_CASE(ci, co) \
-    if (d->cin == ci && d->cout == co) return launch_dp_bwd<ci, co, 8, 16, false, 0, false, false, true>(d, s);
-        DP_CASE(16, 16)
-        DP_CASE(16, 32)
-        DP_CASE(16, 64)
-        DP_CASE(32, 32)
-        DP_CASE(32, 64)
-        DP_CASE(64, 64)
-        DP_CASE(64, 16)
-#undef DP_CASE
-#endif
-        return YUNET_EINVAL;
+    DpRoute r;
+    if (const int rc = dp_bwd_route(d, YUNET_ACT_DTYPE, &r)) return rc;
+    if (r.family == DP_BWD16S) return ACT_SUFFIX(launch_dp_bwd16s)(d, r, s);
+    if (r.family == DP_BWD64) return ACT_SUFFIX(launch_dp_bwd64)(d, r, s);
+#define X(ci, co, th_, tw_, pk, g, pl, ft)                   \
+    if (DP_BWD_IS(r, ci, co, th_, pk, g, pl)) {              \
+        DP_FULL_##ft(ci, co, th_, tw_, pk, g, pl)            \
+        return DP_BWD_LAUNCH(ci, co, th_, tw_, pk, g, pl, false); \
     }
-    return dp_bwd_dispatch<false>(d, s);
+    DP_BWD_TILE_INSTANCES(X)
+#undef X
+    return YUNET_EINVAL;
 }
+#undef DP_FULL_0
+#undef DP_FULL_1
+#undef DP_BWD_LAUNCH

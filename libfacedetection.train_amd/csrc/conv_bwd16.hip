@@ -28,7 +28,7 @@
 // byte per element when the unit feeds max_pool2d: YunetDP.pool_idx) and dx -- z is not read.
 #include "common.h"
 #include "dp_bwd_parts.h"
-#include "bwd_grid.h"
+#include "dp_route.h"
 
 namespace {
 namespace b16s {
@@ -486,14 +486,12 @@ int launch_bwd16s(const YunetDP* d, hipStream_t stream) {
 // (non-accumulating) dx.  d->z is NOT read: it must be this unit's forward output for d->x and the weights.  Compiled once
 // per activation storage type: with bf16 storage x is read as bf16 and z is recomputed from it in fp32 -- the UNROUNDED z
 // the BatchNorm sums were taken from (the tile kernel reads the rounded one).
-int ACT_SUFFIX(launch_dp_bwd16s)(const YunetDP* d, hipStream_t stream) {
-    if (d->x_dtype != YUNET_ACT_DTYPE) return YUNET_EINVAL;
+int ACT_SUFFIX(launch_dp_bwd16s)(const YunetDP* d, const DpRoute& r, hipStream_t stream) {
+    if (r.det) {      // the producer's BN-backward sums into order-fixed rows (dp_route.h: dp_bwd_det): the DET instances, fp32 storage
 #ifndef YUNET_ACT_BF16
-    // the producer's BN-backward sums into order-fixed rows (bwd_grid.h: dp_bwd_det): the DET instances, fast level only
-    if (dp_bwd_det(d)) {
-        if (!dp_bwd_det_fast(d)) return YUNET_EINVAL;
-        return d->pool_idx ? launch_bwd16s<true, true>(d, stream) : launch_bwd16s<false, true>(d, stream);
-    }
+        return r.pool ? launch_bwd16s<true, true>(d, stream) : launch_bwd16s<false, true>(d, stream);
 #endif
-    return d->pool_idx ? launch_bwd16s<true>(d, stream) : launch_bwd16s<false>(d, stream);
+        return YUNET_EINVAL;
+    }
+    return r.pool ? launch_bwd16s<true>(d, stream) : launch_bwd16s<false>(d, stream);
 }

@@ -2,7 +2,7 @@
 // launch_dp_bwd64 (common.h).
 #include "common.h"
 #include "dp_bwd_parts.h"
-#include "bwd_grid.h"
+#include "dp_route.h"
 
 #include <type_traits>
 
@@ -858,21 +858,20 @@ int launch_dp_bwd64(const YunetDP* d, hipStream_t stream) {
 }
 // the six instances the dispatcher reaches, in the form DET
 template <bool DET>
-int launch_dp_bwd64_form(const YunetDP* d, int nw, hipStream_t stream) {
-    if (d->pool_idx) return nw == 4 ? launch_dp_bwd64<4, false, true, DET>(d, stream) : launch_dp_bwd64<8, false, true, DET>(d, stream);
-    if (dp_use_pack_bwd(d->N, d->H, d->W, d->cin, d->cout))
-        return nw == 4 ? launch_dp_bwd64<4, true, false, DET>(d, stream) : launch_dp_bwd64<8, true, false, DET>(d, stream);
-    return nw == 4 ? launch_dp_bwd64<4, false, false, DET>(d, stream) : launch_dp_bwd64<8, false, false, DET>(d, stream);
+int launch_dp_bwd64_form(const YunetDP* d, const DpRoute& r, hipStream_t stream) {
+    if (r.pool) return r.nw == 4 ? launch_dp_bwd64<4, false, true, DET>(d, stream) : launch_dp_bwd64<8, false, true, DET>(d, stream);
+    if (r.packed) return r.nw == 4 ? launch_dp_bwd64<4, true, false, DET>(d, stream) : launch_dp_bwd64<8, true, false, DET>(d, stream);
+    return r.nw == 4 ? launch_dp_bwd64<4, false, false, DET>(d, stream) : launch_dp_bwd64<8, false, false, DET>(d, stream);
 }
 
 }  // namespace
 
-// conv_bwd.hip's dispatcher: nw = bwd64_nw(N, H, W) (bwd_grid.h: the choice also fixes the rows of wgrad_partials);
+// conv_bwd.hip's dispatcher: r.nw = bwd64_nw(N, H, W) (bwd_grid.h: the choice also fixes the rows of wgrad_partials);
 // pooled dy (YunetDP.pool_idx: unpacked levels only, yunet_dp_pool_fusion_ok), else the packed canvas on the small levels
-int ACT_SUFFIX(launch_dp_bwd64)(const YunetDP* d, int nw, hipStream_t stream) {
+int ACT_SUFFIX(launch_dp_bwd64)(const YunetDP* d, const DpRoute& r, hipStream_t stream) {
 #ifndef YUNET_ACT_BF16
-    // a launch that produces the producer's BN-backward sums into order-fixed rows (bwd_grid.h: dp_bwd_det)
-    if (dp_bwd_det(d)) return bn_det_fast(d->in_bn) ? launch_dp_bwd64_form<true>(d, nw, stream) : YUNET_EINVAL;
+    // a launch that produces the producer's BN-backward sums into order-fixed rows (dp_route.h: dp_bwd_det)
+    if (r.det) return launch_dp_bwd64_form<true>(d, r, stream);
 #endif
-    return launch_dp_bwd64_form<false>(d, nw, stream);
+    return r.det ? YUNET_EINVAL : launch_dp_bwd64_form<false>(d, r, stream);
 }

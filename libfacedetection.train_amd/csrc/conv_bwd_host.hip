@@ -1,7 +1,10 @@
 // conv_bwd_host.hip -- the parts of the backward that do not depend on the activation storage type (compiled once):
 // the grid-size queries, the BatchNorm parameter gradient and the reduction of the per-workgroup partial rows.
+#include <cstdio>
+#include <cstring>
+
 #include "common.h"
-#include "bwd_grid.h"
+#include "dp_route.h"
 
 namespace {
 
@@ -144,6 +147,33 @@ extern "C" int yunet_dp_pool_fusion_ok(int N, int H, int W, int cin, int cout) {
 }
 extern "C" int yunet_dp_bwd_reads_z(const YunetDP* d) {
     return d && dp_bwd_streams16(d) ? 0 : 1;
+}
+extern "C" int yunet_dp_fwd_group_one_grid(const YunetDP* const* units, int n) {
+    if (!units || n < 1 || !units[0] || (units[0]->x_dtype != YUNET_F32 && units[0]->x_dtype != YUNET_BF16)) return 0;
+    return dp_fwd_one_grid(units, n, units[0]->x_dtype) ? 1 : 0;
+}
+// the route of a descriptor (dp_route.h) as the kernel's own name with every template argument
+extern "C" int yunet_dp_route(const YunetDP* d, int backward, char* name, int cap) {
+    DpRoute r;
+    if (!d || !name || (d->x_dtype != YUNET_F32 && d->x_dtype != YUNET_BF16)) return YUNET_EINVAL;      // (x_dtype names the build)
+    if (backward ? dp_bwd_route(d, d->x_dtype, &r) : dp_fwd_route(d, d->x_dtype, &r)) return YUNET_EINVAL;
+    const char *pk = r.packed ? "true" : "false", *pl = r.pool ? "true" : "false", *fl = r.full ? "true" : "false",
+               *dt = r.det ? "true" : "false";
+    char buf[96];
+    int len = -1;
+    switch (r.family) {
+    case DP_FWD16S: len = snprintf(buf, sizeof buf, "dp_fwd16s_kernel<%d,%s,%s>", r.cout, pl, dt); break;
+    case DP_FWD64S: len = snprintf(buf, sizeof buf, "dp_fwd64s_kernel<%s,%s>", pl, dt); break;
+    case DP_BWD16S: len = snprintf(buf, sizeof buf, "dp_bwd16s_kernel<%s,%s>", pl, dt); break;
+    case DP_BWD64: len = snprintf(buf, sizeof buf, "dp_bwd64_kernel<%d,%s,%s,%s>", r.nw, pk, pl, dt); break;
+    case DP_TILE:
+        len = backward ? snprintf(buf, sizeof buf, "dp_bwd_kernel<%d,%d,%d,%d,%s,%d,%s,%s,%s>", r.cin, r.cout, r.th, r.tw, pk, r.gemm, pl, fl, dt)
+                       : snprintf(buf, sizeof buf, "dp_fwd_kernel<%d,%d,%d,%d,%s,%s,%s>", r.cin, r.cout, r.th, r.tw, pk, pl, dt);
+        break;
+    }
+    if (len < 0 || len >= (int)sizeof buf || len >= cap) return YUNET_EINVAL;
+    memcpy(name, buf, (size_t)len + 1);
+    return 0;
 }
 extern "C" int yunet_stem_bwd_blocks(int N, int H, int W) {
     const long long tiles = (long long)N * ((W / 2 + SB_TW - 1) / SB_TW) * ((H / 2 + SB_TH - 1) / SB_TH);

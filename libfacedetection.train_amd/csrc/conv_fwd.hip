@@ -13,7 +13,7 @@
 
 #include <stdlib.h>
 
-#include "common.h"
+#include "dp_route.h"
 
 namespace {
 
@@ -730,7 +730,7 @@ __global__ void bn_running_kernel(const double* __restrict__ stats, float* __res
 #endif
 
 // persistent grid of the element-wise forward kernels: 8 workgroups of 256 per CU, grid-stride loops
-inline int ew_grid(long long total) {
+inline int ew_fwd_grid(long long total) {
     long long b = (total + 255) / 256;
     return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
 }
@@ -758,110 +758,33 @@ extern "C" int yunet_stem_fwd_det(const float* img, const float* w, const float*
 }
 #endif
 
+// map a route (dp_route.h) to its instance; the DET forms exist with fp32 storage only
+#ifndef YUNET_ACT_BF16
+#define DP_DET_1(...) launch_dp_fwd<__VA_ARGS__, true>(d, s)
+#else
+#define DP_DET_1(...) YUNET_EINVAL
+#endif
+#define DP_DET_0(...) YUNET_EINVAL
 extern "C" int ACT_SUFFIX(yunet_dp_fwd)(const YunetDP* d, void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    if (d->x_dtype != YUNET_ACT_DTYPE) return YUNET_EINVAL;
-    if (d->z_dtype != YUNET_ACT_DTYPE && !(d->cout == 16 && d->z_dtype == YUNET_F32)) return YUNET_EINVAL;
-    if (d->in_transform != YUNET_T_IDENTITY && d->in_transform != YUNET_T_BNRELU) return YUNET_EINVAL;
-    const bool det = d->out_has_bn && YUNET_DET_ROWS(d->out_bn.det_rows);
-    // the fast deterministic level (YUNET_DET_FAST, fp32 storage): the dispatch of the default mode; the launchers of the
-    // wave-streaming kernels pick their DET instances from the descriptor
-    const bool det_fast = det && bn_det_fast(d->out_bn) && YUNET_ACT_DTYPE == YUNET_F32;
-    // units with 16 input channels: wave-streaming kernels (conv_fwd16.hip)
-    const bool fwd16s = (!det || det_fast) && d->cin == 16 && (d->cout == 16 || (d->cout == 64 && !d->pool_out)) && d->z_dtype == YUNET_ACT_DTYPE &&
-                        !d->prof && yunet_options().fwd16s &&
-                        (!d->pool_out || (yunet_dp_pool_fusion_ok(d->N, d->H, d->W, 16, 16) && d->out_bn.gamma && d->pool_idx &&
-                                          !(reinterpret_cast<uintptr_t>(d->pool_idx) & 3)));
-    // a null z (include/yunet_hip.h): the pooled 16 -> 16 unit on that kernel alone; every other kernel stores through it
-    if (!d->z && !(fwd16s && d->pool_out)) return YUNET_EINVAL;
-    if (det) {
-        // deterministic BatchNorm sums (include/yunet_hip.h): the tile kernel in its DET form for every unit -- the same
-        // choice of tile, packed canvas and fused pooling as below, none of the wave-streaming kernels
-#ifndef YUNET_ACT_BF16
-        if (d->z_dtype != YUNET_ACT_DTYPE || !d->out_bn.stats) return YUNET_EINVAL;
-        if (det_fast) {
-            // the predicates of the default dispatch below, in its order; what they leave falls through to the tile kernels,
-            // whose DET instances are the ones of the plain deterministic level (same tiles, packed canvas and fused pooling)
-            if (fwd16s) return launch_dp_fwd16s(d, s);
-            const bool pool_ok = d->pool_out && yunet_dp_pool_fusion_ok(d->N, d->H, d->W, d->cin, d->cout) && d->out_bn.gamma &&
-                                 d->pool_idx && !(reinterpret_cast<uintptr_t>(d->pool_idx) & 3);
-            const bool packed_tile = dp_use_pack(d->N, d->H, d->W, d->cin, d->cout) && yunet_options().fwd64s < 2;
-            if (d->cin == 64 && d->cout == 64 && (unsigned long long)d->prof < 64ull && yunet_options().fwd64s &&
-                (d->pool_out ? pool_ok : !packed_tile))
-                return launch_dp_fwd64s(d, s);
-        }
-        if (d->pool_out) {
-            if (!yunet_dp_pool_fusion_ok(d->N, d->H, d->W, d->cin, d->cout) || !d->out_bn.gamma || !d->pool_idx ||
-                (reinterpret_cast<uintptr_t>(d->pool_idx) & 3))
-                return YUNET_EINVAL;
-            if (d->cin == 16) return launch_dp_fwd<16, 16, 16, 32, false, true, true>(d, s);
-            if (d->cin == 32) return launch_dp_fwd<32, 64, 8, 16, false, true, true>(d, s);
-            return launch_dp_fwd<64, 64, 8, 16, false, true, true>(d, s);
-        }
-        if (d->cin == 16 && d->cout == 16 && d->W >= 64 && d->H >= 32) return launch_dp_fwd<16, 16, 16, 32, false, false, true>(d, s);
-        if (dp_use_pack(d->N, d->H, d->W, d->cin, d->cout) && d->cout == 64) return launch_dp_fwd<64, 64, 8, 16, true, false, true>(d, s);
-#define DP_CASE(ci, co) \
-    if (d->cin == ci && d->cout == co) return launch_dp_fwd<ci, co, 8, 16, false, false, true>(d, s);
-        DP_CASE(16, 16)
-        DP_CASE(16, 32)
-        DP_CASE(16, 64)
-        DP_CASE(32, 32)
-        DP_CASE(32, 64)
-        DP_CASE(64, 64)
-#undef DP_CASE
-#endif
-        return YUNET_EINVAL;
-    }
-    if (fwd16s) return ACT_SUFFIX(launch_dp_fwd16s)(d, s);
-    if (d->pool_out) {
-        // also write the raw max_pool2d winners + their window positions (fused pooling)
-        if (!yunet_dp_pool_fusion_ok(d->N, d->H, d->W, d->cin, d->cout) || !d->out_bn.gamma || !d->pool_idx ||   // (out_has_bn may be 0: eval())
-            (reinterpret_cast<uintptr_t>(d->pool_idx) & 3))
-            return YUNET_EINVAL;
-        if (d->cin == 16) return launch_dp_fwd<16, 16, 16, 32, false, true>(d, s);
-        if (d->cin == 32) return launch_dp_fwd<32, 64, 8, 16, false, true>(d, s);
-        if ((unsigned long long)d->prof < 64ull && yunet_options().fwd64s && d->z_dtype == YUNET_ACT_DTYPE) return ACT_SUFFIX(launch_dp_fwd64s)(d, s);
-        return launch_dp_fwd<64, 64, 8, 16, false, true>(d, s);
-    }
-#define DP_CASE(ci, co) \
-    if (d->cin == ci && d->cout == co) return launch_dp_fwd<ci, co, 8, 16>(d, s);
-    if (d->cin == 16 && d->cout == 16 && d->W >= 64 && d->H >= 32)
-        return launch_dp_fwd<16, 16, 16, 32>(d, s);   // 160x160 / 80x80 levels: bigger tile
-    // 20x20 / 10x10 levels: packed canvas -- except the fp32 64 -> 64 units, which run on the wave-streaming kernel
-    // (one or two 14-column strips per image; option fwd64s = 1 puts them back here: 20 x 20 0.0324 -> 0.0266 ms,
-    // 10 x 10 0.0152 -> 0.0132 ms, profiles/r04_fwd_small.log)
-    if (dp_use_pack(d->N, d->H, d->W, d->cin, d->cout) && !(d->cout == 64 && d->z_dtype == YUNET_ACT_DTYPE && yunet_options().fwd64s >= 2))
-        return d->cout == 64 ? launch_dp_fwd<64, 64, 8, 16, true>(d, s) : launch_dp_fwd<64, 16, 8, 16, true>(d, s);
-    // the plain 64 -> 64 unit: wave-streaming kernel (conv_fwd64.hip); the phase-clock debug mode stays on the
-    // tile kernel
-    if (d->cin == 64 && d->cout == 64 && d->z_dtype == YUNET_ACT_DTYPE && (unsigned long long)d->prof < 64ull && yunet_options().fwd64s)
-        return ACT_SUFFIX(launch_dp_fwd64s)(d, s);
-    DP_CASE(16, 16)
-    DP_CASE(16, 32)
-    DP_CASE(16, 64)
-    DP_CASE(32, 32)
-    DP_CASE(32, 64)
-    DP_CASE(64, 64)
-    DP_CASE(64, 16)
-#undef DP_CASE
+    DpRoute r;
+    if (const int rc = dp_fwd_route(d, YUNET_ACT_DTYPE, &r)) return rc;
+    if (r.family == DP_FWD16S) return ACT_SUFFIX(launch_dp_fwd16s)(d, r, s);
+    if (r.family == DP_FWD64S) return ACT_SUFFIX(launch_dp_fwd64s)(d, r, s);
+#define X(ci, co, th_, tw_, pk, pl, dt) \
+    if (DP_FWD_IS(r, ci, co, th_, pk, pl)) return r.det ? DP_DET_##dt(ci, co, th_, tw_, pk, pl) : launch_dp_fwd<ci, co, th_, tw_, pk, pl>(d, s);
+    DP_FWD_TILE_INSTANCES(X)
+#undef X
     return YUNET_EINVAL;
 }
+#undef DP_DET_0
+#undef DP_DET_1
 
-// Independent units in one call (include/yunet_hip.h).  One launch when every unit is a plain 64 -> 64 unit that
-// yunet_dp_fwd would put on the wave-streaming kernel (conv_fwd64.hip) -- the same tests as above, in the same order --
-// else the units go out one after the other.
+// Independent units in one call (include/yunet_hip.h): one launch where dp_fwd_one_grid (dp_route.h) says so, else the units
+// go out one after the other.
 extern "C" int ACT_SUFFIX(yunet_dp_fwd_group)(const YunetDP* const* units, int n, void* stream) {
     if (!units || n < 1 || n > YUNET_DP_GROUP_MAX) return YUNET_EINVAL;
-    bool one_grid = n >= 2 && yunet_options().fwd_group != 0;
-    for (int i = 0; i < n && one_grid; ++i) {
-        const YunetDP* d = units[i];
-        one_grid = d && !(d->out_has_bn && YUNET_DET_ROWS(d->out_bn.det_rows)) &&
-                   d->x_dtype == YUNET_ACT_DTYPE && d->z_dtype == YUNET_ACT_DTYPE && d->cin == 64 && d->cout == 64 &&
-                   d->z && !d->pool_out && !d->prof && yunet_options().fwd64s != 0 &&
-                   (d->in_transform == YUNET_T_IDENTITY || d->in_transform == YUNET_T_BNRELU) &&
-                   !(dp_use_pack(d->N, d->H, d->W, d->cin, d->cout) && yunet_options().fwd64s < 2);
-    }
-    if (one_grid) return ACT_SUFFIX(launch_dp_fwd64s_group)(units, n, (hipStream_t)stream);
+    if (dp_fwd_one_grid(units, n, YUNET_ACT_DTYPE)) return ACT_SUFFIX(launch_dp_fwd64s_group)(units, n, (hipStream_t)stream);
     for (int i = 0; i < n; ++i) {
         if (!units[i]) return YUNET_EINVAL;
         const int rc = ACT_SUFFIX(yunet_dp_fwd)(units[i], stream);
@@ -874,7 +797,7 @@ extern "C" int ACT_SUFFIX(yunet_pool_fwd)(const float* z, const YunetBN* bn, flo
                                           int C, void* stream) {
     if ((H & 1) || (W & 1) || (C & 3) || (256 % (C / 4)) || C > 64) return YUNET_EINVAL;
     const long long total = (long long)N * (H / 2) * (W / 2) * (C / 4);
-    hipLaunchKernelGGL(pool_fwd_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(pool_fwd_kernel, dim3(ew_fwd_grid(total)), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const act_t*>(z), *bn, reinterpret_cast<act_t*>(out), N, H, W, C);
     return hip_status();
 }
@@ -884,7 +807,7 @@ extern "C" int ACT_SUFFIX(yunet_upadd_fwd)(const float* za, const YunetBN* bna, 
                                            void* stream) {
     if ((H & 1) || (W & 1) || (C & 3) || (256 % (C / 4)) || C > 64) return YUNET_EINVAL;
     const long long total = (long long)N * H * W * (C / 4);
-    hipLaunchKernelGGL(upadd_fwd_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(upadd_fwd_kernel, dim3(ew_fwd_grid(total)), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const act_t*>(za), *bna, reinterpret_cast<const act_t*>(zb), *bnb,
                        reinterpret_cast<act_t*>(out), N, H, W, C);
     return hip_status();

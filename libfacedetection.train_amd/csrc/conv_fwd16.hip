@@ -15,7 +15,7 @@
 // middle / top tap row of z(X - 1), z(X), z(X + 1) (accumulate form): z(X - 1) is complete -> BN sums, -> slot -> P ->
 // 16-byte stores.  POOL (16 -> 16 units that feed max_pool2d only, YunetDP.pool_out): the 2 x 2 winners after BN + ReLU
 // and their window positions (dp_fwd_kernel<..., POOL>'s rule), from column pairs a lane owns and the row pair a band holds.
-#include "common.h"
+#include "dp_route.h"
 
 namespace {
 namespace f16s {
@@ -342,15 +342,14 @@ int launch_fwd16s(const YunetDP* d, hipStream_t stream) {
 
 // conv_fwd.hip's dispatcher: units with 16 input channels and 16 or 64 output channels (fused pooling: 16 -> 16); compiled
 // once per activation storage type (fp32 | -DYUNET_ACT_BF16: x, z and the pooled winners as bf16, same arithmetic)
-int ACT_SUFFIX(launch_dp_fwd16s)(const YunetDP* d, hipStream_t stream) {
+int ACT_SUFFIX(launch_dp_fwd16s)(const YunetDP* d, const DpRoute& r, hipStream_t stream) {
+    if (r.det) {      // BatchNorm sums into order-fixed rows (YunetBN::det_rows): the DET instances, fp32 storage
 #ifndef YUNET_ACT_BF16
-    // BatchNorm sums into order-fixed rows (YunetBN::det_rows): the DET instances, fast level only
-    if (d->out_has_bn && YUNET_DET_ROWS(d->out_bn.det_rows)) {
-        if (!bn_det_fast(d->out_bn)) return YUNET_EINVAL;
-        if (d->cout == 16) return d->pool_out ? launch_fwd16s<16, true, true>(d, stream) : launch_fwd16s<16, false, true>(d, stream);
+        if (r.cout == 16) return r.pool ? launch_fwd16s<16, true, true>(d, stream) : launch_fwd16s<16, false, true>(d, stream);
         return launch_fwd16s<64, false, true>(d, stream);
-    }
 #endif
-    if (d->cout == 16) return d->pool_out ? launch_fwd16s<16, true>(d, stream) : launch_fwd16s<16, false>(d, stream);
+        return YUNET_EINVAL;
+    }
+    if (r.cout == 16) return r.pool ? launch_fwd16s<16, true>(d, stream) : launch_fwd16s<16, false>(d, stream);
     return launch_fwd16s<64, false>(d, stream);
 }

@@ -30,7 +30,7 @@
 // winners are stored as bf16 and the pointwise product is ONE bf16 matrix instruction per block on a = bf16(relu(bn(x)))
 // and bf16(W1) (fp32 accumulation) instead of the exact three-way split -- the arithmetic of the bf16 tile kernel
 // (conv_fwd.hip); depthwise, bias and BN sums (of the unrounded values) stay fp32.
-#include "common.h"
+#include "dp_route.h"
 
 namespace {
 namespace f64s {
@@ -524,14 +524,12 @@ int ACT_SUFFIX(launch_dp_fwd64s_group)(const YunetDP* const* ds, int n, hipStrea
     return hip_status();
 }
 
-int ACT_SUFFIX(launch_dp_fwd64s)(const YunetDP* d, hipStream_t stream) {
-    if (d->x_dtype != YUNET_ACT_DTYPE || d->z_dtype != YUNET_ACT_DTYPE || !d->z) return YUNET_EINVAL;
+int ACT_SUFFIX(launch_dp_fwd64s)(const YunetDP* d, const DpRoute& r, hipStream_t stream) {
+    if (r.det) {      // BatchNorm sums into order-fixed rows (YunetBN::det_rows): the DET instances, fp32 storage
 #ifndef YUNET_ACT_BF16
-    // BatchNorm sums into order-fixed rows (YunetBN::det_rows): the DET instances, fast level only
-    if (d->out_has_bn && YUNET_DET_ROWS(d->out_bn.det_rows)) {
-        if (!bn_det_fast(d->out_bn)) return YUNET_EINVAL;
-        return d->pool_out ? launch_fwd64s<true, true>(d, stream) : launch_fwd64s<false, true>(d, stream);
-    }
+        return r.pool ? launch_fwd64s<true, true>(d, stream) : launch_fwd64s<false, true>(d, stream);
 #endif
-    return d->pool_out ? launch_fwd64s<true>(d, stream) : launch_fwd64s<false>(d, stream);
+        return YUNET_EINVAL;
+    }
+    return r.pool ? launch_fwd64s<true>(d, stream) : launch_fwd64s<false>(d, stream);
 }

@@ -26,6 +26,7 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, n), f'{n} is declared in include/yunet_hip.h but not exported'
     assert sorted(L.EXPORTED) == names, 'ctypes signature table and header disagree'
     assert lib.yunet_abi_version() == 12
+    assert 'yunet_dp_route' in names and 'yunet_dp_fwd_group_one_grid' in names          # (additive: the ABI number stays)
     # ABI 12: one pixel-pass entry and one decide entry; the nine names they replace are in neither header nor library
     gone = [('pixels', s) for s in ('window', 'photo', 'window_photo', 'canvas', 'mosaic')] + [('decide', 'ms'),
                                                                                                  ('decide', 'padded')]

@@ -16,10 +16,10 @@ Strided buffers come from tests/dp_layout.py: N * stride elements, strides that 
 (x, z, dy, the other levels' rows of dflat) NaN, output gaps (z, dx, the other levels' rows of flat) a sentinel that must
 come back bit for bit.
 
-The id of a case names the instance dp_bwd_dispatch (csrc/conv_bwd.hip) sends it to; assert_route() proves the route
-from what the host can see: yunet_dp_bwd_reads_z, yunet_dp_pool_fusion_ok and yunet_dp_bwd_blocks against the tile count
-of the instance's tile.  The forward dispatch has no such queries: assert_fwd_route() holds the option values and the
-shape rules of yunet_dp_fwd that the forward ids assume."""
+The id of a case names the instance yunet_dp_bwd (csrc/dp_route.h: dp_bwd_route) sends it to; assert_route() proves the
+route from what the host can see: yunet_dp_bwd_reads_z, yunet_dp_pool_fusion_ok and yunet_dp_bwd_blocks against the tile
+count of the instance's tile, and yunet_dp_route, which names the instance.  assert_fwd_route() holds the option values and
+the shape rules of dp_fwd_route that the forward ids assume, and asks yunet_dp_route for the name as well."""
 import contextlib
 import ctypes as C
 import functools
@@ -31,6 +31,7 @@ import torch.nn.functional as F
 
 import bf16_ref as R
 import dp_layout as D
+from route_cases import route as dp_route
 from test_bf16_kernels_gpu import check_grads as bf16_check_grads
 from test_kernels_gpu import bn_ref, mk_unit, nchw, nhwc, rel_err, rel_err_ch, stats_of
 
@@ -377,9 +378,30 @@ def bwd_tiles(c):
     return n * ceil(w, tw) * ceil(h, th)
 
 
+def tf(v):
+    return 'true' if v else 'false'
+
+
+def bwd_instance(c, streams):
+    """the kernel instance the id of a backward case claims, spelled as the kernel's own name (non-deterministic form);
+    a whole-tile map runs the FULL instance where one exists (the exact-fp32 32 -> 64 unit without pooled dy has none)"""
+    cin, cout, pooled = c.cin, c.cout, c.idx is not None
+    packed = c.kind.endswith('packed')
+    if streams:
+        return f'dp_bwd16s_kernel<{tf(pooled)},false>'
+    if c.kind.startswith('bwd64'):
+        return f"dp_bwd64_kernel<{4 if c.kind == 'bwd64-4w' else 8},{tf(packed)},{tf(pooled)},false>"
+    th, tw = (16, 32) if c.kind in ('big16', 'bwd16s') else (8, 16)
+    opts = c.opts or {}
+    split = (cin, cout) == (32, 64) and opts.get('bwd32_split', 1) and not opts.get('bwd_fp32mma', 0)
+    full = c.h % th == 0 and c.w % tw == 0 and not packed and (
+        th == 16 or split or (pooled and cin == 32) or (not pooled and (cin, cout) in ((16, 32), (16, 64), (32, 32))))
+    return f'dp_bwd_kernel<{cin},{cout},{th},{tw},{tf(packed)},{int(bool(split))},{tf(pooled)},{tf(full)},false>'
+
+
 def assert_route(c):
     """what the host can see of the dispatch: the query that separates the wave-streaming kernel, the fusion query, the
-    packed-canvas rule, the whole-tile rule and the grid of the instance's tile"""
+    packed-canvas rule, the whole-tile rule and the grid of the instance's tile; yunet_dp_route names the instance"""
     k, L = K(), lib()
     n, h, w, cin, cout = c.n, c.h, c.w, c.cin, c.cout
     packed = h <= 20 and w <= 20 and n >= 4 and cin == 64
@@ -389,6 +411,8 @@ def assert_route(c):
             d, keep = descriptor(c, acc, need_dx)
             streams = c.kind in ('bwd16s', 'big16') and not acc and need_dx
             assert L.load().yunet_dp_bwd_reads_z(C.byref(d)) == (0 if streams else 1), (c.id, acc, need_dx)
+            d.wgrad_partials, d.wgrad_blocks = c.dy.data_ptr(), k.dp_grid(n, h, w, cin, cout)     # (any buffer: host only)
+            assert dp_route(L.load(), d, 1) == bwd_instance(c, streams), (c.id, acc, need_dx)
         if c.kind == 'big16':           # ... and with the option off the plain launch stays on the tile kernel
             with options({'bwd16s': 0}):
                 d, keep = descriptor(c)
@@ -538,10 +562,10 @@ def option(name):
 
 
 def assert_fwd_route(c):
-    """The forward dispatch has no host query; the ids rely on yunet_dp_fwd (csrc/conv_fwd.hip), non-deterministic BN sums,
-    no prof, in this order: `fwd16s` (option fwd16s != 0: every 16 -> 16 / 16 -> 64 unit, the pooled 16 -> 64 excepted),
-    the fused-pool branch (32 -> 64: the tile kernel), the packed-canvas line (dp_use_pack: N >= 4, H, W <= 20, cin = 64 --
-    except the 64 -> 64 unit with activation-typed z under fwd64s >= 2), the fwd64s line (64 -> 64, fwd64s != 0), DP_CASE.
+    """The ids rely on dp_fwd_route (csrc/dp_route.h), non-deterministic BN sums, no prof, in this order: `fwd16s` (option
+    fwd16s != 0: every 16 -> 16 / 16 -> 64 unit, the pooled 16 -> 64 excepted), the fused-pool branch (32 -> 64: the tile
+    kernel), the packed-canvas line (dp_use_pack: N >= 4, H, W <= 20, cin = 64 -- except the 64 -> 64 unit with
+    activation-typed z under fwd64s >= 2), the fwd64s line (64 -> 64, fwd64s != 0), the tile instances.
     Hold the option values and the shape rules the kinds assume, so that a changed default shows up here."""
     n, h, w, cin, cout = c.n, c.h, c.w, c.cin, c.cout
     with options(c.opts):
@@ -552,6 +576,18 @@ def assert_fwd_route(c):
                 'fwd packed' if use_pack and not (cout == 64 and fwd64s >= 2) else
                 'fwd64s' if cin == 64 and cout == 64 and fwd64s and not c.spec.get('pool') else 'fwd tile')
         assert c.kind == want, (c.id, c.kind, want, fwd16s, fwd64s)
+        # ... and yunet_dp_route names that instance (the descriptor of a dense launch; host only)
+        k, pool = K(), bool(c.spec.get('pool'))
+        in_bn = k.BN(c.sx, c.gi, c.bi, c.cnt) if c.in_on else None
+        out_bn = k.BN(torch.zeros(2 * cout, dtype=torch.float64, device=DEV), c.go, c.bo, c.cnt) if c.out_on else None
+        z = torch.empty(n, h, w, cout, device=DEV, dtype=c.x.dtype if c.out_on else F32)
+        d = k._dp_desc(c.x, *c.W, z, in_bn, out_bn)
+        if pool:
+            d.pool_out = d.pool_idx = z.data_ptr()
+        name = {'fwd16s': f'dp_fwd16s_kernel<{cout},{tf(pool)},false>', 'fwd64s': f'dp_fwd64s_kernel<{tf(pool)},false>',
+                'fwd packed': f'dp_fwd_kernel<{cin},{cout},8,16,true,false,false>',
+                'fwd tile': f'dp_fwd_kernel<{cin},{cout},8,16,false,{tf(pool)},false>'}[c.kind]
+        assert dp_route(lib().load(), d, 0) == name, (c.id, name)
 
 
 def run_fwd(c, xs=0, zs=0, level=None):
@@ -630,6 +666,25 @@ def test_head_fwd_writes_its_level_of_flat(cid, later):
     assert r['z'].dtype == F32
     assert_same_fwd(c, r)
     assert_same_fwd(c, run_fwd(c, level=lv, xs=gap(c, 'small')))
+
+
+def test_an_ablation_mask_leaves_the_group():
+    """needs no launch: a 64 -> 64 unit whose prof is an ablation mask (< 64) routes to dp_fwd64s on its own, as without
+    the mask; yunet_dp_fwd_group puts into one grid only units with that route AND a NULL prof, so a group with this unit
+    goes out one by one: yunet_dp_fwd_group_one_grid, the predicate the entry branches on, says so (tests/test_dp_route.py
+    holds it against the recorded entry over every triple)"""
+    k, c = K(), case('fwd64s', 'fwd')
+    st = torch.zeros(128, dtype=torch.float64, device=DEV)
+    d = k._dp_desc(c.x, *c.W, torch.empty(c.n, c.h, c.w, 64, device=DEV), k.BN(c.sx, c.gi, c.bi, c.cnt),
+                   k.BN(st, c.go, c.bo, c.cnt))
+    L = lib()
+    plain = dp_route(L.load(), d, 0)
+    q = L.load().yunet_dp_fwd_group_one_grid
+    pair = (C.POINTER(L.YunetDP) * 2)(C.pointer(d), C.pointer(d))
+    assert q(pair, 2) == 1
+    d.prof = 1
+    assert plain == dp_route(L.load(), d, 0) == 'dp_fwd64s_kernel<false,false>'
+    assert q(pair, 2) == 0
 
 
 def test_fwd_group_of_three_strided_units():
