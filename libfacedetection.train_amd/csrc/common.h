@@ -131,31 +131,56 @@ struct BNCoef {
 // The first eight replicas are loaded unconditionally (replicas past `slots` re-read replica 0 and count as
 // zero): eight independent loads in flight.  As a loop over `slots` the loads were issued one latency after the
 // other at the start of every workgroup, and eight replicas made the 20 x 20 backward launch 9 us SLOWER.
-__device__ __forceinline__ double bn_sum(const double* __restrict__ s, int slots, int C, int i) {
-    double v[8];
+// Split in two so that a prologue can put every table load in flight, issue its first activation loads behind them and only
+// then wait for the sums: bn_sum_issue() holds the loads, bn_sum_finish() the additions (and the replicas past the eighth).
+__device__ __forceinline__ void bn_sum_issue(const double* __restrict__ s, int slots, int C, int i, double (&v)[8]) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) v[k] = s[(k < slots ? k : 0) * 2 * C + i];
+}
+__device__ __forceinline__ double bn_sum_finish(const double* __restrict__ s, int slots, int C, int i, double (&v)[8]) {
 #pragma unroll
     for (int k = 1; k < 8; ++k) v[k] = k < slots ? v[k] : 0.0;
     double r = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
     for (int k = 8; k < slots; ++k) r += s[k * 2 * C + i];
     return r;
 }
+__device__ __forceinline__ double bn_sum(const double* __restrict__ s, int slots, int C, int i) {
+    double v[8];
+    bn_sum_issue(s, slots, C, i, v);
+    return bn_sum_finish(s, slots, C, i, v);
+}
 __device__ __forceinline__ double* bn_slot(const double* base, int slots, int C) {
     return const_cast<double*>(base) + (slots > 1 ? (int)(blockIdx.x % (unsigned)slots) * 2 * C : 0);
 }
-__device__ __forceinline__ BNCoef bn_coef(const YunetBN& bn, int C, int c) {
+// the loads of bn_coef() | its arithmetic (see bn_sum_issue)
+struct BNCoefRaw {
+    double s[8], q[8];
+    float gamma, beta;
+};
+__device__ __forceinline__ BNCoefRaw bn_coef_issue(const YunetBN& bn, int C, int c) {
+    BNCoefRaw r;
+    bn_sum_issue(bn.stats, bn.slots, C, c, r.s);
+    bn_sum_issue(bn.stats, bn.slots, C, C + c, r.q);
+    r.gamma = bn.gamma[c];
+    r.beta = bn.beta[c];
+    return r;
+}
+__device__ __forceinline__ BNCoef bn_coef_finish(const YunetBN& bn, int C, int c, BNCoefRaw& r) {
     const double inv = 1.0 / (double)bn.count;
-    const double mean = bn_sum(bn.stats, bn.slots, C, c) * inv;
-    double var = bn_sum(bn.stats, bn.slots, C, C + c) * inv - mean * mean;
+    const double mean = bn_sum_finish(bn.stats, bn.slots, C, c, r.s) * inv;
+    double var = bn_sum_finish(bn.stats, bn.slots, C, C + c, r.q) * inv - mean * mean;
     var = var < 0.0 ? 0.0 : var;
     BNCoef k;
     k.mean = (float)mean;
     k.mean_lo = (float)(mean - (double)k.mean);
     k.invstd = (float)(1.0 / sqrt(var + (double)bn.eps));
-    k.scale = bn.gamma[c] * k.invstd;
-    k.beta = bn.beta[c];
+    k.scale = r.gamma * k.invstd;
+    k.beta = r.beta;
     return k;
+}
+__device__ __forceinline__ BNCoef bn_coef(const YunetBN& bn, int C, int c) {
+    BNCoefRaw r = bn_coef_issue(bn, C, c);
+    return bn_coef_finish(bn, C, c, r);
 }
 // The element-wise kernels (pool / upsample-add) derive the coefficients ONCE per workgroup: thread c < C computes
 // channel c into an LDS table [5][C] (mean | scale | beta | invstd | mean_lo) and every thread picks up its four
@@ -181,6 +206,34 @@ struct BNBwd {
     float mean, invstd, k1, c1, c2;
     float mean_lo, c1_lo;
 };
+// the loads of bn_bwd_coef() | its arithmetic (see bn_sum_issue): 34 loads in flight instead of four rounds of eight
+struct BNBwdRaw {
+    BNCoefRaw f;
+    double bs[8], bq[8];
+};
+__device__ __forceinline__ BNBwdRaw bn_bwd_coef_issue(const YunetBN& bn, int C, int c) {
+    BNBwdRaw r;
+    r.f = bn_coef_issue(bn, C, c);
+    bn_sum_issue(bn.bstats, bn.slots, C, c, r.bs);
+    bn_sum_issue(bn.bstats, bn.slots, C, C + c, r.bq);
+    return r;
+}
+__device__ __forceinline__ BNBwd bn_bwd_coef_finish(const YunetBN& bn, int C, int c, BNBwdRaw& r) {
+    const BNCoef f = bn_coef_finish(bn, C, c, r.f);
+    const double inv = 1.0 / (double)bn.count;
+    BNBwd k;
+    k.mean = f.mean;
+    k.invstd = f.invstd;
+    k.k1 = f.scale;
+    const double c1 = bn_sum_finish(bn.bstats, bn.slots, C, c, r.bs) * inv;
+    k.c1 = (float)c1;
+    k.c1_lo = (float)(c1 - (double)k.c1);
+    k.c2 = (float)(bn_sum_finish(bn.bstats, bn.slots, C, C + c, r.bq) * inv);
+    k.mean_lo = f.mean_lo;
+    return k;
+}
+// (the one-call form keeps its own body: the tile, element-wise and stem kernels that use it were not re-measured with
+// their 34 loads in one batch)
 __device__ __forceinline__ BNBwd bn_bwd_coef(const YunetBN& bn, int C, int c) {
     const BNCoef f = bn_coef(bn, C, c);
     const double inv = 1.0 / (double)bn.count;
@@ -311,6 +364,28 @@ inline int yunet_cu_count() {
 // the compiler waits out every load before it issues the next one (s_waitcnt vmcnt(0) in front of each LDS store): the
 // 64 x 64 pointwise weights of dp_fwd64s were 16 consecutive L2 / HBM round trips per workgroup, ~10 us in front of
 // every launch -- half the duration of the 10 x 10 launches.
+// staged_issue() is the first half (the loads), staged_put() the second: a prologue that has activation loads to issue
+// calls them apart, with those loads in between.
+template <int COUNT, int NT>
+__device__ __forceinline__ void staged_issue(const float* __restrict__ src, int tid, float (&v)[(COUNT + NT - 1) / NT]) {
+    constexpr int IT = (COUNT + NT - 1) / NT;
+    constexpr bool EXACT = COUNT % NT == 0;
+#pragma unroll
+    for (int k = 0; k < IT; ++k) {          // (no branch: an element past the table re-reads the last one and is never put)
+        const int i = tid + k * NT;
+        v[k] = src[(EXACT || i < COUNT) ? i : COUNT - 1];
+    }
+}
+template <int COUNT, int NT, typename F>
+__device__ __forceinline__ void staged_put(int tid, const float (&v)[(COUNT + NT - 1) / NT], F&& put) {
+    constexpr int IT = (COUNT + NT - 1) / NT;
+    constexpr bool EXACT = COUNT % NT == 0;
+#pragma unroll
+    for (int k = 0; k < IT; ++k) {
+        const int i = tid + k * NT;
+        if (EXACT || i < COUNT) put(i, v[k]);
+    }
+}
 template <int COUNT, int NT, typename F>
 __device__ __forceinline__ void staged_table(const float* __restrict__ src, int tid, F&& put) {
     constexpr int IT = (COUNT + NT - 1) / NT;
@@ -321,11 +396,14 @@ __device__ __forceinline__ void staged_table(const float* __restrict__ src, int 
         const int i = tid + k * NT;
         v[k] = (EXACT || i < COUNT) ? src[i] : 0.0f;
     }
+    staged_put<COUNT, NT>(tid, v, put);
+}
+// The same for a table whose COUNT is a multiple of 4 NT, as 16-byte loads: thread `tid` takes elements 4 (tid + k NT) .. + 3.
+template <int COUNT, int NT>
+__device__ __forceinline__ void staged_issue4(const float* __restrict__ src, int tid, float4 (&v)[COUNT / (4 * NT)]) {
+    static_assert(COUNT % (4 * NT) == 0, "whole float4 passes");
 #pragma unroll
-    for (int k = 0; k < IT; ++k) {
-        const int i = tid + k * NT;
-        if (EXACT || i < COUNT) put(i, v[k]);
-    }
+    for (int k = 0; k < COUNT / (4 * NT); ++k) v[k] = reinterpret_cast<const float4*>(src)[tid + k * NT];
 }
 #endif
 

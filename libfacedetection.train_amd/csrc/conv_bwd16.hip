@@ -81,12 +81,17 @@ __global__ __launch_bounds__(b16s::NTHR, 1) void dp_bwd16s_kernel(const YunetDP 
     // ---- prologue: tables ---------------------------------------------------------------------------------------
     for (int i = tid; i < C * 9; i += NTHR) s_w2[(i % 9) * C + i / 9] = d.w_dw[i];
     if (tid < C) {
+        // the sums of both BatchNorms in flight together (as bn_bwd_coef() then bn_coef() they were five rounds of eight
+        // loads, each waited out before the next was issued)
+        BNBwdRaw oraw = bn_bwd_coef_issue(d.out_bn, C, tid);
+        BNCoefRaw iraw;
+        if (bn_in) iraw = bn_coef_issue(d.in_bn, C, tid);
         s_b2[tid] = d.b_dw[tid];
         s_b1[tid] = d.b_pw[tid];
-        const BNFold f = bn_fold(bn_bwd_coef(d.out_bn, C, tid));
+        const BNFold f = bn_fold(bn_bwd_coef_finish(d.out_bn, C, tid, oraw));
         s_fold[tid] = f.a; s_fold[C + tid] = f.b; s_fold[2 * C + tid] = f.dh; s_fold[3 * C + tid] = f.dl;
         if (bn_in) {
-            const BNCoef k = bn_coef(d.in_bn, C, tid);
+            const BNCoef k = bn_coef_finish(d.in_bn, C, tid, iraw);
             s_in[tid] = k.mean; s_in[C + tid] = k.scale; s_in[2 * C + tid] = k.beta; s_in[3 * C + tid] = k.invstd;
             s_in[4 * C + tid] = k.mean_lo;
         } else {

@@ -359,17 +359,23 @@ void dp_bwd64_kernel(const YunetDP d, const PackGeom pk) {
     for (int c = tid; c < C; c += NT) s_b1[c] = d.b_pw[c];
     staged_table<C * 9, NT>(d.w_dw, tid, [&](int i, float w) { s_w2[(i % 9) * C + i / 9] = w; });
     for (int c = tid; c < C; c += NT) {
+        // the sums of both BatchNorms in flight together (as bn_bwd_coef() then bn_coef() they were five rounds of eight
+        // loads, each waited out before the next was issued)
+        BNBwdRaw oraw;
+        BNCoefRaw iraw;
+        if (bn_out) oraw = bn_bwd_coef_issue(d.out_bn, C, c);
+        if (bn_in) iraw = bn_coef_issue(d.in_bn, C, c);
         // dz = k1 * (dy - c1 - xhat * c2) folded into dz = A dy + B z + D (bn_fold in common.h): two FMAs and an
         // add per element instead of nine operations
         if (bn_out) {
-            const BNFold f = bn_fold(bn_bwd_coef(d.out_bn, C, c));
+            const BNFold f = bn_fold(bn_bwd_coef_finish(d.out_bn, C, c, oraw));
             s_co[c] = f.a; s_co[C + c] = f.b; s_co[2 * C + c] = f.dh; s_co[3 * C + c] = f.dl;
         } else {
             s_co[c] = d.dy_scale ? d.dy_scale[c] : 1.0f;
             s_co[C + c] = 0.f; s_co[2 * C + c] = 0.f; s_co[3 * C + c] = 0.f;
         }
         if (bn_in) {
-            const BNCoef k = bn_coef(d.in_bn, C, c);
+            const BNCoef k = bn_coef_finish(d.in_bn, C, c, iraw);
             s_ci[c] = k.mean; s_ci[C + c] = k.scale; s_ci[2 * C + c] = k.beta;
             s_ci[3 * C + c] = k.invstd; s_ci[4 * C + c] = k.mean_lo;
         } else {

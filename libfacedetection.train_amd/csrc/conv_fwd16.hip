@@ -60,23 +60,63 @@ __device__ __forceinline__ void dp_fwd16s_body(const YunetDP d, const int R) {
     const int H = d.H, W = d.W;
     const bool bn_in = d.in_transform == YUNET_T_BNRELU;
 
-    staged_table<COUT * 9, NTHR>(d.w_dw, tid, [&](int i, float w) { s_w2[(i % 9) * COUT + i / 9] = w; });
-    for (int i = tid; i < COUT; i += NTHR) { s_b2[i] = d.b_dw[i]; s_b1[i] = d.b_pw[i]; }
-    if (tid < CIN) {
-        if (bn_in) {
-            const BNCoef k = bn_coef(d.in_bn, CIN, tid);
-            s_in[tid] = k.mean; s_in[CIN + tid] = k.scale; s_in[2 * CIN + tid] = k.beta;
-        } else {
-            s_in[tid] = 0.f; s_in[CIN + tid] = 1.f; s_in[2 * CIN + tid] = 0.f;
-        }
-    }
-    for (int i = tid; i < (DET ? WAVES : 1) * 2 * COUT; i += NTHR) s_st[i] = 0.0;
+    const int strips = (W + OUTW - 1) / OUTW, bands = (H + R - 1) / R;
+    const int tasks_img = strips * bands, ntasks = d.N * tasks_img;
+    // activation storage of this build (common.h: act_t = float | bf16): x, z and the pooled winners
+    const unsigned xbytes = (unsigned)(H * W * CIN) * ACT_B, zbytes = (unsigned)(H * W * COUT) * ACT_B;
+    const unsigned poel = (unsigned)((H >> 1) * (W >> 1) * COUT), pobytes = poel * ACT_B;
+    const int total_waves = (int)gridDim.x * WAVES;
+    const int t0 = first_tile() * WAVES + wid;              // the wave's first task (none: t0 >= ntasks)
+
+    // ---- prologue: every load is issued before the first value is used -- the tables, behind them the first input row of
+    // the wave's first task (conv_fwd64.hip has the reasons for the order and for the straight-line form) -- then the LDS
+    // writes, the fp64 chain of bn_coef and the barrier run under that fetch
+    constexpr int TC = COUT < NTHR ? COUT : NTHR;
+    static_assert(COUT <= NTHR && (TC & (TC - 1)) == 0, "one bias pair per thread");
+    const float b2v = d.b_dw[tid & (TC - 1)], b1v = d.b_pw[tid & (TC - 1)];
+    BNCoefRaw inraw;
+    if (bn_in) inraw = bn_coef_issue(d.in_bn, CIN, tid & (CIN - 1));
+    float sgn = 1.0f;                                         // fused pooling: which raw value wins a window after BN + ReLU
+    if constexpr (POOL) sgn = d.out_bn.gamma[cc];
+    float w2v[(COUT * 9 + NTHR - 1) / NTHR];
+    staged_issue<COUT * 9, NTHR>(d.w_dw, tid, w2v);
     // A operands of the pointwise product: W1[co = 16 mt + l15][ci = 4 g + s]
     float w1a[MT][4];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int s = 0; s < 4; ++s) w1a[mt][s] = d.w_pw[(16 * mt + l15) * CIN + 4 * g + s];
+    // the next row of x in flight (layout P): row y of the image behind r_x, strip pixel 0 at image column xs; `on` = false
+    // (a wave without a task) sends every lane to the out-of-range offset, which is answered with zeros without a fetch
+    act_raw4 lx[NT];
+    auto load_x = [&](auto r_x, int xs, int y, bool on) {
+        const bool yin = on && (unsigned)y < (unsigned)H;
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int col = xs + 16 * nt + l15;
+            lx[nt] = act_bufld4(r_x, (yin && (unsigned)col < (unsigned)W) ? (unsigned)((y * W + col) * CIN + 4 * g) * ACT_B : xbytes);
+        }
+    };
+    {
+        const bool has = t0 < ntasks;
+        const int n = has ? t0 / tasks_img : 0, rr = t0 - n * tasks_img;
+        const int band = rr / strips, strip = rr - band * strips;
+        const auto r_x = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<act_t*>(const_cast<float*>(d.x)) + (size_t)n * d.x_img_stride, 0, xbytes, 0x00020000);
+        load_x(r_x, strip * OUTW - HALO, band * R - 1, has);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    staged_put<COUT * 9, NTHR>(tid, w2v, [&](int i, float w) { s_w2[(i % 9) * COUT + i / 9] = w; });
+    if (tid < COUT) { s_b2[tid] = b2v; s_b1[tid] = b1v; }
+    if (tid < CIN) {
+        if (bn_in) {
+            asm volatile("" : "+v"(inraw.gamma), "+v"(inraw.beta));      // (opaque: see conv_fwd64.hip)
+            const BNCoef k = bn_coef_finish(d.in_bn, CIN, tid, inraw);
+            s_in[tid] = k.mean; s_in[CIN + tid] = k.scale; s_in[2 * CIN + tid] = k.beta;
+        } else {
+            s_in[tid] = 0.f; s_in[CIN + tid] = 1.f; s_in[2 * CIN + tid] = 0.f;
+        }
+    }
+    for (int i = tid; i < (DET ? WAVES : 1) * 2 * COUT; i += NTHR) s_st[i] = 0.0;
     __syncthreads();
     float wt[9];
 #pragma unroll
@@ -85,11 +125,7 @@ __device__ __forceinline__ void dp_fwd16s_body(const YunetDP d, const int R) {
     const float4 im = *reinterpret_cast<const float4*>(s_in + 4 * g), isc = *reinterpret_cast<const float4*>(s_in + CIN + 4 * g),
                  ibt = *reinterpret_cast<const float4*>(s_in + 2 * CIN + 4 * g);
     const float relu_floor = bn_in ? 0.0f : -__builtin_inff();
-    float sgn = 1.0f;                                         // fused pooling: which raw value wins a window after BN + ReLU
-    if constexpr (POOL) {
-        const float gm = d.out_bn.gamma[cc];
-        sgn = gm > 0.0f ? 1.0f : (gm < 0.0f ? -1.0f : 0.0f);
-    }
+    if constexpr (POOL) sgn = sgn > 0.0f ? 1.0f : (sgn < 0.0f ? -1.0f : 0.0f);
     float* slot_a = sm + wid * WAVE_F;
     float* slot_z = slot_a + SLOT;
     unsigned char* slot_i = reinterpret_cast<unsigned char*>(slot_z + SLOT);     // [16 pooled pixels][16 channels]
@@ -98,14 +134,7 @@ __device__ __forceinline__ void dp_fwd16s_body(const YunetDP d, const int R) {
 #pragma unroll
     for (int k = 0; k < NSEG; ++k) zacc0[k] = zacc1[k] = 0.0f;
 
-    const int strips = (W + OUTW - 1) / OUTW, bands = (H + R - 1) / R;
-    const int tasks_img = strips * bands, ntasks = d.N * tasks_img;
-    // activation storage of this build (common.h: act_t = float | bf16): x, z and the pooled winners
-    const unsigned xbytes = (unsigned)(H * W * CIN) * ACT_B, zbytes = (unsigned)(H * W * COUT) * ACT_B;
-    const unsigned poel = (unsigned)((H >> 1) * (W >> 1) * COUT), pobytes = poel * ACT_B;
-    const int total_waves = (int)gridDim.x * WAVES;
-
-    for (int task = first_tile() * WAVES + wid; task < ntasks; task += total_waves) {
+    for (int task = t0; task < ntasks; task += total_waves) {
         const int n = task / tasks_img, rr = task - n * tasks_img;
         const int band = rr / strips, strip = rr - band * strips;
         const int y0 = band * R, y1 = (y0 + R < H) ? y0 + R : H;
@@ -123,14 +152,8 @@ __device__ __forceinline__ void dp_fwd16s_body(const YunetDP d, const int R) {
             omask |= ((unsigned)(xs + j) < (unsigned)W && j >= HALO && j < PXW - HALO) ? (1u << k) : 0u;
         }
         auto colP = [&](int nt) { return xs + 16 * nt + l15; };
-        act_raw4 lx[NT];
-        auto issue_x = [&](int y) {
-            const bool yin = (unsigned)y < (unsigned)H;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                lx[nt] = act_bufld4(r_x, (yin && (unsigned)colP(nt) < (unsigned)W) ? (unsigned)((y * W + colP(nt)) * CIN + 4 * g) * ACT_B : xbytes);
-        };
-        issue_x(y0 - 1);
+        auto issue_x = [&](int y) { load_x(r_x, xs, y, true); };
+        if (task != t0) issue_x(y0 - 1);      // the first task's first row is in flight since the prologue
         float ts0 = 0.0f, ts1 = 0.0f;                         // BN sums of the band: channel cc over the lane's output pixels
 
 #pragma unroll 1

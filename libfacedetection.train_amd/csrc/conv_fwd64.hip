@@ -75,27 +75,92 @@ __device__ __forceinline__ void dp_fwd64s_body(const YunetDP& d, const int R, co
     const int H = d.H, W = d.W;
     const bool bn_in = d.in_transform == YUNET_T_BNRELU;
 
-    // ---- prologue: tables ---------------------------------------------------------------------------------
-    staged_table<C * C, NTHR>(d.w_pw, tid, [&](int i, float w) {
-        const int co = i / C, ci = i % C;
-        const __bf16 h = (__bf16)w;
-        const int at = co * C + (((ci >> 3) ^ (co & (NCH - 1))) << 3) + (ci & 7);
-        s_w1p[at] = h;
-#ifndef YUNET_ACT_BF16
-        const float r1 = w - (float)h;
-        const __bf16 m = (__bf16)r1;
-        const __bf16 l = (__bf16)(r1 - (float)m);
-        s_w1p[C * C + at] = m; s_w1p[2 * C * C + at] = l;
+    // prof < 64 is a debug ablation mask (tools/ubench: ABL), not a pointer: 1 skip the matrix instructions,
+    // 2 skip the depthwise phase, 4 skip the z stores, 8 skip the input loads (results are then wrong)
+    const unsigned abl = (unsigned)(unsigned long long)d.prof;
+    const int strips = (W + TW - 1) / TW, bands = (H + R - 1) / R;
+    const int tasks_img = strips * bands, ntasks = d.N * tasks_img;
+    const unsigned xbytes = (unsigned)(H * W * C) * ACT_B;        // x and z: [H][W][64] in the activation storage type
+    const int total_waves = nblk * WAVES;
+    const int t0 = first * WAVES + wid;                           // the wave's first task (none: t0 >= ntasks)
+
+    // ---- prologue -----------------------------------------------------------------------------------------
+    // Every load of the prologue is issued before the first value is used, in the order "tables, then activations":
+    // the table loads (L2 hits after the first workgroups), behind them the first input row of the wave's first task
+    // -- a cold fetch that depends on none of the tables (vector-memory returns are counted in order: tables queued
+    // behind it would wait for it, conv_bwd64.hip) -- and only then the LDS writes, the fp64 chain of bn_coef and the
+    // barrier, all under that fetch.  The main loop takes the row from the registers.
+    // The issue part is STRAIGHT-LINE code (clamped indices instead of `if (tid < C)`, an out-of-range offset instead of
+    // `if (the wave has a task)`): the compiler's wait counts are those of the path with the fewest loads behind the
+    // awaited one, so a branch around the row loads made every table wait drain the row as well (vmcnt(1) in front of
+    // the first W1 value).  For the same reason the tables consumed last (W1) are issued last.
+    const int tc = tid & (C - 1);
+    const float b2v = d.b_dw[tc], b1v = d.b_pw[tc];
+    BNCoefRaw inraw;
+    if (bn_in) inraw = bn_coef_issue(d.in_bn, C, tc);             // (wave-uniform; older than everything waited for with a count)
+    float sg[4] = {1.f, 1.f, 1.f, 1.f};      // fused pooling: which raw value wins a window after BN + ReLU
+    if constexpr (POOL) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sg[i] = d.out_bn.gamma[(lane & 15) * 4 + i];
+    }
+    float w2v[(C * 9 + NTHR - 1) / NTHR];
+    staged_issue<C * 9, NTHR>(d.w_dw, tid, w2v);
+    float4 w1v[C * C / (4 * NTHR)];                               // W1 as 16-byte loads: elements 4 (tid + 256 k) .. + 3
+    staged_issue4<C * C, NTHR>(d.w_pw, tid, w1v);
+    u32x4 xr[4] = {u32x4{0, 0, 0, 0}, u32x4{0, 0, 0, 0}, u32x4{0, 0, 0, 0}, u32x4{0, 0, 0, 0}};
+    // one input row: this lane's pixel, its 16 channels of the two k blocks (the matrix role), from byte offset o
+    auto load_row = [&](auto r_x, unsigned o) {
+#ifdef YUNET_ACT_BF16
+        xr[0] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o, 0, 0);          // 8 bf16 channels of block 0
+        xr[2] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o + 64, 0, 0);     // ... of block 1
+#else
+        xr[0] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o, 0, 0);
+        xr[1] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o + 16, 0, 0);
+        xr[2] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o + 128, 0, 0);
+        xr[3] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o + 144, 0, 0);
 #endif
-    });
-    staged_table<C * 9, NTHR>(d.w_dw, tid, [&](int i, float w) { s_w2[(i % 9) * C + i / 9] = w; });
+    };
+    {
+        // a wave without a task (and the ablation that skips the input loads) fetches nothing: its four loads go to the
+        // out-of-range offset of image 0's descriptor, which the range check answers with zeros without a memory access
+        const bool has = t0 < ntasks && !(abl & 8);
+        const int n = has ? t0 / tasks_img : 0, rr = t0 - n * tasks_img;
+        const int band = rr / strips, strip = rr - band * strips;
+        const int y0 = band * R, rs = y0 > 0 ? y0 - 1 : 0, col = strip * TW - 1 + l15;
+        const auto r_x = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<act_t*>(const_cast<float*>(d.x)) + (size_t)n * d.x_img_stride, 0, xbytes, 0x00020000);
+        const unsigned xlane = (unsigned)col < (unsigned)W ? (unsigned)(col * C + 8 * g) * ACT_B : xbytes;
+        load_row(r_x, has ? xlane + (unsigned)(rs * W * C) * ACT_B : xbytes);
+    }
+    __builtin_amdgcn_sched_barrier(0);       // (the scheduler moved the first W1 conversions, and their wait, above the row loads)
+    // ---- ... consumed: tables to LDS -------------------------------------------------------------------------
+#pragma unroll
+    for (int k = 0; k < C * C / (4 * NTHR); ++k) {
+        const int i = 4 * (tid + k * NTHR), co = i / C, ci = i % C;       // ci .. ci + 3: one half of a 16-byte chunk
+        const int at = co * C + (((ci >> 3) ^ (co & (NCH - 1))) << 3) + (ci & 7);
+        const float w4[4] = {w1v[k].x, w1v[k].y, w1v[k].z, w1v[k].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float w = w4[e];
+            const __bf16 h = (__bf16)w;
+            s_w1p[at + e] = h;
+#ifndef YUNET_ACT_BF16
+            const float r1 = w - (float)h;
+            const __bf16 m = (__bf16)r1;
+            const __bf16 l = (__bf16)(r1 - (float)m);
+            s_w1p[C * C + at + e] = m; s_w1p[2 * C * C + at + e] = l;
+#endif
+        }
+    }
+    staged_put<C * 9, NTHR>(tid, w2v, [&](int i, float w) { s_w2[(i % 9) * C + i / 9] = w; });
     if (tid < C) {
-        s_b2[tid] = d.b_dw[tid];
+        s_b2[tid] = b2v;
         s_b1[tid] = 0.0f;
-        s_b1[C + tid] = d.b_pw[tid];
+        s_b1[C + tid] = b1v;
         float sc = 1.0f, sh = 0.0f;
         if (bn_in) {
-            const BNCoef k = bn_coef(d.in_bn, C, tid);
+            // opaque copies: as plain values the compiler converts beta to fp64 -- and waits for it -- where it is loaded
+            asm volatile("" : "+v"(inraw.gamma), "+v"(inraw.beta));
+            const BNCoef k = bn_coef_finish(d.in_bn, C, tid, inraw);
             sc = k.scale;
             // beta - mean * scale with the mean carried as (hi, lo)
             sh = (float)((double)k.beta - ((double)k.mean + (double)k.mean_lo) * (double)k.scale);
@@ -113,25 +178,17 @@ __device__ __forceinline__ void dp_fwd64s_body(const YunetDP& d, const int R, co
     __syncthreads();
 
     const float relu_floor = bn_in ? 0.0f : -__builtin_inff();
-    float sg[4] = {1.f, 1.f, 1.f, 1.f};      // fused pooling: which raw value wins a window after BN + ReLU
     if constexpr (POOL) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const float gm = d.out_bn.gamma[(lane & 15) * 4 + i];
+            const float gm = sg[i];
             sg[i] = gm > 0.0f ? 1.0f : (gm < 0.0f ? -1.0f : 0.0f);
         }
     }
-    // prof < 64 is a debug ablation mask (tools/ubench: ABL), not a pointer: 1 skip the matrix instructions,
-    // 2 skip the depthwise phase, 4 skip the z stores, 8 skip the input loads (results are then wrong)
-    const unsigned abl = (unsigned)(unsigned long long)d.prof;
     float* pslot = s_p + wid * SLOT_FLOATS;
-    const int strips = (W + TW - 1) / TW, bands = (H + R - 1) / R;
-    const int tasks_img = strips * bands, ntasks = d.N * tasks_img;
-    const unsigned xbytes = (unsigned)(H * W * C) * ACT_B;        // x and z: [H][W][64] in the activation storage type
     const int cq = l15, cgrp = g;                       // depthwise role of the lane: channel quad, column group
-    const int total_waves = nblk * WAVES;
 
-    for (int t = first * WAVES + wid; t < ntasks; t += total_waves) {
+    for (int t = t0; t < ntasks; t += total_waves) {
         const int n = t / tasks_img, rr = t - n * tasks_img;
         const int band = rr / strips, strip = rr - band * strips;
         const int y0 = band * R, y1 = (y0 + R < H) ? y0 + R : H;
@@ -169,21 +226,11 @@ __device__ __forceinline__ void dp_fwd64s_body(const YunetDP& d, const int R, co
             }
         }
         const int rs = y0 > 0 ? y0 - 1 : 0, re = y1 < H ? y1 : H - 1;
-        u32x4 xr[4] = {u32x4{0, 0, 0, 0}, u32x4{0, 0, 0, 0}, u32x4{0, 0, 0, 0}, u32x4{0, 0, 0, 0}};
         auto issue = [&](int y) {
             if (abl & 8) return;
-            const unsigned o = xlane + (unsigned)(y * W * C) * ACT_B;
-#ifdef YUNET_ACT_BF16
-            xr[0] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o, 0, 0);          // 8 bf16 channels of block 0
-            xr[2] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o + 64, 0, 0);     // ... of block 1
-#else
-            xr[0] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o, 0, 0);
-            xr[1] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o + 16, 0, 0);
-            xr[2] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o + 128, 0, 0);
-            xr[3] = __builtin_amdgcn_raw_buffer_load_b128(r_x, o + 144, 0, 0);
-#endif
+            load_row(r_x, xlane + (unsigned)(y * W * C) * ACT_B);
         };
-        issue(rs);
+        if (t != t0) issue(rs);               // the first task's first row is in flight since the prologue
         const float4 b2 = *reinterpret_cast<const float4*>(s_b2 + cq * 4);
         float4 oa[4], ob[4];
 #pragma unroll
@@ -404,11 +451,14 @@ __device__ __forceinline__ void dp_fwd64s_body(const YunetDP& d, const int R, co
     if (d.out_has_bn) {
         __syncthreads();
         if constexpr (DET) {
-            if (tid < 2 * C) {
+            // (the thread index rebuilt from the wave number: as `tid` its byte offset, shared with the prologue's W1 address,
+            // was kept across the whole kernel and spilled in the plain instance)
+            const int te = wid * 64 + lane;
+            if (te < 2 * C) {
                 double v = 0.0;
 #pragma unroll
-                for (int wv = 0; wv < WAVES; ++wv) v += s_st[wv * 2 * C + tid];
-                bn_det_add(d.out_bn.stats, C, tid, v);
+                for (int wv = 0; wv < WAVES; ++wv) v += s_st[wv * 2 * C + te];
+                bn_det_add(d.out_bn.stats, C, te, v);
             }
         } else
         if (tid < 2 * C) atomic_add_f64(bn_slot(d.out_bn.stats, d.out_bn.slots, C) + tid, s_st[tid]);
