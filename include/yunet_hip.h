@@ -343,7 +343,9 @@ typedef struct YunetLossCfg {
  * losses/cross_entropy_loss.py:85-145, iou_loss.py, smooth_l1_loss.py:10-32,
  * losses/utils.py:29-55).  norm[0] is the (all-reduced) mean num_pos, clamped to >= 1
  * inside.  dflat [N,P,16] receives d(loss_c)/d(flat) for the loss that owns channel c,
- * each with unit upstream gradient.  partials [blocks,4] -> losses via
+ * each with unit upstream gradient.  dflat may be NULL (here, in yunet_loss_terms and as p[6] of a YUNET_OP_LOSS):
+ * a value-only instance of the kernel runs, which stores no gradient and writes the same partial rows bit for bit
+ * (a validation step; cfg.defer_num_total works as in the other form).  partials [blocks,4] -> losses via
  * yunet_loss_finalize: losses[5] = {cls, bbox, obj, kps, total}, total = ((cls+bbox)+obj)+kps
  * in fp32 -- the sum _parse_losses builds (mmdet/models/detectors/base.py:206-209).
  * `mirror` (nullable) receives the same five floats a second time: the host keeps it behind

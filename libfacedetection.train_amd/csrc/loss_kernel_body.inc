@@ -3,7 +3,12 @@
 //   loss_terms_kernel  EXT = true: adds the terms of YunetLossTerms `tm` and YUNET_BOX_BOUNDED, each chosen by a launch-uniform code.
 // Text inclusion, not an inlined function: the default instance keeps its pointer arguments' __restrict__ as kernel arguments
 // and compiles to the code it had before the second instance existed (profiles/loss_terms_codegen.txt).
-// In scope: the kernel's arguments, `constexpr bool EXT`, `tm` (YunetLossTerms) and `bal_b` (BalancedL1Loss's b).
+// In scope: the kernel's arguments, `constexpr bool EXT`, `constexpr bool GRAD`, `tm` (YunetLossTerms) and `bal_b`
+// (BalancedL1Loss's b).
+// GRAD = false (loss_value_kernel, loss_terms_value_kernel: the validation step, dflat == NULL): the four float4 stores are
+// not compiled, `o` and the derivative halves of the dual numbers are dead and leave the code.  The value half of every
+// dual operation is the same sequence of single-rounded fp32 operations in both forms (-ffp-contract=off), so `acc` and
+// the partial rows equal the gradient-writing instance's bit for bit.
     // cfg.defer_num_total: norm[0] (the all-reduced positives, possibly still in flight on another stream) is NOT
     // read: the cls / bbox / obj terms and their gradients leave this kernel un-normalised (x 1.0 is exact) and
     // loss_finalize_kernel applies 1 / max(num_total, 1) to the losses and hands it to the head backward as dy_scale
@@ -114,11 +119,13 @@
             }
             acc[3] += lk;
         }
-        float4* dst = reinterpret_cast<float4*>(dflat + e * 16);
-        dst[0] = make_float4(o[0], o[1], o[2], o[3]);
-        dst[1] = make_float4(o[4], o[5], o[6], o[7]);
-        dst[2] = make_float4(o[8], o[9], o[10], o[11]);
-        dst[3] = make_float4(o[12], o[13], o[14], o[15]);
+        if (GRAD) {
+            float4* dst = reinterpret_cast<float4*>(dflat + e * 16);
+            dst[0] = make_float4(o[0], o[1], o[2], o[3]);
+            dst[1] = make_float4(o[4], o[5], o[6], o[7]);
+            dst[2] = make_float4(o[8], o[9], o[10], o[11]);
+            dst[3] = make_float4(o[12], o[13], o[14], o[15]);
+        }
     }
     // deterministic block reduction -> one partial row per block
     __shared__ float s_p[LOSS_THREADS / 64][4];

@@ -1204,6 +1204,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_kernel(
     const float* __restrict__ gt_kps, Levels L, YunetLossCfg cfg, const float* __restrict__ norm,
     int N, int P, int Gmax, float* __restrict__ dflat, float* __restrict__ partials) {
     constexpr bool EXT = false;
+    constexpr bool GRAD = true;
     constexpr YunetLossTerms tm{};
     constexpr float bal_b = 0.0f;
 #include "loss_kernel_body.inc"
@@ -1216,6 +1217,33 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_terms_kernel(
     const float* __restrict__ gt_kps, Levels L, YunetLossCfg cfg, YunetLossTerms tm, float bal_b,
     const float* __restrict__ norm, int N, int P, int Gmax, float* __restrict__ dflat, float* __restrict__ partials) {
     constexpr bool EXT = true;
+    constexpr bool GRAD = true;
+#include "loss_kernel_body.inc"
+}
+
+// The value-only instances (dflat == NULL at the entry points: a validation step has no backward).  Same arguments minus
+// dflat, same grid, same partial rows.
+__global__ __launch_bounds__(LOSS_THREADS) void loss_value_kernel(
+    const float* __restrict__ flat, const int32_t* __restrict__ gt_inds,
+    const float* __restrict__ max_overlaps, const float* __restrict__ gt_boxes,
+    const float* __restrict__ gt_kps, Levels L, YunetLossCfg cfg, const float* __restrict__ norm,
+    int N, int P, int Gmax, float* __restrict__ partials) {
+    constexpr bool EXT = false;
+    constexpr bool GRAD = false;
+    constexpr YunetLossTerms tm{};
+    constexpr float bal_b = 0.0f;
+    constexpr float* dflat = nullptr;
+#include "loss_kernel_body.inc"
+}
+
+__global__ __launch_bounds__(LOSS_THREADS) void loss_terms_value_kernel(
+    const float* __restrict__ flat, const int32_t* __restrict__ gt_inds,
+    const float* __restrict__ max_overlaps, const float* __restrict__ gt_boxes,
+    const float* __restrict__ gt_kps, Levels L, YunetLossCfg cfg, YunetLossTerms tm, float bal_b,
+    const float* __restrict__ norm, int N, int P, int Gmax, float* __restrict__ partials) {
+    constexpr bool EXT = true;
+    constexpr bool GRAD = false;
+    constexpr float* dflat = nullptr;
 #include "loss_kernel_body.inc"
 }
 
@@ -1370,8 +1398,12 @@ extern "C" int yunet_loss_terms(const float* flat, const int32_t* gt_inds, const
     }
     Levels L = make_levels(lv);
     if (L.base[YUNET_MAX_LEVELS] != P) return YUNET_EINVAL;
-    hipLaunchKernelGGL(loss_terms_kernel, dim3(blocks), dim3(LOSS_THREADS), 0, (hipStream_t)stream, flat, gt_inds,
-                       max_overlaps, gt_boxes, gt_kps, L, *cfg, tm, bal_b, norm, N, P, Gmax, dflat, partials);
+    if (!dflat)     // losses alone
+        hipLaunchKernelGGL(loss_terms_value_kernel, dim3(blocks), dim3(LOSS_THREADS), 0, (hipStream_t)stream, flat, gt_inds,
+                           max_overlaps, gt_boxes, gt_kps, L, *cfg, tm, bal_b, norm, N, P, Gmax, partials);
+    else
+        hipLaunchKernelGGL(loss_terms_kernel, dim3(blocks), dim3(LOSS_THREADS), 0, (hipStream_t)stream, flat, gt_inds,
+                           max_overlaps, gt_boxes, gt_kps, L, *cfg, tm, bal_b, norm, N, P, Gmax, dflat, partials);
     return -(int)hipGetLastError();
 }
 
@@ -1385,9 +1417,13 @@ extern "C" int yunet_loss(const float* flat, const int32_t* gt_inds, const float
                                 partials, blocks, stream);
     Levels L = make_levels(lv);
     if (L.base[YUNET_MAX_LEVELS] != P) return YUNET_EINVAL;
-    hipLaunchKernelGGL(loss_kernel, dim3(blocks), dim3(LOSS_THREADS), 0, (hipStream_t)stream, flat,
-                       gt_inds, max_overlaps, gt_boxes, gt_kps, L, *cfg, norm, N, P, Gmax, dflat,
-                       partials);
+    if (!dflat)     // losses alone
+        hipLaunchKernelGGL(loss_value_kernel, dim3(blocks), dim3(LOSS_THREADS), 0, (hipStream_t)stream, flat,
+                           gt_inds, max_overlaps, gt_boxes, gt_kps, L, *cfg, norm, N, P, Gmax, partials);
+    else
+        hipLaunchKernelGGL(loss_kernel, dim3(blocks), dim3(LOSS_THREADS), 0, (hipStream_t)stream, flat,
+                           gt_inds, max_overlaps, gt_boxes, gt_kps, L, *cfg, norm, N, P, Gmax, dflat,
+                           partials);
     return -(int)hipGetLastError();
 }
 

@@ -737,6 +737,58 @@ class Plan:
                 self.fwd_eval[idx].dp.z = self.c_fwd_eval[idx].dp.z = zt.buf.data_ptr()
         return self.c_fwd_eval
 
+    def val_ops(self):
+        """c_val: the validation step of this plan, built on the first call like the eval list's
+        missing tensors.  `val` = the eval conv stack exactly as fwd_eval has it (mode-2 fill from the running statistics,
+        out_has_bn = 0, stem scratch block, no OP_BN_FOLD), then the OP_ASSIGN and OP_LOSS_NORM that _build_eval skips,
+        then OP_LOSS with a null dflat (the kernel's value-only instance) and OP_LOSS_FINALIZE without the mirror behind
+        the flat gradient.  No running-statistics update (fwd_b[2:]), no backward, no memset: nothing a validation step
+        writes is read by a later training step before that step writes it itself.
+        The deferred form (world size > 1): `val_a` = `val` up to OP_LOSS_NORM, `val_loss_def` = the loss with
+        defer_num_total, `val_rest_def` = finalize reading `norm`; dy_norm is not written (no backward reads it).
+        The training lists are not touched: every record here is a copy."""
+        if getattr(self, 'c_val', None) is not None:
+            return self.c_val
+        self.eval_ops()                                     # the eval list with every tensor behind it
+        stack = [self._clone_op(op) for op in self.fwd_eval]
+        assign, norm = self._clone_op(self.fwd_a[self.assign_idx]), self._clone_op(self.fwd_a[self.assign_idx + 1])
+        assert assign.opcode == L.OP_ASSIGN and norm.opcode == L.OP_LOSS_NORM
+        loss, fin = self._clone_op(self.fwd_b[0]), self._clone_op(self.fwd_b[1])
+        assert loss.opcode == L.OP_LOSS and fin.opcode == L.OP_LOSS_FINALIZE
+        loss.p[6] = None                                    # dflat: losses alone
+        fin.p[2] = None                                     # the logged scalars of a validation step ride in no gradient all-reduce
+        loss_def, fin_def = self._clone_op(loss), self._clone_op(fin)
+        loss_def.loss.defer_num_total = 1
+        fin_def.p[3] = self.norm.data_ptr()
+        self.val_a = stack + [assign, norm]
+        self.val = self.val_a + [loss, fin]
+        self.val_loss_def, self.val_rest_def = [loss_def], [fin_def]
+        self.val_assign_idx = len(stack)
+        self.c_val_a = self._carray(self.val_a)
+        self.c_val_loss_def = self._carray(self.val_loss_def)
+        self.c_val_rest_def = self._carray(self.val_rest_def)
+        self.c_val = self._carray(self.val)
+        self._val_gt_bound = None
+        self._bind_val()
+        return self.c_val
+
+    def _bind_val(self, img=None):
+        """The validation lists read the GT tensors the plan is bound to right now (bind_gt) and, with `img`, that image."""
+        ptrs = (self.gt_boxes.data_ptr(), self.gt_kps.data_ptr(), self.gt_count.data_ptr())
+        if ptrs != self._val_gt_bound:
+            ai = self.val_assign_idx
+            for arr in (self.c_val, self.c_val_a):
+                assert arr[ai].opcode == L.OP_ASSIGN
+                arr[ai].p[1], arr[ai].p[2], arr[ai].p[4] = ptrs
+            for op in (self.c_val[ai + 2], self.c_val_loss_def[0]):
+                assert op.opcode == L.OP_LOSS
+                op.p[3], op.p[4] = ptrs[0], ptrs[1]
+            self._val_gt_bound = ptrs
+        if img is not None:
+            for which, idx in self.img_ptr_ops:
+                if which == 'fwd_a':                        # same position as in fwd_eval (set_img)
+                    self.c_val[idx].p[0] = self.c_val_a[idx].p[0] = img.data_ptr()
+
     def _build_deferred(self):
         """`c_fwd_b_loss` / `c_fwd_b_rest` from fwd_b, and the GT binding state (`own_gt`, `_gt_bound`).
         N > 1: the same two phases with the num_pos normaliser DEFERRED -- the loss kernel leaves the cls / bbox /
@@ -1340,6 +1392,45 @@ class YuNetEngine:
             self._exec(plan.c_fwd_b, 'yunet_exec(fwd_b)')
         if plan.nbt_step is not None:                # 1 | frozen layers: a 0 / 1 vector, or None when every layer is frozen
             self.params.num_batches_tracked += plan.nbt_step
+        return plan.losses
+
+    @torch.no_grad()
+    def forward_val(self, img, gt_bboxes, gt_keypointss):
+        """The validation step: the eval-mode conv stack (BatchNorm on the running statistics), assignment and the four
+        losses, no gradient.  Same arguments and returned tensor as forward().  The plan is the one of the engine's CURRENT
+        key (precision, deterministic level, freeze signature as the last training step left it): a geometry the training
+        step has a plan for gets no second one.  Parameters, the flat gradient, the BatchNorm buffers and the accumulation
+        state are not written; the plan's activations, `flat`, the assignment and `losses` are -- so it runs between
+        training steps, not between a forward and its backward."""
+        assert img.is_cuda and img.dtype == torch.float32 and img.is_contiguous()
+        n, _, h, w = img.shape
+        pb = getattr(gt_bboxes, 'padded', None)
+        cnt_t = getattr(gt_bboxes, 'counts', None)
+        if pb is not None:
+            max_gt = int(pb.shape[1])
+        elif cnt_t is not None:
+            max_gt = max(int(cnt_t.max()), 1)
+        else:
+            max_gt = max([int(b.shape[0]) for b in gt_bboxes] + [1])
+        self._check_oneshot()
+        plan = self.get_plan(n, h, w, max_gt)
+        self.plan = plan
+        self._val_img = img          # (not _img: the backward list keeps reading the training step's image)
+        c_val = plan.val_ops()
+        self.stage_gt(plan, gt_bboxes, gt_keypointss)
+        plan._bind_val(img)
+        if self.world_size > 1 or (self.always_bucket and torch.distributed.is_initialized()):
+            # the reference reduces num_pos across ranks in loss() whatever the mode (yunet_head.py:493-497): as in forward()
+            self._exec(plan.c_val_a, 'yunet_exec(val_a)')
+            main, side = torch.cuda.current_stream(), self._comm_stream()
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                self.reduce_num_pos(plan.norm, side)
+            self._exec(plan.c_val_loss_def, 'yunet_exec(val: loss)')
+            main.wait_stream(side)
+            self._exec(plan.c_val_rest_def, 'yunet_exec(val: finalize)')
+        else:
+            self._exec(c_val, 'yunet_exec(val)')
         return plan.losses
 
     def scale_buffer(self):

@@ -624,8 +624,10 @@ def loss_norm(img_stats, inv_world=1.0):
 
 
 def loss(flat, gt_inds, ovl, gt_boxes, gt_kps, img_stats, sizes, strides, cfg, inv_world=1.0,
-         norm=None):
-    """-> (losses [4] = cls,bbox,obj,kps ; dflat [N,P,16] ; norm [3])."""
+         norm=None, grad=True, partials=None):
+    """-> (losses [4] = cls,bbox,obj,kps ; dflat [N,P,16] ; norm [3]).
+    grad=False: losses alone -- the kernel's value-only instance runs, no dflat is allocated and None stands in its place.
+    partials: a [yunet_loss_blocks(N, P), 4] fp32 tensor to receive the per-block rows (default: a temporary)."""
     n, p, _ = flat.shape
     gmax = gt_boxes.shape[1]
     dev = flat.device
@@ -633,8 +635,10 @@ def loss(flat, gt_inds, ovl, gt_boxes, gt_kps, img_stats, sizes, strides, cfg, i
     if norm is None:
         norm = loss_norm(img_stats, inv_world)
     blocks = lib.yunet_loss_blocks(n, p)
-    part = torch.empty(blocks, 4, device=dev, dtype=torch.float32)
-    dflat = torch.empty_like(flat)
+    part = partials if partials is not None else torch.empty(blocks, 4, device=dev, dtype=torch.float32)
+    if tuple(part.shape) != (blocks, 4) or part.dtype != torch.float32 or not part.is_contiguous() or part.device != dev:
+        raise ValueError(f'partials must be a contiguous fp32 [{blocks}, 4] tensor on {dev}')
+    dflat = torch.empty_like(flat) if grad else None
     lv = make_levels(sizes, strides)
     terms = getattr(cfg, 'terms', None)               # None: the default terms, which yunet_loss_terms hands to yunet_loss
     L.check(lib.yunet_loss_terms(_p(flat), _p(gt_inds), _p(ovl), _p(gt_boxes), _p(gt_kps), C.byref(lv),

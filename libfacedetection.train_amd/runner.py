@@ -351,7 +351,7 @@ PRIORITY = dict(HIGHEST=0, VERY_HIGH=10, HIGH=30, ABOVE_NORMAL=40, NORMAL=50, BE
 class Hook:
     """mmcv.runner.Hook: the stage methods an EpochBasedRunner calls."""
     stages = ('before_run', 'before_train_epoch', 'before_train_iter', 'after_train_iter',
-              'after_train_epoch', 'after_run')
+              'after_train_epoch', 'before_val_epoch', 'before_val_iter', 'after_val_iter', 'after_val_epoch', 'after_run')
 
     def before_run(self, runner): pass                    # noqa: E704
     def after_run(self, runner): pass                     # noqa: E704
@@ -370,6 +370,19 @@ class Hook:
         self.before_iter(runner)
 
     def after_train_iter(self, runner):
+        self.after_iter(runner)
+
+    # the validation epochs of a workflow (EpochBasedRunner.val), mapped onto the generic stages as mmcv's base class does
+    def before_val_epoch(self, runner):
+        self.before_epoch(runner)
+
+    def after_val_epoch(self, runner):
+        self.after_epoch(runner)
+
+    def before_val_iter(self, runner):
+        self.before_iter(runner)
+
+    def after_val_iter(self, runner):
         self.after_iter(runner)
 
     def every_n_iters(self, runner, n):
@@ -761,11 +774,32 @@ class LoggerHook(Hook):
         if runner.rank == 0:
             self.log(runner, rec)
 
+    def after_val_epoch(self, runner):
+        """The epoch mean of a validation epoch (EpochBasedRunner.val): one entry in runner.log_buffer, however many
+        logger hooks, with the conventions of the EvalHook entry -- epoch = training epochs completed, iter = iterations
+        completed."""
+        mean = runner.val_epoch_mean()
+        if mean is None:
+            return
+        rec = dict(mode='val', epoch=runner.epoch, iter=runner.iter, **mean)
+        if not runner._val_logged:
+            runner._val_logged = True
+            runner.log_buffer.append(rec)
+        if runner.rank == 0:
+            self.log_val(runner, rec)
+
     def log(self, runner, rec):
         raise NotImplementedError
 
+    def log_val(self, runner, rec):
+        pass
+
 
 class TextLoggerHook(LoggerHook):
+    def log_val(self, runner, rec):
+        keys = [k for k in rec if k not in ('mode', 'iter', 'epoch')]
+        runner.logger('Epoch(val) [%d][%d]\t%s' % (rec['epoch'], runner.val_iters, ', '.join(f'{k}: {rec[k]:.4f}' for k in keys)))
+
     def log(self, runner, rec):
         keys = [k for k in rec if k not in ('iter', 'epoch', 'lr', 'time')]
         runner.logger(f"Epoch [{rec['epoch']}][{rec['iter']}] lr: {rec['lr']:.3e}, time: {rec['time']:.4f}, " +
@@ -805,6 +839,14 @@ class TensorboardLoggerHook(LoggerHook):
                 self.writer.add_scalar(('train/' + k) if k != 'lr' else 'learning_rate', v, rec['iter'])
         self.writer.flush()
 
+    def log_val(self, runner, rec):
+        if self.writer is None:
+            return
+        for k, v in rec.items():
+            if k not in ('mode', 'iter', 'epoch'):
+                self.writer.add_scalar('val/' + k, v, rec['iter'])
+        self.writer.flush()
+
     def after_run(self, runner):
         if self.writer is not None:
             self.writer.close()
@@ -832,6 +874,9 @@ class EpochBasedRunner:
         self.epoch, self.iter, self.inner_iter = 0, 0, 0
         self.hooks, self.outputs, self.log_buffer = [], None, []
         self.data_source, self.device, self.data_batch = None, 'cuda', None
+        self.mode = 'train'                     # 'train' | 'val': the workflow entry that is running
+        self.val_sums = self.val_keys = self._val_mean = None
+        self.val_iters, self._val_logged = 0, False
 
     @property
     def max_epochs(self):
@@ -917,14 +962,122 @@ class EpochBasedRunner:
         self.epoch += 1
         return True
 
+    @staticmethod
+    def check_workflow(workflow):
+        """-> [(mode, n)]: a list of ('train' | 'val', positive int) with at least one 'train' entry (mmcv's loop ends on
+        the epoch count, which only training moves).  Anything else: ValueError naming the entry."""
+        if not isinstance(workflow, (list, tuple)) or not workflow:
+            raise ValueError(f"workflow {workflow!r}: a non-empty list of ('train' | 'val', positive int) entries")
+        out = []
+        for entry in workflow:
+            ok = isinstance(entry, (list, tuple)) and len(entry) == 2 and entry[0] in ('train', 'val') and \
+                isinstance(entry[1], int) and not isinstance(entry[1], bool) and entry[1] > 0
+            if not ok:
+                raise ValueError(f"workflow entry {entry!r}: expected ('train' | 'val', positive int)")
+            out.append((entry[0], entry[1]))
+        if not any(m == 'train' for m, _ in out):
+            raise ValueError(f"workflow {workflow!r}: no ('train', n) entry -- the run would never reach max_epochs")
+        return out
+
+    @staticmethod
+    def val_pass_index(workflow, epoch, entry, rep):
+        """The number of validation epochs the workflow completed before repetition `rep` of its entry `entry`, reached with
+        `epoch` training epochs done -- counted from epoch 0 of the run, so a resumed run continues the sequence.
+        With T training and V validation epochs per cycle, t and v of them in front of the entry:
+        cycles = max(0, ceil((epoch - t) / T)) (whole cycles behind us; ceil: the last 'train' entry of a run may stop short
+        at max_epochs), index = cycles * V + v + rep."""
+        per_t = sum(n for m, n in workflow if m == 'train')
+        per_v = sum(n for m, n in workflow if m == 'val')
+        pre_t = sum(n for m, n in workflow[:entry] if m == 'train')
+        pre_v = sum(n for m, n in workflow[:entry] if m == 'val')
+        cycles = max(0, -((pre_t - epoch) // per_t))
+        return cycles * per_v + pre_v + rep
+
+    def val(self, data_source, pass_index=0):
+        """One validation epoch (mmcv EpochBasedRunner.val): the model in eval(), autograd off, every batch through
+        model.val_step -- the same loss dict as a training step, BatchNorm on the running statistics, nothing updated.
+        `iter` and `epoch` do not move.  Pass `pass_index` draws data_source.batch(pass_index * iters_per_epoch + i).
+        value * num_samples of every logged scalar and num_samples are summed on the device in fp64 (plain torch ops, no
+        host read per iteration); val_epoch_mean() is sum(v n) / sum(n), mmcv's LogBuffer.average."""
+        self.model.eval()
+        self.mode = 'val'
+        self.val_sums, self.val_keys, self.val_iters = None, None, data_source.iters_per_epoch
+        self._val_mean, self._val_logged = None, False
+        per = data_source.iters_per_epoch
+        with torch.no_grad():
+            self.call_hook('before_val_epoch')
+            for i in range(per):
+                self.inner_iter = i
+                self.data_batch = data_source.batch(pass_index * per + i, self.device)
+                self.call_hook('before_val_iter')
+                self.outputs = self.model.val_step(self.data_batch, self.optimizer)
+                self._val_accumulate(self.outputs)
+                self.call_hook('after_val_iter')
+                self.data_batch = None
+            if self.val_sums is not None and self.world_size > 1 and torch.distributed.is_initialized():
+                # one collective per validation epoch: [sum(v n) x k | sum(n)] over the ranks
+                t = self.val_sums
+                if t.is_cuda and torch.distributed.get_backend() != 'nccl':      # CPU process group: through the host
+                    h = t.cpu()
+                    torch.distributed.all_reduce(h)
+                    t.copy_(h)
+                else:
+                    torch.distributed.all_reduce(t)
+            self.call_hook('after_val_epoch')
+        return True
+
+    def _val_accumulate(self, outputs):
+        log_vars = outputs.get('log_vars') or {}
+        if not log_vars:
+            return
+        n = outputs.get('num_samples', 1)
+        vec = outputs.get('log_tensor')          # the logged scalars as one device tensor, in log_vars' order (YuNet.val_step)
+        if vec is None:                          # any other model: its log_vars are host numbers
+            vec = torch.tensor([float(v) for v in log_vars.values()], dtype=torch.float64)
+        if self.val_sums is None:
+            self.val_keys = list(log_vars)
+            self.val_sums = torch.zeros(len(self.val_keys) + 1, device=vec.device, dtype=torch.float64)
+        k = len(self.val_keys)
+        self.val_sums[:k] += vec[:k].to(torch.float64) * n
+        self.val_sums[k] += n
+
+    def val_epoch_mean(self):
+        """{key: sum(value * num_samples) / sum(num_samples)} of the validation epoch that just ran (python floats; the one
+        host read of the epoch), or None when its steps logged nothing."""
+        if self.val_sums is None:
+            return None
+        if self._val_mean is None:
+            k = len(self.val_keys)
+            self._val_mean = dict(zip(self.val_keys, (self.val_sums[:k] / self.val_sums[k]).tolist()))
+        return self._val_mean
+
     def run(self, data_sources, workflow=(('train', 1),), device='cuda'):
+        """mmcv's EpochBasedRunner.run: cycle through the (mode, n) entries of `workflow`, source i serving entry i, until
+        `epoch` reaches max_epochs; a 'train' entry stops early there, a 'val' entry that follows the last training epoch
+        still runs.  A run cut by max_iters inside an epoch ends at once (no validation epoch follows)."""
         self.device = device
-        src = data_sources[0] if isinstance(data_sources, (list, tuple)) else data_sources
-        self.data_source = src
+        workflow = self.check_workflow(workflow)
+        sources = list(data_sources) if isinstance(data_sources, (list, tuple)) else [data_sources]
+        if len(sources) != len(workflow):
+            raise ValueError(f'{len(sources)} data source(s) for a workflow of {len(workflow)} entries {workflow!r}: one source '
+                             f'per entry')
+        self.data_source = sources[[m for m, _ in workflow].index('train')]     # max_iters: the length of a training epoch
         self.call_hook('before_run')
-        while self.epoch < self._max_epochs:
-            if not self.train(src):
-                break
+        go = True
+        while go and self.epoch < self._max_epochs:
+            for i, (mode, n) in enumerate(workflow):
+                for rep in range(n):
+                    if mode == 'train':
+                        if self.epoch >= self._max_epochs:
+                            break
+                        self.mode = 'train'
+                        go = self.train(sources[i])
+                    else:
+                        self.val(sources[i], self.val_pass_index(workflow, self.epoch, i, rep))
+                    if not go:
+                        break
+                if not go:
+                    break
         self.call_hook('after_run')
         return self.log_buffer
 
@@ -1109,7 +1262,9 @@ def train_detector(model, dataset, cfg, distributed=False, validate=False, times
         runner.resume(resume_from)
     elif cfg.get('load_from'):
         runner.load_checkpoint(cfg.load_from)
-    return runner.run([dataset], cfg.get('workflow', [('train', 1)]), device=device)
+    # `dataset`: one source, or one per workflow entry (tools/train.py builds the second from data.val for a two-entry workflow)
+    sources = list(dataset) if isinstance(dataset, (list, tuple)) else [dataset]
+    return runner.run(sources, cfg.get('workflow', [('train', 1)]), device=device)
 
 
 # the reference's custom hooks (mmdet/core/hook/: EMA, box-size statistics, loss check) register themselves in HOOKS

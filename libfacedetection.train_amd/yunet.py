@@ -479,16 +479,24 @@ class YuNet(nn.Module):
                                'path is implemented as HIP kernels only, there is no CPU fallback')
         if gt_keypointss is None:
             raise ValueError('the shipped configs train with use_kps=True: gt_keypointss is required')
-        if not self.training:
-            raise RuntimeError('forward_train requires model.train() (batch-statistics BatchNorm)')
         eng = self._ensure_engine(img.device)
-        self._sync_frozen(eng)
+        if self.training:
+            self._sync_frozen(eng)
+        # (model.eval(): the modules' flags are NOT read -- every BatchNorm says eval there, and syncing that would build an
+        # all-frozen plan with activation buffers of its own; the validation step runs on the plan of the engine's current key)
         ev = getattr(self, '_log_last_event', None)
         if ev is not None:
             # the previous step's logged scalars are copied to the host on a side stream from buffers
             # this step overwrites (a 20-byte copy issued milliseconds ago: never an actual wait)
             torch.cuda.current_stream().wait_event(ev)
             self._log_last_event = None
+        if not self.training:
+            # the workflow's validation step (runner.EpochBasedRunner.val): the reference's forward_train under eval() --
+            # BatchNorm on the running statistics, the same four losses, nothing written back.  The tensors carry no graph.
+            l = eng.forward_val(img.float().contiguous(), gt_bboxes, gt_keypointss).detach().clone()
+            out = dict(loss_cls=l[0], loss_bbox=l[1], loss_obj=l[2], loss_kps=l[3])
+            self._last = (out, l[4], l[:5])
+            return out
         losses = eng.forward(img.float().contiguous(), gt_bboxes, gt_keypointss)
         l = _EngineStep.apply(self._anchor, self, losses)
         out = dict(loss_cls=l[0], loss_bbox=l[1], loss_obj=l[2], loss_kps=l[3])
@@ -555,6 +563,11 @@ class YuNet(nn.Module):
             loss, log_vars = self._parse_engine_losses(last[1])
         else:
             loss, log_vars = self._parse_losses(losses)
-        return dict(loss=loss, log_vars=log_vars, num_samples=len(data['img_metas']))
+        out = dict(loss=loss, log_vars=log_vars, num_samples=len(data['img_metas']))
+        if last is not None and len(last) == 3 and last[0] is losses:
+            # a validation step (model.eval()): the five scalars once more as this rank's device tensor, in log_vars' order --
+            # what the runner sums per validation epoch without a host read
+            out['log_tensor'] = last[2]
+        return out
 
     val_step = train_step

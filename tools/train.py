@@ -104,9 +104,13 @@ def prepare_config(args):
     return cfg
 
 
-def build_source(cfg, rank, world, seed):
-    """The training data source named by data.train.type (the role of build_dataset + build_dataloader)."""
-    dcfg = cfg.data.train
+VAL_SEED_OFFSET = 1000003      # the validation source's seed stream: the train source's seed + this constant
+
+
+def build_source(cfg, rank, world, seed, dcfg=None):
+    """The data source named by dcfg.type (the role of build_dataset + build_dataloader); dcfg = the dataset config to
+    build, cfg.data.train by default."""
+    dcfg = cfg.data.train if dcfg is None else dcfg
     if dcfg.get('type') == 'MultiImageMixDataset':      # Mosaic: the wrapped dataset with the two pipeline lists as one
         from yunet_amd.datasets import flatten_multi_image_mix
         dcfg = type(dcfg)(flatten_multi_image_mix(dcfg))
@@ -119,7 +123,7 @@ def build_source(cfg, rank, world, seed):
         from yunet_amd.datasets import RetinaFaceSource
         cache = dcfg.get('cache')                        # data.train.cache=device|host: decode once (SourceStore)
         if cache not in (None, 'device', 'host'):
-            raise ValueError(f"data.train.cache must be device or host (or unset), got {cache!r}")
+            raise ValueError(f"data.train.cache must be device or host (or unset), got {cache!r}")      # (data.val.cache: the workflow's source)
         host_fetch = dcfg.get('host_fetch')              # data.train.host_fetch=dma|kernel (cache=host only)
         dataset = yunet_amd.build_dataset(dcfg)
         return RetinaFaceSource(dataset, dcfg['pipeline'], samples_per_gpu=cfg.data.samples_per_gpu, rank=rank,
@@ -128,6 +132,32 @@ def build_source(cfg, rank, world, seed):
                      'MultiImageMixDataset for Mosaic), '
                      'SyntheticWiderFace (ready batches) or SyntheticSourceImages (decoded synthetic '
                      'sources + the reference train pipeline on the GPU)')
+
+
+def val_source_config(cfg):
+    """The dataset config of a workflow's validation source (the reference's tools/train.py:214-217): a copy of data.val
+    with data.train's pipeline -- the flattened list when data.train is a MultiImageMixDataset -- and no test_mode."""
+    import copy
+    if cfg.data.get('val') is None:
+        raise ValueError(f"workflow {cfg.workflow!r} has a second entry, which takes its batches from data.val with "
+                         f"data.train's pipeline: the config has no data.val")
+    train = cfg.data.train
+    if train.get('type') == 'MultiImageMixDataset':
+        from yunet_amd.datasets import flatten_multi_image_mix
+        train = flatten_multi_image_mix(train)
+    val = copy.deepcopy(dict(cfg.data.val))
+    val['pipeline'] = copy.deepcopy(train['pipeline'])
+    val.pop('test_mode', None)
+    return type(cfg.data.train)(val)
+
+
+def build_sources(cfg, rank, world, seed):
+    """One source per workflow entry: the training source, and for a two-entry workflow the validation source, built like
+    the first (samples_per_gpu, sampler rule, cache / host_fetch handling) from val_source_config on its own seed stream."""
+    sources = [build_source(cfg, rank, world, seed)]
+    if len(cfg.get('workflow', [('train', 1)])) == 2:
+        sources.append(build_source(cfg, rank, world, seed + VAL_SEED_OFFSET, dcfg=val_source_config(cfg)))
+    return sources
 
 
 def main(argv=None):
@@ -154,8 +184,9 @@ def main(argv=None):
     cfg['seed'] = seed
     model = yunet_amd.build_detector(cfg.model)
     model.init_weights()
-    ds = build_source(cfg, rank, world, args.seed if args.seed is not None else 0)
-    main.last_source = ds                      # (measurement tools read the source's own timing: tools/train_e2e.py)
+    sources = build_sources(cfg, rank, world, args.seed if args.seed is not None else 0)
+    ds = sources[0] if len(sources) == 1 else sources      # a one-entry workflow hands over the source itself, as before
+    main.last_source = sources[0]              # (measurement tools read the source's own timing: tools/train_e2e.py)
     meta = dict(config=cfg.pretty_text, seed=seed, exp_name=os.path.basename(args.config), CLASSES=('face',))
     hist = R.train_detector(model, ds, cfg, distributed=distributed, validate=not args.no_validate,
                             timestamp=timestamp, meta=meta, max_iters=args.max_iters)
