@@ -544,6 +544,35 @@ int yunet_nms(const float* boxes, const float* scores, const int32_t* counts, in
 int yunet_detect(const float* flat, const YunetLevels* lv, int N, int P, float score_thr,
                  float iou_thr, int max_out, float* dets, float* kps, int32_t* count, void* scratch,
                  void* stream);
+/* Soft-NMS (test_cfg.nms = dict(type='soft_nms', iou_threshold, sigma, min_score, method)): the two entry points above
+ * with mmcv.ops.soft_nms in place of the greedy sweep, for ONE class and offset 0 (additive: the ABI number stays).
+ * Restated from mmcv 1.3.17's softnms_cpu -- mmcv is not part of the reference tree, so this is unpinned against it
+ * (as the greedy NMS is).  Candidates: score >= score_thr with the score BEFORE any decay.  Then
+ * rounds: the live candidate with the largest CURRENT score goes out with that score; every other live candidate's
+ * score is multiplied (one fp32 multiply) by
+ *    NAIVE    0 when IoU >= iou_thr, else 1
+ *    LINEAR   1 - IoU when IoU >= iou_thr, else 1
+ *    GAUSSIAN expf(-(IoU * IoU) / sigma), always (iou_thr unused)
+ * and the candidate is dropped when its score is then below min_score -- also when the factor was 1, so a candidate
+ * that starts below min_score (score_thr < min_score) survives only as the first selection.  Emitted scores are
+ * non-increasing; at most max_out rows (= truncating the full result).  Equal current scores: the lower index first --
+ * upstream's choice depends on its swap history, so EXACT score ties may resolve differently from mmcv.  NaN scores
+ * are unsupported.  Outputs and scratch as yunet_detect / yunet_nms (kps: landmarks of the selected priors; keep:
+ * indices into the set).  YUNET_EINVAL: soft == NULL, a method outside 0..2, a non-finite iou_thr / min_score, or
+ * (GAUSSIAN) sigma <= 0 or non-finite. */
+#define YUNET_SOFTNMS_NAIVE 0
+#define YUNET_SOFTNMS_LINEAR 1
+#define YUNET_SOFTNMS_GAUSSIAN 2
+typedef struct YunetSoftNms {
+    int32_t method;                 /* YUNET_SOFTNMS_* */
+    float iou_thr, sigma, min_score;
+} YunetSoftNms;
+int yunet_detect_soft(const float* flat, const YunetLevels* lv, int N, int P, float score_thr,
+                      const YunetSoftNms* soft, int max_out, float* dets, float* kps, int32_t* count,
+                      void* scratch, void* stream);
+int yunet_soft_nms(const float* boxes, const float* scores, const int32_t* counts, int N, int K,
+                   float score_thr, const YunetSoftNms* soft, int max_out, float* dets, int32_t* keep,
+                   int32_t* count, void* scratch, void* stream);
 
 /* ---- device input pipeline ----------------------------------------
  * The reference's TRAIN pipeline (configs/yunet_n.py:36-56) on the device:

@@ -62,6 +62,13 @@ class YunetLevels(C.Structure):
                 ('w', C.c_int32 * MAX_LEVELS), ('stride', C.c_int32 * MAX_LEVELS)]
 
 
+SOFTNMS_NAIVE, SOFTNMS_LINEAR, SOFTNMS_GAUSSIAN = 0, 1, 2       # YUNET_SOFTNMS_* (YunetSoftNms.method)
+
+
+class YunetSoftNms(C.Structure):
+    _fields_ = [('method', C.c_int32), ('iou_thr', C.c_float), ('sigma', C.c_float), ('min_score', C.c_float)]
+
+
 class YunetLossCfg(C.Structure):
     _fields_ = [('box_loss', C.c_int32), ('w_cls', C.c_float), ('w_box', C.c_float),
                 ('w_obj', C.c_float), ('w_kps', C.c_float), ('box_eps', C.c_float),
@@ -186,6 +193,10 @@ _SIGNATURES = {
                               C.c_int] + [C.c_void_p] * 5),
     'yunet_detect_scratch_bytes': (C.c_size_t, [C.c_int, C.c_int]),
     'yunet_nms': (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 5),
+    'yunet_detect_soft': (C.c_int, [C.c_void_p, C.POINTER(YunetLevels), C.c_int, C.c_int, C.c_float, C.POINTER(YunetSoftNms),
+                                   C.c_int] + [C.c_void_p] * 5),
+    'yunet_soft_nms': (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_float, C.POINTER(YunetSoftNms), C.c_int] +
+                       [C.c_void_p] * 5),
     'yunet_aug_decide': (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.POINTER(YunetAugCfg), C.c_int, C.c_int, C.c_int, C.c_uint32,
                                                       C.c_int] + [C.c_void_p] * 5),
     'yunet_aug_pixels': (C.c_int, [C.POINTER(YunetAugPixels), C.POINTER(YunetAugCfg), C.c_int, C.c_void_p, C.c_void_p]),

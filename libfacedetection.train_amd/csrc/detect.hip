@@ -9,7 +9,12 @@
 //   keys (score bits, ~prior index) sorted descending in LDS (bitonic), so equal scores keep the
 //   lower prior index first; sorted boxes live in LDS (first BOX_CAP) and a global scratch;
 //   a suppressed candidate's key is zeroed in place.
+// Soft-NMS (mmcv.ops.soft_nms, restated from mmcv 1.3.17's softnms_cpu: test_cfg.nms.type = 'soft_nms') is a second
+// pair of kernels on the same compaction, sort and decode: the score in the high half of a key is rewritten after
+// every selection, so each round is an arg-max over the live keys followed by a decay pass (soft_rounds below).
 // Compiled with -ffp-contract=off (same single-rounding arithmetic as the torch reference).
+#include <cmath>
+
 #include "common.h"
 #include "levels.h"
 
@@ -89,10 +94,88 @@ __device__ __forceinline__ float key_score(unsigned k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
+// Soft-NMS rounds over the sorted, decoded candidates.  keys[i] = score_key(CURRENT score) << 32 | ~index, 0 = dead
+// (selected earlier, or decayed below min_score); the box of position i never moves.  One round:
+//   arg-max over the live keys (a max over u64: larger score first, then -- the low half -- the lower index),
+//   the winner goes out with its current score, every other live candidate is decayed against it
+//   (score *= weight, one fp32 multiply) and dies when its score falls below min_score -- also when weight == 1,
+//   as in mmcv, so a candidate that STARTS below min_score survives only as the first selection.
+// Thread t owns the positions t, t + DET_THREADS, ... in every pass: a key is read and rewritten by one thread only, so
+// the rounds need no barrier for the keys, and the decay pass of round r already collects that thread's maximum for
+// round r + 1.  The only shared state is the 16 wave maxima; they alternate between two buffers, so one barrier per
+// round is enough (a thread can write buffer b again only after passing the barrier of the round in between, which no
+// thread still reading b has reached).
+// Every thread computes the same winner from the same 16 entries, so `win == 0` (nothing live) is a uniform break, and
+// the loop is counted: a round removes at least its selection, so min(K, max_out) rounds always suffice.
 template <typename KeyPtr, typename Src>
+__device__ __forceinline__ void soft_rounds(KeyPtr keys, int K, const Src& src, const YunetSoftNms cfg, int max_out,
+                                            const float4* __restrict__ gbox, const float4* sbox,
+                                            float* __restrict__ dn, float* __restrict__ kn,
+                                            int32_t* __restrict__ keep_n, int32_t* __restrict__ count_n) {
+    constexpr int WAVES = DET_THREADS / 64;
+    __shared__ unsigned long long s_red[2][WAVES];
+    __shared__ int s_pos[2][WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned long long bk = 0ull;       // this thread's largest live key and its position
+    int bp = 0;
+    for (int i = tid; i < K; i += DET_THREADS) {
+        const unsigned long long k = keys[i];
+        if (k > bk) { bk = k; bp = i; }
+    }
+    const int rounds = K < max_out ? K : max_out;
+    int kept = 0;
+    for (int r = 0; r < rounds; ++r) {
+        const int buf = r & 1;
+        unsigned long long wk = bk;
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) {
+            const unsigned long long o = __shfl_xor(wk, m, 64);
+            wk = o > wk ? o : wk;
+        }
+        // live keys are unique (the index half), so exactly one lane holds the wave's maximum; lane 0 reports an empty wave
+        if (wk != 0ull ? bk == wk : lane == 0) { s_red[buf][wave] = wk; s_pos[buf][wave] = bp; }
+        __syncthreads();
+        unsigned long long win = 0ull;
+        int wp = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) {
+            const unsigned long long k = s_red[buf][w];
+            if (k > win) { win = k; wp = s_pos[buf][w]; }
+        }
+        if (win == 0ull) break;
+        const float4 bi = wp < DET_BOX_CAP ? sbox[wp] : gbox[wp];
+        if (tid == 0) {
+            dn[r * 5 + 0] = bi.x; dn[r * 5 + 1] = bi.y; dn[r * 5 + 2] = bi.z; dn[r * 5 + 3] = bi.w;
+            dn[r * 5 + 4] = key_score((unsigned)(win >> 32));
+            src.extra((int)(0xFFFFFFFFu - (unsigned)(win & 0xFFFFFFFFull)), r, kn, keep_n);
+        }
+        kept = r + 1;
+        if (kept == rounds) break;      // nothing is selected after this round: its decay pass would be unread
+        bk = 0ull;
+        bp = 0;
+        for (int j = tid; j < K; j += DET_THREADS) {
+            const unsigned long long k = keys[j];
+            if (k == 0ull) continue;
+            if (j == wp) { keys[j] = 0ull; continue; }
+            const float4 bj = j < DET_BOX_CAP ? sbox[j] : gbox[j];
+            const float ovr = nms_iou(bi, bj);
+            float weight = 1.0f;
+            if (cfg.method == YUNET_SOFTNMS_GAUSSIAN) weight = expf(-(ovr * ovr) / cfg.sigma);
+            else if (ovr >= cfg.iou_thr) weight = cfg.method == YUNET_SOFTNMS_LINEAR ? 1.0f - ovr : 0.0f;
+            const float s = key_score((unsigned)(k >> 32)) * weight;
+            const unsigned long long nk =
+                s < cfg.min_score ? 0ull : ((unsigned long long)score_key(s) << 32) | (k & 0xFFFFFFFFull);
+            keys[j] = nk;
+            if (nk > bk) { bk = nk; bp = j; }
+        }
+    }
+    if (tid == 0) *count_n = kept;
+}
+
+template <bool SOFT, typename KeyPtr, typename Src>
 __device__ __forceinline__ void sort_decode_nms(KeyPtr keys, int padn, int K, const Src& src, float iou_thr,
-                                                int max_out, float4* __restrict__ gbox, float4* sbox,
-                                                float* __restrict__ dn, float* __restrict__ kn,
+                                                const YunetSoftNms soft, int max_out, float4* __restrict__ gbox,
+                                                float4* sbox, float* __restrict__ dn, float* __restrict__ kn,
                                                 int32_t* __restrict__ keep_n, int32_t* __restrict__ count_n) {
     const int tid = threadIdx.x;
     for (int k = 2; k <= padn; k <<= 1)
@@ -115,6 +198,10 @@ __device__ __forceinline__ void sort_decode_nms(KeyPtr keys, int padn, int K, co
         if (i < DET_BOX_CAP) sbox[i] = b;
     }
     __syncthreads();
+    if constexpr (SOFT) {
+        soft_rounds(keys, K, src, soft, max_out, gbox, sbox, dn, kn, keep_n, count_n);
+        return;
+    }
     // ---- greedy NMS in score order ---------------------------------------------------------------------
     // `kept` lives in a register of EVERY thread: keys[i] is uniform after the barrier that ends the
     // previous iteration, so all threads count the same survivors and take the same break (a shared
@@ -161,64 +248,46 @@ __device__ __forceinline__ void sort_decode_nms(KeyPtr keys, int padn, int K, co
 // over the next power of two above their number, not above P: any P fits (a 1024x1024 test image has
 // P = 21504), and the usual few hundred candidates sort in a fraction of the time.
 //   scratch per image: float4 boxes[P] | u64 keys[padP]      (padP = next power of two >= P)
+// Two kernel templates, one body (detect_kernel_body.inc): the Soft-NMS instances are kernels of their own, so the
+// greedy ones keep their instruction streams.
 template <bool FROM_HEAD>
 __global__ __launch_bounds__(DET_THREADS) void detect_kernel(
     const float* __restrict__ flat, const float* __restrict__ in_scores, const int32_t* __restrict__ in_count,
     const Levels L, int P, int padP, int lds_keys, float score_thr,
     float iou_thr, int max_out, float* __restrict__ dets, float* __restrict__ kps_out,
     int32_t* __restrict__ keep, int32_t* __restrict__ count, unsigned char* __restrict__ scratch) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned long long* skeys = reinterpret_cast<unsigned long long*>(smem);           // [lds_keys]
-    float4* sbox = reinterpret_cast<float4*>(smem + (size_t)lds_keys * 8);             // [DET_BOX_CAP]
-    __shared__ int s_k;
-    const int n = blockIdx.x, tid = threadIdx.x;
-    // FROM_HEAD: flat = [N,P,16] head outputs; else flat = [N,P,4] boxes with in_scores [N,P] and an
-    // optional per-set element count (yunet_nms: the merged candidates of test-time augmentation)
-    const FlatSrc hsrc{flat + (size_t)n * P * 16, L};
-    const BoxSrc bsrc{flat + (size_t)n * P * 4, in_scores ? in_scores + (size_t)n * P : nullptr};
-    const int Pn = (!FROM_HEAD && in_count) ? min(in_count[n], P) : P;
-    unsigned char* sc = scratch + (size_t)n * ((size_t)P * 16 + (size_t)padP * 8);
-    float4* gbox = reinterpret_cast<float4*>(sc);
-    unsigned long long* gkeys = reinterpret_cast<unsigned long long*>(sc + (size_t)P * 16);
-    const bool small = padP <= lds_keys;       // every prior fits in LDS: no global key traffic at all
-
-    // ---- scores, threshold, compaction (order is irrelevant: the keys are sorted next) -----------------
-    if (tid == 0) s_k = 0;
-    __syncthreads();
-    for (int p = tid; p < Pn; p += DET_THREADS) {
-        float sc_;
-        const bool ok = FROM_HEAD ? hsrc.score(p, score_thr, sc_) : bsrc.score(p, score_thr, sc_);
-        if (ok) {
-            const unsigned long long key =
-                ((unsigned long long)score_key(sc_) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)p);
-            const int slot = atomicAdd(&s_k, 1);
-            if (small) skeys[slot] = key;
-            else gkeys[slot] = key;
-        }
-    }
-    __syncthreads();
-    const int K = s_k;
-    int padn = 2;
-    while (padn < K) padn <<= 1;
-    float* dn = dets + (size_t)n * max_out * 5;
-    float* kn = kps_out ? kps_out + (size_t)n * max_out * 10 : nullptr;
-    int32_t* kp = keep ? keep + (size_t)n * max_out : nullptr;
-    auto run = [&](auto keys) {
-        if constexpr (FROM_HEAD) sort_decode_nms(keys, padn, K, hsrc, iou_thr, max_out, gbox, sbox, dn, kn, kp, count + n);
-        else sort_decode_nms(keys, padn, K, bsrc, iou_thr, max_out, gbox, sbox, dn, kn, kp, count + n);
-    };
-    if (padn <= lds_keys) {
-        if (!small)
-            for (int i = tid; i < K; i += DET_THREADS) skeys[i] = gkeys[i];
-        for (int i = K + tid; i < padn; i += DET_THREADS) skeys[i] = 0ull;
-        __syncthreads();
-        run(skeys);
-    } else {
-        for (int i = K + tid; i < padn; i += DET_THREADS) gkeys[i] = 0ull;
-        __syncthreads();
-        run(gkeys);
-    }
+    constexpr bool SOFT = false;
+    constexpr YunetSoftNms soft{};
+#include "detect_kernel_body.inc"
 }
+
+template <bool FROM_HEAD>
+__global__ __launch_bounds__(DET_THREADS) void detect_soft_kernel(
+    const float* __restrict__ flat, const float* __restrict__ in_scores, const int32_t* __restrict__ in_count,
+    const Levels L, int P, int padP, int lds_keys, float score_thr,
+    const YunetSoftNms soft, int max_out, float* __restrict__ dets, float* __restrict__ kps_out,
+    int32_t* __restrict__ keep, int32_t* __restrict__ count, unsigned char* __restrict__ scratch) {
+    constexpr bool SOFT = true;
+    constexpr float iou_thr = 0.0f;
+#include "detect_kernel_body.inc"
+}
+
+bool soft_cfg_ok(const YunetSoftNms* c) {
+    if (!c || c->method < YUNET_SOFTNMS_NAIVE || c->method > YUNET_SOFTNMS_GAUSSIAN) return false;
+    if (!std::isfinite(c->iou_thr) || !std::isfinite(c->min_score)) return false;
+    if (c->method == YUNET_SOFTNMS_GAUSSIAN && !(std::isfinite(c->sigma) && c->sigma > 0.0f)) return false;
+    return true;
+}
+
+// launch geometry of the two Soft-NMS entry points (the greedy ones' rule): LDS keys for P candidates, dynamic-LDS size
+struct DetLaunch { int padP, lds_keys; size_t smem; };
+DetLaunch soft_launch(int P) {
+    int padP = 2;
+    while (padP < P) padP <<= 1;
+    const int lds_keys = padP < DET_LDS_KEYS ? padP : DET_LDS_KEYS;
+    return {padP, lds_keys, (size_t)lds_keys * 8 + (size_t)DET_BOX_CAP * 16};
+}
+constexpr size_t DET_SMEM_MAX = (size_t)DET_LDS_KEYS * 8 + (size_t)DET_BOX_CAP * 16;
 
 }  // namespace
 
@@ -275,6 +344,46 @@ extern "C" int yunet_nms(const float* boxes, const float* scores, const int32_t*
     Levels L{};
     hipLaunchKernelGGL(detect_kernel<false>, dim3(N), dim3(DET_THREADS), smem, (hipStream_t)stream, boxes, scores,
                        counts, L, K, padP, lds_keys, score_thr, iou_thr, max_out, dets, (float*)nullptr, keep, count,
+                       (unsigned char*)scratch);
+    return hip_status();
+}
+
+extern "C" int yunet_detect_soft(const float* flat, const YunetLevels* lv, int N, int P, float score_thr,
+                                 const YunetSoftNms* soft, int max_out, float* dets, float* kps, int32_t* count,
+                                 void* scratch, void* stream) {
+    if (!flat || !lv || !dets || !count || !scratch || N < 1 || P < 1 || P > (1 << 24) || max_out < 1 || !soft_cfg_ok(soft))
+        return YUNET_EINVAL;
+    const Levels L = make_levels(lv);
+    if (L.base[YUNET_MAX_LEVELS] != P) return YUNET_EINVAL;
+    const DetLaunch g = soft_launch(P);
+    static PerDevice attr_set;
+    if (per_device(attr_set, [] {
+            return hipFuncSetAttribute(reinterpret_cast<const void*>(detect_soft_kernel<true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)DET_SMEM_MAX) == hipSuccess ? 1 : -1;
+        }) < 0)
+        return YUNET_EINVAL;
+    hipLaunchKernelGGL(detect_soft_kernel<true>, dim3(N), dim3(DET_THREADS), g.smem, (hipStream_t)stream, flat,
+                       (const float*)nullptr, (const int32_t*)nullptr, L, P, g.padP, g.lds_keys, score_thr, *soft,
+                       max_out, dets, kps, (int32_t*)nullptr, count, (unsigned char*)scratch);
+    return hip_status();
+}
+
+extern "C" int yunet_soft_nms(const float* boxes, const float* scores, const int32_t* counts, int N, int K,
+                              float score_thr, const YunetSoftNms* soft, int max_out, float* dets, int32_t* keep,
+                              int32_t* count, void* scratch, void* stream) {
+    if (!boxes || !scores || !dets || !count || !scratch || N < 1 || K < 1 || K > (1 << 24) || max_out < 1 ||
+        !soft_cfg_ok(soft))
+        return YUNET_EINVAL;
+    const DetLaunch g = soft_launch(K);
+    static PerDevice attr_set;
+    if (per_device(attr_set, [] {
+            return hipFuncSetAttribute(reinterpret_cast<const void*>(detect_soft_kernel<false>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)DET_SMEM_MAX) == hipSuccess ? 1 : -1;
+        }) < 0)
+        return YUNET_EINVAL;
+    Levels L{};
+    hipLaunchKernelGGL(detect_soft_kernel<false>, dim3(N), dim3(DET_THREADS), g.smem, (hipStream_t)stream, boxes, scores,
+                       counts, L, K, g.padP, g.lds_keys, score_thr, *soft, max_out, dets, (float*)nullptr, keep, count,
                        (unsigned char*)scratch);
     return hip_status();
 }

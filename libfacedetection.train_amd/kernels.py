@@ -343,10 +343,22 @@ def make_levels(sizes, strides):
     return lv
 
 
-def detect(flat, sizes, strides, score_thr=0.02, iou_thr=0.45, max_out=None, with_kps=True):
+SOFT_NMS_METHODS = {'naive': L.SOFTNMS_NAIVE, 'linear': L.SOFTNMS_LINEAR, 'gaussian': L.SOFTNMS_GAUSSIAN}
+
+
+def make_soft_nms(iou_thr=0.3, sigma=0.5, min_score=1e-3, method='linear'):
+    """-> YunetSoftNms (mmcv.ops.soft_nms's values and defaults; method by name)."""
+    if method not in SOFT_NMS_METHODS:
+        raise ValueError(f'soft_nms method {method!r}: one of {sorted(SOFT_NMS_METHODS)}')
+    return L.YunetSoftNms(SOFT_NMS_METHODS[method], float(iou_thr), float(sigma), float(min_score))
+
+
+def detect(flat, sizes, strides, score_thr=0.02, iou_thr=0.45, max_out=None, with_kps=True, soft=None):
     """flat [N,P,16] raw head outputs -> (dets [N,max_out,5], kps [N,max_out,10] or None, count [N]).
-    Rows at or beyond count[i] are unspecified."""
+    Rows at or beyond count[i] are unspecified.  soft = dict(iou_thr, sigma, min_score, method) (any subset; defaults of
+    make_soft_nms) runs Soft-NMS in place of the greedy sweep (yunet_detect_soft; iou_thr is then the dict's)."""
     _chk_f32(flat)
+    cfg = None if soft is None else make_soft_nms(**soft)
     n, p = flat.shape[0], flat.shape[1]
     max_out = p if max_out is None or max_out < 0 else int(max_out)
     dev = flat.device
@@ -355,9 +367,14 @@ def detect(flat, sizes, strides, score_thr=0.02, iou_thr=0.45, max_out=None, wit
     count = torch.empty(n, device=dev, dtype=torch.int32)
     scratch = torch.empty(int(L.load().yunet_detect_scratch_bytes(n, p)), device=dev, dtype=torch.uint8)
     lv = make_levels(sizes, strides)
-    L.check(L.load().yunet_detect(_p(flat), C.byref(lv), n, p, float(score_thr), float(iou_thr), max_out,
-                                  _p(dets), _p(kps) if with_kps else None, _p(count), _p(scratch), _stream()),
-            'yunet_detect')
+    if cfg is None:
+        L.check(L.load().yunet_detect(_p(flat), C.byref(lv), n, p, float(score_thr), float(iou_thr), max_out,
+                                      _p(dets), _p(kps) if with_kps else None, _p(count), _p(scratch), _stream()),
+                'yunet_detect')
+    else:
+        L.check(L.load().yunet_detect_soft(_p(flat), C.byref(lv), n, p, float(score_thr), C.byref(cfg), max_out,
+                                           _p(dets), _p(kps) if with_kps else None, _p(count), _p(scratch), _stream()),
+                'yunet_detect_soft')
     return dets, kps, count
 
 
@@ -385,6 +402,24 @@ def nms(boxes, scores, iou_thr=0.45, score_thr=float('-inf'), max_out=None, coun
     scratch = torch.empty(int(L.load().yunet_detect_scratch_bytes(n, k)), device=dev, dtype=torch.uint8)
     L.check(L.load().yunet_nms(_p(boxes), _p(scores), _p(counts), n, k, float(score_thr), float(iou_thr),
                                max_out, _p(dets), _p(keep), _p(count), _p(scratch), _stream()), 'yunet_nms')
+    return dets, keep, count
+
+
+def soft_nms(boxes, scores, iou_thr=0.3, sigma=0.5, min_score=1e-3, method='linear', score_thr=float('-inf'),
+             max_out=None, counts=None):
+    """Single-class Soft-NMS (mmcv.ops.soft_nms, offset 0) of explicit candidates: the arguments and results of nms();
+    dets[..., 4] holds the decayed scores, non-increasing.  Exact score ties go to the lower index."""
+    _chk_f32(boxes, scores)
+    cfg = make_soft_nms(iou_thr, sigma, min_score, method)
+    n, k = scores.shape
+    max_out = k if max_out is None or max_out < 0 else int(max_out)
+    dev = boxes.device
+    dets = torch.empty(n, max_out, 5, device=dev, dtype=torch.float32)
+    keep = torch.empty(n, max_out, device=dev, dtype=torch.int32)
+    count = torch.empty(n, device=dev, dtype=torch.int32)
+    scratch = torch.empty(int(L.load().yunet_detect_scratch_bytes(n, k)), device=dev, dtype=torch.uint8)
+    L.check(L.load().yunet_soft_nms(_p(boxes), _p(scores), _p(counts), n, k, float(score_thr), C.byref(cfg),
+                                    max_out, _p(dets), _p(keep), _p(count), _p(scratch), _stream()), 'yunet_soft_nms')
     return dets, keep, count
 
 

@@ -211,7 +211,10 @@ class YuNet(nn.Module):
         if cfg is None:
             raise ValueError('test_cfg (score_thr, nms.iou_threshold, max_per_img) is required')
         from . import kernels as K
+        from .yunet_head import soft_nms_args
         nms_cfg = cfg.get('nms', dict(type='nms', iou_threshold=0.45))
+        # the merge is Soft-NMS when the config says so (the same keys as the head's own path); validated before any launch
+        soft = soft_nms_args(nms_cfg) if nms_cfg.get('type', 'nms') == 'soft_nms' else None
         boxes, scores = [], []
         for img, metas in zip(imgs, img_metas):
             if img.shape[0] != 1:
@@ -229,8 +232,12 @@ class YuNet(nn.Module):
         boxes, scores = torch.cat(boxes), torch.cat(scores)
         if boxes.shape[0] == 0:
             return [[torch.zeros(0, 5).numpy()]]
-        dets, _, cnt = K.nms(boxes[None].contiguous(), scores[None].contiguous(),
-                             nms_cfg.get('iou_threshold', 0.45), max_out=cfg.get('max_per_img', -1))
+        if soft is not None:
+            dets, _, cnt = K.soft_nms(boxes[None].contiguous(), scores[None].contiguous(),
+                                      max_out=cfg.get('max_per_img', -1), **soft)
+        else:
+            dets, _, cnt = K.nms(boxes[None].contiguous(), scores[None].contiguous(),
+                                 nms_cfg.get('iou_threshold', 0.45), max_out=cfg.get('max_per_img', -1))
         out = dets[0, :int(cnt[0])].clone()
         if not rescale:
             sf0 = torch.as_tensor(img_metas[0][0]['scale_factor'], dtype=torch.float32, device=out.device).reshape(-1)

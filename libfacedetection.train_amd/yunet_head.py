@@ -33,6 +33,23 @@ def pad_gt(gt_bboxes, gt_kpss, device):
     return gb, gk, torch.tensor(counts, dtype=torch.int32, device=device)
 
 
+def soft_nms_args(nms):
+    """test_cfg.nms = dict(type='soft_nms', ...) -> the `soft` dict of kernels.detect / the keywords of kernels.soft_nms,
+    with mmcv.ops.soft_nms's keys and defaults.  class_agnostic and split_thr (batched_nms's own keys) change nothing
+    with one class and are ignored; offset != 0 is not built; any other key is an error."""
+    known = ('type', 'iou_threshold', 'sigma', 'min_score', 'method', 'offset', 'class_agnostic', 'split_thr')
+    for key in nms:
+        if key not in known:
+            raise ValueError(f"test_cfg.nms (soft_nms): unknown key {key!r}")
+    if nms.get('offset', 0) != 0:
+        raise NotImplementedError(f"test_cfg.nms (soft_nms): offset={nms.get('offset')!r} (only offset=0 is built)")
+    method = nms.get('method', 'linear')
+    if method not in K.SOFT_NMS_METHODS:
+        raise ValueError(f"test_cfg.nms (soft_nms): unknown method {method!r} (one of {sorted(K.SOFT_NMS_METHODS)})")
+    return dict(iou_thr=nms.get('iou_threshold', 0.3), sigma=nms.get('sigma', 0.5),
+                min_score=nms.get('min_score', 1e-3), method=method)
+
+
 class _LossStep(torch.autograd.Function):
     """flat [N,P,16] -> (loss_cls, loss_bbox, loss_obj, loss_kps); the kernel already produced
     d(loss_i)/d(flat) for the loss that owns each channel."""
@@ -239,6 +256,9 @@ class YuNet_Head(nn.Module):
         if cfg is None:
             raise ValueError('test_cfg (score_thr, nms.iou_threshold, max_per_img) is required')
         nms = cfg.get('nms', dict(type='nms', iou_threshold=0.45))
+        if nms.get('type', 'nms') == 'soft_nms':
+            return K.detect(flat, sizes, self.strides, cfg.get('score_thr', 0.02), max_out=cfg.get('max_per_img', -1),
+                            soft=soft_nms_args(nms))
         if nms.get('type', 'nms') != 'nms':
             raise NotImplementedError(f"nms type {nms.get('type')!r}")
         return K.detect(flat, sizes, self.strides, cfg.get('score_thr', 0.02),

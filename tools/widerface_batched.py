@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """tools/test_widerface.py through the batched device test pipeline (yunet_amd/test_pipeline.py): the same command line
 (CONFIG CHECKPOINT [--out DIR] [--save-preds] [--thr T] [--mode M] [--gt-path D] [--max-images N]) plus `--cache device`,
-`--score {host,device}`, `--group canvas` and `--max-batch-pixels N|none`.
+`--score {host,device}`, `--group canvas`, `--max-batch-pixels N|none` and `--cfg-options K=V ...` (the overrides of
+tools/train.py, e.g. model.test_cfg.nms.type=soft_nms model.test_cfg.nms.iou_threshold=0.3; after the positional arguments).
 
 `data.test.samples_per_gpu` is read as the reference's tool reads it (default 1) and `data.test.pipeline` is rewritten
 for --mode as the reference's tool does (img_scale of the MultiScaleFlipAug, the size of its Pad; an empty list is the
@@ -63,6 +64,9 @@ def own_parser():
                      metavar='N|none',
                      help="canvas pixels a grouped batch may hold, 'none' for no cap (also data.test.max_batch_pixels; "
                           'default samples_per_gpu * 1024 * 1024)')
+    from yunet_amd.registry import DictAction
+    own.add_argument('--cfg-options', nargs='+', action=DictAction,
+                     help='override settings of the config, key.sub=value (e.g. model.test_cfg.nms.type=soft_nms)')
     return own
 
 
@@ -83,6 +87,8 @@ def main():
     from yunet_amd import evaluation as E
     from yunet_amd.test_pipeline import DeviceTestPipeline
     cfg = yunet_amd.Config.fromfile(a.config)
+    if b.cfg_options is not None:
+        cfg.merge_from_dict(b.cfg_options)
     tcfg = dict(cfg.data.test)
     gt_path = a.gt_path or os.path.join(os.path.dirname(tcfg['ann_file']), 'gt')
     if a.thr != -1.:
