@@ -151,7 +151,8 @@ def bwd_ref(x, w1, b1, w2, b2, z, dy, in_bn=None, out_bn=None, dy_scale=None, bf
     output (ReLU mask applied; out_bn.bstats = its sums) or, without out_bn, wrt z scaled per channel by dy_scale.
     pool_idx: dy is the pooled gradient, routed to the recorded window positions.
     bf16_gemm: dp_bwd64's rule (p, dW1, da from bf16(a) and bf16(W1)).
-    -> dict(dx, dw1, db1, dw2, db2, in_bst) and amb = {dw1, dw2}: the ambiguous-operand terms."""
+    -> dict(dx, dw1, db1, dw2, db2, in_bst), da = dx before the input ReLU's mask, and amb = {dw1, dw2}: the
+    ambiguous-operand terms."""
     x, w1, b1, w2, b2, z, dy, dy_scale = _f64(x, w1, b1, w2, b2, z, dy, dy_scale)
     if pool_idx is not None:
         dy = expand_pooled(dy, pool_idx)
@@ -191,7 +192,7 @@ def bwd_ref(x, w1, b1, w2, b2, z, dy, in_bn=None, out_bn=None, dy_scale=None, bf
         amb['dw1'] = pd.abs().reshape(-1, pd.shape[-1]).t() @ d_a.reshape(-1, d_a.shape[-1])
         dp_amb = d_a @ rne_bf16(w1).abs().t()
         amb['dw2'] = depthwise_wgrad(dp_amb, dz.abs())
-    return dict(dx=dx, dw1=W1.grad, db1=B1.grad, dw2=W2.grad, db2=B2.grad, in_bst=in_bst, amb=amb)
+    return dict(dx=dx, da=da, dw1=W1.grad, db1=B1.grad, dw2=W2.grad, db2=B2.grad, in_bst=in_bst, amb=amb)
 
 
 def depthwise_wgrad(p, dz):
