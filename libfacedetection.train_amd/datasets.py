@@ -12,6 +12,7 @@ cv2.imread) and hands decoded uint8 sources to `pipelines.DevicePipeline`, which
 RandomSquareCrop -> Resize -> RandomFlip -> collate as HIP kernels
 (`RetinaFaceSource.batch`, the counterpart of `runner.SyntheticSourceImages`).
 """
+import logging
 import os
 
 import numpy as np
@@ -20,6 +21,7 @@ import torch
 from .builder import DATASETS
 
 NK = 5
+_log = logging.getLogger(__name__)
 
 
 def parse_ann_line(line, min_size=None, test_mode=False):
@@ -213,6 +215,12 @@ def flatten_multi_image_mix(dcfg):
     return inner
 
 
+def gt_counts(dataset):
+    """Non-ignored faces per image of dataset.data_infos -- the rows get_ann_info returns as `bboxes`; read from the
+    annotations, no image is decoded."""
+    return [int(len(dataset.get_ann_info(i)['bboxes'])) for i in range(len(getattr(dataset, 'data_infos', ())))]
+
+
 class RetinaFaceSource:
     """Training data source over a RetinaFaceDataset: iteration `it` of rank r is batch it % iters_per_epoch of the
     reference's DistributedGroupSampler(dataset, samples_per_gpu, world, r, seed) in epoch it // iters_per_epoch
@@ -227,11 +235,45 @@ class RetinaFaceSource:
                     crop-window rectangles travel (WindowFeed).  host_fetch (cache='host' only): None or 'dma' = one
                     hipMemcpy2DAsync per rectangle after a host wait on the plan; 'kernel' = the GPU reads the
                     rectangles from the pinned store itself (yunet_fetch_windows), no host wait.
-    All three give bit-identical batches; the image sizes of the labelv2 headers must be the decoded ones."""
+    All three give bit-identical batches; the image sizes of the labelv2 headers must be the decoded ones.
+
+    GT rows.  Every crop's GT is padded to one width for the whole run (one engine plan per batch geometry, nothing is
+    read back per batch); faces a crop keeps beyond it are dropped (status 2, counted by truncated()).
+    gt_capacity=None     : 64 rows (128 for max_gt > 64); the constructor warns when the dataset has larger images.
+    gt_capacity='dataset': the largest image's face count, so no crop can be truncated.
+    gt_capacity=int      : that many faces.
+    Both are rounded by pipelines.gt_capacity_rows (a power of two >= 64, at most 4096; with a Mosaic in the pipeline at
+    most 256 per image: its merged GT stays within 1024 rows, and a larger image can still truncate a merged canvas)."""
 
     def __init__(self, dataset, pipeline, samples_per_gpu=16, rank=0, world=1, seed=0, max_gt=64, workers=4,
-                 cache=None, host_fetch=None):
-        from .pipelines import DevicePipeline
+                 cache=None, host_fetch=None, gt_capacity=None):
+        from .pipelines import DevicePipeline, gt_capacity_rows
+        counts = gt_counts(dataset)
+        mosaic = any((p.get('type') if isinstance(p, dict) else type(p).__name__) == 'Mosaic' for p in pipeline)
+        if gt_capacity is None:
+            rows = 64 if max_gt <= 64 else 128
+        else:
+            if max_gt != 64:
+                raise ValueError(f'RetinaFaceSource: gt_capacity={gt_capacity!r} and max_gt={max_gt!r} both size the GT '
+                                 'rows; give one of them')
+            if isinstance(gt_capacity, str) and gt_capacity != 'dataset':
+                raise ValueError(f"RetinaFaceSource gt_capacity must be 'dataset' or an integer >= 1 (or unset), "
+                                 f'got {gt_capacity!r}')
+            want = max([1] + counts) if gt_capacity == 'dataset' else gt_capacity
+            rows = gt_capacity_rows(want, mosaic=mosaic)
+        self.gt_rows = rows                     # padded GT rows per source image (a Mosaic merges four: pipe.gmax = 4 rows)
+        over = [c for c in counts if c > rows]
+        if over:
+            if gt_capacity == 'dataset':        # only under Mosaic
+                lift = 'Mosaic takes at most 256 rows per image (1024 merged): such an image can still truncate a canvas'
+            else:
+                lift = "gt_capacity='dataset' (data.train.gt_capacity=dataset) sizes the rows for the largest image"
+                if mosaic and max(over) > 256:
+                    lift += ', under Mosaic up to 256 per image (1024 merged)'
+            _log.warning(f'RetinaFaceSource: {len(over)} images have more than {rows} faces (largest {max(over)}); '
+                         f'{sum(c - rows for c in over)} faces beyond the capacity of {rows} GT rows are dropped from '
+                         f'training whenever a crop keeps them -- {lift}')
+        self._trunc = None                      # device int64 [2]: (images, rows) truncated so far
         if cache not in (None, 'device', 'host'):
             raise ValueError(f"RetinaFaceSource cache must be None, 'device' or 'host', got {cache!r}")
         if host_fetch not in (None, 'dma', 'kernel'):
@@ -241,7 +283,7 @@ class RetinaFaceSource:
         self.host_fetch = host_fetch
         self.cache, self.store, self._feed, self._decoding = cache, None, None, {}
         self.ds, self.bs, self.rank, self.world, self.seed = dataset, samples_per_gpu, rank, world, seed
-        self.pipe = DevicePipeline(pipeline, seed=seed + 7919 * rank, gmax=64 if max_gt <= 64 else 128)
+        self.pipe = DevicePipeline(pipeline, seed=seed + 7919 * rank, gmax=rows)
         self.pipe.check_plan_cache()
         if cache != 'device':
             self.pipe.require_resident(f'RetinaFaceSource(cache={cache!r})')
@@ -338,9 +380,32 @@ class RetinaFaceSource:
         if device is None:
             raise RuntimeError('RetinaFaceSource augments on the GPU: a device is required')
         if self.cache is not None:
-            return self._cached_batch(it, device)
-        from .pipelines import SourceBatch
-        samples = self._decoded(it)
-        src = SourceBatch.from_lists([s['img'] for s in samples], [s['gt_bboxes'] for s in samples],
-                                     [s['gt_keypointss'] for s in samples], device)
-        return self.pipe(src, it)
+            out = self._cached_batch(it, device)
+        else:
+            from .pipelines import SourceBatch
+            samples = self._decoded(it)
+            src = SourceBatch.from_lists([s['img'] for s in samples], [s['gt_bboxes'] for s in samples],
+                                         [s['gt_keypointss'] for s in samples], device)
+            out = self.pipe(src, it)
+        self._count_truncated()
+        return out
+
+    def _count_truncated(self):
+        """Adds the last batch's truncated images / dropped rows to the device counters: tensor ops on the batch's own
+        stream, nothing is read back."""
+        from . import _lib as L
+        p = self.pipe.params
+        cut = p[:, 6] == 2
+        if self.pipe.mosaic is not None:        # a merged GT beyond gmax: status bit 2 of the geometry table
+            cut = cut | ((self.pipe.geom[:, L.MOSAIC_STATUS] & 2) != 0)
+        rows = (p[:, 4] - self.pipe.gmax).clamp_min(0)
+        add = torch.stack([cut.sum(), rows.sum()])
+        self._trunc = add if self._trunc is None else self._trunc + add
+
+    def truncated(self):
+        """(images, rows): how many images of the batches so far lost GT to the padded width (status 2 of the decide;
+        under Mosaic also a truncated merge), and how many kept faces lay beyond it.  Reading synchronises."""
+        if self._trunc is None:
+            return 0, 0
+        images, rows = self._trunc.tolist()
+        return int(images), int(rows)

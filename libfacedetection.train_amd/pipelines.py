@@ -293,6 +293,25 @@ class SourceBatch:
 
 
 MOSAIC_MAX_GT = 1024        # GT rows per image the engine's assign kernels are tested to
+GT_ROWS_MIN = 64            # the default padded width; a capacity never goes below it
+GT_ROWS_MAX = 4096          # yunet_assign_cfg stages Gmax 16-byte GT records in at most 64 KB of LDS
+
+
+def gt_capacity_rows(max_count, mosaic=False):
+    """Padded GT rows per source image for a capacity of `max_count` faces: the smallest power of two that is
+    >= max(max_count, 64).  mosaic=True: at most MOSAIC_MAX_GT // 4, since the merged GT of four images has to stay
+    within MOSAIC_MAX_GT rows (a larger image can then truncate a merged canvas, status 2)."""
+    if isinstance(max_count, bool) or int(max_count) != max_count or int(max_count) < 1:
+        raise ValueError(f'a GT capacity is an integer >= 1, got {max_count!r}')
+    rows = GT_ROWS_MIN
+    while rows < int(max_count):
+        rows *= 2
+    if mosaic:
+        return min(rows, MOSAIC_MAX_GT // 4)
+    if rows > GT_ROWS_MAX:
+        raise ValueError(f'a GT capacity of {int(max_count)} faces needs {rows} padded rows: the assign launch stages its '
+                         f'GT rows in LDS and takes at most {GT_ROWS_MAX} (64 KB at 16 bytes a row)')
+    return rows
 
 
 def _ptr(t):

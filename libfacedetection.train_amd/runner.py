@@ -1202,9 +1202,10 @@ def optimizer_hook_config(cfg, distributed=False):
 
 
 def train_detector(model, dataset, cfg, distributed=False, validate=False, timestamp=None,
-                   meta=None, max_iters=None, device='cuda', log=print):
+                   meta=None, max_iters=None, device='cuda', log=print, extra_hooks=()):
     """mmdet/apis/train.py:117-246 surface: DDP wrap, optimizer, EpochBasedRunner, fp16 / optimizer /
     lr / checkpoint / logger hooks from the config, auto-resume / resume / load_from, run.
+    extra_hooks: Hook objects of the caller, registered after the config's at priority LOWEST.
     Returns the logged history (one dict of python floats per logging interval)."""
     if wants_deterministic(cfg):
         if cfg.get('fp16', None) is not None or \
@@ -1255,6 +1256,8 @@ def train_detector(model, dataset, cfg, distributed=False, validate=False, times
                                           **batched, **eval_cfg), 'LOW')
         else:
             log(f"validate: {val_cfg.get('ann_file')} not found -- no EvalHook registered")
+    for h in extra_hooks:
+        runner.register_hook(h, 'LOWEST')
     resume_from = cfg.get('resume_from')
     if not resume_from and cfg.get('auto_resume') and cfg.get('work_dir'):
         resume_from = find_latest_checkpoint(cfg.work_dir)

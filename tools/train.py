@@ -11,6 +11,7 @@ Multi-GPU (one process per GPU, RCCL):
       tools/train.py configs/yunet_n.py --launcher pytorch
 """
 import argparse
+import logging
 import os
 import sys
 import time
@@ -125,9 +126,12 @@ def build_source(cfg, rank, world, seed, dcfg=None):
         if cache not in (None, 'device', 'host'):
             raise ValueError(f"data.train.cache must be device or host (or unset), got {cache!r}")      # (data.val.cache: the workflow's source)
         host_fetch = dcfg.get('host_fetch')              # data.train.host_fetch=dma|kernel (cache=host only)
+        gt_capacity = dcfg.get('gt_capacity')            # data.train.gt_capacity=dataset|N: padded GT rows (RetinaFaceSource)
+        if isinstance(gt_capacity, str) and gt_capacity.isdigit():
+            gt_capacity = int(gt_capacity)
         dataset = yunet_amd.build_dataset(dcfg)
         return RetinaFaceSource(dataset, dcfg['pipeline'], samples_per_gpu=cfg.data.samples_per_gpu, rank=rank,
-                                world=world, seed=seed, cache=cache, host_fetch=host_fetch)
+                                world=world, seed=seed, cache=cache, host_fetch=host_fetch, gt_capacity=gt_capacity)
     raise SystemExit('data sources: RetinaFaceDataset (labelv2 + image files, augmented on the GPU; also wrapped in '
                      'MultiImageMixDataset for Mosaic), '
                      'SyntheticWiderFace (ready batches) or SyntheticSourceImages (decoded synthetic '
@@ -160,6 +164,27 @@ def build_sources(cfg, rank, world, seed):
     return sources
 
 
+class TruncatedGtReport(R.Hook):
+    """After every training / validation epoch (and at the end of a run cut short): one WARNING per source whose batches
+    lost GT rows to the padded width since the last report (RetinaFaceSource.truncated()).  Silent otherwise."""
+
+    def __init__(self, sources, names):
+        self.sources = [(n, s) for n, s in zip(names, sources) if hasattr(s, 'truncated')]
+        self.seen = {n: (0, 0) for n, _ in self.sources}
+
+    def after_epoch(self, runner):
+        for name, src in self.sources:
+            images, rows = src.truncated()          # the one host read per epoch
+            d_images, d_rows = images - self.seen[name][0], rows - self.seen[name][1]
+            self.seen[name] = (images, rows)
+            if d_images or d_rows:
+                logging.getLogger('yunet_amd.datasets').warning(
+                    f'epoch {runner.epoch + 1}: {name} lost {d_rows} GT faces of {d_images} images to the {src.pipe.gmax} '
+                    f'padded GT rows (they train as background) -- {name}.gt_capacity=dataset keeps them')
+
+    after_run = after_epoch
+
+
 def main(argv=None):
     args = parse_args(argv)
     cfg = prepare_config(args)
@@ -189,7 +214,8 @@ def main(argv=None):
     main.last_source = sources[0]              # (measurement tools read the source's own timing: tools/train_e2e.py)
     meta = dict(config=cfg.pretty_text, seed=seed, exp_name=os.path.basename(args.config), CLASSES=('face',))
     hist = R.train_detector(model, ds, cfg, distributed=distributed, validate=not args.no_validate,
-                            timestamp=timestamp, meta=meta, max_iters=args.max_iters)
+                            timestamp=timestamp, meta=meta, max_iters=args.max_iters,
+                            extra_hooks=[TruncatedGtReport(sources, ['data.train', 'data.val'])])
     dump = os.environ.get('YUNET_DUMP_PARAM_SUM')
     if dump:
         # launcher tests: every rank leaves a checksum of its parameters (data-parallel ranks must end identical)
