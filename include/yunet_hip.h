@@ -158,6 +158,19 @@ int yunet_stem_bwd(const float* img, const float* z, const float* dy, const Yune
 int yunet_stem_bwd_rz(const float* img, const float* w, const float* b, const float* dy, const YunetBN* bn,
                       float* wgrad_partials, int wgrad_blocks, int N, int H, int W, int cmid, void* stream);
 
+/* Gradient with respect to the image: the backward-data of Conv_head.conv1 through bn1 (additive: the ABI number stays).
+ *   dz = scale (dy - (sum dy + xhat sum(dy xhat)) / count) per z pixel and channel, from `bn` exactly as the weight-gradient
+ *   entries above derive it (a frozen layer's reader descriptor has zero bstats: dz = scale dy, and z is not read);
+ *   dimg[n][c][y][x] = sum_k sum_(ky,kx) w[k][c][ky][kx] dz[n][(y + 1 - ky) / 2][(x + 1 - kx) / 2][k] over the taps whose
+ *   quotients are integers inside the map, in fp32 FMAs in a fixed order (no atomics: same input, same bits).
+ * z [N,H/2,W/2,cmid] the stem's raw output as stored (fp32; bf16 for the _bf16 entry), dy [N,H/2,W/2,cmid] fp32 = the
+ * gradient w.r.t. bn1's output with the ReLU mask applied (what yunet_stem_bwd reads), w [cmid,3,3,3], dimg [N,3,H,W] fp32
+ * NCHW, 16-byte aligned: every element is written exactly once with plain stores.  YUNET_EINVAL, nothing launched, for a
+ * NULL pointer (z, dy, bn and its four pointers, w, dimg), odd H or W, cmid != 16 or N < 1.
+ * In an op list: YUNET_OP_STEM_BWD_DX. */
+int yunet_stem_bwd_dx(const float* z, const float* dy, const YunetBN* bn, const float* w, float* dimg,
+                      int N, int H, int W, int cmid, void* stream);
+
 int yunet_dp_fwd(const YunetDP* d, void* stream);
 int yunet_dp_bwd(const YunetDP* d, void* stream);
 
@@ -467,7 +480,9 @@ enum {
     YUNET_OP_SGD, YUNET_OP_MEMSET, YUNET_OP_BN_BATCH, YUNET_OP_REDUCE_BATCH,
     YUNET_OP_FORK, YUNET_OP_JOIN,
     YUNET_OP_ADD,     /* ABI 9: yunet_add(p[0], p[1], p[2], n = i[1] << 32 | i[0]) */
-    YUNET_OP_BN_FOLD  /* yunet_bn_fold(p[0], i[0], i[1]); YUNET_OP_STEM_FWD with i[4] = det_rows > 0 is yunet_stem_fwd_det */
+    YUNET_OP_BN_FOLD, /* yunet_bn_fold(p[0], i[0], i[1]); YUNET_OP_STEM_FWD with i[4] = det_rows > 0 is yunet_stem_fwd_det */
+    YUNET_OP_STEM_BWD_DX  /* yunet_stem_bwd_dx[_bf16 by i[11]](z = p[1], dy = p[2], &bn[0], w = p[3], dimg = p[0],
+                             N = i[0], H = i[1], W = i[2], cmid = i[3]) */
 };
 /* Lanes (ABI 4).  The head chains of the pyramid levels (share conv -> fused head, and their backward) are
  * mutually independent: mmdet/models/dense_heads/yunet_head.py:175-247 walks them in a Python loop, and on the
@@ -507,6 +522,8 @@ int yunet_stem_fwd_bf16(const float* img, const float* w, const float* b, float*
 int yunet_stem_bwd_bf16(const float* img, const float* z, const float* dy, const YunetBN* bn,
                         float* wgrad_partials, int wgrad_blocks, int N, int H, int W, int cmid,
                         void* stream);
+int yunet_stem_bwd_dx_bf16(const float* z, const float* dy, const YunetBN* bn, const float* w, float* dimg,
+                           int N, int H, int W, int cmid, void* stream);
 int yunet_dp_fwd_bf16(const YunetDP* d, void* stream);
 int yunet_dp_fwd_group_bf16(const YunetDP* const* units, int n, void* stream);
 int yunet_dp_bwd_bf16(const YunetDP* d, void* stream);

@@ -33,7 +33,8 @@ CLS_BCE, CLS_VARIFOCAL = 0, 1                                     # YUNET_CLS_* 
 KPS_SMOOTH_L1, KPS_L1, KPS_MSE, KPS_BALANCED_L1 = 0, 1, 2, 3      # YUNET_KPS_* (YunetLossTerms.kps_loss)
 (OP_STEM_FWD, OP_STEM_BWD, OP_DP_FWD, OP_DP_BWD, OP_POOL_FWD, OP_POOL_BWD, OP_UPADD_FWD,
  OP_UPADD_BWD, OP_BN_RUNNING, OP_BN_PARAM_GRAD, OP_REDUCE_PARTIALS, OP_ASSIGN, OP_LOSS_NORM,
- OP_LOSS, OP_LOSS_FINALIZE, OP_SGD, OP_MEMSET, OP_BN_BATCH, OP_REDUCE_BATCH, OP_FORK, OP_JOIN, OP_ADD, OP_BN_FOLD) = range(1, 24)
+ OP_LOSS, OP_LOSS_FINALIZE, OP_SGD, OP_MEMSET, OP_BN_BATCH, OP_REDUCE_BATCH, OP_FORK, OP_JOIN, OP_ADD, OP_BN_FOLD,
+ OP_STEM_BWD_DX) = range(1, 25)
 OP_LANE, MAX_LANES = 10, 2          # YunetOp.i[OP_LANE]: side stream of the op (0 = the caller's stream)
 OP_GROUP, DP_GROUP_MAX = 9, 3       # YunetOp.i[OP_GROUP] = g: this DP_FWD op and the g - 1 after it are independent (ABI 10)
 
@@ -163,6 +164,7 @@ _SIGNATURES = {
     'yunet_stem_bwd': (C.c_int, [C.c_void_p] * 3 + [C.POINTER(YunetBN), C.c_void_p] +
                        [C.c_int] * 5 + [C.c_void_p]),
     'yunet_stem_bwd_rz': (C.c_int, [C.c_void_p] * 4 + [C.POINTER(YunetBN), C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+    'yunet_stem_bwd_dx': (C.c_int, [C.c_void_p] * 2 + [C.POINTER(YunetBN)] + [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
     'yunet_dp_fwd': (C.c_int, [C.POINTER(YunetDP), C.c_void_p]),
     'yunet_dp_bwd': (C.c_int, [C.POINTER(YunetDP), C.c_void_p]),
     'yunet_dp_fwd_group': (C.c_int, [C.POINTER(C.POINTER(YunetDP)), C.c_int, C.c_void_p]),
@@ -267,7 +269,7 @@ _SIGNATURES = {
     'yunet_allreduce': (C.c_int, [C.POINTER(YunetComm), C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     'yunet_comm_status': (C.c_int, [C.POINTER(YunetComm)]),
 }
-for _n in ('yunet_stem_fwd', 'yunet_stem_bwd', 'yunet_dp_fwd', 'yunet_dp_bwd', 'yunet_dp_fwd_group', 'yunet_pool_fwd', 'yunet_pool_bwd',
+for _n in ('yunet_stem_fwd', 'yunet_stem_bwd', 'yunet_stem_bwd_dx', 'yunet_dp_fwd', 'yunet_dp_bwd', 'yunet_dp_fwd_group', 'yunet_pool_fwd', 'yunet_pool_bwd',
            'yunet_pool_bwd_add', 'yunet_upadd_fwd', 'yunet_upadd_bwd'):
     _SIGNATURES[_n + '_bf16'] = _SIGNATURES[_n]      # same arguments, bf16 activation storage
 

@@ -182,6 +182,7 @@ extern "C" int yunet_set_option(const char* name, int value) {
 extern "C" {
 int yunet_stem_fwd_bf16(const float*, const float*, const float*, float*, double*, int, int, int, int, void*);
 int yunet_stem_bwd_bf16(const float*, const float*, const float*, const YunetBN*, float*, int, int, int, int, int, void*);
+int yunet_stem_bwd_dx_bf16(const float*, const float*, const YunetBN*, const float*, float*, int, int, int, int, void*);
 int yunet_dp_fwd_bf16(const YunetDP*, void*);
 int yunet_dp_fwd_group_bf16(const YunetDP* const*, int, void*);
 int yunet_dp_bwd_bf16(const YunetDP*, void*);
@@ -277,6 +278,10 @@ extern "C" int yunet_exec(const YunetOp* ops, int n_ops, void* main_stream) {
                 rc = (o.i[11] == YUNET_BF16 ? yunet_stem_bwd_bf16 : yunet_stem_bwd)((const float*)o.p[0], (const float*)o.p[1], (const float*)o.p[2],
                                     &o.bn[0], (float*)o.p[3], o.i[4], o.i[0], o.i[1], o.i[2], o.i[3],
                                     stream);
+                break;
+            case YUNET_OP_STEM_BWD_DX:
+                rc = (o.i[11] == YUNET_BF16 ? yunet_stem_bwd_dx_bf16 : yunet_stem_bwd_dx)((const float*)o.p[1], (const float*)o.p[2], &o.bn[0],
+                                    (const float*)o.p[3], (float*)o.p[0], o.i[0], o.i[1], o.i[2], o.i[3], stream);
                 break;
             case YUNET_OP_DP_FWD: {
                 // a group of independent units (include/yunet_hip.h: YUNET_OP_GROUP): one call, and where the kernels allow

@@ -17,6 +17,7 @@
 //   backward: z is RECOMPUTED (never read), dz = A dy + B z + D (bn_fold), dW[co][tap] += dz^T patch as a second
 //             matrix product with K = the strip's 32 pixels (dz transposed through a 2.5 KB LDS slot, the patch
 //             gathered in im2col order), db = sum dz.  Per output pixel it reads 48 B of image + 64 B of dy.
+// The gradient with respect to the image (stem_bwd_dx_kernel, below the two) is a tile kernel on the VALU: see there.
 #include "common.h"
 
 namespace {
@@ -284,7 +285,169 @@ int stem_rows(int N, int Ho, int Wo, int waves) {
     return best;
 }
 
+// ----------------------------------------------------------------------------- stem backward-data
+// dimg = conv_transpose(dz, W) with dz = A dy + B z + D (bn_fold, the coefficient chain of the weight gradient above):
+//   dimg[n][c][y][x] = sum_k sum_(ky,kx) W[k][c][ky][kx] dz[n][(y + 1 - ky) / 2][(x + 1 - kx) / 2][k]
+// over the taps whose quotients are integers inside the map: an even row takes ky = 1 (z row y / 2), an odd row ky = 0
+// (z row (y + 1) / 2) and ky = 2 (z row (y - 1) / 2); columns alike.  No index is ever negative, and the one row / column
+// past the map that an odd last row / column asks for is staged as zero.
+//
+// One workgroup owns TZH x TZW z pixels = 2 TZH x 2 TZW image pixels of the three planes.  Staging: dz of the tile plus one
+// halo row and column goes to LDS, channel-major ([channel][row][34 columns]; 16-byte dy / z loads, all of a thread's loads
+// issued before the first is consumed).  Compute: thread (tr, tc) owns z row tr and z columns 2 tc, 2 tc + 1 -> 2 rows x 4
+// columns x 3 planes, one 16-byte store each (a wave row = 256 contiguous bytes of a plane).  It walks the 16 channels: six dz
+// values from LDS (an aligned pair + one, both rows) and the channel's 27 weights, which are addressed from a wave-uniform
+// pointer -- scalar loads into scalar registers, one scalar operand per FMA -- for 54 fp32 FMAs in a fixed order.  (With
+// the channel loop fully unrolled the compiler loads all 432 weights up front and spills scalar registers into lanes of
+// vector registers: 3 400 lane reads around 860 FMAs.)  No sums of its own, no atomics: order-fixed as written.
+// z is read as stored (fp32 | bf16) in both builds.  Recomputing it from the image as stem_mma_kernel<true> does would
+// trade these 64 bytes per z pixel for 48 bytes of image, the 7 k-step product and its LDS ring; a layer whose backward
+// sums are all zero (frozen BatchNorm: B = 0 in every channel) does not read z at all.
+namespace sdx {
+constexpr int C = 16, TZH = 16, TZW = 32, NTHR = 256;
+constexpr int LH = TZH + 1, LW = TZW + 1, LWP = TZW + 2;        // staged rows x columns; even row pitch: aligned pairs
+constexpr int ITEMS = LH * LW * 4;                  // (pixel, channel quad) pairs of the staged tile
+constexpr int NIT = (ITEMS + NTHR - 1) / NTHR;
+static_assert(NTHR == TZH * (TZW / 2) && NTHR % 4 == 0, "thread (tr, tc) <-> z row tr, z columns 2 tc, 2 tc + 1");
+}  // namespace sdx
+
+__global__ __launch_bounds__(sdx::NTHR) void stem_bwd_dx_kernel(const act_t* __restrict__ z, const float* __restrict__ dy,
+                                                                const YunetBN bn, const float* __restrict__ w,
+                                                                float* __restrict__ dimg, const int N, const int H, const int W) {
+    using namespace sdx;
+    __shared__ __attribute__((aligned(16))) float s_dz[C * LH * LWP];
+    __shared__ __attribute__((aligned(16))) float s_k[4][C];
+    const int tid = threadIdx.x;
+    const int Ho = H / 2, Wo = W / 2;
+    if (tid < C) {
+        const BNFold f = bn_fold(bn_bwd_coef(bn, C, tid));
+        s_k[0][tid] = f.a; s_k[1][tid] = f.b; s_k[2][tid] = f.dh; s_k[3][tid] = f.dl;
+    }
+    const int tiles_x = (Wo + TZW - 1) / TZW, tiles_y = (Ho + TZH - 1) / TZH;
+    const int n = (int)blockIdx.x / (tiles_x * tiles_y), r = (int)blockIdx.x - n * tiles_x * tiles_y;
+    const int i0 = (r / tiles_x) * TZH, j0 = (r % tiles_x) * TZW;
+    __syncthreads();
+    const int quad = tid & 3;                            // the channel quad of every item this thread stages
+    float fa[4], fb[4], fdh[4], fdl[4];
+    bool need_z = false;
+#pragma unroll
+    for (int i = 0; i < C; ++i) need_z = need_z || s_k[1][i] != 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        fa[i] = s_k[0][4 * quad + i]; fb[i] = s_k[1][4 * quad + i]; fdh[i] = s_k[2][4 * quad + i]; fdl[i] = s_k[3][4 * quad + i];
+    }
+    // ---- dz of the tile + halo -> LDS ------------------------------------------------------------------------------------
+    {
+        float4 g4[NIT], z4[NIT];
+        bool ok[NIT];
+        size_t off[NIT];
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int pix = (tid + NTHR * it) >> 2;
+            const int lr = pix / LW, lc = pix - lr * LW;
+            const int oy = i0 + lr, ox = j0 + lc;
+            ok[it] = pix < LH * LW && oy < Ho && ox < Wo;
+            off[it] = (((size_t)n * Ho + oy) * Wo + ox) * C + 4 * quad;
+            g4[it] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (ok[it]) g4[it] = *reinterpret_cast<const float4*>(dy + off[it]);
+        }
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            z4[it] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (need_z && ok[it]) z4[it] = act_ld4(z + off[it]);
+        }
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            const int pix = (tid + NTHR * it) >> 2;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (ok[it]) {
+                v.x = bn_dz_folded(g4[it].x, z4[it].x, fa[0], fb[0], fdh[0], fdl[0]);
+                v.y = bn_dz_folded(g4[it].y, z4[it].y, fa[1], fb[1], fdh[1], fdl[1]);
+                v.z = bn_dz_folded(g4[it].z, z4[it].z, fa[2], fb[2], fdh[2], fdl[2]);
+                v.w = bn_dz_folded(g4[it].w, z4[it].w, fa[3], fb[3], fdh[3], fdl[3]);
+            }
+            if (pix < LH * LW) {
+                const int lr = pix / LW, lc = pix - lr * LW;
+                float* dst = s_dz + (4 * quad * LH + lr) * LWP + lc;
+                dst[0] = v.x; dst[LH * LWP] = v.y; dst[2 * LH * LWP] = v.z; dst[3 * LH * LWP] = v.w;
+            }
+        }
+    }
+    __syncthreads();
+    // ---- 2 rows x 4 columns x 3 planes per thread ------------------------------------------------------------------------
+    const int tr = tid >> 4, tc = tid & 15;
+    float acc[3][2][4];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int yy = 0; yy < 2; ++yy)
+#pragma unroll
+            for (int xx = 0; xx < 4; ++xx) acc[c][yy][xx] = 0.0f;
+    const float* dzp = s_dz + tr * LWP + 2 * tc;
+#pragma unroll 2
+    for (int k = 0; k < C; ++k) {
+        const float* wk = w + k * 27;                     // W[k][c][ky][kx]: wave-uniform
+        float d[2][3];                                    // [z row tr + rr][z column 2 tc + cc]
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+            const float* p = dzp + (k * LH + rr) * LWP;
+            const float2 v = *reinterpret_cast<const float2*>(p);
+            d[rr][0] = v.x; d[rr][1] = v.y; d[rr][2] = p[2];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int yy = 0; yy < 2; ++yy)
+#pragma unroll
+                for (int ty = 0; ty <= yy; ++ty) {
+                    // even row: ky = 1, z row tr; odd row: ky = 0, z row tr + 1, then ky = 2, z row tr
+                    const int ky = yy == 0 ? 1 : 2 * ty, rr = yy == 0 ? 0 : 1 - ty;
+#pragma unroll
+                    for (int xx = 0; xx < 4; ++xx)
+#pragma unroll
+                        for (int tx = 0; tx <= (xx & 1); ++tx) {
+                            const int kx = (xx & 1) == 0 ? 1 : 2 * tx;
+                            const int cc = (xx >> 1) + ((xx & 1) == 0 ? 0 : 1 - tx);
+                            acc[c][yy][xx] = fmaf(wk[c * 9 + ky * 3 + kx], d[rr][cc], acc[c][yy][xx]);
+                        }
+                }
+    }
+    const int oy = i0 + tr, x = 2 * j0 + 4 * tc;
+    if (oy < Ho && x < W) {
+        float* dst = dimg + (((size_t)n * 3) * H + 2 * oy) * W + x;
+        const size_t plane = (size_t)H * W;
+        if ((W & 3) == 0) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int yy = 0; yy < 2; ++yy)
+                    *reinterpret_cast<f32x4*>(dst + c * plane + yy * W) = f32x4{acc[c][yy][0], acc[c][yy][1], acc[c][yy][2], acc[c][yy][3]};
+        } else {                                           // W = 4 m + 2: rows start on 8-byte boundaries only
+            const bool two = x + 2 < W;
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int yy = 0; yy < 2; ++yy) {
+                    *reinterpret_cast<float2*>(dst + c * plane + yy * W) = make_float2(acc[c][yy][0], acc[c][yy][1]);
+                    if (two) *reinterpret_cast<float2*>(dst + c * plane + yy * W + 2) = make_float2(acc[c][yy][2], acc[c][yy][3]);
+                }
+        }
+    }
+}
+
 }  // namespace
+
+// Gradient with respect to the image (include/yunet_hip.h): one workgroup per 16 x 32 tile of z pixels and image.
+extern "C" int ACT_SUFFIX(yunet_stem_bwd_dx)(const float* z, const float* dy, const YunetBN* bn, const float* w, float* dimg,
+                                             int N, int H, int W, int cmid, void* stream) {
+    if (!z || !dy || !bn || !w || !dimg || !bn->stats || !bn->bstats || !bn->gamma || !bn->beta) return YUNET_EINVAL;
+    if (cmid != sdx::C || N < 1 || H < 2 || W < 2 || (H & 1) || (W & 1)) return YUNET_EINVAL;
+    const long long tiles = (long long)N * ((W / 2 + sdx::TZW - 1) / sdx::TZW) * ((H / 2 + sdx::TZH - 1) / sdx::TZH);
+    if (tiles >= (1ll << 31)) return YUNET_EINVAL;
+    hipLaunchKernelGGL(stem_bwd_dx_kernel, dim3((unsigned)tiles), dim3(sdx::NTHR), 0, (hipStream_t)stream,
+                       reinterpret_cast<const act_t*>(z), dy, *bn, w, dimg, N, H, W);
+    return hip_status();
+}
 
 // conv_fwd.hip (forward) and conv_bwd_host.hip (yunet_stem_bwd_rz) dispatch here (option stem_mma).  The forward is compiled once per activation storage type (fp32 |
 // -DYUNET_ACT_BF16: z stored as bf16, BN sums of the unrounded values); the weight gradient with its recomputed z is fp32-storage

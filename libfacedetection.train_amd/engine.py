@@ -319,6 +319,10 @@ class Plan:
         # deterministic mode: order-fixed BatchNorm sums (per-workgroup rows + fold ops), no lanes, no grouped launches
         level = det_level(getattr(eng, 'deterministic', False))
         self.det = bool(level)
+        # image gradient (YuNetEngine.set_input_grad): the backward runs down to the stem whatever is
+        # frozen and ends with one OP_STEM_BWD_DX.  Off: every list below is the one it always was.
+        self.input_grad = bool(getattr(eng, 'input_grad', False))
+        self.dimg_ptr_ops = []  # indices in `bwd` of the ops that take the image-gradient pointer (set_dimg)
         if self.det and eng.precision == 'bf16':
             raise NotImplementedError(f"deterministic={level!r} with precision='bf16': the order-fixed BatchNorm sums exist for the "
                                       'fp32 storage build only')
@@ -956,7 +960,8 @@ class Plan:
         self.img_ptr_ops.append(('fwd_a', len(self.fwd_a) - 1))
         if self.det and not frozen:
             self.fwd_a.append(self._fold_op('backbone.model0.bn1', False))
-        z0.needs_grad = self._trainable('stem', 'backbone.model0.bn1')
+        stem_trains = self._trainable('stem', 'backbone.model0.bn1')
+        z0.needs_grad = stem_trains or self.input_grad
         has_job = self._conv_trainable('stem')
         blocks = K.stem_grid(self.n, self.h, self.w)
         width = 16 * 27 + 16
@@ -970,14 +975,22 @@ class Plan:
             assert z0.grad is not None
             if self._bwd_fold('backbone.model0.bn1'):
                 self.bwd.append(self._fold_op('backbone.model0.bn1', True))
-            op = self._op(L.OP_STEM_BWD, p=[None, z0.buf.data_ptr(), z0.grad.data_ptr(),
-                                            part.data_ptr(), wp, bp],      # wp, bp: fp32 storage recomputes z from the image
-                          i=[self.n, self.h, self.w, 16, blocks])
-            op.bn[0] = self._reader_bn(self._bn_struct('backbone.model0.bn1', cnt), 'backbone.model0.bn1')
-            self.bwd.append(op)
-            self.img_ptr_ops.append(('bwd', len(self.bwd) - 1))
-            if has_job:
-                self.reduce_jobs.append((part.data_ptr(), gptr, blocks, width, 0))
+            if stem_trains:               # (image gradient under a frozen stem: no weight gradient, no reduce job)
+                op = self._op(L.OP_STEM_BWD, p=[None, z0.buf.data_ptr(), z0.grad.data_ptr(),
+                                                part.data_ptr(), wp, bp],      # wp, bp: fp32 storage recomputes z from the image
+                              i=[self.n, self.h, self.w, 16, blocks])
+                op.bn[0] = self._reader_bn(self._bn_struct('backbone.model0.bn1', cnt), 'backbone.model0.bn1')
+                self.bwd.append(op)
+                self.img_ptr_ops.append(('bwd', len(self.bwd) - 1))
+                if has_job:
+                    self.reduce_jobs.append((part.data_ptr(), gptr, blocks, width, 0))
+            if self.input_grad:
+                # dimg (p[0], patched per backward: set_dimg) from the same dy, z as stored and the same reader descriptor
+                op = self._op(L.OP_STEM_BWD_DX, p=[None, z0.buf.data_ptr(), z0.grad.data_ptr(), wp],
+                              i=[self.n, self.h, self.w, 16])
+                op.bn[0] = self._reader_bn(self._bn_struct('backbone.model0.bn1', cnt), 'backbone.model0.bn1')
+                self.bwd.append(op)
+                self.dimg_ptr_ops.append(len(self.bwd) - 1)
         self.bwd_nodes.append((self._lane, bwd, self._join_before))
 
     def _dp_desc(self, x, name, z, z_img_stride=None):
@@ -1168,19 +1181,32 @@ class Plan:
             arr[0].p[3], arr[0].p[4] = ptrs[0], ptrs[1]
         self._gt_bound = ptrs
 
+    def _set_bwd_p0(self, idx, ptr):
+        """p[0] of backward op `idx`, in the one-list form and in the two-segment copies of the backward list."""
+        self.c_bwd[idx].p[0] = ptr
+        if self.split_off is not None:
+            if idx < self.split_ops:
+                self.c_bwd_a[idx].p[0] = ptr
+                self.c_bwd_a_k[idx].p[0] = ptr
+            else:
+                self.c_bwd_b[idx - self.split_ops].p[0] = ptr
+
     def set_img(self, img):
         ptr = img.data_ptr()
         for which, idx in self.img_ptr_ops:
-            arr = {'fwd_a': self.c_fwd_a, 'bwd': self.c_bwd}[which]
-            arr[idx].p[0] = ptr
             if which == 'fwd_a':
+                self.c_fwd_a[idx].p[0] = ptr
                 self.c_fwd_eval[idx].p[0] = ptr       # same position: op 0 is replaced, not removed
-            elif self.split_off is not None:          # the two-segment copy of the backward list
-                if idx < self.split_ops:
-                    self.c_bwd_a[idx].p[0] = ptr
-                    self.c_bwd_a_k[idx].p[0] = ptr
-                else:
-                    self.c_bwd_b[idx - self.split_ops].p[0] = ptr
+            else:
+                self._set_bwd_p0(idx, ptr)
+
+    def set_dimg(self, dimg):
+        """Where this backward writes the image gradient ([N,3,H,W] fp32 contiguous): a tensor of the caller's, never a
+        buffer of the plan -- autograd may keep it as img.grad while later steps run."""
+        assert self.input_grad and tuple(dimg.shape) == (self.n, 3, self.h, self.w)
+        assert dimg.dtype == torch.float32 and dimg.is_contiguous()
+        for idx in self.dimg_ptr_ops:
+            self._set_bwd_p0(idx, dimg.data_ptr())
 
 
 class YuNetEngine:
@@ -1211,6 +1237,10 @@ class YuNetEngine:
         # freeze signature (set_frozen): (BatchNorm layers on their running statistics, parameters without gradient)
         self.frozen = (_NONE, _NONE)
         self._frozen_key = ()
+        # image gradient (set_input_grad): plans are keyed by it; `input_grad_out` = the tensor the
+        # last backward of such a plan wrote
+        self.input_grad = False
+        self.input_grad_out = None
         # gradient accumulation (set_grad_accumulation): off -- backward() overwrites the flat gradient
         self.grad_accumulation = False
         self._acc = None                # fp32 [layout.numel]: the total saved in front of a backward; allocated on first use
@@ -1282,6 +1312,12 @@ class YuNetEngine:
                                       'fp32 storage build only')
         self.deterministic = flag
 
+    def set_input_grad(self, flag=True):
+        """On: the plans used from now on end their backward with the gradient w.r.t. the image (OP_STEM_BWD_DX) and run
+        it down to the stem whatever is frozen; backward() then leaves a fresh [N,3,H,W] fp32 tensor in `input_grad_out`.
+        Off (default): no op, no buffer, the same op lists.  Plans of both kinds coexist."""
+        self.input_grad = bool(flag)
+
     def set_grad_accumulation(self, flag=True):
         """On: backward() ADDS this call's gradient to what params.grad held before the call (torch's .grad semantics)
         instead of overwriting it -- unless the buffer is known to hold no total (mark_grad_zeroed(), backward(fresh=True)),
@@ -1329,6 +1365,7 @@ class YuNetEngine:
             gmax *= 2
         key = (n, h, w, gmax, self.precision) + (('det-fast' if self.deterministic == 'fast' else 'det',) if self.deterministic else ())
         key += self._frozen_key          # () with nothing frozen: the key it always was
+        key += ('input-grad',) if self.input_grad else ()
         plan = self.plans.get(key)
         if plan is None:
             if h % 32 or w % 32:
@@ -1446,6 +1483,11 @@ class YuNetEngine:
         last one).  `fresh`: the caller knows the buffer holds no total (the parameters' .grad were None)."""
         plan = self.plan
         keep = self._accum_save(fresh)
+        self.input_grad_out = None
+        if plan.input_grad:
+            # a fresh tensor from torch's allocator on the launch stream, which is the stream the stem's ops run on
+            self.input_grad_out = torch.empty(plan.n, 3, plan.h, plan.w, device=self.device, dtype=torch.float32)
+            plan.set_dimg(self.input_grad_out)
         if grad_scales is not None:
             s = [float(v) for v in grad_scales]
             vec = [s[0]] + [s[1]] * 4 + [s[2]] + [s[3]] * 10

@@ -3,7 +3,7 @@
 The reference's blocks are ordinary nn.Modules (mmdet/models/utils/yunet_layer.py:30-36, 57-62, 79-82,
 backbones/yunet_backbone.py:33-41, necks/tfpn.py:33-45): any detector can train through them.  The registered
 classes of this package therefore carry a gradient of their own: one torch.autograd.Function per ConvDPUnit
-(`yunet_dp_fwd` / `yunet_dp_bwd`) and one for the stem (`yunet_stem_fwd` / `yunet_stem_bwd[_rz]`), NCHW in / NCHW out
+(`yunet_dp_fwd` / `yunet_dp_bwd`) and one for the stem (`yunet_stem_fwd` / `yunet_stem_bwd[_rz]` / `yunet_stem_bwd_dx`), NCHW in / NCHW out
 like the reference modules, BatchNorm in train mode (batch statistics, running statistics updated) or eval mode
 (running statistics).  `YuNet.forward_train` does NOT go through here -- it runs the fused engine (one autograd node
 for the whole step, BatchNorm split across kernel boundaries, no activation tensor materialised); this file is the
@@ -122,8 +122,8 @@ class _DPUnitFn(torch.autograd.Function):
 
 
 class _StemFn(torch.autograd.Function):
-    """relu(bn1(conv3x3 stride 2 (img)))  (yunet_layer.py:57-62).  The image is a leaf in every detector: no input
-    gradient is produced (asking for one raises)."""
+    """relu(bn1(conv3x3 stride 2 (img)))  (yunet_layer.py:57-62).  An image that asks for a gradient gets it from
+    `yunet_stem_bwd_dx` (the backward-data of the convolution through bn1), in its own dtype and memory format."""
 
     @staticmethod
     def forward(ctx, img, w, b, gamma, beta, running_mean, running_var, eps, training):
@@ -139,6 +139,8 @@ class _StemFn(torch.autograd.Function):
         mean, invstd, scale = _bn_coef(stats, count, gamma.detach(), beta.detach(), eps)
         y = torch.relu_((z - mean) * scale + beta.detach())
         ctx.training, ctx.eps, ctx.count = bool(training), eps, count
+        ctx.img_dtype = img.dtype
+        ctx.img_channels_last = img.dim() == 4 and not img.is_contiguous() and img.is_contiguous(memory_format=torch.channels_last)
         ctx.save_for_backward(im, z, wc, bc, gamma.detach(), beta.detach(), stats, mean, invstd, scale)
         out_stats = stats if training else torch.empty(0, device=img.device, dtype=torch.float64)
         ctx.mark_non_differentiable(out_stats)
@@ -147,9 +149,6 @@ class _StemFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gy, _gstats):
-        if ctx.needs_input_grad[0]:
-            raise NotImplementedError('the stem kernels do not produce a gradient w.r.t. the image (it is a leaf in '
-                                      'every detector of the reference); detach the input')
         im, z, wc, bc, gamma, beta, stats, mean, invstd, scale = ctx.saved_tensors
         gyh = _nhwc(gy.float())
         pre = (z - mean) * scale + beta
@@ -159,7 +158,12 @@ class _StemFn(torch.autograd.Function):
         bstats = sums if ctx.training else torch.zeros_like(sums)
         bn = K.BN(stats, gamma, beta, ctx.count, ctx.eps, bstats=bstats)
         dw, db = K.stem_bwd(im, z, dy, bn, wc, bc)
-        return None, dw, db, sums[16:].float(), sums[:16].float(), None, None, None, None
+        dimg = None
+        if ctx.needs_input_grad[0]:
+            dimg = K.stem_bwd_dx(im, z, dy, bn, wc, bc).to(ctx.img_dtype)
+            if ctx.img_channels_last:
+                dimg = dimg.contiguous(memory_format=torch.channels_last)
+        return dimg, dw, db, sums[16:].float(), sums[:16].float(), None, None, None, None
 
 
 def _track(bn, stats, count):
@@ -198,7 +202,7 @@ def fused_dp_units(units, x):
 
 
 def stem(m, x):
-    """The dense 3x3 stride-2 conv + bn1 + ReLU of Conv_head (differentiable w.r.t. the parameters)."""
+    """The dense 3x3 stride-2 conv + bn1 + ReLU of Conv_head (differentiable w.r.t. the parameters and the image)."""
     bn = m.bn1
     n, _, h, w = x.shape
     y, stats = _StemFn.apply(x, m.conv1.weight, m.conv1.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,

@@ -128,6 +128,21 @@ def stem_bwd(img, z, dy, bn, w=None, b=None):
     return out[:432].view(16, 3, 3, 3), out[432:]
 
 
+def stem_bwd_dx(img, z, dy, bn, w, b=None):
+    """-> dimg [N,3,H,W] fp32 NCHW: the gradient w.r.t. the image given dy = grad wrt bn1 output (ReLU-masked), the stem's raw
+    output z as stored (fp32 | bf16) and its weights w [16,3,3,3] (yunet_stem_bwd_dx[_bf16]).  Same arguments as stem_bwd:
+    `img` gives the shape, and the bias does not enter this gradient."""
+    _chk_act(z)
+    _chk_f32(dy, w)
+    n, _, h, wd = img.shape
+    assert tuple(z.shape) == (n, h // 2, wd // 2, 16) and dy.shape == z.shape and w.numel() == 432
+    dimg = torch.empty(n, 3, h, wd, device=z.device, dtype=torch.float32)
+    bnc = bn.c()
+    fn = getattr(L.load(), 'yunet_stem_bwd_dx' + _act(z)[1])
+    L.check(fn(_p(z), _p(dy), C.byref(bnc), _p(w), _p(dimg), n, h, wd, 16, _stream()), 'yunet_stem_bwd_dx')
+    return dimg
+
+
 def reduce_partials(part, out, accumulate=False):
     L.check(L.load().yunet_reduce_partials(_p(part), part.shape[0], part.shape[1], _p(out),
                                            int(accumulate), _stream()), 'yunet_reduce_partials')

@@ -110,10 +110,13 @@ class _EngineStep(torch.autograd.Function):
     buffer the parameters' .grad tensors are views of."""
 
     @staticmethod
-    def forward(ctx, anchor, model, losses):
+    def forward(ctx, anchor, model, losses, img=None):
         """-> loss_cls, loss_bbox, loss_obj, loss_kps and their total (written by the finalize
-        kernel): train_step backpropagates the total directly, no tensor arithmetic in between."""
+        kernel): train_step backpropagates the total directly, no tensor arithmetic in between.
+        `img`: the caller's image when it asked for a gradient (the step ran on an input_grad plan)."""
         ctx.model = model
+        ctx.img_meta = None if img is None else (img.dtype, img.dim() == 4 and not img.is_contiguous()
+                                                 and img.is_contiguous(memory_format=torch.channels_last))
         ctx.set_materialize_grads(False)      # undefined output grads stay None: backward()'s fast path below
         out = losses.detach().clone()
         return out[0], out[1], out[2], out[3], out[4]
@@ -133,7 +136,19 @@ class _EngineStep(torch.autograd.Function):
         # nothing to accumulate onto (engine.set_grad_accumulation)
         eng.backward(fresh=model._sentinel[1].grad is None)
         model._after_backward()
-        return None, None, None
+        if ctx.img_meta is None:
+            return None, None, None
+        # the image gradient the backward list just wrote (a fresh tensor: autograd may keep it as img.grad), in the
+        # image's dtype and memory format
+        dimg = eng.input_grad_out
+        eng.input_grad_out = None
+        if not ctx.needs_input_grad[3]:
+            return None, None, None, None
+        dtype, channels_last = ctx.img_meta
+        dimg = dimg.to(dtype)
+        if channels_last:
+            dimg = dimg.contiguous(memory_format=torch.channels_last)
+        return None, None, None, dimg
 
 
 @DETECTORS.register_module()
@@ -504,8 +519,15 @@ class YuNet(nn.Module):
             out = dict(loss_cls=l[0], loss_bbox=l[1], loss_obj=l[2], loss_kps=l[3])
             self._last = (out, l[4], l[:5])
             return out
-        losses = eng.forward(img.float().contiguous(), gt_bboxes, gt_keypointss)
-        l = _EngineStep.apply(self._anchor, self, losses)
+        # an image that asks for a gradient selects the plan whose backward ends with it
+        want_dimg = torch.is_grad_enabled() and img.requires_grad
+        eng.set_input_grad(want_dimg)
+        if want_dimg:
+            losses = eng.forward(img.detach().float().contiguous(), gt_bboxes, gt_keypointss)
+            l = _EngineStep.apply(self._anchor, self, losses, img)
+        else:
+            losses = eng.forward(img.float().contiguous(), gt_bboxes, gt_keypointss)
+            l = _EngineStep.apply(self._anchor, self, losses)
         out = dict(loss_cls=l[0], loss_bbox=l[1], loss_obj=l[2], loss_kps=l[3])
         self._last = (out, l[4])          # lets train_step use the kernel's total and log record
         return out
