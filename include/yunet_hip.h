@@ -791,6 +791,46 @@ int yunet_aug_pixels(const YunetAugPixels* a, const YunetAugCfg* cfg, int N, flo
 int yunet_aug_mosaic_canvas(const uint8_t* store, const long long* store_off, const int32_t* geom,
                             const YunetMosaicCfg* mcfg, int N, float* canvas, void* stream);
 
+/* CutOut (transforms.py:2143-2214) on the finished batch tensor of yunet_aug_pixels: between RandomFlip (or a POST
+ * PhotoMetricDistortion) and Normalize, so the fill value reaches the network as it is written.
+ *
+ * Draws of image n come from a SUB-STREAM of the generator: key mix32(stream_key(seed, iteration, n) ^
+ * YUNET_CUTOUT_SALT), counter from 0, one u32 per randint in the reference's call order, with
+ * randint(lo, hi) = lo + ((u32 * (hi - lo)) >> 32):
+ *   draw 0          n_holes = randint(n_lo, n_hi + 1)             (made when n_lo == n_hi too)
+ *   draw 1 + 3j     x1 = randint(0, w)                            hole j
+ *   draw 2 + 3j     y1 = randint(0, h)
+ *   draw 3 + 3j     index = randint(0, n_cand)                    (made with one candidate too)
+ * so windows, flips, GT, photometric tables and mosaic geometry are the same numbers with CutOut present or absent, and
+ * a hole's draws are addressed by its index.  w = h = the image's own edge S_n: E, or params[n][7] on a multi-scale
+ * canvas (read on the device; a value above E counts as E, one below 1 gives the image no hole).
+ *   shape mode (with_ratio == 0): (cw, ch) = cand[index], integers held as doubles
+ *   ratio mode (with_ratio != 0): cw = (int)(cand[index][0] * (double)w), ch likewise -- Python's int(ratio * w)
+ *   x2 = min(x1 + cw, w), y2 = min(y1 + ch, h)          (np.clip; the lower clip never acts, cw, ch >= 0)
+ * and img[n, c, y1:y2, x1:x2] = fill[c].  A hole may be empty (cw or ch 0); holes never reach the zero border of a
+ * multi-scale canvas; overlapping holes store the same values.
+ *
+ * holes [N, YUNET_CUTOUT_WORDS] int32 per image: word 0 n_holes, word 1 draws consumed (1 + 3 * n_holes), then
+ * (x1, y1, x2, y2) per slot, zeros in the slots at and beyond n_holes. */
+#define YUNET_CUTOUT_SALT 0x4355544Fu  /* "CUTO" */
+#define YUNET_CUTOUT_MAX_HOLES 16
+#define YUNET_CUTOUT_MAX_CANDIDATES 8
+#define YUNET_CUTOUT_WORDS 66          /* 2 + 4 * YUNET_CUTOUT_MAX_HOLES */
+typedef struct YunetCutoutCfg {
+    int32_t n_lo, n_hi;          /* n_holes from the closed interval [n_lo, n_hi], 0 <= n_lo <= n_hi <= MAX_HOLES */
+    int32_t n_cand;              /* entries used in cand, 1..YUNET_CUTOUT_MAX_CANDIDATES */
+    int32_t with_ratio;          /* 0: cand are shapes in pixels, else ratios of the image's edge */
+    double cand[YUNET_CUTOUT_MAX_CANDIDATES][2];   /* (w, h) per candidate, non-negative and finite */
+    float fill[3];               /* fill_in per channel of the batch tensor (BGR) */
+    uint32_t seed;
+} YunetCutoutCfg;
+/* One workgroup per (image, hole slot) on the current stream, in place on img [N, 3, E, E] fp32; params NULL: every
+ * image's edge is E, else [N,8] of yunet_aug_decide (multiscale != 0).  YUNET_EINVAL, before any launch, for N < 1, E
+ * outside [1, YUNET_AUG_MAX_EDGE], a null cfg / img / holes, n_lo < 0, n_lo > n_hi, n_hi > YUNET_CUTOUT_MAX_HOLES,
+ * n_cand outside [1, YUNET_CUTOUT_MAX_CANDIDATES], a negative or non-finite candidate or a non-finite fill. */
+int yunet_aug_cutout(const YunetCutoutCfg* cfg, uint32_t iteration, int N, int E, const int32_t* params, float* img,
+                     int32_t* holes, void* stream);
+
 /* The TEST pipeline of a batch (test_pipeline.DeviceTestPipeline; csrc/test_pipeline.hip), one launch: decoded uint8
  * HWC sources addressed as for yunet_aug_pixels (src, src_off [N], src_hw [N,2]) -> out_img [N, 3, Hc, Wc] fp32 planar.
  * table [N,4] int32 (device, written by the host) = (nh, nw, flip, 0) per image.  Inside the top-left nh x nw corner:

@@ -133,6 +133,16 @@ class YunetMosaicCfg(C.Structure):
                 ('bbox_clip_border', C.c_int32), ('skip_filter', C.c_int32), ('reserved_', C.c_int32)]
 
 
+# CutOut (YUNET_CUTOUT_*): sub-stream salt, hole slots / candidates per configuration, table words per image
+CUTOUT_SALT, CUTOUT_MAX_HOLES, CUTOUT_MAX_CANDIDATES = 0x4355544F, 16, 8
+CUTOUT_WORDS = 2 + 4 * CUTOUT_MAX_HOLES     # n_holes, draws, then (x1, y1, x2, y2) per slot
+
+
+class YunetCutoutCfg(C.Structure):
+    _fields_ = [('n_lo', C.c_int32), ('n_hi', C.c_int32), ('n_cand', C.c_int32), ('with_ratio', C.c_int32),
+                ('cand', (C.c_double * 2) * CUTOUT_MAX_CANDIDATES), ('fill', C.c_float * 3), ('seed', C.c_uint32)]
+
+
 class YunetAugPixels(C.Structure):
     """The pixel pass of yunet_aug_pixels: rect / position / out_hw / geom select the form (include/yunet_hip.h)."""
     _fields_ = [('src', C.c_void_p), ('src_off', C.c_void_p), ('src_hw', C.c_void_p), ('rect', C.c_void_p),
@@ -207,6 +217,7 @@ _SIGNATURES = {
     'yunet_aug_mosaic_decide': (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 +
                                 [C.POINTER(YunetMosaicCfg), C.c_uint32] + [C.c_void_p] * 6),
     'yunet_aug_mosaic_canvas': (C.c_int, [C.c_void_p] * 3 + [C.POINTER(YunetMosaicCfg), C.c_int, C.c_void_p, C.c_void_p]),
+    'yunet_aug_cutout': (C.c_int, [C.POINTER(YunetCutoutCfg), C.c_uint32, C.c_int, C.c_int] + [C.c_void_p] * 4),
     'yunet_test_pixels': (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p]),
     'yunet_rescale_dets': (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]),
     'yunet_score_wider': (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_longlong, C.c_longlong, C.c_double, C.c_void_p, C.c_int] +

@@ -16,6 +16,9 @@
 // cfg.out_size; CANVAS = true writes image n into the top-left S_n x S_n corner of an out_hw x out_hw canvas whose
 // remaining pixels are 0 (DefaultFormatBundle's padding_value through mmcv's collate).
 //
+// CutOut (transforms.py:2143-2214) is a third launch on the finished batch tensor: aug_cutout_kernel, one workgroup per
+// (image, hole).
+//
 // Built with -ffp-contract=off: every float operation is the single rounded operation numpy
 // performs, so boxes / keypoints are bit-identical to the reference and pixels to the oracle.
 #include <cfloat>
@@ -620,7 +623,74 @@ __global__ __launch_bounds__(256) void aug_pixels_kernel(
     }
 }
 
+// ---- CutOut (transforms.py:2143-2214; include/yunet_hip.h YUNET_CUTOUT_*) ----------------------------------------------
+__device__ __forceinline__ uint32_t cutout_key(uint32_t seed, uint32_t iteration, uint32_t image) {
+    return mix32(stream_key(seed, iteration, image) ^ YUNET_CUTOUT_SALT);
+}
+// int(candidate) / int(ratio * edge) of a non-negative finite double; 2^30 stands for anything larger (x2 / y2 are
+// clipped to the edge, at most YUNET_AUG_MAX_EDGE, so the result is the same and x1 + extent stays within int32)
+__device__ __forceinline__ int cutout_extent(double v) {
+    return (int)(v > 1073741824.0 ? 1073741824.0 : v);
+}
+
+// One workgroup per (image, hole slot) on the finished batch tensor [N, 3, E, E].  The draws are random-access in the
+// counter: workgroup (n, j) reads draw 0 (the hole count) and the three draws of its own hole, writes its slot of the
+// table (slot 0's workgroup the two header words too) and, when j < n_holes, stores fill[c] over
+// img[n, c, y1:y2, x1:x2].  PARAMS: the image's edge is params[n][AUG_P_SIZE] (the multi-scale canvas), clamped to E;
+// else E.  Holes of one image may overlap: they store the same values, so no order between workgroups is needed.
+template <bool PARAMS>
+__global__ __launch_bounds__(256) void aug_cutout_kernel(const YunetCutoutCfg cfg, uint32_t iteration, int E,
+                                                         const int32_t* __restrict__ params, float* __restrict__ img,
+                                                         int32_t* __restrict__ holes) {
+    const int n = blockIdx.x / YUNET_CUTOUT_MAX_HOLES, j = blockIdx.x % YUNET_CUTOUT_MAX_HOLES;
+    int S = PARAMS ? params[8 * n + AUG_P_SIZE] : E;
+    if (S > E) S = E;
+    const uint32_t key = cutout_key(cfg.seed, iteration, (uint32_t)n);
+    // an image without an edge (S < 1: not a table of this pipeline) gets no hole; the count draw is made all the same
+    const int drawn = cfg.n_lo + bounded(rand_u32(key, 0u), cfg.n_hi + 1 - cfg.n_lo);
+    const int nh = S < 1 ? 0 : drawn;
+    int x1 = 0, y1 = 0, x2 = 0, y2 = 0;
+    if (j < nh) {
+        x1 = bounded(rand_u32(key, 1u + 3u * j), S);
+        y1 = bounded(rand_u32(key, 2u + 3u * j), S);
+        const int idx = bounded(rand_u32(key, 3u + 3u * j), cfg.n_cand);
+        const double cw_ = cfg.cand[idx][0], ch_ = cfg.cand[idx][1];
+        const int cw = cutout_extent(cfg.with_ratio ? cw_ * (double)S : cw_);      // int(ratio_w * w), Python's double
+        const int ch = cutout_extent(cfg.with_ratio ? ch_ * (double)S : ch_);
+        x2 = x1 + cw < S ? x1 + cw : S;                                            // np.clip(x1 + cutout_w, 0, w)
+        y2 = y1 + ch < S ? y1 + ch : S;
+    }
+    if (threadIdx.x == 0) {
+        int32_t* t = holes + (size_t)n * YUNET_CUTOUT_WORDS;
+        if (j == 0) { t[0] = nh; t[1] = 1 + 3 * nh; }
+        int32_t* s = t + 2 + 4 * j;
+        s[0] = x1; s[1] = y1; s[2] = x2; s[3] = y2;
+    }
+    const int hw = x2 - x1, hh = y2 - y1;
+    if (hw <= 0 || hh <= 0) return;
+    const size_t plane = (size_t)E * E;
+    float* o = img + (size_t)n * 3 * plane + (size_t)y1 * E + x1;
+    const float f0 = cfg.fill[0], f1 = cfg.fill[1], f2 = cfg.fill[2];
+    for (int i = threadIdx.x; i < hw * hh; i += 256) {       // consecutive lanes: consecutive pixels of a row segment
+        const int y = i / hw, x = i - y * hw;
+        float* q = o + (size_t)y * E + x;
+        q[0] = f0;
+        q[plane] = f1;
+        q[2 * plane] = f2;
+    }
+}
+
 }  // namespace
+
+static bool cutout_cfg_ok(const YunetCutoutCfg* c) {
+    if (!c || c->n_lo < 0 || c->n_lo > c->n_hi || c->n_hi > YUNET_CUTOUT_MAX_HOLES || c->n_cand < 1 ||
+        c->n_cand > YUNET_CUTOUT_MAX_CANDIDATES)
+        return false;
+    for (int i = 0; i < c->n_cand; ++i)
+        for (int k = 0; k < 2; ++k)
+            if (!std::isfinite(c->cand[i][k]) || c->cand[i][k] < 0.0) return false;
+    return std::isfinite(c->fill[0]) && std::isfinite(c->fill[1]) && std::isfinite(c->fill[2]);
+}
 
 static bool aug_cfg_ok(const YunetAugCfg* cfg) {
     return cfg && cfg->n_choice >= 1 && cfg->n_choice <= 8 && cfg->gmax >= 1 && cfg->max_attempts >= 1 &&
@@ -742,5 +812,17 @@ extern "C" int yunet_aug_mosaic_canvas(const uint8_t* store, const long long* st
     if (bx > 256) bx = 256;
     hipLaunchKernelGGL(mosaic_canvas_kernel, dim3(bx, N), dim3(256), 0, (hipStream_t)stream, store, store_off, geom,
                        mcfg->img_scale, mcfg->pad_val, canvas);
+    return hip_status();
+}
+
+extern "C" int yunet_aug_cutout(const YunetCutoutCfg* cfg, uint32_t iteration, int N, int E, const int32_t* params,
+                                float* img, int32_t* holes, void* stream) {
+    if (!cutout_cfg_ok(cfg) || N < 1 || N > INT32_MAX / YUNET_CUTOUT_MAX_HOLES || E < 1 || E > YUNET_AUG_MAX_EDGE ||
+        !img || !holes)
+        return YUNET_EINVAL;
+    with_bool(params != nullptr, [&](auto ms) {
+        hipLaunchKernelGGL((aug_cutout_kernel<decltype(ms)::value>), dim3(N * YUNET_CUTOUT_MAX_HOLES), dim3(256), 0,
+                           (hipStream_t)stream, *cfg, iteration, E, params, img, holes);
+    });
     return hip_status();
 }

@@ -7,7 +7,8 @@
 
 `RandomSquareCrop -> Resize(keep_ratio=False) -> RandomFlip -> Normalize(0, 1) ->
 DefaultFormatBundle -> Collect` run as two HIP kernels (csrc/augment.hip), three with an optional
-`PhotoMetricDistortion` before RandomSquareCrop or after RandomFlip; the classes below carry
+`PhotoMetricDistortion` before RandomSquareCrop or after RandomFlip, and one more launch with an
+optional `CutOut` in front of Normalize; the classes below carry
 the configuration under the reference's registry names (mmdet/datasets/pipelines/transforms.py,
 formatting.py, loading.py) so the reference's config files build unchanged.  Decoding image files
 (LoadImageFromFile) is outside this stage: sources arrive as uint8 HWC arrays.
@@ -190,6 +191,71 @@ class Mosaic(_Carrier):
         return c
 
 
+def _is_number(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+
+
+@PIPELINES.register_module()
+class CutOut(_Carrier):
+    """transforms.py:2143-2214 with the reference's constructor; its assertions are ValueErrors here.  Runs as
+    yunet_aug_cutout on the finished batch tensor, between RandomFlip (or a POST PhotoMetricDistortion) and Normalize;
+    its draws come from a sub-stream of the pipeline's generator (include/yunet_hip.h YUNET_CUTOUT_SALT).  `n_holes` is
+    an int or the closed interval (a, b); a candidate is one (w, h) pair or a list of pairs -- pixels for `cutout_shape`,
+    fractions of the image's edge for `cutout_ratio`; `fill_in` is a scalar or three values in the image's channel
+    order (BGR).  Limits of this build: at most _lib.CUTOUT_MAX_HOLES holes and _lib.CUTOUT_MAX_CANDIDATES candidates."""
+
+    def __init__(self, n_holes, cutout_shape=None, cutout_ratio=None, fill_in=(0, 0, 0)):
+        if (cutout_shape is None) == (cutout_ratio is None):
+            raise ValueError('CutOut: either cutout_shape or cutout_ratio should be specified, not both and not neither')
+        with_ratio = cutout_ratio is not None
+        arg = 'cutout_ratio' if with_ratio else 'cutout_shape'
+        if isinstance(n_holes, (tuple, list)):
+            if len(n_holes) != 2 or not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in n_holes) \
+                    or not 0 <= n_holes[0] < n_holes[1]:
+                raise ValueError(f'CutOut: n_holes={n_holes!r} must be an int or (a, b) with 0 <= a < b')
+            n_holes = (int(n_holes[0]), int(n_holes[1]))
+        elif isinstance(n_holes, (int, np.integer)) and not isinstance(n_holes, bool) and n_holes >= 0:
+            n_holes = (int(n_holes), int(n_holes))
+        else:
+            raise ValueError(f'CutOut: n_holes={n_holes!r} must be a non-negative int or (a, b) with 0 <= a < b')
+        if n_holes[1] > L.CUTOUT_MAX_HOLES:
+            raise ValueError(f'CutOut: n_holes up to {n_holes[1]} exceeds the {L.CUTOUT_MAX_HOLES} holes per image of '
+                             'this build (YUNET_CUTOUT_MAX_HOLES)')
+        cands = cutout_ratio if with_ratio else cutout_shape
+        if not isinstance(cands, (list, tuple)) or len(cands) == 0:
+            raise ValueError(f'CutOut: {arg}={cands!r} must be one (w, h) pair or a list of pairs')
+        if all(_is_number(v) for v in cands):       # one pair (the reference tells it from a list by the tuple type)
+            cands = [cands]
+        pairs = []
+        for c in cands:
+            if not isinstance(c, (list, tuple)) or len(c) != 2 or not all(_is_number(v) for v in c):
+                raise ValueError(f'CutOut: {arg} entry {c!r} is not a (w, h) pair of numbers')
+            if not all(math.isfinite(float(v)) and float(v) >= 0 for v in c):
+                raise ValueError(f'CutOut: {arg} entry {c!r} must be non-negative and finite')
+            if not with_ratio and not all(float(v) == int(v) for v in c):
+                raise ValueError(f'CutOut: cutout_shape entry {c!r} must be whole pixels')
+            pairs.append((float(c[0]), float(c[1])) if with_ratio else (int(c[0]), int(c[1])))
+        if len(pairs) > L.CUTOUT_MAX_CANDIDATES:
+            raise ValueError(f'CutOut: {arg} has {len(pairs)} candidates, this build takes at most '
+                             f'{L.CUTOUT_MAX_CANDIDATES} (YUNET_CUTOUT_MAX_CANDIDATES)')
+        fill = [fill_in] * 3 if _is_number(fill_in) else fill_in
+        if not isinstance(fill, (list, tuple)) or len(fill) != 3 \
+                or not all(_is_number(v) and math.isfinite(float(v)) for v in fill):
+            raise ValueError(f'CutOut: fill_in={fill_in!r} must be a finite scalar or three finite values (B, G, R)')
+        super().__init__(n_holes=n_holes, fill_in=fill_in, **{arg: cutout_ratio if with_ratio else cutout_shape})
+        self.with_ratio, self.candidates, self.fill = with_ratio, pairs, tuple(float(v) for v in fill)
+
+    def c_cfg(self, seed):
+        c = L.YunetCutoutCfg()
+        (c.n_lo, c.n_hi), c.n_cand, c.with_ratio = self.n_holes, len(self.candidates), int(self.with_ratio)
+        for i, (w, h) in enumerate(self.candidates):
+            c.cand[i][0], c.cand[i][1] = float(w), float(h)
+        for i, v in enumerate(self.fill):
+            c.fill[i] = v
+        c.seed = seed & 0xFFFFFFFF
+        return c
+
+
 def _mix32(x):
     x &= 0xFFFFFFFF
     x ^= x >> 16
@@ -335,6 +401,17 @@ class DevicePipeline:
     def __init__(self, pipeline, seed=0, gmax=64, pad_value=128.0, max_attempts=250, max_retries=64):
         steps = [build_from_cfg(p, PIPELINES) if isinstance(p, dict) else p for p in pipeline]
         names = [type(s).__name__ for s in steps]
+        self.cutout, self.cutout_cfg, self.cutout_holes = None, None, None
+        if 'CutOut' in names:
+            at = names.index('CutOut')
+            if names.count('CutOut') > 1 or at == 0 or names[at + 1:at + 2] != ['Normalize'] \
+                    or names[at - 1] not in ('RandomFlip', 'PhotoMetricDistortion'):
+                raise NotImplementedError(
+                    'DevicePipeline runs CutOut once, immediately in front of Normalize (after RandomFlip and after a '
+                    f'PhotoMetricDistortion that follows RandomFlip); got {names}')
+            self.cutout = steps[at]
+            steps, names = steps[:at] + steps[at + 1:], names[:at] + names[at + 1:]
+            self.cutout_cfg = self.cutout.c_cfg(seed)
         self.mosaic, self.mosaic_cfg, self.geom = None, None, None
         if 'Mosaic' in names:
             at = names.index('Mosaic')
@@ -446,7 +523,19 @@ class DevicePipeline:
         a.src_hw, a.params, a.pparams = _ptr(src.src_hw if merged is None else merged[3]), _ptr(params), _ptr(pp)
         a.geom, a.out_hw = _ptr(self.geom if merged is not None else None), out_hw
         L.check(L.load().yunet_aug_pixels(C.byref(a), C.byref(self.cfg), n, _ptr(img), _stream()), 'yunet_aug_pixels')
+        if self.cutout is not None:
+            self._cutout(img, params if out_hw else None, iteration, dev)
         return self._collate(img, gb, gk, cnt, params, dev)
+
+    def _cutout(self, img, params, iteration, dev):
+        """yunet_aug_cutout on the current stream, in place on the batch tensor; `params`: the decide's table on a
+        multi-scale canvas (the kernel reads each image's S_n from it), None at the fixed size.  The hole table
+        [N, CUTOUT_WORDS] int32 stays in `cutout_holes`."""
+        n, edge = int(img.shape[0]), int(img.shape[-1])
+        holes = torch.empty(n, L.CUTOUT_WORDS, device=dev, dtype=torch.int32)
+        L.check(L.load().yunet_aug_cutout(C.byref(self.cutout_cfg), int(iteration) & 0xFFFFFFFF, n, edge, _ptr(params),
+                                          _ptr(img), _ptr(holes), _stream()), 'yunet_aug_cutout')
+        self.cutout_holes = holes
 
     def _mosaic_decide(self, store, n, iteration, dev):
         """yunet_aug_mosaic_decide on the current stream -> merged = (boxes, keypoints, counts, hw): the merged GT,
