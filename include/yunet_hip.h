@@ -831,6 +831,72 @@ typedef struct YunetCutoutCfg {
 int yunet_aug_cutout(const YunetCutoutCfg* cfg, uint32_t iteration, int N, int E, const int32_t* params, float* img,
                      int32_t* holes, void* stream);
 
+/* RandomAffine (transforms.py:2787-3001) with the five landmarks, on the finished batch tensor and the finished GT of
+ * yunet_aug_decide: after RandomFlip (and a POST PhotoMetricDistortion), in front of CutOut / Normalize.  border is
+ * (0, 0): width = height = the image's own edge S_n (E, or params[n][7] on a multi-scale canvas, clamped to E).
+ *
+ * Draws of image n come from a SUB-STREAM: key mix32(stream_key(seed, iteration, n) ^ YUNET_AFFINE_SALT), counter from
+ * 0, one u32 per random.uniform(a, b) = a + (b - a) * (u32 / 2^32) in doubles, in the reference's call order:
+ *   draw 0  rotation degrees   uniform(-max_rotate_degree, max_rotate_degree)
+ *   draw 1  scaling ratio      uniform(scale_lo, scale_hi)
+ *   draw 2  shear x degrees    uniform(-max_shear_degree, max_shear_degree)
+ *   draw 3  shear y degrees    likewise
+ *   draw 4  translate x ratio  uniform(-max_translate_ratio, max_translate_ratio)     (trans_x = draw * width, a double)
+ *   draw 5  translate y ratio  likewise                                               (trans_y = draw * height)
+ * so windows, flips, GT, photometric tables, mosaic geometry and CutOut holes are the same numbers with the step
+ * present or absent.  M = T @ Sh @ R @ Sc: cos / sin / tan of the radians in fp64, every factor rounded to fp32, the
+ * 3 x 3 products in fp32 from left to right (each entry a0*b0 + a1*b1 + a2*b2, no fused multiply-add).  The bottom row
+ * of M is (0, 0, 1) exactly, so the reference's division by the third coordinate is a division by 1.
+ *
+ * GT: the corners (x1,y1) (x1,y2) (x2,y2) (x2,y1) of a box through M in fp32, min / max, the clip to [0, S] under
+ * bbox_clip_border; a row survives find_inside_bboxes (x1 < S, x2 > 0, y1 < S, y2 > 0) and, with skip_filter == 0,
+ * filter_gt_bboxes on (box * (float)scale): w > min_bbox_size and h > min_bbox_size, w * h / (ow * oh + 1e-16) >
+ * min_area_ratio, max(w / (h + 1e-16), h / (w + 1e-16)) < max_aspect_ratio, all in fp32.  Survivors are compacted in
+ * order with their keypoint rows: (x, y) of the five points through M, clipped to [0, S] under bbox_clip_border, the
+ * third value as it was.  Rows at and beyond the new count are 0.
+ *
+ * table [N, YUNET_AFFINE_WORDS] doubles per image: the six draws, M row-major (fp32 values), the upper two rows of
+ * M^-1 row-major (computed in fp64 from M), rows before, rows after, S. */
+#define YUNET_AFFINE_SALT 0x41464649u  /* "AFFI" */
+#define YUNET_AFFINE_WORDS 24
+#define YUNET_AFFINE_DRAWS 0           /* 6 */
+#define YUNET_AFFINE_M 6               /* 9 */
+#define YUNET_AFFINE_INV 15            /* 6: i00 i01 i02 i10 i11 i12 */
+#define YUNET_AFFINE_ROWS_IN 21
+#define YUNET_AFFINE_ROWS_OUT 22
+#define YUNET_AFFINE_EDGE 23
+#define YUNET_AFFINE_MAX_SHEAR 45.0    /* degrees: below it det(Sh) = 1 - tan(sx) tan(sy) > 0, so M never mirrors */
+typedef struct YunetAffineCfg {
+    double max_rotate_degree;    /* finite */
+    double max_translate_ratio;  /* in [0, 1] */
+    double scale_lo, scale_hi;   /* 0 < scale_lo <= scale_hi, finite */
+    double max_shear_degree;     /* |.| < YUNET_AFFINE_MAX_SHEAR */
+    float min_bbox_size, min_area_ratio, max_aspect_ratio;   /* finite; read with skip_filter == 0 */
+    float border_val[3];         /* per channel of the batch tensor (BGR), finite */
+    int32_t bbox_clip_border, skip_filter;
+    int32_t gmax;                /* padded GT rows per image, in and out: 1..4096 */
+    uint32_t seed;
+} YunetAffineCfg;
+/* One workgroup per image on the current stream.  in_boxes [N, gmax, 4], in_kps [N, gmax, 15], in_count [N] (a count
+ * outside [0, gmax] is clamped) -> out_boxes / out_kps / out_count of the same shapes (other buffers than the inputs)
+ * and table.  params NULL: every image's edge is E, else [N,8] of yunet_aug_decide (multiscale != 0).  YUNET_EINVAL,
+ * before any launch, for a null cfg / in / out / table pointer, N < 1, E outside [1, YUNET_AUG_MAX_EDGE], an output
+ * that is its input, and a configuration outside the ranges above. */
+int yunet_aug_affine_decide(const YunetAffineCfg* cfg, uint32_t iteration, int N, int E, const int32_t* params,
+                            const float* in_boxes, const float* in_kps, const int32_t* in_count, float* out_boxes,
+                            float* out_kps, int32_t* out_count, double* table, void* stream);
+/* The pixels of cv2.warpPerspective(img, M, (S, S), borderValue=border_val), bilinear: out[n, c, y, x] for x, y < S_n
+ * samples in[n, c] at (sx, sy) = M^-1 (x, y, 1) -- the table's six inverse words rounded to fp32, sx = (i00 * x + i01 * y)
+ * + i02 in fp32 -- with x0 = floor(sx), fx = sx - x0 and the weights (1-fx)(1-fy), fx(1-fy), (1-fx)fy, fx fy; a tap outside
+ * [0, S_n) contributes border_val[c], a pixel whose four taps are all outside is border_val[c]; a coordinate
+ * on the pixel grid (fx = fy = 0) copies its pixel.  Pixels at or beyond
+ * S_n (the multi-scale canvas) are 0.  cv2's fixed-point coordinate table (1/32 pixel) is not reproduced.  in and out
+ * [N, 3, E, E] fp32, different buffers; only the YUNET_AFFINE_INV words of table are read.  YUNET_EINVAL, before any
+ * launch, for a null table / border_val / in / out, in == out, N < 1, E outside [1, YUNET_AUG_MAX_EDGE], more than 2^31 - 1
+ * workgroups (N * ceil(E * E / 256)) or a non-finite border_val. */
+int yunet_aug_affine_pixels(const double* table, const float border_val[3], int N, int E, const int32_t* params,
+                            const float* in, float* out, void* stream);
+
 /* The TEST pipeline of a batch (test_pipeline.DeviceTestPipeline; csrc/test_pipeline.hip), one launch: decoded uint8
  * HWC sources addressed as for yunet_aug_pixels (src, src_off [N], src_hw [N,2]) -> out_img [N, 3, Hc, Wc] fp32 planar.
  * table [N,4] int32 (device, written by the host) = (nh, nw, flip, 0) per image.  Inside the top-left nh x nw corner:

@@ -143,6 +143,18 @@ class YunetCutoutCfg(C.Structure):
                 ('cand', (C.c_double * 2) * CUTOUT_MAX_CANDIDATES), ('fill', C.c_float * 3), ('seed', C.c_uint32)]
 
 
+# RandomAffine (YUNET_AFFINE_*): sub-stream salt, the doubles of a table row and where its parts start
+AFFINE_SALT, AFFINE_WORDS, AFFINE_MAX_SHEAR = 0x41464649, 24, 45.0
+AFFINE_DRAWS, AFFINE_M, AFFINE_INV, AFFINE_ROWS_IN, AFFINE_ROWS_OUT, AFFINE_EDGE = 0, 6, 15, 21, 22, 23
+
+
+class YunetAffineCfg(C.Structure):
+    _fields_ = [('max_rotate_degree', C.c_double), ('max_translate_ratio', C.c_double), ('scale_lo', C.c_double),
+                ('scale_hi', C.c_double), ('max_shear_degree', C.c_double), ('min_bbox_size', C.c_float),
+                ('min_area_ratio', C.c_float), ('max_aspect_ratio', C.c_float), ('border_val', C.c_float * 3),
+                ('bbox_clip_border', C.c_int32), ('skip_filter', C.c_int32), ('gmax', C.c_int32), ('seed', C.c_uint32)]
+
+
 class YunetAugPixels(C.Structure):
     """The pixel pass of yunet_aug_pixels: rect / position / out_hw / geom select the form (include/yunet_hip.h)."""
     _fields_ = [('src', C.c_void_p), ('src_off', C.c_void_p), ('src_hw', C.c_void_p), ('rect', C.c_void_p),
@@ -218,6 +230,8 @@ _SIGNATURES = {
                                 [C.POINTER(YunetMosaicCfg), C.c_uint32] + [C.c_void_p] * 6),
     'yunet_aug_mosaic_canvas': (C.c_int, [C.c_void_p] * 3 + [C.POINTER(YunetMosaicCfg), C.c_int, C.c_void_p, C.c_void_p]),
     'yunet_aug_cutout': (C.c_int, [C.POINTER(YunetCutoutCfg), C.c_uint32, C.c_int, C.c_int] + [C.c_void_p] * 4),
+    'yunet_aug_affine_decide': (C.c_int, [C.POINTER(YunetAffineCfg), C.c_uint32, C.c_int, C.c_int] + [C.c_void_p] * 9),
+    'yunet_aug_affine_pixels': (C.c_int, [C.c_void_p, C.POINTER(C.c_float * 3), C.c_int, C.c_int] + [C.c_void_p] * 4),
     'yunet_test_pixels': (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p]),
     'yunet_rescale_dets': (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]),
     'yunet_score_wider': (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_longlong, C.c_longlong, C.c_double, C.c_void_p, C.c_int] +

@@ -17,7 +17,8 @@
 // remaining pixels are 0 (DefaultFormatBundle's padding_value through mmcv's collate).
 //
 // CutOut (transforms.py:2143-2214) is a third launch on the finished batch tensor: aug_cutout_kernel, one workgroup per
-// (image, hole).
+// (image, hole).  RandomAffine (transforms.py:2787-3001, with the landmarks) runs in front of it as two launches on the
+// finished batch: aug_affine_decide_kernel (draws, matrix, GT) and aug_affine_pixels_kernel (the warp into a second tensor).
 //
 // Built with -ffp-contract=off: every float operation is the single rounded operation numpy
 // performs, so boxes / keypoints are bit-identical to the reference and pixels to the oracle.
@@ -680,7 +681,191 @@ __global__ __launch_bounds__(256) void aug_cutout_kernel(const YunetCutoutCfg cf
     }
 }
 
+// ---- RandomAffine (transforms.py:2787-3001; include/yunet_hip.h YUNET_AFFINE_*) ----------------------------------------
+__device__ __forceinline__ uint32_t affine_key(uint32_t seed, uint32_t iteration, uint32_t image) {
+    return mix32(stream_key(seed, iteration, image) ^ YUNET_AFFINE_SALT);
+}
+// random.uniform(a, b) = a + (b - a) * random_sample(), Python's doubles
+__device__ __forceinline__ double affine_uniform(uint32_t u, double a, double b) {
+    return a + (b - a) * ((double)u * (1.0 / 4294967296.0));
+}
+// c = a @ b of two float32 3 x 3 matrices: every entry a0*b0 + a1*b1 + a2*b2, summed from the left
+__device__ __forceinline__ void affine_matmul(const float* a, const float* b, float* c) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            c[3 * i + j] = (a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j]) + a[3 * i + 2] * b[6 + j];
+}
+__device__ __forceinline__ float affine_clip(float v, float hi, bool clip) {
+    return clip ? fminf(fmaxf(v, 0.0f), hi) : v;
+}
+
+// One 64-lane workgroup per image: the six draws, M and its inverse (every lane computes them, lane 0 stores the table
+// row), then the rows of the image in steps of 64 -- each lane transforms one row, a ballot gives the surviving rows
+// their places in order.  in_* and out_* are different buffers.  PARAMS as in aug_cutout_kernel.
+template <bool PARAMS>
+__global__ __launch_bounds__(64) void aug_affine_decide_kernel(
+    const YunetAffineCfg cfg, uint32_t iteration, int E, const int32_t* __restrict__ params,
+    const float* __restrict__ in_boxes, const float* __restrict__ in_kps, const int32_t* __restrict__ in_count,
+    float* __restrict__ out_boxes, float* __restrict__ out_kps, int32_t* __restrict__ out_count,
+    double* __restrict__ table) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    int S = PARAMS ? params[8 * n + AUG_P_SIZE] : E;
+    S = S > E ? E : S < 0 ? 0 : S;
+    const int gmax = cfg.gmax;
+    const int G = in_count[n] < 0 ? 0 : in_count[n] > gmax ? gmax : in_count[n];
+    const uint32_t key = affine_key(cfg.seed, iteration, (uint32_t)n);
+    double d[6];
+    d[0] = affine_uniform(rand_u32(key, 0u), -cfg.max_rotate_degree, cfg.max_rotate_degree);
+    d[1] = affine_uniform(rand_u32(key, 1u), cfg.scale_lo, cfg.scale_hi);
+    d[2] = affine_uniform(rand_u32(key, 2u), -cfg.max_shear_degree, cfg.max_shear_degree);
+    d[3] = affine_uniform(rand_u32(key, 3u), -cfg.max_shear_degree, cfg.max_shear_degree);
+    d[4] = affine_uniform(rand_u32(key, 4u), -cfg.max_translate_ratio, cfg.max_translate_ratio);
+    d[5] = affine_uniform(rand_u32(key, 5u), -cfg.max_translate_ratio, cfg.max_translate_ratio);
+    const double to_rad = 3.14159265358979323846 / 180.0;                 // math.radians: x * (pi / 180)
+    const double rad = d[0] * to_rad;
+    const float co = (float)cos(rad), si = (float)sin(rad), sc = (float)d[1];
+    const float R[9] = {co, -si, 0.0f, si, co, 0.0f, 0.0f, 0.0f, 1.0f};
+    const float Sc[9] = {sc, 0.0f, 0.0f, 0.0f, sc, 0.0f, 0.0f, 0.0f, 1.0f};
+    const float Sh[9] = {1.0f, (float)tan(d[2] * to_rad), 0.0f, (float)tan(d[3] * to_rad), 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+    const float T[9] = {1.0f, 0.0f, (float)(d[4] * (double)S), 0.0f, 1.0f, (float)(d[5] * (double)S), 0.0f, 0.0f, 1.0f};
+    float A[9], B[9], M[9];
+    affine_matmul(T, Sh, A);
+    affine_matmul(A, R, B);
+    affine_matmul(B, Sc, M);
+
+    const float fS = (float)S;
+    const bool clip = cfg.bbox_clip_border != 0, filter = cfg.skip_filter == 0;
+    const float* bx = in_boxes + (size_t)n * gmax * 4;
+    const float* kp = in_kps + (size_t)n * gmax * 15;
+    float* ob = out_boxes + (size_t)n * gmax * 4;
+    float* ok = out_kps + (size_t)n * gmax * 15;
+    int kept = 0;
+    for (int base = 0; base < G; base += 64) {
+        const int g = base + lane;
+        bool keep = false;
+        float w0 = 0.0f, w1 = 0.0f, w2 = 0.0f, w3 = 0.0f;
+        if (g < G) {
+            const float* b = bx + 4 * g;
+            const float px[4] = {b[0], b[0], b[2], b[2]}, py[4] = {b[1], b[3], b[3], b[1]};
+            float xs[4], ys[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                xs[c] = (M[0] * px[c] + M[1] * py[c]) + M[2];
+                ys[c] = (M[3] * px[c] + M[4] * py[c]) + M[5];
+            }
+            w0 = affine_clip(fminf(fminf(xs[0], xs[1]), fminf(xs[2], xs[3])), fS, clip);
+            w1 = affine_clip(fminf(fminf(ys[0], ys[1]), fminf(ys[2], ys[3])), fS, clip);
+            w2 = affine_clip(fmaxf(fmaxf(xs[0], xs[1]), fmaxf(xs[2], xs[3])), fS, clip);
+            w3 = affine_clip(fmaxf(fmaxf(ys[0], ys[1]), fmaxf(ys[2], ys[3])), fS, clip);
+            keep = w0 < fS && w2 > 0.0f && w1 < fS && w3 > 0.0f;                           // find_inside_bboxes
+            if (filter) {                                                                  // filter_gt_bboxes
+                const float ow = b[2] * sc - b[0] * sc, oh = b[3] * sc - b[1] * sc;        // bboxes * scaling_ratio
+                const float ww = w2 - w0, wh = w3 - w1;
+                const float aspect = fmaxf(ww / (wh + 1e-16f), wh / (ww + 1e-16f));
+                keep = keep && ww > cfg.min_bbox_size && wh > cfg.min_bbox_size &&
+                       ww * wh / (ow * oh + 1e-16f) > cfg.min_area_ratio && aspect < cfg.max_aspect_ratio;
+            }
+        }
+        const unsigned long long m = __ballot(keep);
+        if (keep) {
+            const int idx = kept + __popcll(m & ((1ull << lane) - 1ull));       // idx <= g < gmax
+            float* o = ob + 4 * idx;
+            o[0] = w0; o[1] = w1; o[2] = w2; o[3] = w3;
+            const float* k = kp + 15 * g;
+            float* q = ok + 15 * idx;
+#pragma unroll
+            for (int j = 0; j < 5; ++j) {
+                const float x = k[3 * j], y = k[3 * j + 1];
+                q[3 * j + 0] = affine_clip((M[0] * x + M[1] * y) + M[2], fS, clip);
+                q[3 * j + 1] = affine_clip((M[3] * x + M[4] * y) + M[5], fS, clip);
+                q[3 * j + 2] = k[3 * j + 2];
+            }
+        }
+        kept += __popcll(m);
+    }
+    for (int i = kept * 4 + lane; i < gmax * 4; i += 64) ob[i] = 0.0f;
+    for (int i = kept * 15 + lane; i < gmax * 15; i += 64) ok[i] = 0.0f;
+    if (lane == 0) {
+        const double a = M[0], b = M[1], c = M[2], e = M[3], f = M[4], h = M[5];
+        const double det = a * f - b * e;
+        double* t = table + (size_t)n * YUNET_AFFINE_WORDS;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) t[YUNET_AFFINE_DRAWS + i] = d[i];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) t[YUNET_AFFINE_M + i] = (double)M[i];
+        double* v = t + YUNET_AFFINE_INV;
+        v[0] = f / det; v[1] = -b / det; v[2] = (b * h - c * f) / det;
+        v[3] = -e / det; v[4] = a / det; v[5] = (c * e - a * h) / det;
+        t[YUNET_AFFINE_ROWS_IN] = (double)G; t[YUNET_AFFINE_ROWS_OUT] = (double)kept; t[YUNET_AFFINE_EDGE] = (double)S;
+        out_count[n] = kept;
+    }
+}
+
+// One thread per pixel of the E x E plane, one row of workgroups per image (blockIdx.x = n * blocks_per_image + block):
+// consecutive lanes store consecutive pixels of each of the three planes; coordinates, taps and weights are worked out
+// once per pixel and shared by the channels.  PARAMS as in aug_cutout_kernel; pixels at or beyond S_n are 0.
+template <bool PARAMS>
+__global__ __launch_bounds__(256) void aug_affine_pixels_kernel(
+    const double* __restrict__ table, float bv0, float bv1, float bv2, int E, int blocks_per_image,
+    const int32_t* __restrict__ params, const float* __restrict__ in, float* __restrict__ out) {
+    const int n = blockIdx.x / blocks_per_image;
+    const int i = (blockIdx.x - n * blocks_per_image) * 256 + threadIdx.x;
+    if (i >= E * E) return;
+    int S = PARAMS ? params[8 * n + AUG_P_SIZE] : E;
+    S = S > E ? E : S;
+    const int y = i / E, x = i - y * E;
+    const size_t plane = (size_t)E * E;
+    const float* src = in + (size_t)n * 3 * plane;
+    float* dst = out + (size_t)n * 3 * plane + i;
+    if (x >= S || y >= S) {
+        dst[0] = 0.0f; dst[plane] = 0.0f; dst[2 * plane] = 0.0f;
+        return;
+    }
+    const double* t = table + (size_t)n * YUNET_AFFINE_WORDS + YUNET_AFFINE_INV;
+    const float fx_ = (float)x, fy_ = (float)y;
+    const float sx = ((float)t[0] * fx_ + (float)t[1] * fy_) + (float)t[2];
+    const float sy = ((float)t[3] * fx_ + (float)t[4] * fy_) + (float)t[5];
+    float v0 = bv0, v1 = bv1, v2 = bv2;
+    // all four taps outside (or a coordinate that is not a number): border_val; the test also keeps x0 / y0 within int
+    if (sx > -1.0f && sx < (float)S && sy > -1.0f && sy < (float)S) {
+        const float flx = floorf(sx), fly = floorf(sy);
+        const int x0 = (int)flx, y0 = (int)fly;                 // in [-1, S - 1]
+        const float ax = sx - flx, ay = sy - fly;
+        const float w00 = (1.0f - ax) * (1.0f - ay), w01 = ax * (1.0f - ay), w10 = (1.0f - ax) * ay, w11 = ax * ay;
+        const bool inx0 = x0 >= 0, inx1 = x0 + 1 < S, iny0 = y0 >= 0, iny1 = y0 + 1 < S;
+        const float* p = src + (ptrdiff_t)y0 * E + x0;          // dereferenced only at taps inside [0, S) x [0, S)
+        const float bv[3] = {bv0, bv1, bv2};
+        float r[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float* pc = p + c * plane;
+            const float t00 = iny0 && inx0 ? pc[0] : bv[c], t01 = iny0 && inx1 ? pc[1] : bv[c];
+            const float t10 = iny1 && inx0 ? pc[E] : bv[c], t11 = iny1 && inx1 ? pc[E + 1] : bv[c];
+            // a coordinate on the pixel grid copies its pixel (the sum would turn a -0.0 into +0.0)
+            r[c] = ax == 0.0f && ay == 0.0f ? t00 : ((w00 * t00 + w01 * t01) + w10 * t10) + w11 * t11;
+        }
+        v0 = r[0]; v1 = r[1]; v2 = r[2];
+    }
+    dst[0] = v0; dst[plane] = v1; dst[2 * plane] = v2;
+}
+
 }  // namespace
+
+static bool affine_cfg_ok(const YunetAffineCfg* c) {
+    if (!c) return false;
+    const double v[5] = {c->max_rotate_degree, c->max_translate_ratio, c->scale_lo, c->scale_hi, c->max_shear_degree};
+    for (double x : v)
+        if (!std::isfinite(x)) return false;
+    const float f[6] = {c->min_bbox_size, c->min_area_ratio, c->max_aspect_ratio, c->border_val[0], c->border_val[1],
+                        c->border_val[2]};
+    for (float x : f)
+        if (!std::isfinite(x)) return false;
+    return c->max_translate_ratio >= 0.0 && c->max_translate_ratio <= 1.0 && c->scale_lo > 0.0 &&
+           c->scale_lo <= c->scale_hi && std::fabs(c->max_shear_degree) < YUNET_AFFINE_MAX_SHEAR && c->gmax >= 1 &&
+           c->gmax <= 4096;
+}
 
 static bool cutout_cfg_ok(const YunetCutoutCfg* c) {
     if (!c || c->n_lo < 0 || c->n_lo > c->n_hi || c->n_hi > YUNET_CUTOUT_MAX_HOLES || c->n_cand < 1 ||
@@ -823,6 +1008,36 @@ extern "C" int yunet_aug_cutout(const YunetCutoutCfg* cfg, uint32_t iteration, i
     with_bool(params != nullptr, [&](auto ms) {
         hipLaunchKernelGGL((aug_cutout_kernel<decltype(ms)::value>), dim3(N * YUNET_CUTOUT_MAX_HOLES), dim3(256), 0,
                            (hipStream_t)stream, *cfg, iteration, E, params, img, holes);
+    });
+    return hip_status();
+}
+
+extern "C" int yunet_aug_affine_decide(const YunetAffineCfg* cfg, uint32_t iteration, int N, int E, const int32_t* params,
+                                       const float* in_boxes, const float* in_kps, const int32_t* in_count,
+                                       float* out_boxes, float* out_kps, int32_t* out_count, double* table,
+                                       void* stream) {
+    if (!affine_cfg_ok(cfg) || N < 1 || E < 1 || E > YUNET_AUG_MAX_EDGE || !in_boxes || !in_kps || !in_count ||
+        !out_boxes || !out_kps || !out_count || !table || in_boxes == out_boxes || in_kps == out_kps ||
+        in_count == out_count)
+        return YUNET_EINVAL;
+    with_bool(params != nullptr, [&](auto ms) {
+        hipLaunchKernelGGL((aug_affine_decide_kernel<decltype(ms)::value>), dim3(N), dim3(64), 0, (hipStream_t)stream,
+                           *cfg, iteration, E, params, in_boxes, in_kps, in_count, out_boxes, out_kps, out_count, table);
+    });
+    return hip_status();
+}
+
+extern "C" int yunet_aug_affine_pixels(const double* table, const float border_val[3], int N, int E,
+                                       const int32_t* params, const float* in, float* out, void* stream) {
+    if (!table || !border_val || !in || !out || in == out || N < 1 || E < 1 || E > YUNET_AUG_MAX_EDGE ||
+        !std::isfinite(border_val[0]) || !std::isfinite(border_val[1]) || !std::isfinite(border_val[2]))
+        return YUNET_EINVAL;
+    const long long per_image = ((long long)E * E + 255) / 256;
+    if (per_image * N > INT32_MAX) return YUNET_EINVAL;
+    with_bool(params != nullptr, [&](auto ms) {
+        hipLaunchKernelGGL((aug_affine_pixels_kernel<decltype(ms)::value>), dim3((unsigned)(per_image * N)), dim3(256), 0,
+                           (hipStream_t)stream, table, border_val[0], border_val[1], border_val[2], E, (int)per_image,
+                           params, in, out);
     });
     return hip_status();
 }

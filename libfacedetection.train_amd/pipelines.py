@@ -7,8 +7,8 @@
 
 `RandomSquareCrop -> Resize(keep_ratio=False) -> RandomFlip -> Normalize(0, 1) ->
 DefaultFormatBundle -> Collect` run as two HIP kernels (csrc/augment.hip), three with an optional
-`PhotoMetricDistortion` before RandomSquareCrop or after RandomFlip, and one more launch with an
-optional `CutOut` in front of Normalize; the classes below carry
+`PhotoMetricDistortion` before RandomSquareCrop or after RandomFlip, two more launches with an optional
+`RandomAffine` after RandomFlip and one more with an optional `CutOut` in front of Normalize; the classes below carry
 the configuration under the reference's registry names (mmdet/datasets/pipelines/transforms.py,
 formatting.py, loading.py) so the reference's config files build unchanged.  Decoding image files
 (LoadImageFromFile) is outside this stage: sources arrive as uint8 HWC arrays.
@@ -256,6 +256,68 @@ class CutOut(_Carrier):
         return c
 
 
+@PIPELINES.register_module()
+class RandomAffine(_Carrier):
+    """transforms.py:2787-3001 with the reference's constructor and one keyword more, `use_kps`, as the reference added
+    it to Mosaic: the five landmarks go through the same matrix as the boxes.  Its assertions are ValueErrors here.  Runs
+    as yunet_aug_affine_decide + yunet_aug_affine_pixels on the finished batch tensor and GT, after RandomFlip (or a POST
+    PhotoMetricDistortion) and in front of CutOut / Normalize; its draws come from a sub-stream of the pipeline's
+    generator (include/yunet_hip.h YUNET_AFFINE_SALT).  `border_val` is a scalar or three values in the image's channel
+    order (BGR).  `border` stays (0, 0): the output keeps the input's size.  |max_shear_degree| stays below
+    _lib.AFFINE_MAX_SHEAR, so that the matrix never mirrors the image (no left / right landmark swap is built)."""
+
+    def __init__(self, max_rotate_degree=10.0, max_translate_ratio=0.1, scaling_ratio_range=(0.5, 1.5),
+                 max_shear_degree=2.0, border=(0, 0), border_val=(114, 114, 114), min_bbox_size=2, min_area_ratio=0.2,
+                 max_aspect_ratio=20, bbox_clip_border=True, skip_filter=True, use_kps=False):
+        if not isinstance(scaling_ratio_range, (list, tuple)) or len(scaling_ratio_range) != 2:
+            raise ValueError(f'RandomAffine: scaling_ratio_range={scaling_ratio_range!r} must be (min, max)')
+        for name, v in (('max_rotate_degree', max_rotate_degree), ('max_translate_ratio', max_translate_ratio),
+                        ('scaling_ratio_range', scaling_ratio_range[0]), ('scaling_ratio_range', scaling_ratio_range[1]),
+                        ('max_shear_degree', max_shear_degree), ('min_bbox_size', min_bbox_size),
+                        ('min_area_ratio', min_area_ratio), ('max_aspect_ratio', max_aspect_ratio)):
+            if not _is_number(v) or not math.isfinite(float(v)):
+                raise ValueError(f'RandomAffine: {name}={v!r} must be a finite number')
+        if not 0 <= max_translate_ratio <= 1:
+            raise ValueError(f'RandomAffine: max_translate_ratio={max_translate_ratio} must lie in [0, 1]')
+        if not 0 < scaling_ratio_range[0] <= scaling_ratio_range[1]:
+            raise ValueError(f'RandomAffine: scaling_ratio_range={tuple(scaling_ratio_range)} must have 0 < min <= max')
+        if not abs(max_shear_degree) < L.AFFINE_MAX_SHEAR:
+            raise ValueError(f'RandomAffine: max_shear_degree={max_shear_degree} must stay below {L.AFFINE_MAX_SHEAR} '
+                             'degrees (YUNET_AFFINE_MAX_SHEAR): beyond it a draw can mirror the image')
+        fill = [border_val] * 3 if _is_number(border_val) else border_val
+        if not isinstance(fill, (list, tuple)) or len(fill) != 3 \
+                or not all(_is_number(v) and math.isfinite(float(v)) for v in fill):
+            raise ValueError(f'RandomAffine: border_val={border_val!r} must be a finite scalar or three finite values '
+                             '(B, G, R)')
+        if not isinstance(border, (list, tuple)) or len(border) != 2 or not all(_is_number(v) for v in border):
+            raise ValueError(f'RandomAffine: border={border!r} must be two numbers')
+        if tuple(border) != (0, 0):
+            raise NotImplementedError(f'RandomAffine(border={tuple(border)}): the output keeps the input\'s size, '
+                                      'border=(0, 0); the crop after Mosaic does here what border does in YOLOX')
+        if not use_kps:
+            raise NotImplementedError('RandomAffine(use_kps=False): the device pipeline always carries the five landmarks '
+                                      '(LoadAnnotations(with_keypoints=True)); write use_kps=True')
+        super().__init__(max_rotate_degree=max_rotate_degree, max_translate_ratio=max_translate_ratio,
+                         scaling_ratio_range=tuple(scaling_ratio_range), max_shear_degree=max_shear_degree, border=(0, 0),
+                         border_val=border_val, min_bbox_size=min_bbox_size, min_area_ratio=min_area_ratio,
+                         max_aspect_ratio=max_aspect_ratio, bbox_clip_border=bool(bbox_clip_border),
+                         skip_filter=bool(skip_filter), use_kps=True)
+        self.fill = tuple(float(v) for v in fill)
+
+    def c_cfg(self, seed, gmax):
+        c = L.YunetAffineCfg()
+        c.max_rotate_degree, c.max_translate_ratio = float(self.max_rotate_degree), float(self.max_translate_ratio)
+        c.scale_lo, c.scale_hi = (float(v) for v in self.scaling_ratio_range)
+        c.max_shear_degree = float(self.max_shear_degree)
+        c.min_bbox_size, c.min_area_ratio = float(self.min_bbox_size), float(self.min_area_ratio)
+        c.max_aspect_ratio = float(self.max_aspect_ratio)
+        for i, v in enumerate(self.fill):
+            c.border_val[i] = v
+        c.bbox_clip_border, c.skip_filter, c.gmax, c.seed = int(self.bbox_clip_border), int(self.skip_filter), gmax, \
+            seed & 0xFFFFFFFF
+        return c
+
+
 def _mix32(x):
     x &= 0xFFFFFFFF
     x ^= x >> 16
@@ -401,6 +463,19 @@ class DevicePipeline:
     def __init__(self, pipeline, seed=0, gmax=64, pad_value=128.0, max_attempts=250, max_retries=64):
         steps = [build_from_cfg(p, PIPELINES) if isinstance(p, dict) else p for p in pipeline]
         names = [type(s).__name__ for s in steps]
+        self.affine, self.affine_cfg, self.affine_table = None, None, None
+        if 'RandomAffine' in names:
+            at = names.index('RandomAffine')
+            before = names[at - 1] if at else None
+            if before == 'PhotoMetricDistortion' and names[max(at - 2, 0)] != 'RandomFlip':
+                before = None
+            if names.count('RandomAffine') > 1 or before not in ('RandomFlip', 'PhotoMetricDistortion') \
+                    or names[at + 1:at + 2] not in (['CutOut'], ['Normalize']):
+                raise NotImplementedError(
+                    'DevicePipeline runs RandomAffine once, after RandomFlip (and after a PhotoMetricDistortion that '
+                    f'follows RandomFlip) and immediately in front of CutOut or Normalize; got {names}')
+            self.affine = steps[at]         # its configuration is made below, once the GT rows per image are known
+            steps, names = steps[:at] + steps[at + 1:], names[:at] + names[at + 1:]
         self.cutout, self.cutout_cfg, self.cutout_holes = None, None, None
         if 'CutOut' in names:
             at = names.index('CutOut')
@@ -477,6 +552,8 @@ class DevicePipeline:
         self.cfg = cfg
         self.photo_cfg = self.photo.c_cfg(self.photo_position) if self.photo is not None else None
         self.gmax = gmax
+        if self.affine is not None:
+            self.affine_cfg = self.affine.c_cfg(seed, gmax)
         self.params = None
         self._pixels = L.YunetAugPixels()       # the pixel pass's descriptor: the per-batch fields are filled in place
         self._pixels.position = self.photo_position
@@ -523,9 +600,27 @@ class DevicePipeline:
         a.src_hw, a.params, a.pparams = _ptr(src.src_hw if merged is None else merged[3]), _ptr(params), _ptr(pp)
         a.geom, a.out_hw = _ptr(self.geom if merged is not None else None), out_hw
         L.check(L.load().yunet_aug_pixels(C.byref(a), C.byref(self.cfg), n, _ptr(img), _stream()), 'yunet_aug_pixels')
+        if self.affine is not None:
+            img, gb, gk, cnt = self._affine(img, gb, gk, cnt, params if out_hw else None, iteration, dev)
         if self.cutout is not None:
             self._cutout(img, params if out_hw else None, iteration, dev)
         return self._collate(img, gb, gk, cnt, params, dev)
+
+    def _affine(self, img, gb, gk, cnt, params, iteration, dev):
+        """yunet_aug_affine_decide + yunet_aug_affine_pixels on the current stream -> (warped batch tensor, boxes,
+        keypoints, counts): the warp cannot run in place, so each is a new tensor.  `params` as for _cutout.  The table
+        [N, AFFINE_WORDS] float64 (draws, M, its inverse, rows before / after, edge) stays in `affine_table`."""
+        n, edge = int(img.shape[0]), int(img.shape[-1])
+        table = torch.empty(n, L.AFFINE_WORDS, device=dev, dtype=torch.float64)
+        ob, ok, oc, out = torch.empty_like(gb), torch.empty_like(gk), torch.empty_like(cnt), torch.empty_like(img)
+        lib, c = L.load(), self.affine_cfg
+        L.check(lib.yunet_aug_affine_decide(C.byref(c), int(iteration) & 0xFFFFFFFF, n, edge, _ptr(params), _ptr(gb),
+                                            _ptr(gk), _ptr(cnt), _ptr(ob), _ptr(ok), _ptr(oc), _ptr(table), _stream()),
+                'yunet_aug_affine_decide')
+        L.check(lib.yunet_aug_affine_pixels(_ptr(table), C.byref(c.border_val), n, edge, _ptr(params), _ptr(img),
+                                            _ptr(out), _stream()), 'yunet_aug_affine_pixels')
+        self.affine_table = table
+        return out, ob, ok, oc
 
     def _cutout(self, img, params, iteration, dev):
         """yunet_aug_cutout on the current stream, in place on the batch tensor; `params`: the decide's table on a
