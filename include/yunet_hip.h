@@ -897,6 +897,96 @@ int yunet_aug_affine_decide(const YunetAffineCfg* cfg, uint32_t iteration, int N
 int yunet_aug_affine_pixels(const double* table, const float border_val[3], int N, int E, const int32_t* params,
                             const float* in, float* out, void* stream);
 
+/* MixUp (transforms.py:2523-2783) with the five landmarks, on the finished batch tensor and the finished GT: after
+ * RandomFlip (a POST PhotoMetricDistortion, RandomAffine), in front of CutOut / Normalize.  The partner is a raw decoded
+ * image of the store with its raw GT (what MultiImageMixDataset hands over as mix_results).  T = the image's own edge
+ * S_n (E, or params[n][7] on a multi-scale canvas, clamped to E); D = img_scale.
+ *
+ * Draws of image n come from a SUB-STREAM: key mix32(stream_key(seed, iteration, n) ^ YUNET_MIXUP_SALT), counter from
+ * 0, in the reference's call order (its `random` is numpy's: randint excludes the upper end):
+ *   up to max_iters  partner = (u32 * M) >> 32, stopping at the first with store_gcnt != 0          (get_indexes)
+ *   -- the last partner drawn has no boxes: NOT APPLIED; no further draw, the GT is copied, the pixels keep their bytes
+ *   jit  = lo + (hi - lo) * (u32 / 2^32)            random.uniform(*ratio_range), doubles
+ *   flip = (u32 / 2^32) > flip_ratio                the reference's inequality
+ *   y_offset = (u32 * (P - T)) >> 32  only if P > T, then x_offset likewise          P = max(J, T)
+ * so windows, flips, GT before MixUp, photometric tables, mosaic geometry, affine tables and CutOut holes are the same
+ * numbers with the step present or absent.  Geometry in integers and doubles, as the Python code has it: partner h x w,
+ * sr = min(D / h, D / w), rw = (int)(w * sr), rh = (int)(h * sr), J = (int)(D * jit), sr *= jit.  rw, rh or J below 1
+ * (cv2 would refuse the empty size): status 4, not applied.
+ *
+ * GT, fp32 with one rounding per operation.  Partner box: * (float)sr; clip to [0, J] under bbox_clip_border; flipped:
+ * (x1, x2) = (J - x2, J - x1); then the copy: minus the offsets, clip to [0, T] under bbox_clip_border.  With
+ * skip_filter == 0 a partner row survives _filter_box_candidates(before the offsets, after): w2 > min_bbox_size,
+ * h2 > min_bbox_size, w2 * h2 / (w1 * h1 + 1e-16) > min_area_ratio, max(w2 / (h2 + 1e-16), h2 / (w2 + 1e-16)) <
+ * max_aspect_ratio.  The image's own rows come first, then the partner's; find_inside_bboxes (x1 < T, x2 > 0, y1 < T,
+ * y2 > 0) runs over all of them, the image's own included; survivors are compacted in order, rows at and beyond the
+ * count are 0, rows beyond gmax are dropped (status 2).  The partner's landmarks: (x, y) * (float)sr, clip to [0, J]
+ * under bbox_clip_border, flipped x = J - x with the points permuted [1, 0, 2, 4, 3], minus the offsets, clip to [0, T]
+ * under bbox_clip_border; the third value as it was.
+ *
+ * table [N, YUNET_MIXUP_WORDS] doubles per image (integers held exactly). */
+#define YUNET_MIXUP_SALT 0x4D495855u   /* "MIXU" */
+#define YUNET_MIXUP_WORDS 18
+#define YUNET_MIXUP_PARTNER 0          /* store index of the last partner drawn */
+#define YUNET_MIXUP_APPLIED 1
+#define YUNET_MIXUP_INDEX_DRAWS 2      /* partner draws made, 1..max_iters */
+#define YUNET_MIXUP_JIT 3
+#define YUNET_MIXUP_FLIP 4
+#define YUNET_MIXUP_J 5
+#define YUNET_MIXUP_RW 6
+#define YUNET_MIXUP_RH 7
+#define YUNET_MIXUP_XOFF 8
+#define YUNET_MIXUP_YOFF 9
+#define YUNET_MIXUP_SX 10              /* 1 / ((double)rw / w): raw-image coordinate scale of the first resize */
+#define YUNET_MIXUP_SY 11              /* 1 / ((double)rh / h) */
+#define YUNET_MIXUP_ROWS_IN 12         /* the image's own rows */
+#define YUNET_MIXUP_ROWS_OUT 13        /* survivors, before the truncation to gmax */
+#define YUNET_MIXUP_STATUS 14          /* bit 2: rows beyond gmax dropped; bit 4: an empty resize, not applied */
+#define YUNET_MIXUP_EDGE 15            /* T */
+#define YUNET_MIXUP_DRAWS 16           /* draws consumed in all */
+#define YUNET_MIXUP_SR 17              /* sr * jit, the box scale as a double */
+typedef struct YunetMixupCfg {
+    double ratio_lo, ratio_hi;   /* 0 < lo <= hi, finite */
+    double flip_ratio;           /* finite */
+    float pad_val;               /* finite: the D x D canvas outside the resized partner */
+    float min_bbox_size, min_area_ratio, max_aspect_ratio;   /* finite; read with skip_filter == 0 */
+    int32_t img_scale;           /* D, 1..YUNET_AUG_MAX_EDGE / 2 */
+    int32_t max_iters;           /* >= 1 */
+    int32_t bbox_clip_border, skip_filter;
+    int32_t gmax;                /* padded GT rows per image, in and out: 1..4096 */
+    uint32_t seed;
+} YunetMixupCfg;
+/* One 64-lane workgroup per image on the current stream.  store_* : the tables of the M images of the store (hw [M,2],
+ * first GT row / GT count [M], boxes [*,4], kps [*,15]).  in_boxes [N, gmax, 4], in_kps [N, gmax, 15], in_count [N] (a
+ * count outside [0, gmax] is clamped) -> out_* of the same shapes (other buffers than the inputs) and table.  params
+ * NULL: every image's edge is E, else [N,8] of yunet_aug_decide (multiscale != 0).  YUNET_EINVAL, before any launch, for
+ * a null pointer, N < 1, M < 1, E outside [1, YUNET_AUG_MAX_EDGE], an output that is its input, and a configuration
+ * outside the ranges above. */
+int yunet_aug_mixup_decide(const YunetMixupCfg* cfg, uint32_t iteration, int N, int E, const int32_t* params, int M,
+                           const int32_t* store_hw, const int32_t* store_goff, const int32_t* store_gcnt,
+                           const float* store_boxes, const float* store_kps, const float* in_boxes, const float* in_kps,
+                           const int32_t* in_count, float* out_boxes, float* out_kps, int32_t* out_count, double* table,
+                           void* stream);
+/* The blend, in place on img [N, 3, E, E] fp32: one thread per pixel, each reads and writes only its own pixel; an
+ * image that is not applied is left alone.  For (x, y) with x, y < T of an applied image: (X, Y) = (x + x_offset,
+ * y + y_offset); X >= J or Y >= J: b' = 0 (the zero padding of padded_img).  Else Xf = flip ? J - 1 - X : X and b is
+ * the float bilinear value (cv2's float path: f = (float)((d + 0.5) * scale - 0.5), both border rules) of (Xf, Y) in
+ * the D x D canvas at scale 1 / ((double)J / D).  A canvas tap (u, v) with u < rw and v < rh is the float bilinear value
+ * of the raw partner image (uint8, w x h) at scales SX / SY; any other tap is pad_val.
+ * Order of summation, every product and sum rounded to fp32 (no fused multiply-add), per channel:
+ *   raw level     r0 = p[y0][x0] * a0 + p[y0][x1] * a1;   r1 = p[y1][x0] * a0 + p[y1][x1] * a1;   c = r0 * b0 + r1 * b1
+ *   canvas level  t0 = c00 * A0 + c01 * A1;               t1 = c10 * A0 + c11 * A1;               b = t0 * B0 + t1 * B1
+ * (horizontal pass, then vertical pass; weight w0 = 1 - f, w1 = f).  b' = trunc(b) (the reference's uint8 padded_img)
+ * and out = trunc(min(max(0.5f * a + 0.5f * b', 0), 255)) (its mixup_img.astype(np.uint8); the saturation is this
+ * project's: a may lie outside [0, 255] after a POST PhotoMetricDistortion, where numpy's cast is undefined).  Pixels at
+ * or beyond T (the border of a multi-scale canvas) are not touched.  Only table and the store are read besides img.
+ * YUNET_EINVAL, before any launch, for a null pointer, N < 1, M < 1, D outside [1, YUNET_AUG_MAX_EDGE / 2], E outside
+ * [1, YUNET_AUG_MAX_EDGE], a non-finite pad_val or more than 2^31 - 1 workgroups (N * ceil(E * E / 256)).  A table row
+ * that is not the decide's (partner outside [0, M), J, rw, rh below 1) leaves its image alone. */
+int yunet_aug_mixup_pixels(const double* table, int D, float pad_val, int N, int E, const int32_t* params, int M,
+                           const uint8_t* store, const long long* store_off, const int32_t* store_hw, float* img,
+                           void* stream);
+
 /* The TEST pipeline of a batch (test_pipeline.DeviceTestPipeline; csrc/test_pipeline.hip), one launch: decoded uint8
  * HWC sources addressed as for yunet_aug_pixels (src, src_off [N], src_hw [N,2]) -> out_img [N, 3, Hc, Wc] fp32 planar.
  * table [N,4] int32 (device, written by the host) = (nh, nw, flip, 0) per image.  Inside the top-left nh x nw corner:

@@ -155,6 +155,19 @@ class YunetAffineCfg(C.Structure):
                 ('bbox_clip_border', C.c_int32), ('skip_filter', C.c_int32), ('gmax', C.c_int32), ('seed', C.c_uint32)]
 
 
+# MixUp (YUNET_MIXUP_*): sub-stream salt, the doubles of a table row
+MIXUP_SALT, MIXUP_WORDS = 0x4D495855, 18
+(MIXUP_PARTNER, MIXUP_APPLIED, MIXUP_INDEX_DRAWS, MIXUP_JIT, MIXUP_FLIP, MIXUP_J, MIXUP_RW, MIXUP_RH, MIXUP_XOFF, MIXUP_YOFF,
+ MIXUP_SX, MIXUP_SY, MIXUP_ROWS_IN, MIXUP_ROWS_OUT, MIXUP_STATUS, MIXUP_EDGE, MIXUP_DRAWS, MIXUP_SR) = range(18)
+
+
+class YunetMixupCfg(C.Structure):
+    _fields_ = [('ratio_lo', C.c_double), ('ratio_hi', C.c_double), ('flip_ratio', C.c_double), ('pad_val', C.c_float),
+                ('min_bbox_size', C.c_float), ('min_area_ratio', C.c_float), ('max_aspect_ratio', C.c_float),
+                ('img_scale', C.c_int32), ('max_iters', C.c_int32), ('bbox_clip_border', C.c_int32),
+                ('skip_filter', C.c_int32), ('gmax', C.c_int32), ('seed', C.c_uint32)]
+
+
 class YunetAugPixels(C.Structure):
     """The pixel pass of yunet_aug_pixels: rect / position / out_hw / geom select the form (include/yunet_hip.h)."""
     _fields_ = [('src', C.c_void_p), ('src_off', C.c_void_p), ('src_hw', C.c_void_p), ('rect', C.c_void_p),
@@ -232,6 +245,10 @@ _SIGNATURES = {
     'yunet_aug_cutout': (C.c_int, [C.POINTER(YunetCutoutCfg), C.c_uint32, C.c_int, C.c_int] + [C.c_void_p] * 4),
     'yunet_aug_affine_decide': (C.c_int, [C.POINTER(YunetAffineCfg), C.c_uint32, C.c_int, C.c_int] + [C.c_void_p] * 9),
     'yunet_aug_affine_pixels': (C.c_int, [C.c_void_p, C.POINTER(C.c_float * 3), C.c_int, C.c_int] + [C.c_void_p] * 4),
+    'yunet_aug_mixup_decide': (C.c_int, [C.POINTER(YunetMixupCfg), C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_int] +
+                               [C.c_void_p] * 13),
+    'yunet_aug_mixup_pixels': (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_int] +
+                               [C.c_void_p] * 5),
     'yunet_test_pixels': (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p]),
     'yunet_rescale_dets': (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p]),
     'yunet_score_wider': (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_longlong, C.c_longlong, C.c_double, C.c_void_p, C.c_int] +

@@ -851,7 +851,242 @@ __global__ __launch_bounds__(256) void aug_affine_pixels_kernel(
     dst[0] = v0; dst[plane] = v1; dst[2 * plane] = v2;
 }
 
+// ---- MixUp (transforms.py:2523-2783; include/yunet_hip.h YUNET_MIXUP_*) ------------------------------------------------
+__device__ __forceinline__ uint32_t mixup_key(uint32_t seed, uint32_t iteration, uint32_t image) {
+    return mix32(stream_key(seed, iteration, image) ^ YUNET_MIXUP_SALT);
+}
+
+// One 64-lane workgroup per image: the draws and the geometry (wave-uniform integers / doubles, every lane computes
+// them, lane 0 stores the table row), then the image's own rows and the partner's rows in steps of 64 -- a ballot gives
+// the surviving rows their places in order, as in aug_affine_decide_kernel.  in_* and out_* are different buffers.
+// PARAMS as in aug_cutout_kernel.
+template <bool PARAMS>
+__global__ __launch_bounds__(64) void aug_mixup_decide_kernel(
+    const YunetMixupCfg cfg, uint32_t iteration, int E, const int32_t* __restrict__ params, int M,
+    const int32_t* __restrict__ store_hw, const int32_t* __restrict__ store_goff, const int32_t* __restrict__ store_gcnt,
+    const float* __restrict__ store_boxes, const float* __restrict__ store_kps, const float* __restrict__ in_boxes,
+    const float* __restrict__ in_kps, const int32_t* __restrict__ in_count, float* __restrict__ out_boxes,
+    float* __restrict__ out_kps, int32_t* __restrict__ out_count, double* __restrict__ table) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    int T = PARAMS ? params[8 * n + AUG_P_SIZE] : E;
+    T = T > E ? E : T < 0 ? 0 : T;
+    const int gmax = cfg.gmax, D = cfg.img_scale;
+    const int G = in_count[n] < 0 ? 0 : in_count[n] > gmax ? gmax : in_count[n];
+    const uint32_t key = mixup_key(cfg.seed, iteration, (uint32_t)n);
+    uint32_t ctr = 0;
+    int partner = 0, pg = 0;
+    for (int i = 0; i < cfg.max_iters; ++i) {                               // get_indexes
+        partner = bounded(rand_u32(key, ctr++), M);
+        pg = store_gcnt[partner];
+        if (pg != 0) break;
+    }
+    const int index_draws = (int)ctr;
+    bool applied = pg > 0;
+    int status = 0, J = 0, rw = 0, rh = 0, xoff = 0, yoff = 0;
+    double jit = 0.0, sr = 0.0, sx = 0.0, sy = 0.0;
+    bool flip = false;
+    const int h = store_hw[2 * partner], w = store_hw[2 * partner + 1];
+    if (applied) {
+        jit = cfg.ratio_lo + (cfg.ratio_hi - cfg.ratio_lo) * ((double)rand_u32(key, ctr++) * (1.0 / 4294967296.0));
+        flip = (double)rand_u32(key, ctr++) * (1.0 / 4294967296.0) > cfg.flip_ratio;
+        if (h > 0 && w > 0) {
+            const double rh_ = (double)D / (double)h, rw_ = (double)D / (double)w;
+            sr = rh_ < rw_ ? rh_ : rw_;
+            rw = (int)((double)w * sr);
+            rh = (int)((double)h * sr);
+        }
+        const double dj = (double)D * jit;
+        J = dj < 1073741824.0 ? (int)dj : 1073741824;
+        if (rw < 1 || rh < 1 || J < 1) {
+            applied = false; status |= 4;
+        } else {
+            sr *= jit;
+            sx = 1.0 / ((double)rw / (double)w);
+            sy = 1.0 / ((double)rh / (double)h);
+            if (J > T) {
+                yoff = bounded(rand_u32(key, ctr++), J - T);
+                xoff = bounded(rand_u32(key, ctr++), J - T);
+            }
+        }
+    }
+    const float fT = (float)T, fJ = (float)J, fsr = (float)sr, fxo = (float)xoff, fyo = (float)yoff;
+    const bool clip = cfg.bbox_clip_border != 0, filter = cfg.skip_filter == 0;
+    const float* bx = in_boxes + (size_t)n * gmax * 4;
+    const float* kp = in_kps + (size_t)n * gmax * 15;
+    float* ob = out_boxes + (size_t)n * gmax * 4;
+    float* ok = out_kps + (size_t)n * gmax * 15;
+    int kept = 0;
+    for (int base = 0; base < G; base += 64) {          // the image's own rows
+        const int g = base + lane;
+        bool keep = g < G;
+        float b[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (keep) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) b[e] = bx[4 * g + e];
+            if (applied) keep = b[0] < fT && b[2] > 0.0f && b[1] < fT && b[3] > 0.0f;      // find_inside_bboxes
+        }
+        const unsigned long long m = __ballot(keep);
+        const int at = kept + __popcll(m & ((1ull << lane) - 1ull));
+        if (keep && at < gmax) {
+            float* o = ob + 4 * at;
+            o[0] = b[0]; o[1] = b[1]; o[2] = b[2]; o[3] = b[3];
+            const float* k = kp + 15 * g;
+            float* q = ok + 15 * at;
+#pragma unroll
+            for (int j = 0; j < 15; ++j) q[j] = k[j];
+        }
+        kept += __popcll(m);
+    }
+    if (applied) {                                      // the partner's rows
+        const float* pb = store_boxes + (size_t)store_goff[partner] * 4;
+        const float* pk = store_kps + (size_t)store_goff[partner] * 15;
+        for (int base = 0; base < pg; base += 64) {
+            const int g = base + lane;
+            bool keep = g < pg;
+            float c[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (keep) {
+                float b[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) b[e] = affine_clip(pb[4 * g + e] * fsr, fJ, clip);
+                if (flip) { const float t = b[0]; b[0] = fJ - b[2]; b[2] = fJ - t; }
+                c[0] = affine_clip(b[0] - fxo, fT, clip); c[2] = affine_clip(b[2] - fxo, fT, clip);
+                c[1] = affine_clip(b[1] - fyo, fT, clip); c[3] = affine_clip(b[3] - fyo, fT, clip);
+                if (filter) {                                                              // _filter_box_candidates
+                    const float w1 = b[2] - b[0], h1 = b[3] - b[1], w2 = c[2] - c[0], h2 = c[3] - c[1];
+                    const float ar = fmaxf(w2 / (h2 + 1e-16f), h2 / (w2 + 1e-16f));
+                    keep = w2 > cfg.min_bbox_size && h2 > cfg.min_bbox_size &&
+                           w2 * h2 / (w1 * h1 + 1e-16f) > cfg.min_area_ratio && ar < cfg.max_aspect_ratio;
+                }
+                keep = keep && c[0] < fT && c[2] > 0.0f && c[1] < fT && c[3] > 0.0f;       // find_inside_bboxes
+            }
+            const unsigned long long m = __ballot(keep);
+            const int at = kept + __popcll(m & ((1ull << lane) - 1ull));
+            if (keep && at < gmax) {
+                float* o = ob + 4 * at;
+                o[0] = c[0]; o[1] = c[1]; o[2] = c[2]; o[3] = c[3];
+                const float* k = pk + 15 * g;
+                float* q = ok + 15 * at;
+#pragma unroll
+                for (int j = 0; j < 5; ++j) {
+                    const int js = flip ? (j == 0 ? 1 : j == 1 ? 0 : j == 3 ? 4 : j == 4 ? 3 : 2) : j;
+                    float x = affine_clip(k[3 * js] * fsr, fJ, clip), y = affine_clip(k[3 * js + 1] * fsr, fJ, clip);
+                    if (flip) x = fJ - x;
+                    q[3 * j] = affine_clip(x - fxo, fT, clip);
+                    q[3 * j + 1] = affine_clip(y - fyo, fT, clip);
+                    q[3 * j + 2] = k[3 * js + 2];
+                }
+            }
+            kept += __popcll(m);
+        }
+    }
+    const int count = kept < gmax ? kept : gmax;
+    for (int i = count * 4 + lane; i < gmax * 4; i += 64) ob[i] = 0.0f;
+    for (int i = count * 15 + lane; i < gmax * 15; i += 64) ok[i] = 0.0f;
+    if (lane == 0) {
+        double* t = table + (size_t)n * YUNET_MIXUP_WORDS;
+        t[YUNET_MIXUP_PARTNER] = (double)partner; t[YUNET_MIXUP_APPLIED] = applied ? 1.0 : 0.0;
+        t[YUNET_MIXUP_INDEX_DRAWS] = (double)index_draws; t[YUNET_MIXUP_JIT] = jit; t[YUNET_MIXUP_FLIP] = flip ? 1.0 : 0.0;
+        t[YUNET_MIXUP_J] = (double)J; t[YUNET_MIXUP_RW] = (double)rw; t[YUNET_MIXUP_RH] = (double)rh;
+        t[YUNET_MIXUP_XOFF] = (double)xoff; t[YUNET_MIXUP_YOFF] = (double)yoff;
+        t[YUNET_MIXUP_SX] = sx; t[YUNET_MIXUP_SY] = sy;
+        t[YUNET_MIXUP_ROWS_IN] = (double)G; t[YUNET_MIXUP_ROWS_OUT] = (double)kept;
+        t[YUNET_MIXUP_STATUS] = (double)(status | (kept > gmax ? 2 : 0)); t[YUNET_MIXUP_EDGE] = (double)T;
+        t[YUNET_MIXUP_DRAWS] = (double)ctr; t[YUNET_MIXUP_SR] = sr;
+        out_count[n] = count;
+    }
+}
+
+// One canvas tap (u, v) of the D x D pad_val canvas that holds the resized partner in its top-left rw x rh corner: the
+// float bilinear value of the raw image, horizontal pass then vertical pass as mosaic_tap has it.  lin_coef_s clamps
+// both taps to the source, so nothing outside the partner image is read.
+__device__ __forceinline__ void mixup_tap(const uint8_t* __restrict__ im, int w, int h, int rw, int rh, double sx,
+                                          double sy, int u, int v, float pad, float* __restrict__ o) {
+    if (u >= rw || v >= rh) {
+        o[0] = pad; o[1] = pad; o[2] = pad;
+        return;
+    }
+    int x0, x1, y0, y1;
+    float a0, a1, b0, b1;
+    lin_coef_s(u, sx, w, x0, x1, a0, a1);
+    lin_coef_s(v, sy, h, y0, y1, b0, b1);
+    const uint8_t* r0 = im + (size_t)y0 * w * 3;
+    const uint8_t* r1 = im + (size_t)y1 * w * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float t0 = (float)r0[3 * x0 + c] * a0 + (float)r0[3 * x1 + c] * a1;
+        const float t1 = (float)r1[3 * x0 + c] * a0 + (float)r1[3 * x1 + c] * a1;
+        o[c] = t0 * b0 + t1 * b1;
+    }
+}
+
+// One thread per pixel of the E x E plane, the workgroups of an image in a row (blockIdx.x = n * blocks_per_image +
+// block): consecutive lanes take consecutive pixels of each plane; coordinates, taps and weights are worked out once
+// per pixel and shared by the channels.  In place: a thread reads and writes its own pixel only.  PARAMS as in
+// aug_cutout_kernel; pixels at or beyond S_n and images that are not applied are not touched.
+template <bool PARAMS>
+__global__ __launch_bounds__(256) void aug_mixup_pixels_kernel(
+    const double* __restrict__ table, int D, float pad, int E, int blocks_per_image, const int32_t* __restrict__ params,
+    int M, const uint8_t* __restrict__ store, const long long* __restrict__ store_off,
+    const int32_t* __restrict__ store_hw, float* __restrict__ img) {
+    const int n = blockIdx.x / blocks_per_image;
+    const int i = (blockIdx.x - n * blocks_per_image) * 256 + threadIdx.x;
+    const double* t = table + (size_t)n * YUNET_MIXUP_WORDS;
+    if (i >= E * E || t[YUNET_MIXUP_APPLIED] == 0.0) return;
+    int T = PARAMS ? params[8 * n + AUG_P_SIZE] : E;
+    T = T > E ? E : T;
+    const int y = i / E, x = i - y * E;
+    if (x >= T || y >= T) return;
+    const int partner = (int)t[YUNET_MIXUP_PARTNER], J = (int)t[YUNET_MIXUP_J], rw = (int)t[YUNET_MIXUP_RW],
+              rh = (int)t[YUNET_MIXUP_RH], xoff = (int)t[YUNET_MIXUP_XOFF], yoff = (int)t[YUNET_MIXUP_YOFF];
+    if (partner < 0 || partner >= M || J < 1 || rw < 1 || rh < 1 || xoff < 0 || yoff < 0) return;
+    const int h = store_hw[2 * partner], w = store_hw[2 * partner + 1];
+    if (h < 1 || w < 1) return;
+    const size_t plane = (size_t)E * E;
+    float* p = img + (size_t)n * 3 * plane + i;
+    float b[3] = {0.0f, 0.0f, 0.0f};
+    const int X = x + xoff, Y = y + yoff;
+    if (X < J && Y < J) {
+        const int Xf = t[YUNET_MIXUP_FLIP] != 0.0 ? J - 1 - X : X;
+        const double cs = 1.0 / ((double)J / (double)D);
+        const double sx = t[YUNET_MIXUP_SX], sy = t[YUNET_MIXUP_SY];
+        int u0, u1, v0, v1;
+        float A0, A1, B0, B1;
+        lin_coef_s(Xf, cs, D, u0, u1, A0, A1);
+        lin_coef_s(Y, cs, D, v0, v1, B0, B1);
+        const uint8_t* im = store + store_off[partner];
+        float c00[3], c01[3], c10[3], c11[3];
+        mixup_tap(im, w, h, rw, rh, sx, sy, u0, v0, pad, c00);
+        mixup_tap(im, w, h, rw, rh, sx, sy, u1, v0, pad, c01);
+        mixup_tap(im, w, h, rw, rh, sx, sy, u0, v1, pad, c10);
+        mixup_tap(im, w, h, rw, rh, sx, sy, u1, v1, pad, c11);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float t0 = c00[c] * A0 + c01[c] * A1;         // horizontal pass
+            const float t1 = c10[c] * A0 + c11[c] * A1;
+            b[c] = truncf(t0 * B0 + t1 * B1);                   // vertical pass; padded_img is uint8
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float v = 0.5f * p[c * plane] + 0.5f * b[c];
+        p[c * plane] = truncf(fminf(fmaxf(v, 0.0f), 255.0f));
+    }
+}
+
 }  // namespace
+
+static bool mixup_cfg_ok(const YunetMixupCfg* c) {
+    if (!c) return false;
+    const double v[3] = {c->ratio_lo, c->ratio_hi, c->flip_ratio};
+    for (double x : v)
+        if (!std::isfinite(x)) return false;
+    const float f[4] = {c->pad_val, c->min_bbox_size, c->min_area_ratio, c->max_aspect_ratio};
+    for (float x : f)
+        if (!std::isfinite(x)) return false;
+    return c->ratio_lo > 0.0 && c->ratio_lo <= c->ratio_hi && c->img_scale >= 1 &&
+           c->img_scale <= YUNET_AUG_MAX_EDGE / 2 && (double)c->img_scale * c->ratio_hi < 1073741824.0 &&
+           c->max_iters >= 1 && c->gmax >= 1 && c->gmax <= 4096;
+}
 
 static bool affine_cfg_ok(const YunetAffineCfg* c) {
     if (!c) return false;
@@ -1038,6 +1273,40 @@ extern "C" int yunet_aug_affine_pixels(const double* table, const float border_v
         hipLaunchKernelGGL((aug_affine_pixels_kernel<decltype(ms)::value>), dim3((unsigned)(per_image * N)), dim3(256), 0,
                            (hipStream_t)stream, table, border_val[0], border_val[1], border_val[2], E, (int)per_image,
                            params, in, out);
+    });
+    return hip_status();
+}
+
+extern "C" int yunet_aug_mixup_decide(const YunetMixupCfg* cfg, uint32_t iteration, int N, int E, const int32_t* params,
+                                      int M, const int32_t* store_hw, const int32_t* store_goff,
+                                      const int32_t* store_gcnt, const float* store_boxes, const float* store_kps,
+                                      const float* in_boxes, const float* in_kps, const int32_t* in_count,
+                                      float* out_boxes, float* out_kps, int32_t* out_count, double* table,
+                                      void* stream) {
+    if (!mixup_cfg_ok(cfg) || N < 1 || M < 1 || E < 1 || E > YUNET_AUG_MAX_EDGE || !store_hw || !store_goff ||
+        !store_gcnt || !store_boxes || !store_kps || !in_boxes || !in_kps || !in_count || !out_boxes || !out_kps ||
+        !out_count || !table || in_boxes == out_boxes || in_kps == out_kps || in_count == out_count)
+        return YUNET_EINVAL;
+    with_bool(params != nullptr, [&](auto ms) {
+        hipLaunchKernelGGL((aug_mixup_decide_kernel<decltype(ms)::value>), dim3(N), dim3(64), 0, (hipStream_t)stream,
+                           *cfg, iteration, E, params, M, store_hw, store_goff, store_gcnt, store_boxes, store_kps,
+                           in_boxes, in_kps, in_count, out_boxes, out_kps, out_count, table);
+    });
+    return hip_status();
+}
+
+extern "C" int yunet_aug_mixup_pixels(const double* table, int D, float pad_val, int N, int E, const int32_t* params,
+                                      int M, const uint8_t* store, const long long* store_off, const int32_t* store_hw,
+                                      float* img, void* stream) {
+    if (!table || !store || !store_off || !store_hw || !img || N < 1 || M < 1 || D < 1 || D > YUNET_AUG_MAX_EDGE / 2 ||
+        E < 1 || E > YUNET_AUG_MAX_EDGE || !std::isfinite(pad_val))
+        return YUNET_EINVAL;
+    const long long per_image = ((long long)E * E + 255) / 256;
+    if (per_image * N > INT32_MAX) return YUNET_EINVAL;
+    with_bool(params != nullptr, [&](auto ms) {
+        hipLaunchKernelGGL((aug_mixup_pixels_kernel<decltype(ms)::value>), dim3((unsigned)(per_image * N)), dim3(256), 0,
+                           (hipStream_t)stream, table, D, pad_val, E, (int)per_image, params, M, store, store_off,
+                           store_hw, img);
     });
     return hip_status();
 }

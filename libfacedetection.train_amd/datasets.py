@@ -186,7 +186,8 @@ class MultiImageMixDataset:
         if dynamic_scale is not None:
             raise RuntimeError('dynamic_scale is deprecated. Please use Resize pipeline to achieve similar functions')
         if skip_type_keys is not None:
-            raise NotImplementedError('MultiImageMixDataset(skip_type_keys=...) is not implemented')
+            assert all(isinstance(skip_type_key, str) for skip_type_key in skip_type_keys)
+        self._skip_type_keys = skip_type_keys
         self.dataset = DATASETS.build(dataset) if isinstance(dataset, dict) else dataset
         self.pipeline_cfg, self.max_refetch = list(pipeline), max_refetch
         self.CLASSES = getattr(self.dataset, 'CLASSES', None)
@@ -196,15 +197,23 @@ class MultiImageMixDataset:
     def __len__(self):
         return len(self.dataset)
 
+    def update_skip_type_keys(self, skip_type_keys):
+        """dataset_wrappers.py:446-456: a sequence of type strings; those steps are skipped from then on."""
+        assert all(isinstance(skip_type_key, str) for skip_type_key in skip_type_keys)
+        self._skip_type_keys = skip_type_keys
+
 
 def flatten_multi_image_mix(dcfg):
     """data.train = dict(type='MultiImageMixDataset', dataset=dict(...), pipeline=[...]) -> the inner dataset's
     configuration with pipeline = its own loading steps + the wrapper's list (the flat list DevicePipeline takes); the
-    wrapper's other keys (cache, host_fed, ... given with --cfg-options) travel to the inner configuration."""
+    wrapper's other keys (cache, host_fed, ... given with --cfg-options) travel to the inner configuration.  The flat
+    configuration has no place for skip_type_keys: take them off first with split_skip_type_keys, which hands them to
+    the source."""
     if dcfg.get('dynamic_scale') is not None:
         raise RuntimeError('dynamic_scale is deprecated. Please use Resize pipeline to achieve similar functions')
     if dcfg.get('skip_type_keys') is not None:
-        raise NotImplementedError('MultiImageMixDataset(skip_type_keys=...) is not implemented')
+        raise NotImplementedError('MultiImageMixDataset(skip_type_keys=...) is not carried by the flat configuration: '
+                                  'split_skip_type_keys(cfg) takes the keys off for the source (skip_type_keys=)')
     inner = dict(dcfg['dataset'])
     if inner.get('type') == 'MultiImageMixDataset':
         raise NotImplementedError('nested MultiImageMixDataset')
@@ -213,6 +222,18 @@ def flatten_multi_image_mix(dcfg):
         if k not in ('type', 'dataset', 'pipeline', 'dynamic_scale', 'skip_type_keys', 'max_refetch'):
             inner[k] = v
     return inner
+
+
+def split_skip_type_keys(dcfg):
+    """A MultiImageMixDataset configuration -> (the configuration without skip_type_keys, the keys as a list or None).
+    The keys keep the reference's assertion, a sequence of str (dataset_wrappers.py:354-366); the caller hands them to
+    the source it builds from the flattened rest (RetinaFaceSource / SyntheticSourceImages skip_type_keys=), which
+    switches those steps off from the first batch on."""
+    keys = dcfg.get('skip_type_keys')
+    if keys is None:
+        return dcfg, None
+    assert all(isinstance(skip_type_key, str) for skip_type_key in keys)
+    return type(dcfg)({k: v for k, v in dcfg.items() if k != 'skip_type_keys'}), list(keys)
 
 
 def gt_counts(dataset):
@@ -246,10 +267,12 @@ class RetinaFaceSource:
     most 256 per image: its merged GT stays within 1024 rows, and a larger image can still truncate a merged canvas)."""
 
     def __init__(self, dataset, pipeline, samples_per_gpu=16, rank=0, world=1, seed=0, max_gt=64, workers=4,
-                 cache=None, host_fetch=None, gt_capacity=None):
+                 cache=None, host_fetch=None, gt_capacity=None, skip_type_keys=None):
         from .pipelines import DevicePipeline, gt_capacity_rows
         counts = gt_counts(dataset)
-        mosaic = any((p.get('type') if isinstance(p, dict) else type(p).__name__) == 'Mosaic' for p in pipeline)
+        self._gt_counts = counts
+        types = [(p.get('type') if isinstance(p, dict) else type(p).__name__) for p in pipeline]
+        mosaic, mixup = 'Mosaic' in types, 'MixUp' in types
         if gt_capacity is None:
             rows = 64 if max_gt <= 64 else 128
         else:
@@ -260,7 +283,7 @@ class RetinaFaceSource:
                 raise ValueError(f"RetinaFaceSource gt_capacity must be 'dataset' or an integer >= 1 (or unset), "
                                  f'got {gt_capacity!r}')
             want = max([1] + counts) if gt_capacity == 'dataset' else gt_capacity
-            rows = gt_capacity_rows(want, mosaic=mosaic)
+            rows = gt_capacity_rows(want, mosaic=mosaic, mixup=mixup)
         self.gt_rows = rows                     # padded GT rows per source image (a Mosaic merges four: pipe.gmax = 4 rows)
         over = [c for c in counts if c > rows]
         if over:
@@ -285,6 +308,8 @@ class RetinaFaceSource:
         self.ds, self.bs, self.rank, self.world, self.seed = dataset, samples_per_gpu, rank, world, seed
         self.pipe = DevicePipeline(pipeline, seed=seed + 7919 * rank, gmax=rows)
         self.pipe.check_plan_cache()
+        if skip_type_keys is not None:
+            self.pipe.update_skip_type_keys(skip_type_keys)
         if cache != 'device':
             self.pipe.require_resident(f'RetinaFaceSource(cache={cache!r})')
         from .samplers import DistributedGroupSampler
@@ -297,6 +322,15 @@ class RetinaFaceSource:
         self.workers = max(0, int(workers))
         self._pool = None
         self._ahead = {}
+
+    @property
+    def dataset(self):
+        """What a hook reaches as runner.data_loader.dataset: the object that takes update_skip_type_keys."""
+        return self
+
+    def update_skip_type_keys(self, skip_type_keys):
+        """MultiImageMixDataset.update_skip_type_keys: forwarded to the device pipeline."""
+        self.pipe.update_skip_type_keys(skip_type_keys)
 
     def _indices(self, it):
         epoch, k = divmod(it, self.iters_per_epoch)
@@ -321,13 +355,16 @@ class RetinaFaceSource:
         return [f.result() for f in futs]
 
     def _partners(self, it, n):
-        """Mosaic: the store indices iteration it's kernel will draw as partners of its n images -- a pure function of
-        (seed, it, image), computed here so that they are decoded before the batch that reads them."""
-        if self.pipe.mosaic is None:
-            return []
-        from .pipelines import mosaic_partners
-        m = len(self.ds.data_infos)
-        return [j for k in range(n) for j in mosaic_partners(self.pipe.cfg.seed, it, k, m)]
+        """Mosaic / MixUp: the store indices iteration it's kernels will draw as partners of its n images -- a pure
+        function of (seed, it, image) and the dataset's GT counts, computed here so that they are decoded before the
+        batch that reads them."""
+        from .pipelines import mixup_partner, mosaic_partners
+        m, out = len(self.ds.data_infos), []
+        if self.pipe.mosaic is not None:
+            out += [j for k in range(n) for j in mosaic_partners(self.pipe.cfg.seed, it, k, m)]
+        if self.pipe.mixup is not None:     # the one MixUp partner per image: the first drawn image that has boxes
+            out += [mixup_partner(self.pipe.cfg.seed, it, k, self._gt_counts, self.pipe.mixup.max_iters) for k in range(n)]
+        return out
 
     def _fill(self, it):
         """Decode the images of iteration it that the store lacks (and queue those of it + 1), store them; -> indices."""
@@ -396,8 +433,10 @@ class RetinaFaceSource:
         from . import _lib as L
         p = self.pipe.params
         cut = p[:, 6] == 2
-        if self.pipe.mosaic is not None:        # a merged GT beyond gmax: status bit 2 of the geometry table
+        if self.pipe.geom is not None:          # a merged GT beyond gmax: status bit 2 of the geometry table
             cut = cut | ((self.pipe.geom[:, L.MOSAIC_STATUS] & 2) != 0)
+        if self.pipe.mixup_table is not None:   # and the same bit of MixUp's table
+            cut = cut | ((self.pipe.mixup_table[:, L.MIXUP_STATUS].to(torch.int64) & 2) != 0)
         rows = (p[:, 4] - self.pipe.gmax).clamp_min(0)
         add = torch.stack([cut.sum(), rows.sum()])
         self._trunc = add if self._trunc is None else self._trunc + add

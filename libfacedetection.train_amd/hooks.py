@@ -3,6 +3,7 @@
     ExpMomentumEMAHook, LinearMomentumEMAHook   (ema.py)       exponential moving average of the model
     YuNetSampleSizeStatisticsHook               (yunet_sample_size_statistics_hook.py)  GT box-size histogram
     CheckInvalidLossHook                        (checkloss_hook.py)  the loss must stay finite
+    YOLOXModeSwitchHook                         (yolox_mode_switch_hook.py)  Mosaic / RandomAffine / MixUp off for the last epochs
 
 Semantics are the reference's; what differs is where the per-iteration work runs.  On a model bound to the fused
 engine the EMA update is ONE launch over the flat parameter / BN buffers and their flat EMA mirror
@@ -264,7 +265,26 @@ class CheckInvalidLossHook(Hook):
             raise AssertionError('loss become infinite or NaN!')
 
 
+class YOLOXModeSwitchHook(Hook):
+    """mmdet/core/hook/yolox_mode_switch_hook.py: at the start of epoch max_epochs - num_last_epochs (counted from 1) the
+    steps named by skip_type_keys are switched off in the data source (DevicePipeline.update_skip_type_keys: they launch
+    nothing from then on) and bbox_head.use_l1 is set, as the reference sets it -- YuNet_Head never reads that attribute,
+    in the reference or here.  The reference's lines that restart a DataLoader with persistent workers have nothing to
+    act on: the pipeline runs in this process, so the switch holds from the next batch."""
+
+    def __init__(self, num_last_epochs=15, skip_type_keys=('Mosaic', 'RandomAffine', 'MixUp')):
+        self.num_last_epochs = num_last_epochs
+        self.skip_type_keys = skip_type_keys
+
+    def before_train_epoch(self, runner):
+        if (runner.epoch + 1) == runner.max_epochs - self.num_last_epochs:
+            runner.logger('No mosaic and mixup aug now!')
+            runner.data_loader.dataset.update_skip_type_keys(self.skip_type_keys)
+            runner.logger('Add additional L1 loss now!')
+            _unwrap(runner.model).bbox_head.use_l1 = True
+
+
 CUSTOM_HOOKS = dict(ExpMomentumEMAHook=ExpMomentumEMAHook, LinearMomentumEMAHook=LinearMomentumEMAHook,
                     YuNetSampleSizeStatisticsHook=YuNetSampleSizeStatisticsHook,
-                    CheckInvalidLossHook=CheckInvalidLossHook)
+                    CheckInvalidLossHook=CheckInvalidLossHook, YOLOXModeSwitchHook=YOLOXModeSwitchHook)
 HOOKS.update(CUSTOM_HOOKS)            # custom_hooks=[dict(type=...)] of a config (runner.register_training_hooks)

@@ -318,6 +318,59 @@ class RandomAffine(_Carrier):
         return c
 
 
+@PIPELINES.register_module()
+class MixUp(_Carrier):
+    """transforms.py:2523-2783 with the reference's constructor and one keyword more, `use_kps`, as the reference added
+    it to Mosaic: the partner's five landmarks are scaled, flipped (left / right swapped) and shifted with its boxes.
+    Runs as yunet_aug_mixup_decide + yunet_aug_mixup_pixels on the finished batch tensor and GT, after RandomFlip (a POST
+    PhotoMetricDistortion, RandomAffine) and in front of CutOut / Normalize; the partner is a raw image of the device
+    store with its raw GT (MultiImageMixDataset's mix_results); its draws come from a sub-stream of the pipeline's
+    generator (include/yunet_hip.h YUNET_MIXUP_SALT).  Its assertions are ValueErrors here."""
+
+    def __init__(self, img_scale=(640, 640), ratio_range=(0.5, 1.5), flip_ratio=0.5, pad_val=114, max_iters=15,
+                 min_bbox_size=5, min_area_ratio=0.2, max_aspect_ratio=20, bbox_clip_border=True, skip_filter=True,
+                 use_kps=False):
+        if not use_kps:
+            raise NotImplementedError('MixUp(use_kps=False): the device pipeline always carries the five landmarks '
+                                      '(LoadAnnotations(with_keypoints=True)); write use_kps=True')
+        if not isinstance(img_scale, (list, tuple)) or len(img_scale) != 2 or not all(_is_number(v) for v in img_scale):
+            raise ValueError(f'MixUp: img_scale={img_scale!r} must be (height, width)')
+        if int(img_scale[0]) != int(img_scale[1]):
+            raise NotImplementedError(f'MixUp(img_scale={tuple(img_scale)}): only the square canvas '
+                                      '(img_scale=(D, D)) is built; the rectangular one is not')
+        D = int(img_scale[0])
+        if not 1 <= D <= L.AUG_MAX_EDGE // 2:
+            raise ValueError(f'MixUp(img_scale=({D}, {D})): D must lie in [1, {L.AUG_MAX_EDGE // 2}]')
+        if isinstance(pad_val, (list, tuple)):
+            raise ValueError(f'MixUp: pad_val={pad_val!r} must be one value (a per-channel pad is not built)')
+        if not isinstance(ratio_range, (list, tuple)) or len(ratio_range) != 2:
+            raise ValueError(f'MixUp: ratio_range={ratio_range!r} must be (min, max)')
+        for name, v in (('ratio_range', ratio_range[0]), ('ratio_range', ratio_range[1]), ('flip_ratio', flip_ratio),
+                        ('pad_val', pad_val), ('min_bbox_size', min_bbox_size), ('min_area_ratio', min_area_ratio),
+                        ('max_aspect_ratio', max_aspect_ratio)):
+            if not _is_number(v) or not math.isfinite(float(v)):
+                raise ValueError(f'MixUp: {name}={v!r} must be a finite number')
+        if not 0 < ratio_range[0] <= ratio_range[1]:
+            raise ValueError(f'MixUp: ratio_range={tuple(ratio_range)} must have 0 < min <= max')
+        if D * float(ratio_range[1]) >= 2 ** 30:
+            raise ValueError(f'MixUp: ratio_range={tuple(ratio_range)} scales the {D} canvas beyond 2^30 pixels')
+        if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)) or max_iters < 1:
+            raise ValueError(f'MixUp: max_iters={max_iters!r} must be an integer >= 1')
+        super().__init__(img_scale=(D, D), ratio_range=tuple(float(v) for v in ratio_range), flip_ratio=flip_ratio,
+                         pad_val=pad_val, max_iters=int(max_iters), min_bbox_size=min_bbox_size,
+                         min_area_ratio=min_area_ratio, max_aspect_ratio=max_aspect_ratio,
+                         bbox_clip_border=bool(bbox_clip_border), skip_filter=bool(skip_filter), use_kps=True)
+
+    def c_cfg(self, seed, gmax):
+        c = L.YunetMixupCfg()
+        (c.ratio_lo, c.ratio_hi), c.flip_ratio, c.pad_val = self.ratio_range, float(self.flip_ratio), float(self.pad_val)
+        c.min_bbox_size, c.min_area_ratio = float(self.min_bbox_size), float(self.min_area_ratio)
+        c.max_aspect_ratio, c.img_scale, c.max_iters = float(self.max_aspect_ratio), self.img_scale[0], self.max_iters
+        c.bbox_clip_border, c.skip_filter, c.gmax, c.seed = int(self.bbox_clip_border), int(self.skip_filter), gmax, \
+            seed & 0xFFFFFFFF
+        return c
+
+
 def _mix32(x):
     x &= 0xFFFFFFFF
     x ^= x >> 16
@@ -334,6 +387,20 @@ def mosaic_partners(seed, iteration, n, m):
     k = _mix32((seed & 0xFFFFFFFF) ^ ((iteration * 0x27D4EB2F) & 0xFFFFFFFF))
     k = _mix32(_mix32(k ^ ((n * 0x9E3779B9) & 0xFFFFFFFF)) ^ L.MOSAIC_SALT)
     return [(_mix32(k ^ ((c * 0x85EBCA6B + 0xC2B2AE35) & 0xFFFFFFFF)) * m) >> 32 for c in range(3)]
+
+
+def mixup_partner(seed, iteration, n, counts, max_iters):
+    """The store index yunet_aug_mixup_decide settles on as the partner of image n of `iteration`, over a store whose
+    image i has counts[i] GT rows: up to max_iters draws, stopping at the first image with boxes.  A pure function of
+    (seed, iteration, n) and the counts, so the host computes it ahead, as it does Mosaic's partners."""
+    k = _mix32((seed & 0xFFFFFFFF) ^ ((iteration * 0x27D4EB2F) & 0xFFFFFFFF))
+    k = _mix32(_mix32(k ^ ((n * 0x9E3779B9) & 0xFFFFFFFF)) ^ L.MIXUP_SALT)
+    i = 0
+    for c in range(max_iters):
+        i = (_mix32(k ^ ((c * 0x85EBCA6B + 0xC2B2AE35) & 0xFFFFFFFF)) * len(counts)) >> 32
+        if counts[i] != 0:
+            break
+    return i
 
 
 @PIPELINES.register_module()
@@ -425,17 +492,18 @@ GT_ROWS_MIN = 64            # the default padded width; a capacity never goes be
 GT_ROWS_MAX = 4096          # yunet_assign_cfg stages Gmax 16-byte GT records in at most 64 KB of LDS
 
 
-def gt_capacity_rows(max_count, mosaic=False):
+def gt_capacity_rows(max_count, mosaic=False, mixup=False):
     """Padded GT rows per source image for a capacity of `max_count` faces: the smallest power of two that is
     >= max(max_count, 64).  mosaic=True: at most MOSAIC_MAX_GT // 4, since the merged GT of four images has to stay
-    within MOSAIC_MAX_GT rows (a larger image can then truncate a merged canvas, status 2)."""
+    within MOSAIC_MAX_GT rows (a larger image can then truncate a merged canvas, status 2).  mixup=True: MixUp appends
+    one more image's rows, so the divisor is 5 with Mosaic and 2 without."""
     if isinstance(max_count, bool) or int(max_count) != max_count or int(max_count) < 1:
         raise ValueError(f'a GT capacity is an integer >= 1, got {max_count!r}')
     rows = GT_ROWS_MIN
     while rows < int(max_count):
         rows *= 2
-    if mosaic:
-        return min(rows, MOSAIC_MAX_GT // 4)
+    if mosaic or mixup:
+        return min(rows, MOSAIC_MAX_GT // ((4 if mosaic else 1) + (1 if mixup else 0)))
     if rows > GT_ROWS_MAX:
         raise ValueError(f'a GT capacity of {int(max_count)} faces needs {rows} padded rows: the assign launch stages its '
                          f'GT rows in LDS and takes at most {GT_ROWS_MAX} (64 KB at 16 bytes a row)')
@@ -463,6 +531,20 @@ class DevicePipeline:
     def __init__(self, pipeline, seed=0, gmax=64, pad_value=128.0, max_attempts=250, max_retries=64):
         steps = [build_from_cfg(p, PIPELINES) if isinstance(p, dict) else p for p in pipeline]
         names = [type(s).__name__ for s in steps]
+        self.mixup, self.mixup_cfg, self.mixup_table, self._skip = None, None, None, frozenset()
+        if 'MixUp' in names:
+            at = names.index('MixUp')
+            before = names[at - 1] if at else None
+            if before == 'PhotoMetricDistortion' and names[max(at - 2, 0)] != 'RandomFlip':
+                before = None
+            if names.count('MixUp') > 1 or before not in ('RandomFlip', 'PhotoMetricDistortion', 'RandomAffine') \
+                    or names[at + 1:at + 2] not in (['CutOut'], ['Normalize']):
+                raise NotImplementedError(
+                    'DevicePipeline runs MixUp once, after RandomFlip (after a PhotoMetricDistortion that follows '
+                    'RandomFlip, and after RandomAffine if there is one) and immediately in front of CutOut or Normalize; '
+                    f'got {names}')
+            self.mixup = steps[at]          # its configuration is made below, once the GT rows per image are known
+            steps, names = steps[:at] + steps[at + 1:], names[:at] + names[at + 1:]
         self.affine, self.affine_cfg, self.affine_table = None, None, None
         if 'RandomAffine' in names:
             at = names.index('RandomAffine')
@@ -505,7 +587,14 @@ class DevicePipeline:
                                  f'the {MOSAIC_MAX_GT} the assignment kernels are tested to')
             self.mosaic = steps[at]
             steps, names = steps[:at] + steps[at + 1:], names[:at] + names[at + 1:]
-            gmax = 4 * gmax                     # rows of the merged GT and of the batch's padded GT
+        # one capacity for the whole pipeline: the rows of the merged GT and of the batch's padded GT
+        rows = (4 if self.mosaic is not None else 1) * gmax + (gmax if self.mixup is not None else 0)
+        if self.mixup is not None and rows > MOSAIC_MAX_GT:
+            raise ValueError(f'MixUp appends one more image\'s rows{" to the four Mosaic merges" if self.mosaic else ""}: '
+                             f'gmax={gmax} gives {rows} GT rows per image, more than the {MOSAIC_MAX_GT} the '
+                             'assignment kernels are tested to')
+        gmax = rows
+        if self.mosaic is not None:
             self.mosaic_cfg = self.mosaic.c_cfg(seed, gmax)
         self.photo, self.photo_position, self.pparams = None, L.PHOTO_NONE, None
         if 'PhotoMetricDistortion' in names:
@@ -554,22 +643,42 @@ class DevicePipeline:
         self.gmax = gmax
         if self.affine is not None:
             self.affine_cfg = self.affine.c_cfg(seed, gmax)
+        if self.mixup is not None:
+            self.mixup_cfg = self.mixup.c_cfg(seed, gmax)
         self.params = None
         self._pixels = L.YunetAugPixels()       # the pixel pass's descriptor: the per-batch fields are filled in place
         self._pixels.position = self.photo_position
-        if self.mosaic is not None:
-            self._pixels.mosaic = C.pointer(self.mosaic_cfg)
+        self._mosaic_ptr = C.pointer(self.mosaic_cfg) if self.mosaic is not None else None
+
+    SKIP_TYPE_KEYS = ('Mosaic', 'RandomAffine', 'MixUp')
+
+    def update_skip_type_keys(self, skip_type_keys):
+        """MultiImageMixDataset.update_skip_type_keys (dataset_wrappers.py:446-456): the named steps launch nothing from
+        the next batch on.  Every step draws from a sub-stream of its own, so the batch is then, byte for byte, that of
+        a pipeline built without them at the same seed and iteration; the padded GT keeps the capacity this pipeline
+        was built with (the engine keeps its plan).  A name this pipeline does not hold is accepted, as by the
+        reference; a name outside SKIP_TYPE_KEYS is not a step that can be switched off here."""
+        assert all(isinstance(k, str) for k in skip_type_keys)
+        bad = [k for k in skip_type_keys if k not in self.SKIP_TYPE_KEYS]
+        if bad:
+            raise NotImplementedError(f'skip_type_keys {bad}: the steps that can be switched off are {self.SKIP_TYPE_KEYS}')
+        self._skip = frozenset(skip_type_keys)
+
+    def _on(self, name):
+        return getattr(self, name.lower() if name != 'RandomAffine' else 'affine') is not None and name not in self._skip
 
     def __call__(self, src, iteration, sizes=None):
         dev = src.src.device
         if dev.type != 'cuda':
             raise RuntimeError('DevicePipeline needs device-resident sources: HIP kernels only, no CPU fallback')
-        if self.mosaic is None:
+        mosaic, mixup = self._on('Mosaic'), self._on('MixUp')
+        if not mosaic and not mixup:
             return self._run(src, iteration, dev, (src.src, src.src_off, None), sizes)
         view, idx = src.store_view()
         if view is None or idx is None:
-            raise NotImplementedError('Mosaic needs sources that are resident on the device')
-        return self._run(src, iteration, dev, (src.src, view.off, None), sizes, store=(view, idx))
+            raise NotImplementedError(f'{"Mosaic" if mosaic else "MixUp"} needs sources that are resident on the device')
+        pix = (src.src, view.off, None) if mosaic else (src.src, src.src_off, None)
+        return self._run(src, iteration, dev, pix, sizes, store=(view, idx))
 
     def _run(self, src, iteration, dev, pix, sizes, store=None):
         """One batch on the current stream: decide -> sizes -> allocate -> photometric table -> pixel pass -> collate.
@@ -582,7 +691,9 @@ class DevicePipeline:
         mmcv's collate pads a group's images at the bottom and right up to the largest.  The value and the stacking are
         the reference's; the bottom / right placement is mmcv's rule, restated here without mmcv at hand."""
         n = src.n
-        merged = self._mosaic_decide(store, n, iteration, dev) if store is not None else None
+        merged = self._mosaic_decide(store, n, iteration, dev) if self._on('Mosaic') else None
+        if merged is None:
+            self.geom = None
         gb, gk, cnt, params = self._decide(src, iteration, dev, merged)
         out_hw = 0
         if self.scale_range is not None:
@@ -599,9 +710,13 @@ class DevicePipeline:
         a.src, a.src_off, a.rect = (_ptr(t) for t in pix)
         a.src_hw, a.params, a.pparams = _ptr(src.src_hw if merged is None else merged[3]), _ptr(params), _ptr(pp)
         a.geom, a.out_hw = _ptr(self.geom if merged is not None else None), out_hw
+        a.mosaic = self._mosaic_ptr if merged is not None else None
         L.check(L.load().yunet_aug_pixels(C.byref(a), C.byref(self.cfg), n, _ptr(img), _stream()), 'yunet_aug_pixels')
-        if self.affine is not None:
+        self.affine_table, self.mixup_table = None, None        # a step that is skipped writes no table
+        if self._on('RandomAffine'):
             img, gb, gk, cnt = self._affine(img, gb, gk, cnt, params if out_hw else None, iteration, dev)
+        if self._on('MixUp'):
+            gb, gk, cnt = self._mixup(store, src, img, gb, gk, cnt, params if out_hw else None, iteration, dev)
         if self.cutout is not None:
             self._cutout(img, params if out_hw else None, iteration, dev)
         return self._collate(img, gb, gk, cnt, params, dev)
@@ -621,6 +736,26 @@ class DevicePipeline:
                                             _ptr(out), _stream()), 'yunet_aug_affine_pixels')
         self.affine_table = table
         return out, ob, ok, oc
+
+    def _mixup(self, store, src, img, gb, gk, cnt, params, iteration, dev):
+        """yunet_aug_mixup_decide + yunet_aug_mixup_pixels on the current stream -> (boxes, keypoints, counts): the blend
+        runs in place on the batch tensor, the GT goes into new tensors.  `store` = (StoreView, batch indices): the
+        partner is any image of the store; `src.src` holds the store's pixels.  `params` as for _cutout.  The table
+        [N, MIXUP_WORDS] float64 stays in `mixup_table`."""
+        view, _ = store
+        n, edge = int(img.shape[0]), int(img.shape[-1])
+        table = torch.empty(n, L.MIXUP_WORDS, device=dev, dtype=torch.float64)
+        ob, ok, oc = torch.empty_like(gb), torch.empty_like(gk), torch.empty_like(cnt)
+        lib, c = L.load(), self.mixup_cfg
+        L.check(lib.yunet_aug_mixup_decide(C.byref(c), int(iteration) & 0xFFFFFFFF, n, edge, _ptr(params), view.m,
+                                           _ptr(view.hw), _ptr(view.goff), _ptr(view.gcnt), _ptr(view.boxes),
+                                           _ptr(view.kps), _ptr(gb), _ptr(gk), _ptr(cnt), _ptr(ob), _ptr(ok), _ptr(oc),
+                                           _ptr(table), _stream()), 'yunet_aug_mixup_decide')
+        L.check(lib.yunet_aug_mixup_pixels(_ptr(table), c.img_scale, c.pad_val, n, edge, _ptr(params), view.m,
+                                           _ptr(src.src), _ptr(view.off), _ptr(view.hw), _ptr(img), _stream()),
+                'yunet_aug_mixup_pixels')
+        self.mixup_table = table
+        return ob, ok, oc
 
     def _cutout(self, img, params, iteration, dev):
         """yunet_aug_cutout on the current stream, in place on the batch tensor; `params`: the decide's table on a
@@ -723,9 +858,10 @@ class DevicePipeline:
     def require_resident(self, what):
         """Mosaic reads four images of the store per output image; a feed that brings only the batch's own pixels (or
         windows of them) to the device cannot serve it."""
-        if self.mosaic is not None:
-            raise NotImplementedError(f'Mosaic over {what}: the partner images\' pixels are not on the device; use '
-                                      "resident sources (SourceStore(placement='device'), cache='device')")
+        for step, name in ((self.mosaic, 'Mosaic'), (self.mixup, 'MixUp')):
+            if step is not None:
+                raise NotImplementedError(f'{name} over {what}: the partner images\' pixels are not on the device; use '
+                                          "resident sources (SourceStore(placement='device'), cache='device')")
 
     def check_plan_cache(self, max_plans=None):
         """square_range walks len(out_sizes) batch geometries, one engine plan each; beyond engine.MAX_PLANS every
@@ -743,13 +879,20 @@ class DevicePipeline:
         """Synchronising status check of the last batch: raises like the reference would misbehave
         (it loops forever on an image whose boxes no crop window can contain)."""
         st = self.params[:, 6].cpu()
-        if self.mosaic is not None:         # merged GT beyond gmax is truncated like the crop's: the same status
+        if self.geom is not None:           # merged GT beyond gmax is truncated like the crop's: the same status
             ms = self.geom[:, L.MOSAIC_STATUS].cpu()
             empty = ((ms & 4) != 0).nonzero().flatten().tolist()
             if empty:
                 raise ValueError(f'Mosaic: a sub-image of images {empty} resizes to an empty size (img_scale too small '
                                  'for its aspect ratio)')
             st = torch.where((st == 0) & ((ms & 2) != 0), torch.full_like(st, 2), st)
+        if self.mixup_table is not None:    # and so are rows beyond it after MixUp appended the partner's
+            xs = self.mixup_table[:, L.MIXUP_STATUS].cpu().to(torch.int64)
+            empty = ((xs & 4) != 0).nonzero().flatten().tolist()
+            if empty:
+                raise ValueError(f'MixUp: the partner of images {empty} resizes to an empty size (img_scale or '
+                                 'ratio_range too small for its aspect ratio)')
+            st = torch.where((st == 0) & ((xs & 2) != 0).to(st.device), torch.full_like(st, 2), st)
         bad = (st == 1).nonzero().flatten().tolist()
         if bad:
             raise ValueError(f'RandomSquareCrop found no window containing a box centre for images {bad} '

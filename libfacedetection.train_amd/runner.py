@@ -142,10 +142,12 @@ class SyntheticSourceImages:
 
     def __init__(self, pipeline, samples_per_gpu=16, iters_per_epoch=403, rank=0, pool=64,
                  src_hw=((768, 1024), (1024, 683), (500, 375), (683, 1024)), max_gt=synthetic.MAX_GT,
-                 seed=0, host_fed=False, timing=False, host_fetch=None, **_):
+                 seed=0, host_fed=False, timing=False, host_fetch=None, skip_type_keys=None, **_):
         from .pipelines import DevicePipeline
         self.pipe = DevicePipeline(pipeline, seed=seed + 7919 * rank, gmax=64 if max_gt <= 64 else 128)
         self.pipe.check_plan_cache()
+        if skip_type_keys is not None:
+            self.pipe.update_skip_type_keys(skip_type_keys)
         self.bs, self.iters_per_epoch, self.rank = samples_per_gpu, iters_per_epoch, rank
         self.pool, self.src_hw, self.max_gt, self.seed = pool, src_hw, max_gt, seed
         if host_fed not in (False, True, 'window'):
@@ -160,6 +162,15 @@ class SyntheticSourceImages:
             self.pipe.require_resident(f'host-fed sources (host_fed={host_fed!r})')
         self._src = None
         self._ev = []
+
+    @property
+    def dataset(self):
+        """What a hook reaches as runner.data_loader.dataset: the object that takes update_skip_type_keys."""
+        return self
+
+    def update_skip_type_keys(self, skip_type_keys):
+        """MultiImageMixDataset.update_skip_type_keys: forwarded to the device pipeline."""
+        self.pipe.update_skip_type_keys(skip_type_keys)
 
     def _pool_sources(self):
         import numpy as np
@@ -177,7 +188,7 @@ class SyntheticSourceImages:
     def _build(self, device):
         from .pipelines import SourceBatch
         imgs, boxes, kps, idx = self._pool_sources()
-        if self.pipe.mosaic is not None:        # the dataset Mosaic draws its partners from is the pool, not the batch
+        if self.pipe.mosaic is not None or self.pipe.mixup is not None:     # partners come from the pool, not the batch
             from .source_store import SourceStore
             store = SourceStore([im.shape[:2] for im in imgs], placement='device', device=device)
             for i, im in enumerate(imgs):
@@ -946,6 +957,7 @@ class EpochBasedRunner:
 
     def train(self, data_source):
         self.model.train()
+        self.data_loader = data_source          # mmcv's EpochBasedRunner.train: what the hooks reach as runner.data_loader
         self.call_hook('before_train_epoch')
         for i in range(data_source.iters_per_epoch):
             self.inner_iter = i

@@ -113,8 +113,11 @@ def build_source(cfg, rank, world, seed, dcfg=None):
     build, cfg.data.train by default."""
     dcfg = cfg.data.train if dcfg is None else dcfg
     if dcfg.get('type') == 'MultiImageMixDataset':      # Mosaic: the wrapped dataset with the two pipeline lists as one
-        from yunet_amd.datasets import flatten_multi_image_mix
+        from yunet_amd.datasets import flatten_multi_image_mix, split_skip_type_keys
+        dcfg, keys = split_skip_type_keys(dcfg)         # skip_type_keys go to the source, which switches those steps off
         dcfg = type(dcfg)(flatten_multi_image_mix(dcfg))
+        if keys is not None:
+            dcfg['skip_type_keys'] = keys
     kw = {k: v for k, v in dcfg.items() if k != 'type'}
     if dcfg.get('type') == 'SyntheticWiderFace':
         return R.SyntheticWiderFace(samples_per_gpu=cfg.data.samples_per_gpu, rank=rank, **kw)
@@ -131,7 +134,8 @@ def build_source(cfg, rank, world, seed, dcfg=None):
             gt_capacity = int(gt_capacity)
         dataset = yunet_amd.build_dataset(dcfg)
         return RetinaFaceSource(dataset, dcfg['pipeline'], samples_per_gpu=cfg.data.samples_per_gpu, rank=rank,
-                                world=world, seed=seed, cache=cache, host_fetch=host_fetch, gt_capacity=gt_capacity)
+                                world=world, seed=seed, cache=cache, host_fetch=host_fetch, gt_capacity=gt_capacity,
+                                skip_type_keys=dcfg.get('skip_type_keys'))
     raise SystemExit('data sources: RetinaFaceDataset (labelv2 + image files, augmented on the GPU; also wrapped in '
                      'MultiImageMixDataset for Mosaic), '
                      'SyntheticWiderFace (ready batches) or SyntheticSourceImages (decoded synthetic '
@@ -147,8 +151,8 @@ def val_source_config(cfg):
                          f"data.train's pipeline: the config has no data.val")
     train = cfg.data.train
     if train.get('type') == 'MultiImageMixDataset':
-        from yunet_amd.datasets import flatten_multi_image_mix
-        train = flatten_multi_image_mix(train)
+        from yunet_amd.datasets import flatten_multi_image_mix, split_skip_type_keys
+        train = flatten_multi_image_mix(split_skip_type_keys(train)[0])
     val = copy.deepcopy(dict(cfg.data.val))
     val['pipeline'] = copy.deepcopy(train['pipeline'])
     val.pop('test_mode', None)
