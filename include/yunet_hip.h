@@ -403,6 +403,28 @@ int yunet_loss_finalize_ex(const float* partials, int blocks, float* losses, flo
                            const float* num_total, float* dy_norm, void* stream);
 int yunet_loss_blocks(int N, int P);
 
+/* ---- ignore regions (additive) ------------------------------------------------------------
+ * yunet_ignore_mark: ign_boxes [N,Imax,4] xyxy fp32 (16-byte aligned), ign_count [N] int32 (clamped to 0 .. Imax; rows at
+ * and beyond an image's count are never read), Imax <= 1024.  The candidate box of prior (x, y, s) is its cell
+ * [x, y, x+s, y+s]; in fp32 iw = max(min(x2, x+s) - max(x1, x), 0), ih likewise, iof = iw * ih / (s * s).  A prior with
+ * gt_inds == 0 whose largest iof over its image's boxes is > thr (strict; thr >= 0) gets gt_inds = -1, mmdet's
+ * AssignResult convention; positives keep their assignment.  n_marked [N] int32 (nullable) receives the number of
+ * priors marked per image (zeroed by a memset in front of the launch).  One launch, between yunet_assign* and yunet_loss*; img_stats and
+ * the normalisers are not touched.
+ * In an op list: YUNET_OP_IGNORE_MARK with p[0] = ign_boxes, p[1] = ign_count, p[2] = gt_inds, p[3] = n_marked,
+ * i[0] = N, i[1] = P, i[2] = Imax, f[0] = thr, lv. */
+int yunet_ignore_mark(const float* ign_boxes, const int32_t* ign_count, const YunetLevels* lv, int N, int P, int Imax,
+                      float thr, int32_t* gt_inds, int32_t* n_marked, void* stream);
+/* yunet_loss_terms with a flag word.  YUNET_LOSS_IGNORE: priors with gt_inds < 0 add nothing to loss_obj (BCE and
+ * Varifocal) and all 16 channels of their dflat row are 0; num_total, loss_cls, loss_bbox and loss_kps are over the
+ * positives and do not change.  Separate instances of the kernel: flags = 0 IS yunet_loss_terms, and a flagged launch
+ * over gt_inds without a negative entry writes the same bytes.  In an op list: YUNET_OP_LOSS with i[8] = flags. */
+enum { YUNET_LOSS_IGNORE = 1 };
+int yunet_loss_terms_ex(const float* flat, const int32_t* gt_inds, const float* max_overlaps,
+                        const float* gt_boxes, const float* gt_kps, const YunetLevels* lv,
+                        const YunetLossCfg* cfg, const YunetLossTerms* terms, int flags, const float* norm, int N, int P,
+                        int Gmax, float* dflat, float* partials, int blocks, void* stream);
+
 /* out[i] = a[i] + b[i] (ABI 9).  The one place the reference's head concatenates predictions that come from DIFFERENT
  * inputs: with per-level towers (YuNet_Head(stacked_convs > 0), yunet_head.py:115-147, 191-207) the cls map is computed
  * from the cls tower and bbox / obj / kps from the reg tower, then flattened side by side (:456-472).  Here each tower
@@ -481,8 +503,9 @@ enum {
     YUNET_OP_FORK, YUNET_OP_JOIN,
     YUNET_OP_ADD,     /* ABI 9: yunet_add(p[0], p[1], p[2], n = i[1] << 32 | i[0]) */
     YUNET_OP_BN_FOLD, /* yunet_bn_fold(p[0], i[0], i[1]); YUNET_OP_STEM_FWD with i[4] = det_rows > 0 is yunet_stem_fwd_det */
-    YUNET_OP_STEM_BWD_DX  /* yunet_stem_bwd_dx[_bf16 by i[11]](z = p[1], dy = p[2], &bn[0], w = p[3], dimg = p[0],
+    YUNET_OP_STEM_BWD_DX, /* yunet_stem_bwd_dx[_bf16 by i[11]](z = p[1], dy = p[2], &bn[0], w = p[3], dimg = p[0],
                              N = i[0], H = i[1], W = i[2], cmid = i[3]) */
+    YUNET_OP_IGNORE_MARK  /* yunet_ignore_mark(p[0], p[1], &lv, i[0], i[1], i[2], f[0], gt_inds = p[2], n_marked = p[3]) */
 };
 /* Lanes (ABI 4).  The head chains of the pyramid levels (share conv -> fused head, and their backward) are
  * mutually independent: mmdet/models/dense_heads/yunet_head.py:175-247 walks them in a Python loop, and on the
@@ -631,6 +654,16 @@ typedef struct YunetAugCfg {
 int yunet_aug_decide(const int32_t* src_hw, const float* boxes, const float* kps, const int32_t* gt_idx, int in_gmax,
                      const YunetAugCfg* cfg, int multiscale, int scale_lo, int scale_hi, uint32_t iteration, int N,
                      int32_t* params, float* out_boxes, float* out_kps, int32_t* out_count, void* stream);
+
+/* gt_bboxes_ignore through the same three transforms (it is a key of bbox_fields).  After yunet_aug_decide on the same
+ * stream, one wavefront per image: reads the window, flip and S_n of params [N,8] and takes the ragged ignore boxes
+ * ign_boxes [sum I,4] (rows of image n: ign_off[n] .. ign_off[n + 1]; NULL when there is none) through the arithmetic
+ * of the GT boxes -- rows whose centre is strictly inside the patch, clipped to it, shifted (transforms.py:1099-1109),
+ * scaled by the decide's factor (cfg out_size, or S_n when params[:,7] > 0) and clipped, flipped.  out_ign [N,imax,4]
+ * (kept rows in order, the first imax of them; rows >= count zeroed), out_icount [N].  An image whose decide failed
+ * (cw == 0) gets count 0.  Draws nothing: every other output of the pipeline keeps its bytes. */
+int yunet_aug_ignore(const int32_t* params, const float* ign_boxes, const int32_t* ign_off, int out_size, int N, int imax,
+                     float* out_ign, int32_t* out_icount, void* stream);
 
 /* PhotoMetricDistortion (transforms.py:1211-1312) inside the pixel pass.  Positions in the pipeline list:
  *   PRE : between LoadAnnotations and RandomSquareCrop -- each in-image source tap is distorted after its uint8 ->

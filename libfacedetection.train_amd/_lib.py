@@ -34,7 +34,9 @@ KPS_SMOOTH_L1, KPS_L1, KPS_MSE, KPS_BALANCED_L1 = 0, 1, 2, 3      # YUNET_KPS_* 
 (OP_STEM_FWD, OP_STEM_BWD, OP_DP_FWD, OP_DP_BWD, OP_POOL_FWD, OP_POOL_BWD, OP_UPADD_FWD,
  OP_UPADD_BWD, OP_BN_RUNNING, OP_BN_PARAM_GRAD, OP_REDUCE_PARTIALS, OP_ASSIGN, OP_LOSS_NORM,
  OP_LOSS, OP_LOSS_FINALIZE, OP_SGD, OP_MEMSET, OP_BN_BATCH, OP_REDUCE_BATCH, OP_FORK, OP_JOIN, OP_ADD, OP_BN_FOLD,
- OP_STEM_BWD_DX) = range(1, 25)
+ OP_STEM_BWD_DX, OP_IGNORE_MARK) = range(1, 26)
+LOSS_IGNORE, LOSS_FLAGS_SLOT = 1, 8  # YUNET_LOSS_IGNORE; YUNET_OP_LOSS carries the flag word in i[8]
+IGNORE_MAX_BOXES, IGNORE_MIN_ROWS = 1024, 16      # rows per image of the padded ignore boxes (yunet_ignore_mark: Imax <= 1024)
 OP_LANE, MAX_LANES = 10, 2          # YunetOp.i[OP_LANE]: side stream of the op (0 = the caller's stream)
 OP_GROUP, DP_GROUP_MAX = 9, 3       # YunetOp.i[OP_GROUP] = g: this DP_FWD op and the g - 1 after it are independent (ABI 10)
 
@@ -236,6 +238,7 @@ _SIGNATURES = {
                        [C.c_void_p] * 5),
     'yunet_aug_decide': (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.POINTER(YunetAugCfg), C.c_int, C.c_int, C.c_int, C.c_uint32,
                                                       C.c_int] + [C.c_void_p] * 5),
+    'yunet_aug_ignore': (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 3),
     'yunet_aug_pixels': (C.c_int, [C.POINTER(YunetAugPixels), C.POINTER(YunetAugCfg), C.c_int, C.c_void_p, C.c_void_p]),
     'yunet_aug_photometric': (C.c_int, [C.POINTER(YunetPhotoCfg), C.c_uint32, C.c_uint32, C.c_int, C.c_void_p,
                                         C.c_void_p]),
@@ -286,6 +289,11 @@ _SIGNATURES = {
     'yunet_loss_terms': (C.c_int, [C.c_void_p] * 5 + [C.POINTER(YunetLevels), C.POINTER(YunetLossCfg),
                                                       C.POINTER(YunetLossTerms), C.c_void_p] + [C.c_int] * 3 +
                          [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'yunet_loss_terms_ex': (C.c_int, [C.c_void_p] * 5 + [C.POINTER(YunetLevels), C.POINTER(YunetLossCfg),
+                                                         C.POINTER(YunetLossTerms), C.c_int, C.c_void_p] + [C.c_int] * 3 +
+                            [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'yunet_ignore_mark': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(YunetLevels), C.c_int, C.c_int, C.c_int, C.c_float] +
+                          [C.c_void_p] * 3),
     'yunet_loss_finalize': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'yunet_loss_finalize_ex': (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5),
     'yunet_sgd_step_ex': (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_float,

@@ -356,12 +356,16 @@ extern "C" int yunet_exec(const YunetOp* ops, int n_ops, void* main_stream) {
                 // the term selection rides in slots this op does not use otherwise (all-zero: yunet_loss itself)
                 const YunetLossTerms tm{o.i[4], o.i[5], o.i[6], o.i[7] & 1, (o.i[7] >> 1) & 1,
                                         o.f[0], o.f[1], o.f[2], o.f[3], o.f[4], o.f[5]};
-                rc = yunet_loss_terms((const float*)o.p[0], (const int32_t*)o.p[1], (const float*)o.p[2],
-                                      (const float*)o.p[3], (const float*)o.p[4], &o.lv, &o.loss, &tm,
-                                      (const float*)o.p[5], o.i[0], o.i[1], o.i[2], (float*)o.p[6],
-                                      (float*)o.p[7], o.i[3], stream);
+                rc = yunet_loss_terms_ex((const float*)o.p[0], (const int32_t*)o.p[1], (const float*)o.p[2],
+                                         (const float*)o.p[3], (const float*)o.p[4], &o.lv, &o.loss, &tm, o.i[8] /* flags */,
+                                         (const float*)o.p[5], o.i[0], o.i[1], o.i[2], (float*)o.p[6],
+                                         (float*)o.p[7], o.i[3], stream);
                 break;
             }
+            case YUNET_OP_IGNORE_MARK:
+                rc = yunet_ignore_mark((const float*)o.p[0], (const int32_t*)o.p[1], &o.lv, o.i[0], o.i[1], o.i[2], o.f[0],
+                                       (int32_t*)o.p[2], (int32_t*)o.p[3], stream);
+                break;
             case YUNET_OP_LOSS_FINALIZE:
                 rc = yunet_loss_finalize_ex((const float*)o.p[0], o.i[0], (float*)o.p[1], (float*)o.p[2],
                                             (const float*)o.p[3], (float*)o.p[4], stream);

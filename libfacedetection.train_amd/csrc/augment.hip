@@ -54,6 +54,21 @@ __device__ __forceinline__ bool centre_inside(const float* b, int p0, int p1, in
     return cx > (float)p0 && cy > (float)p1 && cx < (float)p2 && cy < (float)p3;
 }
 
+// What RandomSquareCrop (clip to the patch, subtract its origin: transforms.py:1104-1107), Resize._resize_bboxes (scale,
+// clip to the output) and RandomFlip.bbox_flip do to one kept row of a key of bbox_fields: the one code path of the GT
+// boxes (aug_decide_kernel) and of the ignore boxes (aug_ignore_kernel).
+__device__ __forceinline__ void crop_resize_flip_box(const float* b, int p0, int p1, int p2, int p3, float sf, float fS,
+                                                     bool flip, float* o) {
+    float x1 = fmaxf(b[0], (float)p0) - (float)p0, y1 = fmaxf(b[1], (float)p1) - (float)p1;
+    float x2 = fminf(b[2], (float)p2) - (float)p0, y2 = fminf(b[3], (float)p3) - (float)p1;
+    x1 = fminf(fmaxf(x1 * sf, 0.0f), fS); y1 = fminf(fmaxf(y1 * sf, 0.0f), fS);
+    x2 = fminf(fmaxf(x2 * sf, 0.0f), fS); y2 = fminf(fmaxf(y2 * sf, 0.0f), fS);
+    if (flip) { const float t = x1; x1 = fS - x2; x2 = fS - t; }
+    o[0] = x1; o[1] = y1; o[2] = x2; o[3] = y2;
+}
+// the Resize factor of a window of edge cw scaled to S (mmcv.imresize: w_scale = S / w)
+__device__ __forceinline__ float resize_factor(int S, int cw) { return (float)((double)S / (double)cw); }
+
 #define AUG_P_LEFT 0
 #define AUG_P_TOP 1
 #define AUG_P_CW 2
@@ -115,7 +130,7 @@ __global__ __launch_bounds__(64) void aug_decide_kernel(
     int kept = 0;
     if (found) {
         const int p0 = left, p1 = top, p2 = left + cw, p3 = top + cw;
-        const float sf = (float)((double)S / (double)cw);     // mmcv.imresize: w_scale = S / w
+        const float sf = resize_factor(S, cw);
         const float fS = (float)S;
         for (int base = 0; base < G; base += 64) {
             const int g = base + lane;
@@ -123,14 +138,7 @@ __global__ __launch_bounds__(64) void aug_decide_kernel(
             const unsigned long long m = __ballot(keep);
             const int idx = kept + __popcll(m & ((1ull << lane) - 1ull));
             if (keep && idx < gmax) {
-                const float* b = bx + 4 * g;
-                float x1 = fmaxf(b[0], (float)p0) - (float)p0, y1 = fmaxf(b[1], (float)p1) - (float)p1;
-                float x2 = fminf(b[2], (float)p2) - (float)p0, y2 = fminf(b[3], (float)p3) - (float)p1;
-                x1 = fminf(fmaxf(x1 * sf, 0.0f), fS); y1 = fminf(fmaxf(y1 * sf, 0.0f), fS);
-                x2 = fminf(fmaxf(x2 * sf, 0.0f), fS); y2 = fminf(fmaxf(y2 * sf, 0.0f), fS);
-                if (flip) { const float t = x1; x1 = fS - x2; x2 = fS - t; }
-                float* o = ob + 4 * idx;
-                o[0] = x1; o[1] = y1; o[2] = x2; o[3] = y2;
+                crop_resize_flip_box(bx + 4 * g, p0, p1, p2, p3, sf, fS, flip, ob + 4 * idx);
                 const float* k = kp + 15 * g;
                 float* q = ok + 15 * idx;
 #pragma unroll
@@ -157,6 +165,41 @@ __global__ __launch_bounds__(64) void aug_decide_kernel(
         p[AUG_P_STATUS] = found ? (kept > gmax ? 2 : 0) : 1; p[AUG_P_SIZE] = MS ? S : 0;
         out_count[n] = count;
     }
+}
+
+// ---- ignore boxes (gt_bboxes_ignore in bbox_fields): one wavefront per image, after aug_decide_kernel on its stream ------
+// Reads the window, flip and S_n the decide left in params and takes the image's ragged ignore rows through the steps the
+// GT boxes took: rows whose centre is strictly inside the patch are kept (transforms.py:1102-1103), in order, the first
+// `imax` of them written; rows >= the count are zero.  An image whose decide failed (cw == 0) gets count 0.  Draws nothing.
+__global__ __launch_bounds__(64) void aug_ignore_kernel(const int32_t* __restrict__ params, const float* __restrict__ ign_boxes,
+                                                        const int32_t* __restrict__ ign_off, int out_size, int imax,
+                                                        float* __restrict__ out_ign, int32_t* __restrict__ out_icount) {
+    const int n = blockIdx.x, lane = threadIdx.x;
+    const int32_t* p = params + 8 * n;
+    const int left = p[AUG_P_LEFT], top = p[AUG_P_TOP], cw = p[AUG_P_CW];
+    const bool flip = p[AUG_P_FLIP] != 0;
+    const int S = p[AUG_P_SIZE] > 0 ? p[AUG_P_SIZE] : out_size;
+    const int i0 = ign_off[n];
+    const int I = cw > 0 ? max(ign_off[n + 1] - i0, 0) : 0;
+    const float* bx = ign_boxes + (size_t)i0 * 4;
+    float* ob = out_ign + (size_t)n * imax * 4;
+    int kept = 0;
+    if (I > 0) {
+        const int p0 = left, p1 = top, p2 = left + cw, p3 = top + cw;
+        const float sf = resize_factor(S, cw);
+        const float fS = (float)S;
+        for (int base = 0; base < I; base += 64) {
+            const int g = base + lane;
+            const bool keep = g < I && centre_inside(bx + 4 * g, p0, p1, p2, p3);
+            const unsigned long long m = __ballot(keep);
+            const int idx = kept + __popcll(m & ((1ull << lane) - 1ull));
+            if (keep && idx < imax) crop_resize_flip_box(bx + 4 * g, p0, p1, p2, p3, sf, fS, flip, ob + 4 * idx);
+            kept += __popcll(m);
+        }
+    }
+    const int count = kept < imax ? kept : imax;
+    for (int i = count * 4 + lane; i < imax * 4; i += 64) ob[i] = 0.0f;
+    if (lane == 0) out_icount[n] = count;
 }
 
 // OpenCV INTER_LINEAR coefficient of one destination coordinate (float32 bilinear, half-pixel
@@ -1162,6 +1205,16 @@ extern "C" int yunet_aug_decide(const int32_t* src_hw, const float* boxes, const
                                params, out_boxes, out_kps, out_count, in_gmax);
         });
     });
+    return hip_status();
+}
+
+extern "C" int yunet_aug_ignore(const int32_t* params, const float* ign_boxes, const int32_t* ign_off, int out_size, int N,
+                                int imax, float* out_ign, int32_t* out_icount, void* stream) {
+    // ign_boxes may be NULL when the batch holds no ignore box at all (ign_off all equal): nothing is read through it
+    if (!params || !ign_off || !out_ign || !out_icount || N < 1 || imax < 1 || out_size < 1 || out_size > YUNET_AUG_MAX_EDGE)
+        return YUNET_EINVAL;
+    hipLaunchKernelGGL(aug_ignore_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, params, ign_boxes, ign_off, out_size,
+                       imax, out_ign, out_icount);
     return hip_status();
 }
 

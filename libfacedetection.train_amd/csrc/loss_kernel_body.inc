@@ -3,8 +3,11 @@
 //   loss_terms_kernel  EXT = true: adds the terms of YunetLossTerms `tm` and YUNET_BOX_BOUNDED, each chosen by a launch-uniform code.
 // Text inclusion, not an inlined function: the default instance keeps its pointer arguments' __restrict__ as kernel arguments
 // and compiles to the code it had before the second instance existed (profiles/loss_terms_codegen.txt).
-// In scope: the kernel's arguments, `constexpr bool EXT`, `constexpr bool GRAD`, `tm` (YunetLossTerms) and `bal_b`
-// (BalancedL1Loss's b).
+// In scope: the kernel's arguments, `constexpr bool EXT`, `constexpr bool GRAD`, `constexpr bool IGN`, `tm`
+// (YunetLossTerms) and `bal_b` (BalancedL1Loss's b).
+// IGN = true (the *_ign instances, YUNET_LOSS_IGNORE): a prior with gt_inds < 0 adds nothing to the loss_obj partial and
+// its dflat row is all zero; every other prior runs the same operations in the same order, so a launch with nothing
+// marked writes the bytes of the IGN = false instance (profiles/ignore_codegen.txt: those compile to what they did).
 // GRAD = false (loss_value_kernel, loss_terms_value_kernel: the validation step, dflat == NULL): the four float4 stores are
 // not compiled, `o` and the derivative halves of the dual numbers are dead and leave the code.  The value half of every
 // dual operation is the same sequence of single-rounded fp32 operations in both forms (-ffp-contract=off), so `acc` and
@@ -28,7 +31,9 @@
         const int gi = gt_inds[e];
         const float t_obj = gi > 0 ? 1.0f : 0.0f;
         const float xo = q1.y;
-        if (EXT && tm.obj_loss == YUNET_CLS_VARIFOCAL) {
+        if (IGN && gi < 0) {
+            // a prior yunet_ignore_mark put inside an ignore region: outside loss_obj, its whole dflat row stays 0
+        } else if (EXT && tm.obj_loss == YUNET_CLS_VARIFOCAL) {
             float gv;
             acc[2] += varifocal(xo, t_obj, tm.obj_alpha, tm.obj_gamma, tm.obj_iou_weighted, &gv);
             o[5] = cfg.w_obj * gv * inv_total;

@@ -1205,6 +1205,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_kernel(
     int N, int P, int Gmax, float* __restrict__ dflat, float* __restrict__ partials) {
     constexpr bool EXT = false;
     constexpr bool GRAD = true;
+    constexpr bool IGN = false;
     constexpr YunetLossTerms tm{};
     constexpr float bal_b = 0.0f;
 #include "loss_kernel_body.inc"
@@ -1218,6 +1219,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_terms_kernel(
     const float* __restrict__ norm, int N, int P, int Gmax, float* __restrict__ dflat, float* __restrict__ partials) {
     constexpr bool EXT = true;
     constexpr bool GRAD = true;
+    constexpr bool IGN = false;
 #include "loss_kernel_body.inc"
 }
 
@@ -1230,6 +1232,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_value_kernel(
     int N, int P, int Gmax, float* __restrict__ partials) {
     constexpr bool EXT = false;
     constexpr bool GRAD = false;
+    constexpr bool IGN = false;
     constexpr YunetLossTerms tm{};
     constexpr float bal_b = 0.0f;
     constexpr float* dflat = nullptr;
@@ -1243,8 +1246,118 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_terms_value_kernel(
     const float* __restrict__ norm, int N, int P, int Gmax, float* __restrict__ partials) {
     constexpr bool EXT = true;
     constexpr bool GRAD = false;
+    constexpr bool IGN = false;
     constexpr float* dflat = nullptr;
 #include "loss_kernel_body.inc"
+}
+
+// The same four with IGN = true (YUNET_LOSS_IGNORE): priors that yunet_ignore_mark set to gt_inds = -1 are outside loss_obj.
+// Launched only when the call or the op asks for them.
+__global__ __launch_bounds__(LOSS_THREADS) void loss_ign_kernel(
+    const float* __restrict__ flat, const int32_t* __restrict__ gt_inds,
+    const float* __restrict__ max_overlaps, const float* __restrict__ gt_boxes,
+    const float* __restrict__ gt_kps, Levels L, YunetLossCfg cfg, const float* __restrict__ norm,
+    int N, int P, int Gmax, float* __restrict__ dflat, float* __restrict__ partials) {
+    constexpr bool EXT = false;
+    constexpr bool GRAD = true;
+    constexpr bool IGN = true;
+    constexpr YunetLossTerms tm{};
+    constexpr float bal_b = 0.0f;
+#include "loss_kernel_body.inc"
+}
+
+__global__ __launch_bounds__(LOSS_THREADS) void loss_terms_ign_kernel(
+    const float* __restrict__ flat, const int32_t* __restrict__ gt_inds,
+    const float* __restrict__ max_overlaps, const float* __restrict__ gt_boxes,
+    const float* __restrict__ gt_kps, Levels L, YunetLossCfg cfg, YunetLossTerms tm, float bal_b,
+    const float* __restrict__ norm, int N, int P, int Gmax, float* __restrict__ dflat, float* __restrict__ partials) {
+    constexpr bool EXT = true;
+    constexpr bool GRAD = true;
+    constexpr bool IGN = true;
+#include "loss_kernel_body.inc"
+}
+
+__global__ __launch_bounds__(LOSS_THREADS) void loss_value_ign_kernel(
+    const float* __restrict__ flat, const int32_t* __restrict__ gt_inds,
+    const float* __restrict__ max_overlaps, const float* __restrict__ gt_boxes,
+    const float* __restrict__ gt_kps, Levels L, YunetLossCfg cfg, const float* __restrict__ norm,
+    int N, int P, int Gmax, float* __restrict__ partials) {
+    constexpr bool EXT = false;
+    constexpr bool GRAD = false;
+    constexpr bool IGN = true;
+    constexpr YunetLossTerms tm{};
+    constexpr float bal_b = 0.0f;
+    constexpr float* dflat = nullptr;
+#include "loss_kernel_body.inc"
+}
+
+__global__ __launch_bounds__(LOSS_THREADS) void loss_terms_value_ign_kernel(
+    const float* __restrict__ flat, const int32_t* __restrict__ gt_inds,
+    const float* __restrict__ max_overlaps, const float* __restrict__ gt_boxes,
+    const float* __restrict__ gt_kps, Levels L, YunetLossCfg cfg, YunetLossTerms tm, float bal_b,
+    const float* __restrict__ norm, int N, int P, int Gmax, float* __restrict__ partials) {
+    constexpr bool EXT = true;
+    constexpr bool GRAD = false;
+    constexpr bool IGN = true;
+    constexpr float* dflat = nullptr;
+#include "loss_kernel_body.inc"
+}
+
+// ---- ignore regions: background priors whose cell lies inside an ignore box leave loss_obj ------------------------------
+// One workgroup per (image, chunk of 256 priors), one prior per thread.  The candidate box of prior (x, y, s) is its cell
+// [x, y, x + s, y + s]; iof = the share of the cell an ignore box covers, in fp32, one rounding per operation (this file
+// is compiled without contraction).  A prior SimOTA left as background (gt_inds == 0) whose largest iof over the image's
+// boxes is > thr becomes gt_inds = -1 (mmdet's AssignResult convention); positives keep their GT.  The image's boxes are
+// staged in LDS, every load issued before the first is consumed; rows >= the image's count are never read.  n_marked
+// (nullable, zeroed by the entry point) takes one integer atomic per workgroup that marked something.
+#define IGN_THREADS 256
+#define IGN_MAX_BOXES 1024
+__global__ __launch_bounds__(IGN_THREADS) void ignore_mark_kernel(
+    const float* __restrict__ ign_boxes, const int32_t* __restrict__ ign_count, Levels L, int P, int Imax, int nchunk,
+    float thr, int32_t* __restrict__ gt_inds, int32_t* __restrict__ n_marked) {
+    __shared__ float4 s_ig[IGN_MAX_BOXES];
+    __shared__ int s_cnt[IGN_THREADS / 64];
+    const int n = blockIdx.x / nchunk, c = blockIdx.x - n * nchunk, tid = threadIdx.x;
+    const int I = max(0, min(ign_count[n], Imax));      // workgroup-uniform
+    if (I == 0) return;
+    const int p = c * IGN_THREADS + tid;
+    const int gi = p < P ? gt_inds[(size_t)n * P + p] : 1;
+    float4 st[IGN_MAX_BOXES / IGN_THREADS];
+#pragma unroll
+    for (int k = 0; k < IGN_MAX_BOXES / IGN_THREADS; ++k) {
+        const int i = k * IGN_THREADS + tid;
+        st[k] = i < I ? *reinterpret_cast<const float4*>(ign_boxes + ((size_t)n * Imax + i) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int k = 0; k < IGN_MAX_BOXES / IGN_THREADS; ++k) {
+        const int i = k * IGN_THREADS + tid;
+        if (i < I) s_ig[i] = st[k];
+    }
+    __syncthreads();
+    bool mark = false;
+    if (gi == 0) {
+        float px, py, s;
+        prior_of(L, p, px, py, s);
+        const float qx = px + s, qy = py + s, area = s * s;
+        float best = 0.0f;
+        for (int i = 0; i < I; ++i) {
+            const float4 b = s_ig[i];
+            const float iw = fmaxf(fminf(b.z, qx) - fmaxf(b.x, px), 0.0f);
+            const float ih = fmaxf(fminf(b.w, qy) - fmaxf(b.y, py), 0.0f);
+            best = fmaxf(best, iw * ih / area);
+        }
+        mark = best > thr;
+        if (mark) gt_inds[(size_t)n * P + p] = -1;
+    }
+    if (!n_marked) return;                               // workgroup-uniform
+    const int wcnt = __popcll(__ballot(mark));
+    if ((tid & 63) == 0) s_cnt[tid >> 6] = wcnt;
+    __syncthreads();
+    if (tid == 0) {
+        int t = 0;
+        for (int w = 0; w < IGN_THREADS / 64; ++w) t += s_cnt[w];
+        if (t) atomicAdd(&n_marked[n], t);
+    }
 }
 
 __global__ void loss_finalize_kernel(const float* __restrict__ partials, int blocks,
@@ -1370,17 +1483,31 @@ extern "C" int yunet_loss_norm(const float* img_stats, int N, float inv_world, f
     return -(int)hipGetLastError();
 }
 
-extern "C" int yunet_loss_terms(const float* flat, const int32_t* gt_inds, const float* max_overlaps,
-                                const float* gt_boxes, const float* gt_kps, const YunetLevels* lv,
-                                const YunetLossCfg* cfg, const YunetLossTerms* terms, const float* norm, int N, int P,
-                                int Gmax, float* dflat, float* partials, int blocks, void* stream) {
+// flags: YUNET_LOSS_IGNORE selects the IGN instances of the kernels (yunet_loss_terms_ex); 0 is yunet_loss_terms as it was
+static int loss_terms_launch(const float* flat, const int32_t* gt_inds, const float* max_overlaps,
+                             const float* gt_boxes, const float* gt_kps, const YunetLevels* lv,
+                             const YunetLossCfg* cfg, const YunetLossTerms* terms, int flags, const float* norm, int N, int P,
+                             int Gmax, float* dflat, float* partials, int blocks, void* stream) {
     if (!lv || !cfg || blocks < 1) return YUNET_EINVAL;
+    if (flags & ~YUNET_LOSS_IGNORE) return YUNET_EINVAL;
+    const bool ign = (flags & YUNET_LOSS_IGNORE) != 0;
     const YunetLossTerms tm = terms ? *terms : YunetLossTerms{};
     const bool dflt = tm.cls_loss == YUNET_CLS_BCE && tm.obj_loss == YUNET_CLS_BCE && tm.kps_loss == YUNET_KPS_SMOOTH_L1 &&
                       cfg->box_loss != YUNET_BOX_BOUNDED;
-    if (dflt)       // the default selection is yunet_loss itself: the same kernel, the same bits
+    if (dflt && !ign)       // the default selection is yunet_loss itself: the same kernel, the same bits
         return yunet_loss(flat, gt_inds, max_overlaps, gt_boxes, gt_kps, lv, cfg, norm, N, P, Gmax, dflat, partials, blocks,
                           stream);
+    if (dflt) {             // ... and with ignore regions the IGN instance of that kernel
+        Levels L = make_levels(lv);
+        if (L.base[YUNET_MAX_LEVELS] != P) return YUNET_EINVAL;
+        if (!dflat)
+            hipLaunchKernelGGL(loss_value_ign_kernel, dim3(blocks), dim3(LOSS_THREADS), 0, (hipStream_t)stream, flat, gt_inds,
+                               max_overlaps, gt_boxes, gt_kps, L, *cfg, norm, N, P, Gmax, partials);
+        else
+            hipLaunchKernelGGL(loss_ign_kernel, dim3(blocks), dim3(LOSS_THREADS), 0, (hipStream_t)stream, flat, gt_inds,
+                               max_overlaps, gt_boxes, gt_kps, L, *cfg, norm, N, P, Gmax, dflat, partials);
+        return -(int)hipGetLastError();
+    }
     if (cfg->box_loss < YUNET_BOX_EIOU || cfg->box_loss > YUNET_BOX_BOUNDED) return YUNET_EINVAL;
     if ((tm.cls_loss != YUNET_CLS_BCE && tm.cls_loss != YUNET_CLS_VARIFOCAL) ||
         (tm.obj_loss != YUNET_CLS_BCE && tm.obj_loss != YUNET_CLS_VARIFOCAL) || tm.kps_loss < YUNET_KPS_SMOOTH_L1 ||
@@ -1399,11 +1526,45 @@ extern "C" int yunet_loss_terms(const float* flat, const int32_t* gt_inds, const
     Levels L = make_levels(lv);
     if (L.base[YUNET_MAX_LEVELS] != P) return YUNET_EINVAL;
     if (!dflat)     // losses alone
-        hipLaunchKernelGGL(loss_terms_value_kernel, dim3(blocks), dim3(LOSS_THREADS), 0, (hipStream_t)stream, flat, gt_inds,
-                           max_overlaps, gt_boxes, gt_kps, L, *cfg, tm, bal_b, norm, N, P, Gmax, partials);
+        hipLaunchKernelGGL(ign ? loss_terms_value_ign_kernel : loss_terms_value_kernel, dim3(blocks), dim3(LOSS_THREADS), 0,
+                           (hipStream_t)stream, flat, gt_inds, max_overlaps, gt_boxes, gt_kps, L, *cfg, tm, bal_b, norm, N, P,
+                           Gmax, partials);
     else
-        hipLaunchKernelGGL(loss_terms_kernel, dim3(blocks), dim3(LOSS_THREADS), 0, (hipStream_t)stream, flat, gt_inds,
-                           max_overlaps, gt_boxes, gt_kps, L, *cfg, tm, bal_b, norm, N, P, Gmax, dflat, partials);
+        hipLaunchKernelGGL(ign ? loss_terms_ign_kernel : loss_terms_kernel, dim3(blocks), dim3(LOSS_THREADS), 0,
+                           (hipStream_t)stream, flat, gt_inds, max_overlaps, gt_boxes, gt_kps, L, *cfg, tm, bal_b, norm, N, P,
+                           Gmax, dflat, partials);
+    return -(int)hipGetLastError();
+}
+
+extern "C" int yunet_loss_terms(const float* flat, const int32_t* gt_inds, const float* max_overlaps,
+                                const float* gt_boxes, const float* gt_kps, const YunetLevels* lv,
+                                const YunetLossCfg* cfg, const YunetLossTerms* terms, const float* norm, int N, int P,
+                                int Gmax, float* dflat, float* partials, int blocks, void* stream) {
+    return loss_terms_launch(flat, gt_inds, max_overlaps, gt_boxes, gt_kps, lv, cfg, terms, 0, norm, N, P, Gmax, dflat,
+                             partials, blocks, stream);
+}
+
+extern "C" int yunet_loss_terms_ex(const float* flat, const int32_t* gt_inds, const float* max_overlaps,
+                                   const float* gt_boxes, const float* gt_kps, const YunetLevels* lv,
+                                   const YunetLossCfg* cfg, const YunetLossTerms* terms, int flags, const float* norm, int N,
+                                   int P, int Gmax, float* dflat, float* partials, int blocks, void* stream) {
+    return loss_terms_launch(flat, gt_inds, max_overlaps, gt_boxes, gt_kps, lv, cfg, terms, flags, norm, N, P, Gmax, dflat,
+                             partials, blocks, stream);
+}
+
+extern "C" int yunet_ignore_mark(const float* ign_boxes, const int32_t* ign_count, const YunetLevels* lv, int N, int P,
+                                 int Imax, float thr, int32_t* gt_inds, int32_t* n_marked, void* stream) {
+    if (!ign_boxes || !ign_count || !gt_inds || !lv || lv->num_levels < 1 || lv->num_levels > YUNET_MAX_LEVELS || N < 1 ||
+        P < 1 || Imax < 1 || Imax > IGN_MAX_BOXES || !(thr >= 0.0f) || (reinterpret_cast<uintptr_t>(ign_boxes) & 15))
+        return YUNET_EINVAL;
+    Levels L = make_levels(lv);
+    if (L.base[YUNET_MAX_LEVELS] != P) return YUNET_EINVAL;
+    const int nchunk = (P + IGN_THREADS - 1) / IGN_THREADS;
+    if ((long long)N * nchunk > 0x7fffffffll) return YUNET_EINVAL;
+    if (n_marked && hipMemsetAsync(n_marked, 0, (size_t)N * sizeof(int32_t), (hipStream_t)stream) != hipSuccess)
+        return -(int)hipGetLastError();
+    hipLaunchKernelGGL(ignore_mark_kernel, dim3(N * nchunk), dim3(IGN_THREADS), 0, (hipStream_t)stream, ign_boxes,
+                       ign_count, L, P, Imax, nchunk, thr, gt_inds, n_marked);
     return -(int)hipGetLastError();
 }
 

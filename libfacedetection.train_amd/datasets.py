@@ -236,6 +236,12 @@ def split_skip_type_keys(dcfg):
     return type(dcfg)({k: v for k, v in dcfg.items() if k != 'skip_type_keys'}), list(keys)
 
 
+def ignore_counts(dataset):
+    """Ignored faces per image of dataset.data_infos -- the rows get_ann_info returns as `bboxes_ignore` (labelv2's
+    ignore flag, and every face below min_size); read from the annotations, no image is decoded."""
+    return [int(len(dataset.get_ann_info(i)['bboxes_ignore'])) for i in range(len(getattr(dataset, 'data_infos', ())))]
+
+
 def gt_counts(dataset):
     """Non-ignored faces per image of dataset.data_infos -- the rows get_ann_info returns as `bboxes`; read from the
     annotations, no image is decoded."""
@@ -264,11 +270,19 @@ class RetinaFaceSource:
     gt_capacity='dataset': the largest image's face count, so no crop can be truncated.
     gt_capacity=int      : that many faces.
     Both are rounded by pipelines.gt_capacity_rows (a power of two >= 64, at most 4096; with a Mosaic in the pipeline at
-    most 256 per image: its merged GT stays within 1024 rows, and a larger image can still truncate a merged canvas)."""
+    most 256 per image: its merged GT stays within 1024 rows, and a larger image can still truncate a merged canvas).
+
+    Ignore boxes (gt_bboxes_ignore: labelv2's ignore flag and the faces below min_size).
+    ignore_capacity=None     : today's batches, byte for byte -- nothing is allocated or launched, no new key.
+    ignore_capacity='dataset': rows for the largest ignore count of any image (from the annotations).
+    ignore_capacity=int      : that many boxes.
+    Both are rounded by pipelines.ignore_capacity_rows (a power of two >= 16, at most 1024); boxes a crop keeps beyond
+    the rows are dropped in order.  The batch then carries `gt_bboxes_ignore` (a DeviceGT), which the model uses when
+    train_cfg.assigner.ignore_iof_thr >= 0.  Not with Mosaic, RandomAffine or MixUp in the pipeline."""
 
     def __init__(self, dataset, pipeline, samples_per_gpu=16, rank=0, world=1, seed=0, max_gt=64, workers=4,
-                 cache=None, host_fetch=None, gt_capacity=None, skip_type_keys=None):
-        from .pipelines import DevicePipeline, gt_capacity_rows
+                 cache=None, host_fetch=None, gt_capacity=None, skip_type_keys=None, ignore_capacity=None):
+        from .pipelines import DevicePipeline, gt_capacity_rows, ignore_capacity_rows
         counts = gt_counts(dataset)
         self._gt_counts = counts
         types = [(p.get('type') if isinstance(p, dict) else type(p).__name__) for p in pipeline]
@@ -306,7 +320,19 @@ class RetinaFaceSource:
         self.host_fetch = host_fetch
         self.cache, self.store, self._feed, self._decoding = cache, None, None, {}
         self.ds, self.bs, self.rank, self.world, self.seed = dataset, samples_per_gpu, rank, world, seed
-        self.pipe = DevicePipeline(pipeline, seed=seed + 7919 * rank, gmax=rows)
+        self.ignore_rows = None                 # padded ignore rows per image; None: the option is off
+        if ignore_capacity is not None:
+            if isinstance(ignore_capacity, str) and ignore_capacity != 'dataset':
+                raise ValueError(f"RetinaFaceSource ignore_capacity must be 'dataset' or an integer >= 0 (or unset), "
+                                 f'got {ignore_capacity!r}')
+            icounts = ignore_counts(dataset)
+            self.ignore_rows = ignore_capacity_rows(max([0] + icounts) if ignore_capacity == 'dataset' else ignore_capacity)
+            iover = [c for c in icounts if c > self.ignore_rows]
+            if iover:
+                _log.warning(f'RetinaFaceSource: {len(iover)} images have more than {self.ignore_rows} ignore boxes (largest '
+                             f'{max(iover)}); {sum(c - self.ignore_rows for c in iover)} boxes beyond the capacity of '
+                             f'{self.ignore_rows} rows are dropped, in order, whenever a crop keeps them')
+        self.pipe = DevicePipeline(pipeline, seed=seed + 7919 * rank, gmax=rows, ignore_rows=self.ignore_rows)
         self.pipe.check_plan_cache()
         if skip_type_keys is not None:
             self.pipe.update_skip_type_keys(skip_type_keys)
@@ -382,14 +408,15 @@ class RetinaFaceSource:
                 fut = self._decoding.pop(i, None)
                 img = fut.result() if fut is not None else self.ds.load_image(i)
                 ann = self.ds.get_ann_info(i)
-                self.store.put(i, img, ann['bboxes'], ann['keypointss'])
+                self.store.put(i, img, ann['bboxes'], ann['keypointss'],
+                               ann['bboxes_ignore'] if self.ignore_rows is not None else None)
         return idx
 
     def _cached_batch(self, it, device):
         from .source_store import SourceStore, WindowFeed
         if self.store is None:
             sizes = [(info['height'], info['width']) for info in self.ds.data_infos]
-            self.store = SourceStore(sizes, placement=self.cache, device=device)
+            self.store = SourceStore(sizes, placement=self.cache, device=device, ignore=self.ignore_rows is not None)
         idx = self._fill(it)
         if self.cache == 'device':
             return self.pipe(self.store.batch(idx), it)
@@ -422,7 +449,8 @@ class RetinaFaceSource:
             from .pipelines import SourceBatch
             samples = self._decoded(it)
             src = SourceBatch.from_lists([s['img'] for s in samples], [s['gt_bboxes'] for s in samples],
-                                         [s['gt_keypointss'] for s in samples], device)
+                                         [s['gt_keypointss'] for s in samples], device,
+                                         [s['gt_bboxes_ignore'] for s in samples] if self.ignore_rows is not None else None)
             out = self.pipe(src, it)
         self._count_truncated()
         return out

@@ -309,8 +309,11 @@ class Plan:
     """Buffers + op lists for one (N, H, W, Gmax) shape, built in the phases __init__ lists (each phase's docstring: what
     it needs from the earlier ones, what it leaves on `self`)."""
 
-    def __init__(self, eng, n, h, w, gmax):
+    def __init__(self, eng, n, h, w, gmax, imax=0):
         self.eng, self.n, self.h, self.w, self.gmax = eng, n, h, w, gmax
+        # ignore regions (DESIGN.md section 21): rows per image of the padded ignore boxes; 0 = off, every list below is the
+        # one it always was.  On: one OP_IGNORE_MARK behind the assignment and OP_LOSS with the YUNET_LOSS_IGNORE flag.
+        self.imax = int(imax)
         self.sw = {name: read_switch(name) for name in PLAN_SWITCHES}      # the environment as it is NOW
         # freeze signature (YuNetEngine.set_frozen; DESIGN.md section 12): BatchNorm layers on their running statistics, and
         # state_dict keys of the parameters without gradient.  Both empty: every list below is the one it always was.
@@ -602,6 +605,11 @@ class Plan:
         self.dy_norm = torch.ones(16, **f32)      # deferred normaliser: per-channel 1 / num_total (loss_finalize_ex)
         self.dy_up = torch.ones(16, **f32)        # deferred mode: the upstream loss scales; dy_scale = dy_up * dy_norm
         self.deferred = False
+        if self.imax:
+            self.ign_boxes = torch.zeros(n, self.imax, 4, **f32)
+            self.ign_count = torch.zeros(n, device=dev, dtype=torch.int32)
+            self.own_ign = (self.ign_boxes, self.ign_count)
+            self._ign_bound = (self.ign_boxes.data_ptr(), self.ign_count.data_ptr(), None)
 
     def _emit_loss_step(self):
         """Assignment + loss_norm close fwd_a; fwd_b = loss, loss_finalize and the BN running-stat update.  Leaves
@@ -618,6 +626,14 @@ class Plan:
         self.fwd_a.append(op)
         self.fwd_a.append(self._op(L.OP_LOSS_NORM, p=[self.img_stats.data_ptr(), self.norm.data_ptr()],
                                    i=[n], f=[1.0 / self.eng.world_size]))
+        if self.imax:
+            # between the assignment and the loss; img_stats / norm are over the positives, which it leaves alone
+            # (no n_marked: the count would cost a memset per step; (plan.gt_inds < 0).sum(1) gives it when wanted)
+            mark = self._op(L.OP_IGNORE_MARK, p=[self.ign_boxes.data_ptr(), self.ign_count.data_ptr(), self.gt_inds.data_ptr()],
+                            i=[n, self.P, self.imax], f=[max(float(self.eng.ignore_iof_thr), 0.0)])
+            mark.lv = self.levels
+            self.mark_idx = len(self.fwd_a)
+            self.fwd_a.append(mark)
         op = self._op(L.OP_LOSS,
                       p=[self.flat.data_ptr(), self.gt_inds.data_ptr(), self.max_overlaps.data_ptr(), self.gt_boxes.data_ptr(),
                          self.gt_kps.data_ptr(), self.norm.data_ptr(), self.dflat.data_ptr(), self.loss_partials.data_ptr()],
@@ -635,6 +651,8 @@ class Plan:
                 op.i[4 + k] = int(v)
             for k, v in enumerate(tf):
                 op.f[k] = float(v)
+        if self.imax:
+            op.i[L.LOSS_FLAGS_SLOT] = L.LOSS_IGNORE
         self.fwd_b.append(op)
         self.fwd_b.append(self._op(L.OP_LOSS_FINALIZE, p=[self.loss_partials.data_ptr(), self.losses.data_ptr(),
                                                          self.eng.params.log_head.data_ptr()], i=[self.loss_blocks]))
@@ -764,7 +782,7 @@ class Plan:
         loss_def, fin_def = self._clone_op(loss), self._clone_op(fin)
         loss_def.loss.defer_num_total = 1
         fin_def.p[3] = self.norm.data_ptr()
-        self.val_a = stack + [assign, norm]
+        self.val_a = stack + [assign, norm] + ([self._clone_op(self.fwd_a[self.mark_idx])] if self.imax else [])
         self.val = self.val_a + [loss, fin]
         self.val_loss_def, self.val_rest_def = [loss_def], [fin_def]
         self.val_assign_idx = len(stack)
@@ -773,6 +791,7 @@ class Plan:
         self.c_val_rest_def = self._carray(self.val_rest_def)
         self.c_val = self._carray(self.val)
         self._val_gt_bound = None
+        self._val_ign_bound = None
         self._bind_val()
         return self.c_val
 
@@ -784,10 +803,17 @@ class Plan:
             for arr in (self.c_val, self.c_val_a):
                 assert arr[ai].opcode == L.OP_ASSIGN
                 arr[ai].p[1], arr[ai].p[2], arr[ai].p[4] = ptrs
-            for op in (self.c_val[ai + 2], self.c_val_loss_def[0]):
+            for op in (self.c_val[ai + 2 + bool(self.imax)], self.c_val_loss_def[0]):
                 assert op.opcode == L.OP_LOSS
                 op.p[3], op.p[4] = ptrs[0], ptrs[1]
             self._val_gt_bound = ptrs
+        if self.imax and self._ign_bound != self._val_ign_bound:
+            for arr in (self.c_val, self.c_val_a):
+                m = arr[ai + 2]
+                assert m.opcode == L.OP_IGNORE_MARK
+                m.p[0], m.p[1] = self._ign_bound[0], self._ign_bound[1]
+                m.f[0] = self.c_fwd_a[self.mark_idx].f[0]
+            self._val_ign_bound = self._ign_bound
         if img is not None:
             for which, idx in self.img_ptr_ops:
                 if which == 'fwd_a':                        # same position as in fwd_eval (set_img)
@@ -860,7 +886,7 @@ class Plan:
         # plan fills those layers twice with the same values (one 64-thread block per layer).  Kept on purpose: every op
         # stays at the index it has in fwd_a, which is what set_img relies on.
         for op in self.fwd_a[1:]:
-            if op.opcode in (L.OP_ASSIGN, L.OP_LOSS_NORM, L.OP_BN_FOLD):
+            if op.opcode in (L.OP_ASSIGN, L.OP_LOSS_NORM, L.OP_BN_FOLD, L.OP_IGNORE_MARK):
                 continue          # test time: no SimOTA on stale GT, gt_inds / norm stay untouched; row 0 of the sums is op 0's
             cp = self._clone_op(op)
             if cp.opcode == L.OP_DP_FWD:
@@ -1181,6 +1207,18 @@ class Plan:
             arr[0].p[3], arr[0].p[4] = ptrs[0], ptrs[1]
         self._gt_bound = ptrs
 
+    def bind_ignore(self, boxes, count, thr):
+        """Point the mark op at padded ignore boxes ([N,Imax,4] fp32, [N] int32, contiguous, on this device) -- the plan's own
+        staging buffers or the data source's, read in place like the GT tensors -- and set its threshold."""
+        bound = (boxes.data_ptr(), count.data_ptr(), float(thr))
+        self.ign_boxes, self.ign_count = boxes, count
+        if bound == self._ign_bound:
+            return
+        m = self.c_fwd_a[self.mark_idx]
+        assert m.opcode == L.OP_IGNORE_MARK
+        m.p[0], m.p[1], m.f[0] = bound
+        self._ign_bound = bound
+
     def _set_bwd_p0(self, idx, ptr):
         """p[0] of backward op `idx`, in the one-list form and in the two-segment copies of the backward list."""
         self.c_bwd[idx].p[0] = ptr
@@ -1241,6 +1279,10 @@ class YuNetEngine:
         # last backward of such a plan wrote
         self.input_grad = False
         self.input_grad_out = None
+        # ignore regions (arch['ignore_iof_thr'], SimOTAAssigner's argument; negative = off): forward() / forward_val() called
+        # with padded ignore boxes use a plan with the mark op and the flagged loss op; without them, or with the threshold
+        # off, the plans and op lists are the ones they always were
+        self.ignore_iof_thr = float(self.arch.get('ignore_iof_thr', -1.0))
         # gradient accumulation (set_grad_accumulation): off -- backward() overwrites the flat gradient
         self.grad_accumulation = False
         self._acc = None                # fp32 [layout.numel]: the total saved in front of a backward; allocated on first use
@@ -1359,19 +1401,20 @@ class YuNetEngine:
             self.frozen = (frozenset(bn_names), frozenset(param_keys))
             self._frozen_key = (('frozen', tuple(sorted(self.frozen[0])), tuple(sorted(self.frozen[1]))),)
 
-    def get_plan(self, n, h, w, max_gt):
+    def get_plan(self, n, h, w, max_gt, imax=0):
         gmax = 64
         while gmax < max_gt:
             gmax *= 2
         key = (n, h, w, gmax, self.precision) + (('det-fast' if self.deterministic == 'fast' else 'det',) if self.deterministic else ())
         key += self._frozen_key          # () with nothing frozen: the key it always was
         key += ('input-grad',) if self.input_grad else ()
+        key += ('ignore', int(imax)) if imax else ()
         plan = self.plans.get(key)
         if plan is None:
             if h % 32 or w % 32:
                 raise ValueError('input height/width must be multiples of 32 (reference: '
                                  'max_pool2d(2) x4 + nearest x2 upsampling must line up)')
-            plan = self.plans[key] = Plan(self, n, h, w, gmax)
+            plan = self.plans[key] = Plan(self, n, h, w, gmax, imax) if imax else Plan(self, n, h, w, gmax)
             # a plan owns every activation / gradient buffer of its shape (hundreds of MB for one 1024 x 1408
             # image).  Training uses one or two shapes; testing at the original image sizes (tools/test_widerface.py
             # --mode 2) walks through hundreds: keep the most recently used ones, drop the rest (a dropped plan
@@ -1391,9 +1434,35 @@ class YuNetEngine:
         L.check(self.lib.yunet_exec(arr, len(arr), stream), what)
 
     # ------------------------------------------------------------------ step phases
-    def forward(self, img, gt_bboxes, gt_keypointss):
+    def stage_ignore(self, plan, ign_boxes, ign_count):
+        """Padded ignore boxes of the batch -> the plan's mark op: bound in place when they are fp32 / int32, contiguous and
+        on this device (the device input pipeline's DeviceGT), copied into the plan's own buffers otherwise."""
+        own_b, own_c = plan.own_ign
+        if tuple(ign_boxes.shape) != tuple(own_b.shape) or ign_count.numel() != plan.n:
+            raise ValueError(f'ignore boxes {tuple(ign_boxes.shape)} / counts {tuple(ign_count.shape)}: expected '
+                             f'{tuple(own_b.shape)} / ({plan.n},)')
+        if (ign_boxes.device == own_b.device and ign_count.device == own_b.device and ign_boxes.dtype == torch.float32 and
+                ign_count.dtype == torch.int32 and ign_boxes.is_contiguous() and ign_count.is_contiguous() and
+                ign_boxes.data_ptr() % 16 == 0):
+            plan.bind_ignore(ign_boxes, ign_count, self.ignore_iof_thr)
+            return
+        plan.bind_ignore(own_b, own_c, self.ignore_iof_thr)
+        own_b.copy_(ign_boxes, non_blocking=True)
+        own_c.copy_(ign_count.reshape(-1), non_blocking=True)
+
+    def _imax(self, ign_boxes, ign_count):
+        """Rows per image of the ignore boxes this step runs with; 0 = the default plan (none passed, or the threshold off)."""
+        if ign_boxes is None or self.ignore_iof_thr < 0:
+            return 0
+        if ign_count is None or ign_boxes.dim() != 3 or ign_boxes.shape[2] != 4 or not 1 <= ign_boxes.shape[1] <= L.IGNORE_MAX_BOXES:
+            raise ValueError('ign_boxes [N,Imax,4] with Imax <= 1024 and ign_count [N] go together')
+        return int(ign_boxes.shape[1])
+
+    def forward(self, img, gt_bboxes, gt_keypointss, ign_boxes=None, ign_count=None):
         """img [N,3,H,W] fp32 CUDA; GT ragged lists.  Returns the device tensor
-        losses[4] = (loss_cls, loss_bbox, loss_obj, loss_kps)."""
+        losses[4] = (loss_cls, loss_bbox, loss_obj, loss_kps).
+        ign_boxes [N,Imax,4] / ign_count [N] (padded ignore boxes; used when ignore_iof_thr >= 0): background priors inside
+        them leave loss_obj."""
         assert img.is_cuda and img.dtype == torch.float32 and img.is_contiguous()
         n, _, h, w = img.shape
         pb = getattr(gt_bboxes, 'padded', None)
@@ -1405,10 +1474,13 @@ class YuNetEngine:
         else:
             max_gt = max([int(b.shape[0]) for b in gt_bboxes] + [1])
         self._check_oneshot()
-        plan = self.get_plan(n, h, w, max_gt)
+        imax = self._imax(ign_boxes, ign_count)
+        plan = self.get_plan(n, h, w, max_gt, imax)
         self.plan = plan
         self._img = img
         self.stage_gt(plan, gt_bboxes, gt_keypointss)
+        if imax:
+            self.stage_ignore(plan, ign_boxes, ign_count)
         plan.set_img(img)
         self._exec(plan.c_fwd_a, 'yunet_exec(fwd_a)')
         was_deferred = plan.deferred
@@ -1432,7 +1504,7 @@ class YuNetEngine:
         return plan.losses
 
     @torch.no_grad()
-    def forward_val(self, img, gt_bboxes, gt_keypointss):
+    def forward_val(self, img, gt_bboxes, gt_keypointss, ign_boxes=None, ign_count=None):
         """The validation step: the eval-mode conv stack (BatchNorm on the running statistics), assignment and the four
         losses, no gradient.  Same arguments and returned tensor as forward().  The plan is the one of the engine's CURRENT
         key (precision, deterministic level, freeze signature as the last training step left it): a geometry the training
@@ -1450,11 +1522,14 @@ class YuNetEngine:
         else:
             max_gt = max([int(b.shape[0]) for b in gt_bboxes] + [1])
         self._check_oneshot()
-        plan = self.get_plan(n, h, w, max_gt)
+        imax = self._imax(ign_boxes, ign_count)
+        plan = self.get_plan(n, h, w, max_gt, imax)
         self.plan = plan
         self._val_img = img          # (not _img: the backward list keeps reading the training step's image)
         c_val = plan.val_ops()
         self.stage_gt(plan, gt_bboxes, gt_keypointss)
+        if imax:
+            self.stage_ignore(plan, ign_boxes, ign_count)
         plan._bind_val(img)
         if self.world_size > 1 or (self.always_bucket and torch.distributed.is_initialized()):
             # the reference reduces num_pos across ranks in loss() whatever the mode (yunet_head.py:493-497): as in forward()

@@ -673,11 +673,40 @@ def loss_norm(img_stats, inv_world=1.0):
     return norm
 
 
+def ignore_capacity_rows(capacity):
+    """Rows per image of the padded ignore boxes: the smallest power of two >= max(capacity, 16), at most 1024."""
+    rows = L.IGNORE_MIN_ROWS
+    while rows < min(int(capacity), L.IGNORE_MAX_BOXES):
+        rows *= 2
+    return rows
+
+
+def ignore_mark(gt_inds, ign_boxes, ign_count, sizes, strides, thr, n_marked=None):
+    """gt_inds [N,P] int32, IN PLACE: background priors (0) whose cell [x, y, x+s, y+s] is covered by an ignore box to a
+    share > thr (strict, thr >= 0) become -1; positives stay.  ign_boxes [N,Imax,4] fp32 xyxy, ign_count [N] int32 (rows
+    beyond an image's count are not read); n_marked: an [N] int32 tensor to receive the marks per image.  -> gt_inds."""
+    _chk_f32(ign_boxes)
+    n, p = gt_inds.shape
+    if (gt_inds.dtype != torch.int32 or not gt_inds.is_contiguous() or ign_boxes.dim() != 3 or ign_boxes.shape[0] != n or
+            ign_boxes.shape[2] != 4 or not ign_boxes.is_contiguous() or ign_count.dtype != torch.int32 or
+            ign_count.numel() != n or not ign_count.is_contiguous()):
+        raise ValueError('ignore_mark: gt_inds [N,P] int32, ign_boxes [N,Imax,4] fp32, ign_count [N] int32, all contiguous')
+    if n_marked is not None and (n_marked.dtype != torch.int32 or n_marked.numel() != n or not n_marked.is_contiguous()):
+        raise ValueError('ignore_mark: n_marked must be a contiguous int32 [N] tensor')
+    if not float(thr) >= 0.0:
+        raise ValueError(f'ignore_mark: thr={thr} must be >= 0 (a negative ignore_iof_thr means off: launch nothing)')
+    lv = make_levels(sizes, strides)
+    L.check(L.load().yunet_ignore_mark(_p(ign_boxes), _p(ign_count), C.byref(lv), n, p, ign_boxes.shape[1], float(thr),
+                                       _p(gt_inds), _p(n_marked), _stream()), 'yunet_ignore_mark')
+    return gt_inds
+
+
 def loss(flat, gt_inds, ovl, gt_boxes, gt_kps, img_stats, sizes, strides, cfg, inv_world=1.0,
-         norm=None, grad=True, partials=None):
+         norm=None, grad=True, partials=None, ignore=False):
     """-> (losses [4] = cls,bbox,obj,kps ; dflat [N,P,16] ; norm [3]).
     grad=False: losses alone -- the kernel's value-only instance runs, no dflat is allocated and None stands in its place.
-    partials: a [yunet_loss_blocks(N, P), 4] fp32 tensor to receive the per-block rows (default: a temporary)."""
+    partials: a [yunet_loss_blocks(N, P), 4] fp32 tensor to receive the per-block rows (default: a temporary).
+    ignore=True: the kernel instances that keep priors with gt_inds < 0 (ignore_mark) out of loss_obj."""
     n, p, _ = flat.shape
     gmax = gt_boxes.shape[1]
     dev = flat.device
@@ -691,9 +720,14 @@ def loss(flat, gt_inds, ovl, gt_boxes, gt_kps, img_stats, sizes, strides, cfg, i
     dflat = torch.empty_like(flat) if grad else None
     lv = make_levels(sizes, strides)
     terms = getattr(cfg, 'terms', None)               # None: the default terms, which yunet_loss_terms hands to yunet_loss
-    L.check(lib.yunet_loss_terms(_p(flat), _p(gt_inds), _p(ovl), _p(gt_boxes), _p(gt_kps), C.byref(lv),
-                                 C.byref(cfg), None if terms is None else C.byref(terms), _p(norm), n, p, gmax, _p(dflat),
-                                 _p(part), blocks, _stream()), 'yunet_loss_terms')
+    if ignore:
+        L.check(lib.yunet_loss_terms_ex(_p(flat), _p(gt_inds), _p(ovl), _p(gt_boxes), _p(gt_kps), C.byref(lv),
+                                        C.byref(cfg), None if terms is None else C.byref(terms), L.LOSS_IGNORE, _p(norm), n, p,
+                                        gmax, _p(dflat), _p(part), blocks, _stream()), 'yunet_loss_terms_ex')
+    else:
+        L.check(lib.yunet_loss_terms(_p(flat), _p(gt_inds), _p(ovl), _p(gt_boxes), _p(gt_kps), C.byref(lv),
+                                     C.byref(cfg), None if terms is None else C.byref(terms), _p(norm), n, p, gmax, _p(dflat),
+                                     _p(part), blocks, _stream()), 'yunet_loss_terms')
     losses = torch.empty(5, device=dev, dtype=torch.float32)      # cls, bbox, obj, kps, total
     L.check(lib.yunet_loss_finalize(_p(part), blocks, _p(losses), None, _stream()), 'yunet_loss_finalize')
     return losses[:4], dflat, norm

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import kernels as K
 from .builder import PIPELINES
 from .registry import build_from_cfg
 from .synthetic import GTList
@@ -431,22 +432,26 @@ class DeviceGT(GTList):
 
 class StoreView:
     """Device tables of a decoded-source store of m images (what yunet_aug_gather reads): byte offsets int64 [m],
-    (h, w) int32 [m,2], first GT row / GT count int32 [m], boxes fp32 [*,4], kps fp32 [*,15]."""
+    (h, w) int32 [m,2], first GT row / GT count int32 [m], boxes fp32 [*,4], kps fp32 [*,15].  Optional, with ignore
+    boxes in the store: first ignore row / ignore count int32 [m] and ign_boxes fp32 [*,4]."""
 
-    def __init__(self, m, off, hw, goff, gcnt, boxes, kps):
+    def __init__(self, m, off, hw, goff, gcnt, boxes, kps, ioff=None, icnt=None, ign_boxes=None):
         self.m, self.off, self.hw, self.goff, self.gcnt, self.boxes, self.kps = int(m), off, hw, goff, gcnt, boxes, kps
+        self.ioff, self.icnt, self.ign_boxes = ioff, icnt, ign_boxes
 
 
 class SourceBatch:
     """A batch of decoded source images and their annotations, resident on the device:
     src uint8 (concatenated HWC images), src_off int64 [N], src_hw int32 [N,2],
     boxes fp32 [sum G,4], kps fp32 [sum G,5,3], gt_off int32 [N+1].
+    Optional (gt_bboxes_ignore; DevicePipeline(ignore_rows=...)): ign_boxes fp32 [sum I,4], ign_off int32 [N+1].
     `view` / `idx` (Mosaic): the tables of the whole store the batch was picked from (StoreView, every image in `src`)
     and the batch's store indices, int32 [N] on the device; a batch made by from_lists is its own store."""
 
-    def __init__(self, src, src_off, src_hw, boxes, kps, gt_off, view=None, idx=None):
+    def __init__(self, src, src_off, src_hw, boxes, kps, gt_off, view=None, idx=None, ign_boxes=None, ign_off=None):
         self.src, self.src_off, self.src_hw = src, src_off, src_hw
         self.boxes, self.kps, self.gt_off = boxes, kps, gt_off
+        self.ign_boxes, self.ign_off = ign_boxes, ign_off
         self.n = int(src_hw.shape[0])
         self.view, self.idx = view, idx
 
@@ -462,8 +467,9 @@ class SourceBatch:
         return self.view, self.idx
 
     @classmethod
-    def from_lists(cls, images, gt_bboxes, gt_keypointss, device):
-        """images: list of uint8 [h, w, 3] arrays / tensors (BGR as decoded); gt lists per image."""
+    def from_lists(cls, images, gt_bboxes, gt_keypointss, device, gt_bboxes_ignore=None):
+        """images: list of uint8 [h, w, 3] arrays / tensors (BGR as decoded); gt lists per image; gt_bboxes_ignore: a list
+        of [I,4] arrays per image (None: the batch carries no ignore tables)."""
         imgs = [np.ascontiguousarray(np.asarray(im.cpu() if torch.is_tensor(im) else im, dtype=np.uint8))
                 for im in images]
         for im in imgs:
@@ -484,7 +490,32 @@ class SourceBatch:
             kps[:sum(cnt)] = torch.cat([torch.as_tensor(np.asarray(k), dtype=torch.float32).reshape(-1, 5, 3)
                                         for k in gt_keypointss])
         d = torch.device(device)
-        return cls(src.to(d), torch.from_numpy(off).to(d), hw.to(d), boxes.to(d), kps.to(d), goff.to(d))
+        ign = {}
+        if gt_bboxes_ignore is not None:
+            if len(gt_bboxes_ignore) != len(imgs):
+                raise ValueError(f'gt_bboxes_ignore: {len(gt_bboxes_ignore)} entries for {len(imgs)} images')
+            ib, io = ragged_ignore(gt_bboxes_ignore)
+            ign = dict(ign_boxes=torch.from_numpy(ib).to(d), ign_off=torch.from_numpy(io).to(d))
+        return cls(src.to(d), torch.from_numpy(off).to(d), hw.to(d), boxes.to(d), kps.to(d), goff.to(d), **ign)
+
+
+def ragged_ignore(per_image):
+    """list of [I_i,4] arrays -> (boxes fp32 [max(1, sum I),4], off int32 [N+1]) on the host."""
+    rows = [np.asarray(b.cpu() if torch.is_tensor(b) else b, dtype=np.float32).reshape(-1, 4) for b in per_image]
+    off = np.concatenate([[0], np.cumsum([r.shape[0] for r in rows])]).astype(np.int32)
+    boxes = np.concatenate(rows + [np.zeros((0 if off[-1] else 1, 4), np.float32)]).astype(np.float32)
+    return np.ascontiguousarray(boxes), off
+
+
+IGNORE_ROWS_MIN, IGNORE_ROWS_MAX = L.IGNORE_MIN_ROWS, L.IGNORE_MAX_BOXES
+
+
+def ignore_capacity_rows(capacity):
+    """Padded ignore rows per image for a capacity of `capacity` boxes: the smallest power of two >= max(capacity, 16),
+    at most 1024 (what yunet_ignore_mark stages in LDS)."""
+    if isinstance(capacity, bool) or int(capacity) != capacity or int(capacity) < 0:
+        raise ValueError(f'an ignore capacity is an integer >= 0, got {capacity!r}')
+    return K.ignore_capacity_rows(capacity)
 
 
 MOSAIC_MAX_GT = 1024        # GT rows per image the engine's assign kernels are tested to
@@ -528,9 +559,23 @@ class DevicePipeline:
     # the crop's pad fill is not distorted) or before index 5 (post: on the resized, flipped image, pad included)
     PHOTO_POSITIONS = {2: L.PHOTO_PRE, 5: L.PHOTO_POST}
 
-    def __init__(self, pipeline, seed=0, gmax=64, pad_value=128.0, max_attempts=250, max_retries=64):
+    def __init__(self, pipeline, seed=0, gmax=64, pad_value=128.0, max_attempts=250, max_retries=64, ignore_rows=None):
         steps = [build_from_cfg(p, PIPELINES) if isinstance(p, dict) else p for p in pipeline]
         names = [type(s).__name__ for s in steps]
+        # ignore boxes (gt_bboxes_ignore): None = off -- nothing is allocated or launched, the batch has no new key.
+        # Otherwise the padded rows per image of batch['gt_bboxes_ignore'] (ignore_capacity_rows); one more launch,
+        # yunet_aug_ignore, behind the decide.  It draws nothing: every other output keeps its bytes.
+        self.ignore_rows = None
+        if ignore_rows is not None:
+            self.ignore_rows = ignore_capacity_rows(ignore_rows)
+            if self.ignore_rows != int(ignore_rows):
+                raise ValueError(f'ignore_rows={ignore_rows}: a power of two in [{IGNORE_ROWS_MIN}, {IGNORE_ROWS_MAX}] '
+                                 '(pipelines.ignore_capacity_rows)')
+            for step, why in (('Mosaic', "the reference's Mosaic drops ignore boxes itself"),
+                              ('RandomAffine', 'ignore boxes through its matrix are not built yet'),
+                              ('MixUp', "the reference's MixUp drops ignore boxes itself")):
+                if step in names:
+                    raise NotImplementedError(f'{step} together with ignore_capacity (ignore boxes in the batch): {why}')
         self.mixup, self.mixup_cfg, self.mixup_table, self._skip = None, None, None, frozenset()
         if 'MixUp' in names:
             at = names.index('MixUp')
@@ -695,6 +740,7 @@ class DevicePipeline:
         if merged is None:
             self.geom = None
         gb, gk, cnt, params = self._decide(src, iteration, dev, merged)
+        ign = self._ignore(src, params, dev) if self.ignore_rows is not None else None
         out_hw = 0
         if self.scale_range is not None:
             sizes = np.asarray(self.read_sizes(params) if sizes is None else sizes, dtype=np.int32)
@@ -719,7 +765,18 @@ class DevicePipeline:
             gb, gk, cnt = self._mixup(store, src, img, gb, gk, cnt, params if out_hw else None, iteration, dev)
         if self.cutout is not None:
             self._cutout(img, params if out_hw else None, iteration, dev)
-        return self._collate(img, gb, gk, cnt, params, dev)
+        return self._collate(img, gb, gk, cnt, params, dev, ign)
+
+    def _ignore(self, src, params, dev):
+        """yunet_aug_ignore on the current stream, behind the decide -> (padded ignore boxes [N,rows,4], counts [N]).  A
+        source without ignore tables stands for no ignore box at all."""
+        n, rows = src.n, self.ignore_rows
+        ob = torch.empty(n, rows, 4, device=dev, dtype=torch.float32)
+        oc = torch.empty(n, device=dev, dtype=torch.int32)
+        off = src.ign_off if src.ign_off is not None else torch.zeros(n + 1, device=dev, dtype=torch.int32)
+        L.check(L.load().yunet_aug_ignore(_ptr(params), _ptr(src.ign_boxes), _ptr(off), self.cfg.out_size, n, rows, _ptr(ob),
+                                          _ptr(oc), _stream()), 'yunet_aug_ignore')
+        return ob, oc
 
     def _affine(self, img, gb, gk, cnt, params, iteration, dev):
         """yunet_aug_affine_decide + yunet_aug_affine_pixels on the current stream -> (warped batch tensor, boxes,
@@ -817,7 +874,7 @@ class DevicePipeline:
         hands the result to `windowed(sizes=...)`."""
         return params[:, 7].cpu().numpy()
 
-    def _collate(self, img, gb, gk, cnt, params, dev):
+    def _collate(self, img, gb, gk, cnt, params, dev, ign=None):
         n, S = img.shape[0], self.out_size
         self.params = params
         boxes, kps = DeviceGT(list(gb)), DeviceGT(list(gk))
@@ -830,7 +887,11 @@ class DevicePipeline:
                      for s in self.sizes]
         else:
             metas = [dict(img_shape=(S, S, 3), pad_shape=(S, S, 3), batch_input_shape=(S, S)) for _ in range(n)]
-        return dict(img=img, img_metas=metas, gt_bboxes=boxes, gt_labels=labels, gt_keypointss=kps)
+        out = dict(img=img, img_metas=metas, gt_bboxes=boxes, gt_labels=labels, gt_keypointss=kps)
+        if ign is not None:      # the multi-scale canvas keeps image n in its top-left corner: the coordinates stand as they are
+            out['gt_bboxes_ignore'] = DeviceGT(list(ign[0]))
+            out['gt_bboxes_ignore'].padded, out['gt_bboxes_ignore'].counts = ign
+        return out
 
     def window_plan(self, src, iteration, dev):
         """The source rectangles this pipeline's pixel pass will read at `iteration` (aug_decide is keyed by

@@ -47,7 +47,7 @@ class SourceStore:
     """Decoded uint8 HWC images of a dataset and their ragged GT in one store.  `sizes`: (h, w) per image, given up
     front; the pixel buffer (sum h * w * 3 bytes, device or pinned host) is allocated on the first put."""
 
-    def __init__(self, sizes, placement='device', device='cuda'):
+    def __init__(self, sizes, placement='device', device='cuda', ignore=False):
         if placement not in ('device', 'host'):
             raise ValueError(f"SourceStore placement must be 'device' or 'host', got {placement!r}")
         hw = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
@@ -66,6 +66,10 @@ class SourceStore:
         self._boxes = np.zeros((0, 4), dtype=np.float32)      # GT rows, appended by put()
         self._kps = np.zeros((0, 15), dtype=np.float32)
         self._g_used = 0
+        # ignore boxes (ignore=True: put() takes them, batch() delivers ign_boxes / ign_off): they travel with the GT
+        # tables, not with the pixels -- host rows per image, the batch's ragged table is built per gather
+        self.ignore = bool(ignore)
+        self._ign = [None] * len(hw)
         self._dev = None                                      # device tables (synced before a gather)
         self._dev_rows = 0
         self._dirty = True
@@ -83,8 +87,9 @@ class SourceStore:
             else:
                 self.data = torch.empty(self.nbytes, dtype=torch.uint8, pin_memory=True)
 
-    def put(self, i, img, boxes, kps):
-        """Store image i (uint8 [h, w, 3] at the size given up front) and its GT (boxes [G,4], kps [G,5,3])."""
+    def put(self, i, img, boxes, kps, ign=None):
+        """Store image i (uint8 [h, w, 3] at the size given up front) and its GT (boxes [G,4], kps [G,5,3]); `ign`: its
+        ignore boxes [I,4] (a store built with ignore=True; None = no ignore box)."""
         i = int(i)
         if not 0 <= i < len(self.hw):
             raise IndexError(f'image {i} outside the store (capacity {len(self.hw)})')
@@ -113,6 +118,8 @@ class SourceStore:
         self._kps[self._g_used:need] = k
         self._goff[i], self._gcnt[i] = self._g_used, g
         self._g_used = need
+        if self.ignore:
+            self._ign[i] = np.zeros((0, 4), np.float32) if ign is None else np.asarray(ign, dtype=np.float32).reshape(-1, 4).copy()
         self._stored[i] = True
         self._dirty = True
 
@@ -170,8 +177,13 @@ class SourceStore:
                                           p(t['gcnt']), p(t['boxes']), p(t['kps']), g, p(src_off), p(src_hw),
                                           p(gt_off), p(boxes), p(kps), stream), 'yunet_aug_gather')
         view = StoreView(len(self.hw), t['off'], t['hw'], t['goff'], t['gcnt'], t['boxes'], t['kps'])
+        ign = {}
+        if self.ignore:
+            from .pipelines import ragged_ignore
+            ib, io = ragged_ignore([self._ign[i] for i in idx])
+            ign = dict(ign_boxes=_h2d(ib, dev), ign_off=_h2d(io, dev))
         sb = SourceBatch(self.data, src_off, src_hw, boxes, kps, gt_off,
-                         view=view if self.placement == 'device' else None, idx=d_idx)
+                         view=view if self.placement == 'device' else None, idx=d_idx, **ign)
         sb.host_off, sb.host_hw = self.offsets[idx], self.hw[idx]
         return sb
 
@@ -332,7 +344,8 @@ class WindowFeed:
         cur.wait_event(P['ev'])
         cur.wait_event(e1)
         sb = P['sb']
-        for t in (sb.src_off, sb.src_hw, sb.boxes, sb.kps, sb.gt_off, P['rect'], P['off']):
+        for t in (sb.src_off, sb.src_hw, sb.boxes, sb.kps, sb.gt_off, P['rect'], P['off']) + \
+                ((sb.ign_boxes, sb.ign_off) if sb.ign_off is not None else ()):
             t.record_stream(cur)
         sizes = None
         if P['sizes_h'] is not None:

@@ -15,6 +15,7 @@ import torch.nn as nn
 
 from .builder import DETECTORS, build_backbone, build_head, build_neck
 from .engine import YuNetEngine, det_level
+from .sim_ota_assigner import pad_ignore
 
 
 class _LogRecord:
@@ -281,6 +282,10 @@ class YuNet(nn.Module):
         # (raises on a reduction, loss type or parameter the fused loss step does not implement)
         # loss_cls / loss_obj / loss_kps: dict(type=, **parameters), present only beside the default terms
         terms = hd.loss_term_specs() if hd.loss_cfg().terms is not None else {}
+        # ignore regions: the key is present only when the assigner's ignore_iof_thr is on
+        thr = getattr(hd.assigner, 'ignore_iof_thr', -1.0)
+        if thr >= 0:
+            terms = dict(terms, ignore_iof_thr=thr)
         return dict(
             **terms,
             stage_channels=bb.stage_channels, downsample_idx=bb.downsample_idx, out_idx=bb.out_idx,
@@ -512,10 +517,12 @@ class YuNet(nn.Module):
             # this step overwrites (a 20-byte copy issued milliseconds ago: never an actual wait)
             torch.cuda.current_stream().wait_event(ev)
             self._log_last_event = None
+        # ignore regions: passed on only when the assigner's ignore_iof_thr is on (off: accepted and unused, as before)
+        ign = self._ignore_args(eng, gt_bboxes_ignore, len(img), img.device)
         if not self.training:
             # the workflow's validation step (runner.EpochBasedRunner.val): the reference's forward_train under eval() --
             # BatchNorm on the running statistics, the same four losses, nothing written back.  The tensors carry no graph.
-            l = eng.forward_val(img.float().contiguous(), gt_bboxes, gt_keypointss).detach().clone()
+            l = eng.forward_val(img.float().contiguous(), gt_bboxes, gt_keypointss, *ign).detach().clone()
             out = dict(loss_cls=l[0], loss_bbox=l[1], loss_obj=l[2], loss_kps=l[3])
             self._last = (out, l[4], l[:5])
             return out
@@ -523,14 +530,22 @@ class YuNet(nn.Module):
         want_dimg = torch.is_grad_enabled() and img.requires_grad
         eng.set_input_grad(want_dimg)
         if want_dimg:
-            losses = eng.forward(img.detach().float().contiguous(), gt_bboxes, gt_keypointss)
+            losses = eng.forward(img.detach().float().contiguous(), gt_bboxes, gt_keypointss, *ign)
             l = _EngineStep.apply(self._anchor, self, losses, img)
         else:
-            losses = eng.forward(img.float().contiguous(), gt_bboxes, gt_keypointss)
+            losses = eng.forward(img.float().contiguous(), gt_bboxes, gt_keypointss, *ign)
             l = _EngineStep.apply(self._anchor, self, losses)
         out = dict(loss_cls=l[0], loss_bbox=l[1], loss_obj=l[2], loss_kps=l[3])
         self._last = (out, l[4])          # lets train_step use the kernel's total and log record
         return out
+
+    @staticmethod
+    def _ignore_args(eng, gt_bboxes_ignore, n, device):
+        """-> () with ignore_iof_thr off, else (padded boxes [N,Imax,4], counts [N]): a DeviceGT's tensors as they are (the
+        engine binds them without a copy), a list of tensors padded on the device, None as zero counts."""
+        if eng.ignore_iof_thr < 0:
+            return ()
+        return pad_ignore(gt_bboxes_ignore, n, device)
 
     def _parse_losses(self, losses):
         """base.py:184-217: total = sum of the entries whose key contains 'loss'; log_vars are

@@ -14,6 +14,7 @@ from . import functional as Fh
 from . import kernels as K
 from .builder import HEADS, build_assigner, build_loss, build_prior_generator, build_sampler
 from .registry import ConfigDict
+from .sim_ota_assigner import pad_ignore
 from .yunet_layer import ConvDPUnit, yunet_init_weights
 
 
@@ -55,17 +56,19 @@ class _LossStep(torch.autograd.Function):
     d(loss_i)/d(flat) for the loss that owns each channel."""
 
     @staticmethod
-    def forward(ctx, flat, gb, gk, cnt, sizes, strides, cfg, radius, world, group):
+    def forward(ctx, flat, gb, gk, cnt, sizes, strides, cfg, radius, world, group, ignore=None):
         rad, topk, iou_w, cls_w = radius if isinstance(radius, tuple) else (radius, 10, 3.0, 1.0)
         gi, ovl, img_stats, _ = K.assign(flat, gb, gk, cnt, sizes, strides, rad, candidate_topk=topk, iou_weight=iou_w,
                                          cls_weight=cls_w)
+        if ignore is not None:       # (boxes [N,Imax,4], counts [N], thr >= 0): background priors inside a region -> -1
+            K.ignore_mark(gi, ignore[0], ignore[1], sizes, strides, ignore[2])
         norm = None
         if world > 1:
             # reduce_mean(num_pos) (yunet_head.py:493-497): norm[0] = local/world, SUM over ranks
             norm = K.loss_norm(img_stats, 1.0 / world)
             torch.distributed.all_reduce(norm[0:1], group=group)
         losses, dflat, norm = K.loss(flat, gi, ovl, gb, gk, img_stats, sizes, strides, cfg,
-                                     1.0 / world, norm)
+                                     1.0 / world, norm, ignore=ignore is not None)
         ctx.save_for_backward(dflat)
         ctx.mark_non_differentiable(gi)
         return losses[0], losses[1], losses[2], losses[3], gi
@@ -76,7 +79,7 @@ class _LossStep(torch.autograd.Function):
         z = dflat.new_zeros(())
         gs = [g if g is not None else z for g in (g_cls, g_box, g_obj, g_kps)]
         scale = torch.stack([gs[0]] + [gs[1]] * 4 + [gs[2]] + [gs[3]] * 10)
-        return (dflat * scale,) + (None,) * 9
+        return (dflat * scale,) + (None,) * 10
 
 
 @HEADS.register_module()
@@ -229,8 +232,14 @@ class YuNet_Head(nn.Module):
             torch.distributed.is_available() and torch.distributed.is_initialized()) else 1
         a = self.assigner            # SimOTAAssigner(center_radius, candidate_topk, iou_weight, cls_weight)
         radius = (a.center_radius, a.candidate_topk, a.iou_weight, a.cls_weight) if a is not None else 2.5
+        # ignore regions (train_cfg.assigner.ignore_iof_thr >= 0; off: the argument is accepted and unused, as in the reference)
+        thr = getattr(a, 'ignore_iof_thr', -1.0)
+        ignore = None
+        if thr >= 0:
+            ib, ic = pad_ignore(gt_bboxes_ignore, num_imgs, flat.device)
+            ignore = (ib, ic, thr)
         l_cls, l_box, l_obj, l_kps, gi = _LossStep.apply(
-            flat, gb, gk, cnt, sizes, self.strides, self.loss_cfg(), radius, world, None)
+            flat, gb, gk, cnt, sizes, self.strides, self.loss_cfg(), radius, world, None, ignore)
         self.last_gt_inds = gi
         return dict(loss_cls=l_cls, loss_bbox=l_box, loss_obj=l_obj, loss_kps=l_kps)
 

@@ -132,10 +132,13 @@ def build_source(cfg, rank, world, seed, dcfg=None):
         gt_capacity = dcfg.get('gt_capacity')            # data.train.gt_capacity=dataset|N: padded GT rows (RetinaFaceSource)
         if isinstance(gt_capacity, str) and gt_capacity.isdigit():
             gt_capacity = int(gt_capacity)
+        ignore_capacity = dcfg.get('ignore_capacity')    # data.train.ignore_capacity=dataset|N: gt_bboxes_ignore in the batch
+        if isinstance(ignore_capacity, str) and ignore_capacity.isdigit():
+            ignore_capacity = int(ignore_capacity)
         dataset = yunet_amd.build_dataset(dcfg)
         return RetinaFaceSource(dataset, dcfg['pipeline'], samples_per_gpu=cfg.data.samples_per_gpu, rank=rank,
                                 world=world, seed=seed, cache=cache, host_fetch=host_fetch, gt_capacity=gt_capacity,
-                                skip_type_keys=dcfg.get('skip_type_keys'))
+                                skip_type_keys=dcfg.get('skip_type_keys'), ignore_capacity=ignore_capacity)
     raise SystemExit('data sources: RetinaFaceDataset (labelv2 + image files, augmented on the GPU; also wrapped in '
                      'MultiImageMixDataset for Mosaic), '
                      'SyntheticWiderFace (ready batches) or SyntheticSourceImages (decoded synthetic '
